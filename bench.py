@@ -17,6 +17,11 @@ touches a GPU) and fails if the node has fewer than N devices.
 (lammps_scripts_reax: ffield.reax.2, QEq to 1e-6 every step, dt 0.25 fs, 10 + 20 MD steps per evaluation), same JSON contract,
 with the roofline block of its HBM-bound kernel (the matrix sweep of the charge equilibration) and its own CPU baseline.
 
+A plain run sets up (replica, equilibration), warms up, times `--steps` updates and prints the headline.  `--full` adds what
+the headline does not need, each outside `value`: the CPU baseline, the roofline block (two more updates with the batch whole),
+the monotonic strain set, the 8-GPU share, the FP64 calibration of the box and the ReaxFF leg.  `--dump-outputs DIR` writes the
+stresses of the last timed update as DIR/stress.npy (float64, one row of six per quadrature point).
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 import argparse
@@ -428,8 +433,23 @@ def attach_comm(eng, new_engine, args, rank, world, device, dist):
     return eng, "host transport (gloo)" + (f" -- RCCL attach failed: {why}" if why else ""), eng.comm_stats()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """what the timed path returned in its last update, one .npy per array; an array beyond the limit keeps a fixed, seeded sample of its rows"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if a.nbytes > DUMP_LIMIT_BYTES:
+            rows = DUMP_LIMIT_BYTES // max(a[0].nbytes, 1)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_leg(args, rank, world, device, cpu, torch, dist):
-    """one workload through the engine: equilibrate (untimed), warm up, time `steps` updates; rank 0 returns the JSON record"""
+    """one workload through the engine: equilibrate (untimed), warm up, time `steps` updates; rank 0 returns the JSON record and the
+    arrays of the last timed update ({} elsewhere)"""
     from scema_amd.systems import synthetic_strains
     reax = args.force_field == "reax"
     d, lens, DT, rate = _workload(args)
@@ -496,8 +516,9 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
     eng.profile(reset=True)
     fence()
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
-        update(args.warmup + k)
+        last = update(args.warmup + k)
     fence()
     elapsed = time.perf_counter() - t0
     own_elapsed = elapsed
@@ -508,30 +529,34 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
     prof = eng.profile()
     comm = {k: v - comm0.get(k, 0) for k, v in eng.comm_stats().items()}   # (without attach_comm's probe; collectives and checksum of warm-up + timed region: what follows is measurement aid)
     checksum_timed = checksum
-    # The roofline kernel WITH THE CHIP TO ITSELF: two more updates after the timed region with the batch issued as one sequence of launches on
-    # one stream (the timed region runs it as two half batches whose launches overlap each other and the other kernels of both halves: a
-    # per-launch time there is not a chip-exclusive time).  The engine's settings are put back exactly as they were found.
-    found = eng.concurrency()
-    if reax:
-        eng.reax_concurrency(0, 0)
-    else:
-        eng.batch_split(0)
-    eng.profile(reset=True)
-    for k in range(2):
-        update(args.warmup + args.steps + k)
-    fence()
-    prof_alone = eng.profile()
-    eng.reax_concurrency(found["reax_halves"], found["reax_overlap"])
-    eng.batch_split(found["split"])
-    assert eng.concurrency() == found
+    # the stresses of the last timed update, copied now: the updates of --full below rewrite the same request vector
+    outputs = {"stress": np.array([a.stress[:] for a in last], dtype=np.float64)} if (rank == 0 and last is not None) else {}
+    # --full: the roofline kernel WITH THE CHIP TO ITSELF: two more updates after the timed region with the batch issued as one sequence of
+    # launches on one stream (the timed region runs it as two half batches whose launches overlap each other and the other kernels of both
+    # halves: a per-launch time there is not a chip-exclusive time).  The engine's settings are put back exactly as they were found.
+    prof_alone = None
+    if args.full:
+        found = eng.concurrency()
+        if reax:
+            eng.reax_concurrency(0, 0)
+        else:
+            eng.batch_split(0)
+        eng.profile(reset=True)
+        for k in range(2):
+            update(args.warmup + args.steps + k)
+        fence()
+        prof_alone = eng.profile()
+        eng.reax_concurrency(found["reax_halves"], found["reax_overlap"])
+        eng.batch_split(found["split"])
+        assert eng.concurrency() == found
     owner, _, cap = eng.last_plan(n)
     nts_mean = req.nts_mean
     rstat = eng.reax_stats() if reax else None
 
-    # The SURVEY 8(d) strain set AS WRITTEN (every draw tensile, update after update) next to the load/unload cycle of the
+    # --full: the SURVEY 8(d) strain set AS WRITTEN (every draw tensile, update after update) next to the load/unload cycle of the
     # headline: a few more updates from the state the timed loop left, timed the same way, never part of `value`.
     mono_rate = None
-    if args.monotonic_updates > 0 and not args.monotonic and args.strain_set == "balanced":
+    if args.full and args.monotonic_updates > 0 and not args.monotonic and args.strain_set == "balanced":
         mono["on"] = True
         fence()
         tm0 = time.perf_counter()
@@ -550,7 +575,7 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
     # one warm-up and three timed updates; never part of `value`.  projected_8gpu_x = 8 x that rate / value (the stress all-gather of 27 kB
     # and the 16-byte handshake are microseconds against 170 ms of MD).
     share8 = None
-    if world == 1 and n >= 64 and n % 8 == 0 and args.share8_updates > 0 and not args.monotonic:
+    if args.full and world == 1 and n >= 64 and n % 8 == 0 and args.share8_updates > 0 and not args.monotonic:
         import ctypes
         mono["on"] = False
         idx = np.arange(0, n, 8)
@@ -570,9 +595,9 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
         fence()
         ts = time.perf_counter() - ts0
         share8 = {"sims": int(len(idx)), "updates": args.share8_updates, "evals_per_s": len(idx) * args.share8_updates / ts, "ms_per_update": 1e3 * ts / args.share8_updates}
-    # calibration of the box (the boxes of a pool differ by 4-6 % under this FP64 load): its FP64 FMA ceiling, measured now (0.2 s)
+    # --full: calibration of the box (the boxes of a pool differ by 4-6 % under this FP64 load): its FP64 FMA ceiling, measured now (0.2 s)
     box_tflops = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             box_tflops = capi.box_fp64_tflops(device)
         except Exception as exc:   # (an A/B library of an older tree has no such entry)
@@ -589,163 +614,168 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
     if rank == 0:
         natoms = int(d["natoms"])
         per_rank = int(cap)
-        # PMC figures cannot be collected inside a timed run: tools/pmc_pair.sh measures them per replica-step on the same
-        # kernel (separate rocprofv3 --pmc passes; gfx950 x2 correction on FETCH_SIZE) and commits profiles/pair_pmc.json
-        pmc, pmc_stale = None, None
-        ppath = os.path.join(ROOT, "profiles", "pair_pmc.json")
-        if os.path.exists(ppath) and natoms == 10368:
-            pmc = json.load(open(ppath))
-            # the counters belong to ONE build of the kernel: the file records the git blob hashes of its sources, and a tree whose
-            # sources differ gets no instruction-issue figure (null + this note) instead of an old count under a new time
-            have = kernel_source_hashes()
-            if pmc.get("kernel_sources") != have:
-                pmc_stale = {"recorded": pmc.get("kernel_sources"), "tree": have}
-                print("bench.py: profiles/pair_pmc.json was taken on other sources of k_pair (re-run tools/pmc_pair.sh): frac_valu_issue and traffic are null",
-                      file=sys.stderr)
-                pmc = None
         value = n * args.steps / elapsed
-        # ---- the roofline record of k_pair (schema 2, round 5; every figure reproduces from a table under profiles/) ----
-        # The kernel is bound by vector-instruction ISSUE, not by HBM: `bound`, `achieved`, `peak`, `frac` describe THAT
-        # bound, measured with the batch whole (the chip to itself); the byte-based figures of SURVEY 8(d) stand beside them as frac_hbm*.
-        #   bytes: N*(4*nbar + 56) + 48 per replica and launch; `stored` = every pair once = half the full per-atom list inside
-        #   cutoff + the reference's skin (counted by the exact list build of each run)
-        def bytes_of(pf):
-            full = pf["pair_alg_bytes"]
-            fixed = pf["pair_sims"] * (56.0 * natoms + 48.0)
-            return 0.5 * (full - fixed) + fixed, full
-        stored, full = bytes_of(prof)
-        pair_s = prof["pair_ms"] * 1e-3
-        launches = max(prof["pair_launches"], 1)
-        union_s = prof.get("pair_union_ms", 0.0) * 1e-3 or pair_s     # time with at least one timed launch running (= the sum when nothing overlaps)
-        in_flight = pair_s / union_s if union_s > 0 else 1.0
-        w_stored, w_full = bytes_of(prof_alone)
-        w_s = prof_alone["pair_ms"] * 1e-3
-        w_launches = max(prof_alone["pair_launches"], 1)
-        w_avg = w_s / w_launches
-        w_sims = prof_alone["pair_sims"] / w_launches
-        nsimd, clk, cyc = 256 * 4, 2.4e9, 4.0
-        peak_issue = nsimd * clk / cyc / 1e9                         # G wave-instructions/s the chip can issue at 4 cycles each
-        insts_per_sim_step = pmc["valu_insts_per_sim_step"] if pmc else None
-        pairs_per_sim_step = 0.5 * (w_full - prof_alone["pair_sims"] * (56.0 * natoms + 48.0)) / 4.0 / max(prof_alone["pair_sims"], 1)   # listed pairs (inside cutoff + skin)
-        frac_issue = (insts_per_sim_step * w_sims / w_avg / 1e9 / peak_issue) if insts_per_sim_step and w_avg > 0 else None
-        # schema 3 (round 6): the top-level achieved / peak / frac are the SURVEY 8(d) byte figures against 8 TB/s -- the yardstick
-        # north_star names --; the bound that actually binds the kernel (vector-instruction issue) stands beside them as frac_valu_issue
-        roof = {"schema": 3, "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
-                "achieved": w_stored / w_s / 1e9 if w_s > 0 else None,
-                "frac": w_stored / w_s / 1e9 / 8000.0 if w_s > 0 else None,
-                "frac_of": "hbm: SURVEY 8(d) bytes of the list the kernel stores (each pair once) / chip-exclusive launch time / 8 TB/s",
-                "binding_bound": "fp64_valu_issue",
-                "frac_valu_issue": frac_issue,
-                "valu_issue_achieved_ginstr_s": (insts_per_sim_step * w_sims / w_avg / 1e9) if insts_per_sim_step and w_avg > 0 else None,
-                "valu_issue_peak_ginstr_s": peak_issue,
-                "frac_hbm": w_stored / w_s / 1e9 / 8000.0 if w_s > 0 else None,
-                "frac_hbm_full_list": w_full / w_s / 1e9 / 8000.0 if w_s > 0 else None,
-                "whole_avg_launch_ms": 1e3 * w_avg, "whole_launches": prof_alone["pair_launches"], "whole_sims_per_launch": w_sims,
-                "whole_alg_bytes_per_launch": w_stored / w_launches, "whole_hbm_gbps": w_stored / w_s / 1e9 if w_s > 0 else None,
-                # 55 flop per pair inside the LJ cutoff (4.876 M of the ~7.7 M listed pairs of a PE-10k replica-step) over the FP64 vector peak
-                "useful_flop_frac": (55.0 * 4.876e6 / 7.725e6 * pairs_per_sim_step * w_sims / w_avg / 78.6e12) if w_avg > 0 else None,
-                "traffic": None, "traffic_source": None, "pmc_stale": pmc_stale,
-                "timed_avg_launch_ms": 1e3 * pair_s / launches, "timed_launches": prof["pair_launches"], "timed_sims_per_launch": prof["pair_sims"] / launches,
-                "avg_launch_ms": 1e3 * pair_s / launches, "launches": prof["pair_launches"], "sims_per_launch": prof["pair_sims"] / launches,   # (names of schema 1: the timed region)
-                "timed_launches_in_flight": in_flight,
-                "frac_hbm_timed_union": stored / union_s / 1e9 / 8000.0 if union_s > 0 else None,
-                "frac_hbm_timed_per_launch": stored / pair_s / 1e9 / 8000.0 if pair_s > 0 else None,
-                "rank0_pair_share_of_wall": union_s / elapsed,
-                "kernel": "k_pair (lj/cut/coul/long force+virial; every pair once, 4-atom cluster rows, LDS reaction-force tiles)",
-                "accounting": "achieved = SURVEY 8(d) algorithmic bytes of a launch -- sum over its replicas of N (4 nbar_stored + 56) + 48, nbar_stored = listed pairs "
-                              "per atom with each pair stored once, counted by the exact list build of every run -- / whole_avg_launch_ms; peak 8 TB/s; frac = "
-                              "achieved / peak (= frac_hbm).  The kernel is NOT bound by HBM but by vector-instruction issue (DESIGN.md 4, 5.3): frac_valu_issue = "
-                              "SQ_INSTS_VALU of a launch (profiles/pair_pmc.json, per replica-step x replicas per launch; null when that file was taken on other "
-                              "sources of the kernel) / whole_avg_launch_ms / (1 024 SIMDs x 2.4 GHz / 4 cycles per wave instruction).  whole_* = two updates after "
-                              "the timed region with the batch as ONE sequence of launches (scema_md_batch_split(0)): HIP-event time per launch with the chip to "
-                              "itself -- what a rocprofv3 kernel table of a SCEMA_MD_SPLIT=0 run shows.  timed_* = the timed region, where the batch runs as two "
-                              "half batches on two streams: launches overlap, so a per-launch event interval is not a chip-exclusive time; frac_hbm_timed_union = "
-                              "bytes / time with at least one pair launch running"}
-        if pmc:
-            roof["traffic"] = pmc["hbm_bytes_per_sim_step_corrected"] * w_sims
-            roof["traffic_source"] = pmc.get("source", "profiles/pair_pmc.json")
-            roof["valu_insts_per_launch"] = insts_per_sim_step * w_sims
         workload = (f"{n} x PE-{natoms} OPLS replicas per update(), {nts_mean:.0f}+{args.nss} MD steps each "
                     "(dt 2 fs, 300 K, lj/cut/coul/long 12/9 + " + ("PPPM" if args.kspace == "pppm" else "Ewald") + " 1e-4 + SHAKE + NVT), persistent per-QP state, "
                     f"replica equilibrated for {args.equil_steps} steps before the timed region")
         if reax:
-            # k_rx_qeq_sweep, the HBM-bound kernel of this path: per launch it reads, for every replica that still
-            # iterates, each stored matrix entry once (8 B value + a 2-byte column index; 4 bytes for replicas beyond 65 536 atoms; only the
-            # entries inside the taper radius are stored) and per row 84 B (row length 4, own preconditioned residual
-            # pair 16, search direction and product pairs read + written 64); the gathered pairs of the columns are cache traffic by design
-            # and not counted.  Entries and rows are counted on the device per sweep taken part in.
-            def sweep_of(pf):
-                t = pf["rx_sweep_ms"] * 1e-3
-                by = (8.0 + pf["rx_sweep_col_bytes"]) * pf["rx_sweep_entries"] + 84.0 * pf["rx_sweep_rows"]
-                return t, by, max(pf["rx_sweep_launches"], 1)
-            sw_s, sw_bytes, sw_n = sweep_of(prof)
-            sw_union = prof.get("rx_sweep_union_ms", 0.0) * 1e-3 or sw_s
-            a_s, a_bytes, a_n = sweep_of(prof_alone)
-            pmc = None
-            ppath = os.path.join(ROOT, "profiles", "reax_pmc.json")
-            if os.path.exists(ppath):
-                pmc = json.load(open(ppath))
-            # schema 2 (round 5): `achieved` / `frac` = the kernel with the chip to itself (two updates after the timed region with the batch as ONE
-            # sequence of launches on one stream: what a rocprofv3 table of such a run shows); the timed region's figures beside them
-            roof = {"schema": 2, "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
-                    "achieved": a_bytes / a_s / 1e9 if a_s > 0 else None, "frac": a_bytes / a_s / 1e9 / 8000.0 if a_s > 0 else None,
-                    "whole_avg_launch_ms": 1e3 * a_s / a_n, "whole_launches": prof_alone["rx_sweep_launches"], "whole_alg_bytes_per_launch": a_bytes / a_n,
-                    # (counters taken with 72 replicas per launch: per replica x the replicas of a whole-batch launch here, as the OPLS block scales its own)
-                    "traffic": (pmc["hbm_bytes_per_sweep_corrected"] * per_rank / 72.0) if pmc and "hbm_bytes_per_sweep_corrected" in pmc else None,
-                    "traffic_source": ((pmc or {}).get("command", "") + "; 72 replicas per launch, scaled by replicas per launch") if pmc else None,
-                    # (the symmetric sweep is not a pure stream any more: its vector-instruction count beside its bytes, same counters, same scaling)
-                    "frac_valu_issue": (pmc["SQ_INSTS_VALU"] * per_rank / 72.0 / (a_s / a_n) / 614.4e9) if pmc and "SQ_INSTS_VALU" in pmc and a_s > 0 else None,
-                    "timed_avg_launch_ms": 1e3 * sw_s / sw_n, "timed_launches": prof["rx_sweep_launches"], "timed_launches_in_flight": sw_s / sw_union if sw_union > 0 else 1.0,
-                    "frac_timed_union": sw_bytes / sw_union / 1e9 / 8000.0 if sw_union > 0 else None,
-                    "frac_timed_per_launch": sw_bytes / sw_s / 1e9 / 8000.0 if sw_s > 0 else None,
-                    "avg_launch_ms": 1e3 * sw_s / sw_n, "launches": prof["rx_sweep_launches"],   # (names of schema 1: the timed region)
-                    "alone": {"frac": a_bytes / a_s / 1e9 / 8000.0 if a_s > 0 else None},       # (schema 1 kept this nested; = frac now)
-                    "kernel": ("k_rx_qeq_sweep_sym (charge equilibration: y = H z for both conjugate-gradient systems; each pair of the symmetric matrix stored ONCE, "
-                               "both of its products in one pass -- the transposed one through LDS atomics: half the bytes of the full rows, and no longer "
-                               "a pure stream)") if prof.get("rx_sweep_symmetric") else
-                              "k_rx_qeq_sweep (charge equilibration: y = H z for both conjugate-gradient systems, one pass over the stored matrix rows)",
-                    "symmetric": bool(prof.get("rx_sweep_symmetric")),
-                    # the stored entry: the upper 48 bits of the FP64 value (rounded to nearest, <= 2^-37 relative = 7e-12, five orders under the
-                    # solver's 1e-6) + a 16-bit column in one 64-bit word -- narrower storage than the reference's FP64 matrix, said here
-                    "matrix_entry_bits": 48 if int(prof["rx_sweep_col_bytes"]) == 0 else 64,
-                    "frac_clock": "HIP events around every sweep launch on its stream (includes the launch-to-launch gap the event pair sees: 13-30 % above "
-                                  "a rocprofv3 kernel duration at these 40-50 us launches; the conservative reading)",
-                    "accounting": f"bytes = ({8 + int(prof['rx_sweep_col_bytes'])} B x stored matrix entries + 84 B x rows, summed over the replicas and sweeps that took part, counted on the "
-                                  "device) / HIP-event time of the kernel's launches (launches that find every replica converged cost time and move nothing); traffic = counter "
-                                  "bytes of ONE sweep over the whole batch (profiles/reax_pmc.json).  whole_* / frac: the batch as one sequence of launches on one stream "
-                                  "(scema_md_reax_concurrency(0, 0)), the chip to itself.  timed_*: the timed region, where the batch runs as two half batches on two "
-                                  "streams, each with its bond-order chain on a side stream -- a launch covers HALF the replicas, launches overlap, and "
-                                  "frac_timed_union = bytes / time with at least one sweep running, next to the other kernels of both halves",
-                    "alg_bytes_per_full_sweep": sw_bytes / max(prof["rx_sweep_rows"] / natoms, 1.0) * per_rank,   # one sweep over every replica of this rank
-                    "stored_entries_per_row": prof["rx_sweep_entries"] / max(prof["rx_sweep_rows"], 1.0),
-                    "rank0_sweep_share_of_wall": sw_s / elapsed,
-                    "qeq_iterations_per_solve": rstat["qeq_iters"] / max(rstat["qeq_solves"], 1)}
             workload = (f"{n} x PE-{natoms} ReaxFF replicas per update() (md_force_field reax: ffield.reax.2 with H C N O, fix qeq/reax to 1e-6 every step), "
                         f"{nts_mean:.0f}+{args.nss} MD steps each (dt {DT} fs, 300 K, NVT, fix deform), persistent per-QP state, replica equilibrated for "
                         f"{args.equil_steps} steps before the timed region")
+        roof = None
+        if args.full:
+            # PMC figures cannot be collected inside a timed run: tools/pmc_pair.sh measures them per replica-step on the same
+            # kernel (separate rocprofv3 --pmc passes; gfx950 x2 correction on FETCH_SIZE) and commits profiles/pair_pmc.json
+            pmc, pmc_stale = None, None
+            ppath = os.path.join(ROOT, "profiles", "pair_pmc.json")
+            if os.path.exists(ppath) and natoms == 10368:
+                pmc = json.load(open(ppath))
+                # the counters belong to ONE build of the kernel: the file records the git blob hashes of its sources, and a tree whose
+                # sources differ gets no instruction-issue figure (null + this note) instead of an old count under a new time
+                have = kernel_source_hashes()
+                if pmc.get("kernel_sources") != have:
+                    pmc_stale = {"recorded": pmc.get("kernel_sources"), "tree": have}
+                    print("bench.py: profiles/pair_pmc.json was taken on other sources of k_pair (re-run tools/pmc_pair.sh): frac_valu_issue and traffic are null",
+                          file=sys.stderr)
+                    pmc = None
+            # ---- the roofline record of k_pair (schema 2, round 5; every figure reproduces from a table under profiles/) ----
+            # The kernel is bound by vector-instruction ISSUE, not by HBM: `bound`, `achieved`, `peak`, `frac` describe THAT
+            # bound, measured with the batch whole (the chip to itself); the byte-based figures of SURVEY 8(d) stand beside them as frac_hbm*.
+            #   bytes: N*(4*nbar + 56) + 48 per replica and launch; `stored` = every pair once = half the full per-atom list inside
+            #   cutoff + the reference's skin (counted by the exact list build of each run)
+            def bytes_of(pf):
+                full = pf["pair_alg_bytes"]
+                fixed = pf["pair_sims"] * (56.0 * natoms + 48.0)
+                return 0.5 * (full - fixed) + fixed, full
+            stored, full = bytes_of(prof)
+            pair_s = prof["pair_ms"] * 1e-3
+            launches = max(prof["pair_launches"], 1)
+            union_s = prof.get("pair_union_ms", 0.0) * 1e-3 or pair_s     # time with at least one timed launch running (= the sum when nothing overlaps)
+            in_flight = pair_s / union_s if union_s > 0 else 1.0
+            w_stored, w_full = bytes_of(prof_alone)
+            w_s = prof_alone["pair_ms"] * 1e-3
+            w_launches = max(prof_alone["pair_launches"], 1)
+            w_avg = w_s / w_launches
+            w_sims = prof_alone["pair_sims"] / w_launches
+            nsimd, clk, cyc = 256 * 4, 2.4e9, 4.0
+            peak_issue = nsimd * clk / cyc / 1e9                         # G wave-instructions/s the chip can issue at 4 cycles each
+            insts_per_sim_step = pmc["valu_insts_per_sim_step"] if pmc else None
+            pairs_per_sim_step = 0.5 * (w_full - prof_alone["pair_sims"] * (56.0 * natoms + 48.0)) / 4.0 / max(prof_alone["pair_sims"], 1)   # listed pairs (inside cutoff + skin)
+            frac_issue = (insts_per_sim_step * w_sims / w_avg / 1e9 / peak_issue) if insts_per_sim_step and w_avg > 0 else None
+            # schema 3 (round 6): the top-level achieved / peak / frac are the SURVEY 8(d) byte figures against 8 TB/s -- the yardstick
+            # north_star names --; the bound that actually binds the kernel (vector-instruction issue) stands beside them as frac_valu_issue
+            roof = {"schema": 3, "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
+                    "achieved": w_stored / w_s / 1e9 if w_s > 0 else None,
+                    "frac": w_stored / w_s / 1e9 / 8000.0 if w_s > 0 else None,
+                    "frac_of": "hbm: SURVEY 8(d) bytes of the list the kernel stores (each pair once) / chip-exclusive launch time / 8 TB/s",
+                    "binding_bound": "fp64_valu_issue",
+                    "frac_valu_issue": frac_issue,
+                    "valu_issue_achieved_ginstr_s": (insts_per_sim_step * w_sims / w_avg / 1e9) if insts_per_sim_step and w_avg > 0 else None,
+                    "valu_issue_peak_ginstr_s": peak_issue,
+                    "frac_hbm": w_stored / w_s / 1e9 / 8000.0 if w_s > 0 else None,
+                    "frac_hbm_full_list": w_full / w_s / 1e9 / 8000.0 if w_s > 0 else None,
+                    "whole_avg_launch_ms": 1e3 * w_avg, "whole_launches": prof_alone["pair_launches"], "whole_sims_per_launch": w_sims,
+                    "whole_alg_bytes_per_launch": w_stored / w_launches, "whole_hbm_gbps": w_stored / w_s / 1e9 if w_s > 0 else None,
+                    # 55 flop per pair inside the LJ cutoff (4.876 M of the ~7.7 M listed pairs of a PE-10k replica-step) over the FP64 vector peak
+                    "useful_flop_frac": (55.0 * 4.876e6 / 7.725e6 * pairs_per_sim_step * w_sims / w_avg / 78.6e12) if w_avg > 0 else None,
+                    "traffic": None, "traffic_source": None, "pmc_stale": pmc_stale,
+                    "timed_avg_launch_ms": 1e3 * pair_s / launches, "timed_launches": prof["pair_launches"], "timed_sims_per_launch": prof["pair_sims"] / launches,
+                    "avg_launch_ms": 1e3 * pair_s / launches, "launches": prof["pair_launches"], "sims_per_launch": prof["pair_sims"] / launches,   # (names of schema 1: the timed region)
+                    "timed_launches_in_flight": in_flight,
+                    "frac_hbm_timed_union": stored / union_s / 1e9 / 8000.0 if union_s > 0 else None,
+                    "frac_hbm_timed_per_launch": stored / pair_s / 1e9 / 8000.0 if pair_s > 0 else None,
+                    "rank0_pair_share_of_wall": union_s / elapsed,
+                    "kernel": "k_pair (lj/cut/coul/long force+virial; every pair once, 4-atom cluster rows, LDS reaction-force tiles)",
+                    "accounting": "achieved = SURVEY 8(d) algorithmic bytes of a launch -- sum over its replicas of N (4 nbar_stored + 56) + 48, nbar_stored = listed pairs "
+                                  "per atom with each pair stored once, counted by the exact list build of every run -- / whole_avg_launch_ms; peak 8 TB/s; frac = "
+                                  "achieved / peak (= frac_hbm).  The kernel is NOT bound by HBM but by vector-instruction issue (DESIGN.md 4, 5.3): frac_valu_issue = "
+                                  "SQ_INSTS_VALU of a launch (profiles/pair_pmc.json, per replica-step x replicas per launch; null when that file was taken on other "
+                                  "sources of the kernel) / whole_avg_launch_ms / (1 024 SIMDs x 2.4 GHz / 4 cycles per wave instruction).  whole_* = two updates after "
+                                  "the timed region with the batch as ONE sequence of launches (scema_md_batch_split(0)): HIP-event time per launch with the chip to "
+                                  "itself -- what a rocprofv3 kernel table of a SCEMA_MD_SPLIT=0 run shows.  timed_* = the timed region, where the batch runs as two "
+                                  "half batches on two streams: launches overlap, so a per-launch event interval is not a chip-exclusive time; frac_hbm_timed_union = "
+                                  "bytes / time with at least one pair launch running"}
+            if pmc:
+                roof["traffic"] = pmc["hbm_bytes_per_sim_step_corrected"] * w_sims
+                roof["traffic_source"] = pmc.get("source", "profiles/pair_pmc.json")
+                roof["valu_insts_per_launch"] = insts_per_sim_step * w_sims
+            if reax:
+                # k_rx_qeq_sweep, the HBM-bound kernel of this path: per launch it reads, for every replica that still
+                # iterates, each stored matrix entry once (8 B value + a 2-byte column index; 4 bytes for replicas beyond 65 536 atoms; only the
+                # entries inside the taper radius are stored) and per row 84 B (row length 4, own preconditioned residual
+                # pair 16, search direction and product pairs read + written 64); the gathered pairs of the columns are cache traffic by design
+                # and not counted.  Entries and rows are counted on the device per sweep taken part in.
+                def sweep_of(pf):
+                    t = pf["rx_sweep_ms"] * 1e-3
+                    by = (8.0 + pf["rx_sweep_col_bytes"]) * pf["rx_sweep_entries"] + 84.0 * pf["rx_sweep_rows"]
+                    return t, by, max(pf["rx_sweep_launches"], 1)
+                sw_s, sw_bytes, sw_n = sweep_of(prof)
+                sw_union = prof.get("rx_sweep_union_ms", 0.0) * 1e-3 or sw_s
+                a_s, a_bytes, a_n = sweep_of(prof_alone)
+                pmc = None
+                ppath = os.path.join(ROOT, "profiles", "reax_pmc.json")
+                if os.path.exists(ppath):
+                    pmc = json.load(open(ppath))
+                # schema 2 (round 5): `achieved` / `frac` = the kernel with the chip to itself (two updates after the timed region with the batch as ONE
+                # sequence of launches on one stream: what a rocprofv3 table of such a run shows); the timed region's figures beside them
+                roof = {"schema": 2, "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
+                        "achieved": a_bytes / a_s / 1e9 if a_s > 0 else None, "frac": a_bytes / a_s / 1e9 / 8000.0 if a_s > 0 else None,
+                        "whole_avg_launch_ms": 1e3 * a_s / a_n, "whole_launches": prof_alone["rx_sweep_launches"], "whole_alg_bytes_per_launch": a_bytes / a_n,
+                        # (counters taken with 72 replicas per launch: per replica x the replicas of a whole-batch launch here, as the OPLS block scales its own)
+                        "traffic": (pmc["hbm_bytes_per_sweep_corrected"] * per_rank / 72.0) if pmc and "hbm_bytes_per_sweep_corrected" in pmc else None,
+                        "traffic_source": ((pmc or {}).get("command", "") + "; 72 replicas per launch, scaled by replicas per launch") if pmc else None,
+                        # (the symmetric sweep is not a pure stream any more: its vector-instruction count beside its bytes, same counters, same scaling)
+                        "frac_valu_issue": (pmc["SQ_INSTS_VALU"] * per_rank / 72.0 / (a_s / a_n) / 614.4e9) if pmc and "SQ_INSTS_VALU" in pmc and a_s > 0 else None,
+                        "timed_avg_launch_ms": 1e3 * sw_s / sw_n, "timed_launches": prof["rx_sweep_launches"], "timed_launches_in_flight": sw_s / sw_union if sw_union > 0 else 1.0,
+                        "frac_timed_union": sw_bytes / sw_union / 1e9 / 8000.0 if sw_union > 0 else None,
+                        "frac_timed_per_launch": sw_bytes / sw_s / 1e9 / 8000.0 if sw_s > 0 else None,
+                        "avg_launch_ms": 1e3 * sw_s / sw_n, "launches": prof["rx_sweep_launches"],   # (names of schema 1: the timed region)
+                        "alone": {"frac": a_bytes / a_s / 1e9 / 8000.0 if a_s > 0 else None},       # (schema 1 kept this nested; = frac now)
+                        "kernel": ("k_rx_qeq_sweep_sym (charge equilibration: y = H z for both conjugate-gradient systems; each pair of the symmetric matrix stored ONCE, "
+                                   "both of its products in one pass -- the transposed one through LDS atomics: half the bytes of the full rows, and no longer "
+                                   "a pure stream)") if prof.get("rx_sweep_symmetric") else
+                                  "k_rx_qeq_sweep (charge equilibration: y = H z for both conjugate-gradient systems, one pass over the stored matrix rows)",
+                        "symmetric": bool(prof.get("rx_sweep_symmetric")),
+                        # the stored entry: the upper 48 bits of the FP64 value (rounded to nearest, <= 2^-37 relative = 7e-12, five orders under the
+                        # solver's 1e-6) + a 16-bit column in one 64-bit word -- narrower storage than the reference's FP64 matrix, said here
+                        "matrix_entry_bits": 48 if int(prof["rx_sweep_col_bytes"]) == 0 else 64,
+                        "frac_clock": "HIP events around every sweep launch on its stream (includes the launch-to-launch gap the event pair sees: 13-30 % above "
+                                      "a rocprofv3 kernel duration at these 40-50 us launches; the conservative reading)",
+                        "accounting": f"bytes = ({8 + int(prof['rx_sweep_col_bytes'])} B x stored matrix entries + 84 B x rows, summed over the replicas and sweeps that took part, counted on the "
+                                      "device) / HIP-event time of the kernel's launches (launches that find every replica converged cost time and move nothing); traffic = counter "
+                                      "bytes of ONE sweep over the whole batch (profiles/reax_pmc.json).  whole_* / frac: the batch as one sequence of launches on one stream "
+                                      "(scema_md_reax_concurrency(0, 0)), the chip to itself.  timed_*: the timed region, where the batch runs as two half batches on two "
+                                      "streams, each with its bond-order chain on a side stream -- a launch covers HALF the replicas, launches overlap, and "
+                                      "frac_timed_union = bytes / time with at least one sweep running, next to the other kernels of both halves",
+                        "alg_bytes_per_full_sweep": sw_bytes / max(prof["rx_sweep_rows"] / natoms, 1.0) * per_rank,   # one sweep over every replica of this rank
+                        "stored_entries_per_row": prof["rx_sweep_entries"] / max(prof["rx_sweep_rows"], 1.0),
+                        "rank0_sweep_share_of_wall": sw_s / elapsed,
+                        "qeq_iterations_per_solve": rstat["qeq_iters"] / max(rstat["qeq_solves"], 1)}
         out = {
             "metric": "stress_evals_per_sec", "value": value, "unit": "evals/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / max(args.steps, 1),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "replica_steps_per_s": value * (nts_mean + args.nss),
-            "box_fp64_tflops": box_tflops,
-            "share8_evals_per_s": share8["evals_per_s"] if share8 else None,
-            "projected_8gpu_x": (8.0 * share8["evals_per_s"] / value) if share8 and value > 0 else None,
             "rccl_fallback": bool(collective and "RCCL attach failed" in collective),
             "config": {"workload": workload, "force_field": args.force_field,
                        "strain_set": args.strain_set + (" (monotonic)" if args.monotonic else " (load/unload: odd updates take the draw with the opposite sign)"),
-                       "strain_set_monotonic_evals_per_s": mono_rate, "strain_set_monotonic_updates": args.monotonic_updates if mono_rate else 0,
                        "n_sims": n, "atoms_per_replica": natoms, "md_steps_per_eval": nts_mean + args.nss,
                        "sharding": "engine planner (host/sim_plan.h): fresh batch i % N, then sticky to the GPU that holds the state, levelled by MD steps",
                        "sims_on_rank0": int((owner == 0).sum()), "collective": collective,
                        "allgathers": comm["allgathers"], "handshakes": comm["handshakes"], "state_migrations": comm["migrations"],
                        "stress_zz_checksum_Pa": checksum_timed,
-                       "share_of_8": (dict(share8, note="quadrature points i % 8 == 0 of the same requests (rank 0's share on 8 GPUs, stmd_sync.h:583), continued from the "
-                                                        "states of the timed loop on this one GPU; outside `value`") if share8 else None),
                        "list_skin_A": prof.get("list_skin_mean", 0.0),
                        "steps_per_list_rebuild": prof["md_steps"] / max(prof["neigh_builds"], 1)},
-            "roofline": roof,
         }
+        if args.full:   # the measurements a plain run leaves out, each outside `value`
+            out.update({"box_fp64_tflops": box_tflops,
+                        "share8_evals_per_s": share8["evals_per_s"] if share8 else None,
+                        "projected_8gpu_x": (8.0 * share8["evals_per_s"] / value) if share8 and value > 0 else None,
+                        "roofline": roof})
+            out["config"].update({
+                "strain_set_monotonic_evals_per_s": mono_rate, "strain_set_monotonic_updates": args.monotonic_updates if mono_rate else 0,
+                "share_of_8": (dict(share8, note="quadrature points i % 8 == 0 of the same requests (rank 0's share on 8 GPUs, stmd_sync.h:583), continued from the "
+                                                 "states of the timed loop on this one GPU; outside `value`") if share8 else None)})
         if cpu is not None:
             out["cpu_baseline"] = dict(cpu, cores_rule=cpu.get("cores_rule") or CORES_RULE["rule"])
         if world > 1:
@@ -754,7 +784,7 @@ def run_leg(args, rank, world, device, cpu, torch, dist):
     if world > 1:
         dist.barrier()
     eng.close()
-    return out
+    return out, outputs
 
 
 def main():
@@ -774,12 +804,12 @@ def main():
     ap.add_argument("--monotonic", action="store_true", help="apply the tensile strain draws update after update (no unloading on odd updates)")
     ap.add_argument("--kspace", default="pppm", choices=["pppm", "ewald"], help="reciprocal part: PPPM (order 5, ik, hipFFT) as the reference's "
                     "`kspace_style pppm 0.0001` asks for (default, the reported configuration) or the plain Ewald sum at the same accuracy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--force-field", default="opls", choices=["opls", "reax"],
                     help="opls: the headline workload (576 x PE-10k); reax: BASELINE config 5, 72 x PE-1620 ReaxFF replicas (--sims / --cells / --nss default to that)")
-    ap.add_argument("--monotonic-updates", type=int, default=4, help="after the timed loop, this many all-tensile updates (the SURVEY 8(d) set as written) are "
+    ap.add_argument("--monotonic-updates", type=int, default=4, help="with --full, after the timed loop, this many all-tensile updates (the SURVEY 8(d) set as written) are "
                     "timed as well and reported as config.strain_set_monotonic_evals_per_s (0: skip; never part of `value`)")
-    ap.add_argument("--share8-updates", type=int, default=3, help="after the timed loop (one GPU, batches of 64 and more): this many updates of the share rank 0 of 8 "
+    ap.add_argument("--share8-updates", type=int, default=3, help="with --full, after the timed loop (one GPU, batches of 64 and more): this many updates of the share rank 0 of 8 "
                     "would run (requests i %% 8 == 0) -> share8_evals_per_s, projected_8gpu_x (0: skip; never part of `value`)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI inside the engine (default); gloo = the engine's host transport over gloo (tests)")
@@ -789,11 +819,18 @@ def main():
                     help="seconds the RCCL attach + its one-update probe may take before every rank moves to the host transport")
     ap.add_argument("--share-gpus", action="store_true", help="tests: let several ranks share a GPU (needs --dist-backend gloo)")
     ap.add_argument("--reax-leg", default="auto", choices=["auto", "on", "off"],
-                    help="after the OPLS loop, outside `value`: a short ReaxFF replica-set leg (BASELINE config 5: 72 x PE-1620, 2 warm-up + 4 timed updates) "
-                         "reported as config.reax in the same JSON line.  auto: for the default workload (576 x PE-10k) on one GPU")
+                    help="with --full, after the OPLS loop, outside `value`: a short ReaxFF replica-set leg (BASELINE config 5: 72 x PE-1620, 2 warm-up + 4 timed "
+                         "updates) reported as config.reax in the same JSON line.  auto: for the default workload (576 x PE-10k) on one GPU")
     ap.add_argument("--ffield", default=os.path.join(ROOT, "examples", "ffield.reax.2"),
                     help="ReaxFF parameter file (the reference's lammps_scripts_reax/ffield.reax.2; the tree keeps a copy as data under examples/)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each outside `value`: the CPU baseline, the roofline block (two more updates "
+                         "with the batch whole), the monotonic strain set, the 8-GPU share, the box's FP64 calibration and the ReaxFF leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed updates, write what the last one returned as DIR/<name>.npy (stress.npy: float64, one row of six per quadrature point)")
     args = ap.parse_args()
+    if args.reax_leg == "on" and not args.full:
+        ap.error("--reax-leg on needs --full")
     if args.force_field == "reax":   # the replica set of BASELINE config 5, unless the command line says otherwise
         given = " ".join(sys.argv[1:])
         if "--sims" not in given: args.sims = 72
@@ -825,15 +862,15 @@ def main():
         dist.destroy_process_group()
         return
 
-    d, lens, DT, rate = _workload(args)
     from scema_amd.systems import synthetic_strains
     reax = args.force_field == "reax"
-    want_reax_leg = (not reax) and world == 1 and (args.reax_leg == "on" or (args.reax_leg == "auto" and args.sims == 576 and list(args.cells) == [6, 9, 16]))
+    want_reax_leg = args.full and (not reax) and world == 1 and (args.reax_leg == "on" or (args.reax_leg == "auto" and args.sims == 576 and list(args.cells) == [6, 9, 16]))
     rargs = _reax_leg_args(args) if want_reax_leg else None
 
-    # CPU baselines first: their worker processes start while nothing in this process has touched the GPU
+    # --full: CPU baselines first: their worker processes start while nothing in this process has touched the GPU
     cpu = cpu_rx = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        d, lens, DT, rate = _workload(args)
         ncpu = _host_cores(0.4)
         if reax:
             cpu = cpu_baseline_reax(tuple(args.cells), synthetic_strains(max(ncpu, 8), lens, seed=2026), args.nss, DT, rate)
@@ -858,10 +895,12 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")   # control plane only (id exchange, barrier, max of the timings); the data path is RCCL
 
-    out = run_leg(args, rank, world, device, cpu, torch, dist)
+    out, outputs = run_leg(args, rank, world, device, cpu, torch, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     if rargs is not None:
         try:
-            r = run_leg(rargs, rank, world, device, cpu_rx, torch, dist)
+            r, _ = run_leg(rargs, rank, world, device, cpu_rx, torch, dist)
         except Exception as exc:   # the headline line must not depend on the second leg
             r = None
             if rank == 0:

@@ -93,3 +93,21 @@ def test_pair_pmc_counters_belong_to_the_kernel_sources_of_this_tree():
     pmc = json.load(open(os.path.join(ROOT, "profiles", "pair_pmc.json")))
     assert pmc["kernel_sources"] == have, "profiles/pair_pmc.json was counted on other sources of k_pair: run tools/pmc_pair.sh on the GPU box and commit its pair_pmc_<tag>.json"
     assert pmc["valu_insts_per_sim_step"] > 1e6 and pmc["hbm_bytes_per_sim_step_corrected"] > 1e6
+
+
+def test_dump_outputs_writes_float64_arrays_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, float64; an array beyond the size limit keeps the same seeded rows every time"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    s = np.arange(36, dtype=np.float64).reshape(6, 6)
+    bench.dump_outputs(str(tmp_path / "a"), {"stress": s})
+    got = np.load(tmp_path / "a" / "stress.npy")
+    assert got.dtype == np.float64 and (got == s).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 48)
+    big = np.arange(600, dtype=np.float64).reshape(100, 6)
+    bench.dump_outputs(str(tmp_path / "b"), {"stress": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"stress": big})
+    b, c = np.load(tmp_path / "b" / "stress.npy"), np.load(tmp_path / "c" / "stress.npy")
+    assert b.shape == (4, 6) and (b == c).all() and (np.diff(b[:, 0]) > 0).all()
+    assert all(any((r == q).all() for q in big) for r in b)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def _run(cmd, ok=True):
 
 def test_two_rank_bench_spawns_its_ranks_and_matches_single_rank():
     one = _run([sys.executable, "bench.py", "--gpus", "1"] + COMMON)
-    two = _run([sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--share-gpus"] + COMMON)
+    two = _run([sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--share-gpus", "--full"] + COMMON)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
     c1, c2 = one["config"]["stress_zz_checksum_Pa"], two["config"]["stress_zz_checksum_Pa"]
     assert abs(c1 - c2) <= 1e-8 * abs(c1), (c1, c2)      # FP64 atomics: summation order differs from run to run
@@ -123,7 +124,7 @@ def test_imbalanced_batch_on_four_ranks():
 def test_reax_replica_set_bench_line():
     """bench.py --force-field reax (BASELINE config 5) at a reduced batch: the same JSON contract, roofline block of the matrix sweep"""
     out = _run([sys.executable, "bench.py", "--force-field", "reax", "--sims", "6", "--steps", "1", "--warmup", "1", "--equil-steps", "20",
-                "--no-cpu-baseline", "--monotonic-updates", "0"])
+                "--no-cpu-baseline", "--monotonic-updates", "0", "--full"])
     assert out["metric"] == "stress_evals_per_sec" and out["value"] > 0 and out["dtype"] == "f64"
     assert out["config"]["force_field"] == "reax" and out["config"]["atoms_per_replica"] == 1620 and "ReaxFF" in out["config"]["workload"]
     r = out["roofline"]
@@ -145,7 +146,7 @@ def test_reax_replica_set_on_two_ranks_matches_one_rank():
 def test_default_run_carries_the_reax_leg_and_reports_environment_switches():
     """the default line's second leg (BASELINE config 5 as config.reax, outside `value`), forced on for a small OPLS batch; and a run
     with a declared switch set says so in config.env_overrides (a clean run: an empty list)"""
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--reax-leg", "on"] + COMMON, capture_output=True, text=True, timeout=900, cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--full", "--reax-leg", "on"] + COMMON, capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1", SCEMA_MD_SPLIT="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -171,3 +172,21 @@ def test_one_pass_step_tail_equals_the_three_kernels():
     for env in ({"SCEMA_MD_FUSED_TAIL": "0"}, {"SCEMA_MD_CELL_BUILD": "0"}):
         b = run(env)
         assert abs(a - b) <= 1e-8 * abs(a), (env, a, b)
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_last_timed_update(tmp_path):
+    """a run without --full times its steps and prints the headline, none of the extra measurements; --dump-outputs writes the stresses
+    of the last timed update (float64, one row per quadrature point), the very numbers the line's checksum sums; --steps sets the timed updates"""
+    args = ["--sims", "6", "--steps", "3", "--warmup", "1", "--nss", "10", "--cells", "4", "6", "12", "--equil-steps", "40"]
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / "o")] + args)
+    assert out["steps"] == 3 and out["value"] > 0 and abs(out["value"] - 6 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    for k in ("roofline", "cpu_baseline", "box_fp64_tflops", "share8_evals_per_s"):
+        assert k not in out, k
+    assert "reax" not in out["config"] and "strain_set_monotonic_evals_per_s" not in out["config"]
+    s = np.load(tmp_path / "o" / "stress.npy")
+    assert s.dtype == np.float64 and s.shape == (6, 6) and np.isfinite(s).all()
+    c = out["config"]["stress_zz_checksum_Pa"]
+    assert abs(s[:, 2].sum() - c) <= 1e-12 * abs(c), (s[:, 2].sum(), c)
+    # (what the plain line leaves out, --full still reports)
+    full = _run([sys.executable, "bench.py", "--gpus", "1", "--full", "--no-cpu-baseline"] + args)
+    assert full["roofline"]["launches"] > 0 and "box_fp64_tflops" in full

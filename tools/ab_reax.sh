@@ -1,12 +1,14 @@
 #!/bin/bash
 # same-box A/B of two builds of the library on the ReaxFF replica set (usage: tools/ab_reax.sh <tag> [steps]); B = scema_amd/libscema_md_b.so
+TOOLS_OUT=${TOOLS_OUT:-tools_out}   # where the runs' logs and profiles go
+mkdir -p $TOOLS_OUT
 T=${1:-abr}; N=${2:-6}
 for V in "a:" "b:SCEMA_MD_LIB=libscema_md_b.so" "a2:" "b2:SCEMA_MD_LIB=libscema_md_b.so"; do
   name=${V%%:*}; envs=${V#*:}
-  env $envs python bench.py --force-field reax --steps $N --warmup 2 --no-cpu-baseline > gpurun_out/${T}_reax_$name.json.log 2> gpurun_out/${T}_reax_$name.err || exit 1
+  env $envs python bench.py --full --force-field reax --steps $N --warmup 2 --no-cpu-baseline > $TOOLS_OUT/${T}_reax_$name.json.log 2> $TOOLS_OUT/${T}_reax_$name.err || exit 1
   python - <<PY
 import json
-d=json.loads(open('gpurun_out/${T}_reax_$name.json.log').read().strip().split('\n')[-1]); r=d['roofline']
+d=json.loads(open('$TOOLS_OUT/${T}_reax_$name.json.log').read().strip().split('\n')[-1]); r=d['roofline']
 print('$name', round(d['value'],1), 'evals/s; sweep avg ms', round(r['avg_launch_ms'],4), 'launches', r['launches'], 'frac', round(r['frac'],3), 'its/solve', round(r['qeq_iterations_per_solve'],2), d['config']['env_overrides'], flush=True)
 PY
 done

@@ -2,27 +2,28 @@
 # usage (on the GPU box, from the repo root): tools/pmc_pair.sh <tag> [kernel-regex] [sims]
 # Separate rocprofv3 --pmc passes (no tracing domains) on a short bench (equilibrated replica, one update of 10+10 steps);
 # prints per-dispatch means of the batch launches only (the single-replica launches of the equilibration run have a
-# smaller grid and are filtered out) and writes gpurun_out/pmc_<tag>.json.
+# smaller grid and are filtered out) and writes $TOOLS_OUT/pmc_<tag>.json.
+TOOLS_OUT=${TOOLS_OUT:-tools_out}   # where the runs' logs and profiles go
 TAG=${1:-x}; RE=${2:-k_pair}; SIMS=${3:-72}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-CACHE=gpurun_out/equil_pe10k.npz
+mkdir -p $TOOLS_OUT
+CACHE=$TOOLS_OUT/equil_pe10k.npz
 # the equilibration (2 000 single-replica steps) runs once, outside the profiler
-[ -f $CACHE ] || python bench.py --sims 1 --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache $CACHE > /dev/null 2>&1
+[ -f $CACHE ] || python bench.py --full --sims 1 --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache $CACHE > /dev/null 2>&1
 export SCEMA_MD_SPLIT=0   # whole batch per launch: the counters are divided by the batch size
 for P in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_ANY" \
          "SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA" \
          "SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_WAVES_LT_64" \
          "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE"; do
   t=$(echo $P | cut -d" " -f1)
-  timeout 400 rocprofv3 --pmc $P --kernel-include-regex "$RE" --output-format csv -d gpurun_out/pmc_${TAG}_$t -- python bench.py --sims $SIMS --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache $CACHE > gpurun_out/pmc_${TAG}_$t.log 2>&1
+  timeout 400 rocprofv3 --pmc $P --kernel-include-regex "$RE" --output-format csv -d $TOOLS_OUT/pmc_${TAG}_$t -- python bench.py --full --sims $SIMS --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache $CACHE > $TOOLS_OUT/pmc_${TAG}_$t.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json, sys
 sys.path.insert(0, '.')
 from bench import kernel_source_hashes
 out = collections.defaultdict(dict)
-for d in sorted(glob.glob('gpurun_out/pmc_${TAG}_*/*/*_counter_collection.csv')):
+for d in sorted(glob.glob('$TOOLS_OUT/pmc_${TAG}_*/*/*_counter_collection.csv')):
     rows = list(csv.DictReader(open(d)))
     gmax = collections.defaultdict(int)
     for r in rows:
@@ -49,6 +50,6 @@ if kp and 'FETCH_SIZE' in out[kp] and 'WRITE_SIZE' in out[kp] and 'SQ_INSTS_VALU
                "GRBM_GUI_ACTIVE": o.get('GRBM_GUI_ACTIVE'),
                "correction": "gfx950: FETCH_SIZE x2 for coalesced streams (MI355X_MICROARCH.md, HBM); WRITE_SIZE as read",
                "source": "profiles/pair_pmc.json: tools/pmc_pair.sh, rocprofv3 --pmc passes (one counter group each, no tracing) on bench.py --sims $SIMS --steps 1 --warmup 0 --nss 10, equilibrated replica; batch launches only"},
-              open('gpurun_out/pair_pmc_${TAG}.json', 'w'), indent=1)
-json.dump({"sims_per_launch": $SIMS, "command": "rocprofv3 --pmc <group> --kernel-include-regex $RE -- python bench.py --sims $SIMS --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache <state after 2000 NVT+SHAKE steps>", "kernels": out}, open('gpurun_out/pmc_${TAG}.json', 'w'), indent=1)
+              open('$TOOLS_OUT/pair_pmc_${TAG}.json', 'w'), indent=1)
+json.dump({"sims_per_launch": $SIMS, "command": "rocprofv3 --pmc <group> --kernel-include-regex $RE -- python bench.py --full --sims $SIMS --steps 1 --warmup 0 --nss 10 --no-cpu-baseline --equil-cache <state after 2000 NVT+SHAKE steps>", "kernels": out}, open('$TOOLS_OUT/pmc_${TAG}.json', 'w'), indent=1)
 PY
