@@ -26,6 +26,7 @@
 #include <ctime>
 #include <array>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -299,9 +300,7 @@ struct scema_md_engine {
   hipStream_t stream2 = nullptr;          // side stream: structure factors next to the bonded kernel
   hipStream_t stream3 = nullptr;          // second half batch of a large launch group (run_phase)
   hipEvent_t ev_up = nullptr;
-  bool split_streams = true;              // SCEMA_MD_SPLIT=0 switches the two-half pipeline off
-  int split_min = 9, split_max = 1 << 30;  // launch groups from this size on are split (SCEMA_MD_SPLIT_MAX puts an upper end back: round 2 measured 336 evals/s either way
-                                         // at 576 and left large groups whole; with round 4's kernels the halves give 437 against 429, profiles/r04_zs_*)
+  bool split_streams = true;              // SCEMA_MD_SPLIT=0 switches the part batches off
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool rx_qeq_failed = false;             // the last ReaxFF run ended with a charge solve that did not converge (eval_chunk's one retry with the Jacobi preconditioner)
   long long rx_precond_fallbacks = 0;     // evaluations that were repeated that way
@@ -407,6 +406,29 @@ int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &s
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
+// the batch skeleton both force stages share (engine_run.cpp)
+struct Part { int off = 0, n = 0; hipStream_t st = nullptr; };   // a part batch: positions [off, off + n) of the launch order, issued on st
+std::vector<int> batch_order(const std::vector<ActiveSim> &sims, int nparts, const std::function<long(int)> &tie = nullptr);
+std::vector<Part> split_parts(int ns, int nparts);
+int part_of(const std::vector<Part> &parts, int pos);
+int active_prefix(const std::vector<SimDev> &h_sims, const Part &p, int step);
+int fork_parts(scema_md_engine *e, const std::vector<Part> &parts, hipEvent_t ev);
+int join_parts(scema_md_engine *e, const std::vector<Part> &parts, const hipEvent_t *done);
+struct BoxRange {
+  std::vector<HostBox> boxes;
+  double w[3] = {1e300, 1e300, 1e300};   // the narrowest perpendicular widths over the run
+  double vol_min = 1e300, vol_max = 0.0;
+};
+bool box_range(const RunSpec &spec, const ActiveSim &A, const double *box, BoxRange &out, std::vector<FlipEvent> &flips);
+void sim_common(SimDev &S, const scema_md_params &P, const RunSpec &spec, const ActiveSim &A, const Slot &sl, SimScalars *sc);
+int run_minimiser(scema_md_engine *e, const std::vector<int> &order, int maxatoms, const RunSpec &spec, bool stop_on_any_overflow,
+                  const std::function<int()> &force, const std::function<int(int)> &map_fault);
+using FlipSchedule = std::map<int, std::vector<std::pair<int, int>>>;
+FlipSchedule flip_schedule(const std::vector<std::vector<FlipEvent>> &flips, const std::vector<SimDev> &h_sims);
+int sum_timed_launches(scema_md_engine *e, size_t n, double &ms, long long &launches, double &union_ms);
+int collect_faults(scema_md_engine *e, int ns);
+void lists_hold(scema_md_engine *e, const std::vector<ActiveSim> &sims, bool valid, bool counts);
+bool keep_list_switch();
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);
@@ -426,5 +448,6 @@ int handshake(scema_md_engine *e, int local_status, double hash);
 int allgather_stresses(scema_md_engine *e, const std::vector<double> &local, scema_mdsim *sims, int n_sims);
 // engine_debug.cpp
 int debug_state(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, State **out, std::unique_ptr<State> &tmp);
+void print_run_timing(const scema_md_engine *e, int ns, double layout_ms, double kspace_ms, double box_ms, double grid_ms, double rest_ms);
 
 }  // namespace scema_eng

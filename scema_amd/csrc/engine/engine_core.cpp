@@ -45,13 +45,8 @@ namespace {
 struct EnvSwitch { const char *name, *what; };
 const EnvSwitch k_env[] = {
     // performance switches with a measured default; a reported run sets none of them
-    {"SCEMA_MD_SPLIT_MAX", "launch groups of this many replicas and more run whole instead of as two half batches (default: none)"},
     {"SCEMA_MD_SPLIT", "0: never run a launch group of 9 simulations and more as part batches on streams of their own"},
-    {"SCEMA_MD_PPPM_SIDE_MIN", "smallest batch whose PPPM chain runs on the side stream next to the pair kernel (default 1; 4 until round 5)"},
-    {"SCEMA_MD_SPLIT_MIN", "launch groups from this many replicas on run as part batches on streams of their own (default 9)"},
-    {"SCEMA_MD_PART_MIN", "SCEMA_MD_PARTS applies to launch groups of this many replicas per part and more (default 2; smaller groups run as two parts)"},
-    {"SCEMA_MD_PARTS", "2-4: this many part batches for every launch group that is split (default: by the size of the group, engine_run.cpp)"},
-    {"SCEMA_MD_CELLS_TARGET", "what-if: take the cell grid (= tiling of the pair kernel) whose number of cells is closest to this among the grids that fit"},
+    {"SCEMA_MD_PARTS", "2-4: this many part batches for every launch group that is split, if it has 2 replicas per part (default: by the size of the group, engine_run.cpp)"},
     {"SCEMA_MD_ONE_STREAM", "no side stream (bonded / k-space chain beside the pair kernel)"},
     {"SCEMA_MD_KEEP_LIST", "0: the sampling run of an evaluation rebuilds its neighbour rows at its start even where those of the straining run still hold"},
     {"SCEMA_MD_SKIN_EXTRA", "list skin = params.skin + this many Angstrom (results do not depend on it)"},
@@ -62,7 +57,6 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_PPPM_FFT", "hipFFT for every PPPM grid (default: grids of up to 2 900 points are solved in LDS)"},
     {"SCEMA_MD_FUSED_TAIL", "0 / 1: force assembly + SHAKE + second kick as three kernels / as k_finish (default: by batch size)"},
     {"SCEMA_MD_BONDED_SIDE", "0: the bonded kernel of a small batch always on the main stream behind the pair kernel (default: behind the PPPM chain on the side stream on steps without a new influence function)"},
-    {"SCEMA_MD_BONDED_SIDE_MIN", "smallest batch whose bonded kernel follows the PPPM chain on the side stream (default 8: below, that chain is the longer one)"},
     {"SCEMA_MD_SMALL_BATCH_MAX", "largest batch that takes the cell grid with the most cells instead of the largest cells (default: launch groups of up to 31 replicas that run whole, i.e. not as part batches)"},
     {"SCEMA_MD_REBUILD_TOGETHER", "0 / 1: every replica rebuilds its neighbour rows on its own trigger / the replicas of a launch rebuild together as soon as one asks for it (default: together in launches of fewer than 128 replicas)"},
     {"SCEMA_MD_CELL_BUILD", "0: cell binning as k_bin + k_cell_scan + k_cell_fill instead of the one-launch k_cell_build"},
@@ -148,8 +142,6 @@ int scema_md_create(const scema_md_params *p, scema_md_engine **out) {
     return SCEMA_MD_ERR_DEVICE;
   }
   if (const char *sp = scema_env("SCEMA_MD_SPLIT")) e->split_streams = atoi(sp) != 0;
-  if (const char *sp = scema_env("SCEMA_MD_SPLIT_MIN")) e->split_min = std::max(2, atoi(sp));
-  if (const char *sp = scema_env("SCEMA_MD_SPLIT_MAX")) e->split_max = std::max(0, atoi(sp));
   if (hipStreamCreateWithFlags(&e->stream3, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e->ev_up, hipEventDisableTiming) != hipSuccess)
     e->stream3 = nullptr;   // an optimisation only
   if (const char *sx = scema_env("SCEMA_MD_SKIN_EXTRA")) e->skin_extra_fixed = std::max(-0.75 * e->p.skin, atof(sx));

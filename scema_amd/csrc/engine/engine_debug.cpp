@@ -1,7 +1,52 @@
-// engine_debug.cpp -- parity / measurement entry points: static evaluations and plain runs on a stored state
+// engine_debug.cpp -- parity / measurement entry points: static evaluations and plain runs on a stored state; the timing printout of a run
 #include "engine.h"
+#include "../md_env.h"
 
 namespace scema_eng {
+
+// SCEMA_MD_TIMING: the lists of the first replica of the run that just ended, the host time of its layout, and the counters of a build
+// with PAIR_COUNT / PAIR_TIMING
+void print_run_timing(const scema_md_engine *e, int ns, double layout_ms, double kspace_ms, double box_ms, double grid_ms, double rest_ms) {
+  if (!scema_env("SCEMA_MD_TIMING") || ns <= 0) return;
+  const SimScalars &c = e->h_sc[0];
+  const SimDev &S0 = e->h_sims[0];
+  fprintf(stderr, "[scema_md] sim 0: cells %dx%dx%d, j table max %d of %d, row max %d of %d, row entries/cluster %.1f, listed pairs/atom %.1f, builds %d\n",
+          S0.nc[0], S0.nc[1], S0.nc[2], c.maxj_seen, S0.capj, c.maxneigh_seen, S0.maxneigh, (double)c.nrowent / (S0.npad / MD_CLUSTER),
+          (double)c.nentries / S0.natoms, c.nbuilds);
+  fprintf(stderr, "[scema_md] host: %.2f ms laying out %d simulations before the first launch of this run (k-space set-up on host threads %.2f, box range %.2f, cell grid %.2f, rest of the loop %.2f)\n",
+          layout_ms, ns, kspace_ms, box_ms, grid_ms, rest_ms);
+  fprintf(stderr, "[scema_md] sim 0: far skin band walked on %d of %d steps; list skin %.2f A\n", c.nfar_steps, c.step, S0.skin);
+#ifdef PAIR_COUNT
+  fprintf(stderr, "[scema_md] k_pair lanes (sim 0, this run): %llu wave-chunks (%llu with work); atom blocks run %llu = %.2f per working chunk, %.1f lanes of 64 in them; "
+          "LJ block run in %llu of them with %.1f lanes; coulomb block in %llu with %.1f lanes; pairs inside the LJ cutoff %llu, inside the coulomb cutoff %llu\n",
+          c.dbg[0], c.dbg[1], c.dbg[2], (double)c.dbg[2] / std::max(1ull, c.dbg[1]), (double)c.dbg[3] / std::max(1ull, c.dbg[2]), c.dbg[5],
+          (double)c.dbg[4] / std::max(1ull, c.dbg[5]), c.dbg[7], (double)c.dbg[6] / std::max(1ull, c.dbg[7]), c.dbg[4], c.dbg[6]);
+#endif
+#ifdef PAIR_TIMING
+  if (c.dbg2[7])
+    fprintf(stderr, "[scema_md] k_pppm_solve clocks (sim 0, thread 0, mean per launch): grid in %.0f, forward passes %.0f, spectra %.0f + %.0f, inverse passes %.0f + %.0f, out + sums %.0f\n",
+            (double)c.dbg2[0] / c.dbg2[7], (double)c.dbg2[1] / c.dbg2[7], (double)c.dbg2[2] / c.dbg2[7], (double)c.dbg2[4] / c.dbg2[7], (double)c.dbg2[3] / c.dbg2[7],
+            (double)c.dbg2[5] / c.dbg2[7], (double)c.dbg2[6] / c.dbg2[7]);
+  fprintf(stderr, "[scema_md] k_pair wave clocks (sim 0, mean per wave): prologue %.0f, rows %.0f, barrier wait %.0f, flush %.0f (%llu waves)\n",
+          (double)c.dbg[0] / c.dbg[4], (double)c.dbg[1] / c.dbg[4], (double)c.dbg[2] / c.dbg[4], (double)c.dbg[3] / c.dbg[4], c.dbg[4]);
+  {   // (the same clocks summed over the whole batch)
+    unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < ns; i++) for (int k = 0; k < 6; k++) a[k] += e->h_sc[i].dbg[k];
+    if (a[4]) fprintf(stderr, "[scema_md] pair kernel wave clocks (whole batch, mean per wave and tile visit): prologue %.0f, rows %.0f, wait %.0f, flush %.0f (of which staging %.0f) (%llu visits)\n",
+                      (double)a[0] / a[4], (double)a[1] / a[4], (double)a[2] / a[4], (double)a[3] / a[4], (double)a[5] / a[4], a[4]);
+  }
+  if (c.nbuilds > 0) {
+    const double nw = (double)c.nbuilds * S0.ncells * MD_TILE_WAVES;
+    fprintf(stderr, "[scema_md] k_neigh_build wave clocks (sim 0, mean per wave and build): table %.0f (boxes and runs %.0f, candidates %.0f), rows %.0f, schedule %.0f; %llu waves of %.0f; %.2f rows per wave of %.1f chunks\n",
+            (double)c.dbg[5] / nw, (double)c.dbg[8] / nw, (double)(c.dbg[5] - c.dbg[8]) / nw, (double)c.dbg[6] / nw, (double)c.dbg[7] / nw, c.dbg[9], nw,
+            (double)c.dbg[11] / nw, (double)c.dbg[10] / std::max(1ull, c.dbg[11]));
+    const double nr = (double)std::max(1ull, c.dbg[11]);
+    fprintf(stderr, "[scema_md] k_neigh_build per row (sim 0, cycles): set-up %.0f, chunk loop %.0f = %.0f per chunk, row end %.0f; of %.1f chunks %.2f walk exclusion lists, %.2f are own-cell chunks\n",
+            (double)c.dbg[12] / nr, (double)c.dbg[13] / nr, (double)c.dbg[13] / std::max(1ull, c.dbg[10]), (double)c.dbg[14] / nr, (double)c.dbg[10] / nr,
+            (double)c.dbg[15] / nr, (double)c.dbg[16] / nr);
+  }
+#endif
+}
 
 // ---- parity / measurement hooks ----
 // qp_id == SCEMA_MD_QP_NONE: a temporary copy of the registered init state (held by `tmp`)
