@@ -370,8 +370,9 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
     GLOBAL_AS int *row = as_global_w(S.neigh) + (size_t)cl * maxrow;
     // (a bounding-sphere test that skipped whole chunks out of the cluster's reach paid before the quarter lists existed; with them it
     // costs more than it saves: 1 607 against 1 549 us per step without it)
-    // the four atoms' exclusion lists (1-2, 1-3 partners) into LDS once: the candidates inside the exclusion gate
-    // then compare against broadcast LDS reads instead of walking the lists in global memory lane by lane
+    // the first 16 exclusion partners of each of the four atoms (whichever special_bonds levels carry a weight other than 1) into
+    // lanes once: the candidates inside the exclusion gate then compare against lane broadcasts instead of walking the lists in
+    // global memory lane by lane
     int exb[NI], exn[NI];
 #pragma unroll
     for (int a = 0; a < NI; a++) {

@@ -203,6 +203,93 @@ def build_ethane_oh(nx: int = 3, ny: int = 3, nz: int = 3, spacing: float = 5.2,
                 box=np.array([0, 0, 0, L[0], L[1], L[2], 0.3, -0.2, 0.25]), x=x, v=v)
 
 
+def build_network(nc: int = 4, drop: float = 0.0, seed: int = 3, jitter: float = 0.04, charge: float = 0.2,
+                  special_lj=(0.0, 0.0, 0.5), special_coul=(0.0, 0.0, 0.5), temperature: float = 300.0) -> dict:
+    """Periodic tetrahedral network: a diamond-cubic lattice of nc^3 cells of 8 sites, every site bonded to its four nearest
+    neighbours through the periodic box -- the branched counterpart of the PE chains (40 partners within three bonds per
+    atom, terms that span up to four bonded tiles, tiles whose halo is several times their owners).  Two atom types, one
+    per sublattice, charges +-`charge`.  Angles, OPLS dihedrals (two types by the sublattice of the second atom; every
+    third listed in reversed atom order; every seventh listed a second time with a third type) and one improper per fully
+    bonded site (two types) are derived from the surviving bond graph: `drop` removes that fraction of the bonds at random,
+    and all four bonds of one site, so that the partner counts run from 0 to 40.
+
+    Bond length 1.55 A (cell 3.58 A: the box holds 2 x 6 A from nc = 4 on).  sigma 1.50 / 1.45 A keeps every pair off the
+    repulsive wall -- the 1-4 pairs (from 2.97 A) and also the two ends of a dropped bond, which face each other at 1.55 A with
+    the full Lennard-Jones term (minimum at 1.66 A) -- so the system can be run, not only evaluated.  Angles are tetrahedral
+    and the impropers sit at 35 degrees, far from the clamps of both terms for any jitter of a few hundredths of an Angstrom."""
+    rb = 1.55
+    a = 4.0 * rb / np.sqrt(3.0)
+    fcc = np.array([[0, 0, 0], [0, 2, 2], [2, 0, 2], [2, 2, 0]])                  # in quarters of the cell
+    arms = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]])
+    m = 4 * nc
+    site = {}
+    pos = []
+    for ix in range(nc):
+        for iy in range(nc):
+            for iz in range(nc):
+                for f in fcc:
+                    for sub in (0, 1):
+                        p = 4 * np.array([ix, iy, iz]) + f + sub * arms[0]
+                        site[tuple(p % m)] = len(pos)
+                        pos.append(p)
+    pos = np.array(pos)
+    natoms = len(pos)
+    typ = (np.arange(natoms) % 2).astype(np.int32)
+    rng = np.random.default_rng(seed)
+    bonds = [(i, site[tuple((pos[i] + d) % m)]) for i in range(0, natoms, 2) for d in arms]
+    btype = [k % 2 for i in range(0, natoms, 2) for k in range(4)]
+    if drop > 0.0:
+        lone = int(rng.integers(natoms))
+        keep = [k and lone not in b for b, k in zip(bonds, rng.random(len(bonds)) >= drop)]
+        bonds = [b for b, k in zip(bonds, keep) if k]
+        btype = [t for t, k in zip(btype, keep) if k]
+    nbr = [[] for _ in range(natoms)]
+    for i, j in bonds:
+        nbr[i].append(j); nbr[j].append(i)
+    angles, atype, dihs, dtype, imps, itype = [], [], [], [], [], []
+    for j in range(natoms):
+        for p in range(len(nbr[j])):
+            for q in range(p + 1, len(nbr[j])):
+                angles.append((nbr[j][p], j, nbr[j][q])); atype.append(int(typ[j]))
+        if len(nbr[j]) == 4:
+            imps.append((j, nbr[j][0], nbr[j][1], nbr[j][2])); itype.append(int(typ[j]))
+    for j, k in bonds:
+        for i in nbr[j]:
+            for l in nbr[k]:
+                if i == k or l == j:
+                    continue
+                nd = len(dihs)
+                dihs.append((i, j, k, l) if nd % 3 else (l, k, j, i)); dtype.append(int(typ[dihs[-1][1]]))
+                if nd % 7 == 0:
+                    dihs.append((i, j, k, l)); dtype.append(2)
+    mass = np.array([12.011, 14.007])
+    eps1 = np.array([0.15, 0.20])
+    sig1 = np.array([1.50, 1.45])
+    x = pos * (a / 4.0) + rng.normal(0.0, jitter, (natoms, 3))
+    q = np.where(typ == 0, charge, -charge).astype(float)
+    mm = mass[typ]
+    v = rng.normal(0.0, 1.0, (natoms, 3)) * np.sqrt(BOLTZ * temperature / (mm * MVV2E))[:, None]
+    v -= (mm[:, None] * v).sum(0) / mm.sum()
+    tcur = (mm[:, None] * v * v).sum() * MVV2E / ((3 * natoms - 3) * BOLTZ)
+    if tcur > 0:
+        v *= np.sqrt(temperature / tcur)
+    i32 = lambda rows, w: np.array(rows, dtype=np.int32).reshape(-1, w)
+    return dict(
+        natoms=natoms, ntypes=2, type=typ, charge=q, mol=np.zeros(natoms, dtype=np.int32), mass=mass,
+        eps=np.sqrt(np.outer(eps1, eps1)), sigma=np.sqrt(np.outer(sig1, sig1)),
+        bonds=i32(bonds, 2), bond_type=np.array(btype, dtype=np.int32),
+        bond_coeff=np.array([[268.0, rb], [300.0, rb + 0.01]]),
+        angles=i32(angles, 3), angle_type=np.array(atype, dtype=np.int32),
+        angle_coeff=np.array([[58.35, np.deg2rad(109.5)], [50.0, np.deg2rad(112.0)]]),
+        dihedrals=i32(dihs, 4), dihedral_type=np.array(dtype, dtype=np.int32),
+        dihedral_coeff=np.array([[1.3, -0.05, 0.2, 0.1], [0.3, 0.2, 0.3, 0.0], [-0.4, 0.0, 0.15, -0.05]]),
+        impropers=i32(imps, 4), improper_type=np.array(itype, dtype=np.int32),
+        improper_coeff=np.array([[4.5, np.deg2rad(35.0)], [2.0, np.deg2rad(30.0)]]),
+        special_lj=np.array(special_lj, dtype=float), special_coul=np.array(special_coul, dtype=float),
+        box=np.array([0.0, 0.0, 0.0, nc * a, nc * a, nc * a, 0.0, 0.0, 0.0]), x=np.ascontiguousarray(x), v=np.ascontiguousarray(v),
+    )
+
+
 def build_pe10k(seed: int = 1234) -> dict:
     """The PE-10k benchmark replica of SURVEY.md 8(d): 10 368 atoms, 300 K with SHAKE-projected velocities."""
     return build_pe(6, 9, 16, 300.0, seed, shake_project=True)
