@@ -889,9 +889,12 @@ static void neigh_build(omd_sim *s) {
     int c[3];
     for (int d = 0; d < 3; d++) {
       double fl = floor(l[d]);
-      s->wrapn[3 * i + d] = (int)fl;
       l[d] -= fl;
-      if (l[d] >= 1.0) l[d] = 0.0; /* guard rounding */
+      if (l[d] >= 1.0) { /* l = -1e-17: the difference rounds to 1.  The image listed at lamda 0 is one box further than floor says */
+        l[d] = 0.0;
+        fl += 1.0;
+      }
+      s->wrapn[3 * i + d] = (int)fl;
       lam[3 * i + d] = l[d];
       c[d] = (int)(l[d] * nb[d]);
       if (c[d] >= nb[d]) c[d] = nb[d] - 1;

@@ -283,9 +283,9 @@ __global__ __launch_bounds__(TPB) void k_bin(const SimDev *sims) {
 #pragma unroll
     for (int d = 0; d < 3; d++) {
       double fl = floor(l[d]);
-      S.wrapn[3 * i + d] = (int)fl;
       double w = l[d] - fl;
-      if (w >= 1.0) w = 0.0;
+      if (w >= 1.0) { w = 0.0; fl += 1.0; }   // l = -1e-17: l - floor(l) rounds to 1.  The image that belongs to cell 0 is the one just below the low face
+      S.wrapn[3 * i + d] = (int)fl;
       int cc = (int)(w * S.nc[d]);
       if (cc >= S.nc[d]) cc = S.nc[d] - 1;
       if (cc < 0) cc = 0;
@@ -458,10 +458,10 @@ __global__ __launch_bounds__(CB_TPB) void k_cell_build(const SimDev *sims, int c
     int key = 0;
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-      const double fl = floor(l[d]);
-      S.wrapn[3 * i + d] = (int)fl;
+      double fl = floor(l[d]);
       double w = l[d] - fl;
-      if (w >= 1.0) w = 0.0;
+      if (w >= 1.0) { w = 0.0; fl += 1.0; }   // (as in k_bin: the image count goes with the cell)
+      S.wrapn[3 * i + d] = (int)fl;
       int cc = (int)(w * S.nc[d]);
       if (cc >= S.nc[d]) cc = S.nc[d] - 1;
       if (cc < 0) cc = 0;
