@@ -341,6 +341,22 @@ int scema_md_batch_split(scema_md_engine *e, int32_t on);
 /* out[3]: the current settings {batch split, ReaxFF part batches, ReaxFF overlap}, so that a caller that changes them for a measurement can
  * put back exactly what it found */
 int scema_md_get_concurrency(const scema_md_engine *e, int32_t *out);
+/* PPPM meshes beyond the LDS (more than 18 432 points for the charge assignment, 6 144 for the interpolation; PE-10k's 12 x 12 x 12 is far
+ * below both).  mode 1 (default): the tiled kernels -- the mesh cut into bricks in (y, z) that are kept (assignment) or staged with a halo of
+ * two rows (interpolation) in LDS; 0: the kernels without LDS of before (global atomics, reads through the caches); -1 keeps the setting.
+ * lds_bytes: the LDS budget of the tile rule AND of the whole-mesh tests, 0 = the device default (144 KB), -1 keeps; a test and measurement
+ * aid that makes small meshes run as several tiles (16 .. 163 840; a mesh whose smallest brick is beyond it takes the kernels without
+ * LDS, scema_md_pppm_paths says so).  Results do not depend on either beyond the order of summation. */
+int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes);
+/* out[8], for the last PPPM launch group: {charge assignment: 0 whole mesh in LDS, 1 tiled, 2 global atomics; interpolation: 0 staged, 1 tiled,
+ * 2 unstaged; largest tile counts of the assignment in y and z; of the interpolation in y and z (1 1 where the kernel is not the tiled one);
+ * the LDS budget in force in bytes; the mode} */
+int scema_md_pppm_paths(const scema_md_engine *e, int32_t out[8]);
+/* The tile rule as a pure host function (no GPU, no engine): for a mesh grid[3] and an LDS budget (0: the device default) the brick
+ * {by, bz} in mesh rows and the tile counts {tiles_y, tiles_z} of which = 0 the charge assignment (nx by bz doubles kept) or 1 the
+ * interpolation (3 nx (by + 4)(bz + 4) doubles staged, the halo on tiled axes only); a mesh that fits whole is one tile; z-slabs (by = ny)
+ * while one plane / five planes fit; zeros = the smallest brick does not fit (8 nx bytes; 600 nx bytes). */
+int scema_md_pppm_tile_shape(const int32_t grid[3], int32_t lds_bytes, int32_t which /* 0 spread, 1 force */, int32_t out[4]);
 /* number of batched hipFFT plans the engine holds for PPPM meshes beyond the in-LDS solve (a plan owns a work area and is bound to a stream
  * when it runs: one per mesh size, batch count and stream of a part batch -- a test reads this), or a negative error code */
 int scema_md_pppm_plan_count(const scema_md_engine *e);

@@ -36,7 +36,7 @@ SYMBOLS = [
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
-    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
+    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -445,6 +445,19 @@ class Engine:
         lib().scema_md_pppm_plan_count.restype = C.c_int
         return int(lib().scema_md_pppm_plan_count(self.h))
 
+    def pppm_tiling(self, mode: int = -1, lds_bytes: int = -1):
+        """tiled PPPM kernels for meshes beyond the LDS (1, default) or the kernels without LDS (0); lds_bytes: the LDS budget of the
+        tile rule and the whole-mesh tests (0: device default); -1 keeps a setting"""
+        self._chk(lib().scema_md_pppm_tiling(self.h, C.c_int32(mode), C.c_int32(lds_bytes)))
+
+    def pppm_paths(self) -> dict:
+        """what the last PPPM launch group took: spread 0 whole / 1 tiled / 2 global atomics, force 0 staged / 1 tiled / 2 unstaged,
+        the largest tile counts (y, z) of either, the LDS budget in force and the mode"""
+        out = (C.c_int32 * 8)()
+        self._chk(lib().scema_md_pppm_paths(self.h, out))
+        return dict(spread=int(out[0]), force=int(out[1]), spread_tiles=(int(out[2]), int(out[3])), force_tiles=(int(out[4]), int(out[5])),
+                    lds_bytes=int(out[6]), mode=int(out[7]))
+
     def concurrency(self) -> dict:
         """the current issue settings: {"split": 0/1, "reax_halves": n, "reax_overlap": 0/1}"""
         out = (C.c_int32 * 3)()
@@ -519,6 +532,19 @@ def kspace_setup(params, box, qsqsum: float, natoms: int):
     if rc != 0:
         raise EngineError(f"scema_md_kspace_setup rc={rc}")
     return g0.value, g1.value, tuple(grid)
+
+
+def pppm_tile_shape(grid, lds_bytes: int = 0, which: int = 0):
+    """(by, bz, tiles_y, tiles_z) of the tiled PPPM kernels for this mesh and LDS budget (0: device default), which = 0 charge assignment,
+    1 interpolation; zeros: the smallest brick does not fit.  scema_md_pppm_tile_shape, a pure host function (no GPU)"""
+    L = lib()
+    L.scema_md_pppm_tile_shape.restype = C.c_int
+    g = (C.c_int32 * 3)(*[int(n) for n in grid])
+    out = (C.c_int32 * 4)()
+    rc = L.scema_md_pppm_tile_shape(g, C.c_int32(lds_bytes), C.c_int32(which), out)
+    if rc != 0:
+        raise EngineError(f"scema_md_pppm_tile_shape rc={rc}")
+    return tuple(int(v) for v in out)
 
 
 def make_sim(qp_id: int, matid: str, replica: int, strain_len, *, most_recent: int | None = None, material: int = 0,

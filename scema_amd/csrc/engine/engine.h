@@ -42,6 +42,7 @@
 #include "md_kernels.h"
 #include "md_equil.h"
 #include "md_pppm.h"
+#include "md_pppm_tile.h"
 #include "md_reax.h"
 #include "md_types.h"
 
@@ -327,6 +328,8 @@ struct scema_md_engine {
   // x and v of every state an update advances, as they were before it: the retry after a list overflow restarts from
   // them, and a failed update (on this rank or on another) puts them back
   std::vector<std::unique_ptr<DevBuf>> bak_x, bak_v;
+  int pppm_tile_mode = 1, pppm_lds_bytes = 0;   // scema_md_pppm_tiling: tiled kernels for meshes beyond the LDS; forced LDS budget (0: mdk_pppm_lds_limit())
+  int pppm_paths[8] = {0, 0, 0, 0, 0, 0, 0, 1}; // scema_md_pppm_paths: what the last PPPM launch group took
   std::map<std::array<int, 6>, hipfftHandle> pppm_plans;   // (nx, ny, nz, batch, stream, distance between grids) -> batched 3-d Z2Z plan
   std::vector<int> h_kpack;   // host copy, alive until the stream has consumed the upload
   int local_stress_count = 0;

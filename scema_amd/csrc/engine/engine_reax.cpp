@@ -564,6 +564,28 @@ int scema_md_get_concurrency(const scema_md_engine *e, int32_t *out) {
   out[2] = e->rx_overlap ? 1 : 0;
   return SCEMA_MD_OK;
 }
+int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (mode < -1 || mode > 1) return fail(e, SCEMA_MD_ERR_ARG, "scema_md_pppm_tiling: mode %d (1 tiled kernels, 0 the kernels without LDS, -1 keeps)", mode);
+  // the smallest brick there is: one x row of a mesh of two points (charge assignment)
+  const int least = 2 * 8, most = 160 * 1024;
+  if (lds_bytes < -1 || (lds_bytes > 0 && (lds_bytes < least || lds_bytes > most)))
+    return fail(e, SCEMA_MD_ERR_ARG, "scema_md_pppm_tiling: an LDS budget of %d bytes (%d .. %d, 0 the device default, -1 keeps)", lds_bytes, least, most);
+  if (mode >= 0) e->pppm_tile_mode = mode;
+  if (lds_bytes >= 0) e->pppm_lds_bytes = lds_bytes;
+  return SCEMA_MD_OK;
+}
+int scema_md_pppm_paths(const scema_md_engine *e, int32_t out[8]) {
+  if (!e || !out) return SCEMA_MD_ERR_ARG;
+  for (int k = 0; k < 8; k++) out[k] = e->pppm_paths[k];
+  return SCEMA_MD_OK;
+}
+int scema_md_pppm_tile_shape(const int32_t grid[3], int32_t lds_bytes, int32_t which, int32_t out[4]) {
+  if (!grid || !out || grid[0] < 1 || grid[1] < 1 || grid[2] < 1 || lds_bytes < 0 || which < 0 || which > 1) return SCEMA_MD_ERR_ARG;
+  const PppmTile t = pppm_tile_shape(grid[0], grid[1], grid[2], lds_bytes > 0 ? lds_bytes : (long long)mdk_pppm_lds_limit(), which);
+  out[0] = t.by; out[1] = t.bz; out[2] = t.ty; out[3] = t.tz;
+  return SCEMA_MD_OK;
+}
 int scema_md_pppm_plan_count(const scema_md_engine *e) { return e ? (int)e->pppm_plans.size() : -SCEMA_MD_ERR_ARG; }
 int scema_md_reax_set(scema_md_engine *e, int32_t exact_gradient, int32_t terms, int32_t qeq_maxiter) {
   if (!e || !e->rx_ready) return fail(e, SCEMA_MD_ERR_ARG, "no ReaxFF force field loaded");

@@ -355,6 +355,8 @@ struct Layout {
       maxgrp = 0, maxclus = 0, maxunits = 0, maxsteps = 0;
   int maxgrid = 0, maxgridp = 0, maxdims = 0;   // PPPM: largest grid of the batch, ... with five more points per x row, largest nx + ny + nz
   bool padx_ok = true;                          // (the padded LDS copies of the spreading and interpolation kernels fold five distinct pad columns per row)
+  PppmLaunch tl;                                // tiled PPPM kernels: budget, mode and the largest tile counts and LDS sizes of the batch (md_pppm_tile.h)
+  bool tl_sp_fits = true, tl_fo_fits = true;    // no mesh of the batch whose smallest brick is beyond the budget
   bool any_validate = false;   // some simulation may keep the rows its slot holds (SimDev::keep_list: 1 from the run, 2 from the update before)
 };
 
@@ -433,7 +435,10 @@ struct OplsRun {
   OplsRun(scema_md_engine *e_, std::vector<ActiveSim> &sims_, const RunSpec &spec_)
       : e(e_), sims(sims_), spec(spec_), P(e_->p), ns((int)sims_.size()), cutmax_all(std::max(P.cut_lj, P.cut_coul)), cle(P.cut_coul <= P.cut_lj),
         ev((spec_.sample || spec_.ev_always || (spec_.nh && spec_.npt)) ? 1 : 0), pol(plan_launch(e_, (int)sims_.size())), flips(sims_.size()),
-        koff(sims_.size(), 0) {}
+        koff(sims_.size(), 0) {
+    L.tl.budget = e->pppm_lds_bytes > 0 ? e->pppm_lds_bytes : (int)mdk_pppm_lds_limit();
+    L.tl.mode = e->pppm_tile_mode;
+  }
 
   void kspace_setup();
   int make_parts();
@@ -639,6 +644,15 @@ int OplsRun::lay_out_sim(int pos) {
     L.maxgrid = std::max(L.maxgrid, S.pg[0] * S.pg[1] * S.pg[2]);
     if (S.pg[0] < 5) L.padx_ok = false;
     L.maxgridp = std::max(L.maxgridp, (S.pg[0] + 5) * S.pg[1] * S.pg[2]);
+    for (int which = 0; which < 2; which++) {
+      const PppmTile t = pppm_tile_shape(S.pg[0], S.pg[1], S.pg[2], L.tl.budget, which);
+      bool &fits = which ? L.tl_fo_fits : L.tl_sp_fits;
+      if (t.ty == 0) { fits = false; continue; }
+      int &my = which ? L.tl.fo_ty : L.tl.sp_ty, &mz = which ? L.tl.fo_tz : L.tl.sp_tz, &mt = which ? L.tl.fo_tiles : L.tl.sp_tiles;
+      size_t &ml = which ? L.tl.fo_lds : L.tl.sp_lds;
+      my = std::max(my, t.ty); mz = std::max(mz, t.tz); mt = std::max(mt, t.ty * t.tz);
+      ml = std::max(ml, (size_t)pppm_tile_bytes(S.pg[0], S.pg[1], S.pg[2], t.by, t.bz, which));
+    }
   }
   S.nk = (int)ew.kn.size() / 3;
   for (int d = 0; d < 3; d++) S.kmaxd[d] = std::max(ew.kmaxd[d], 0);
@@ -747,16 +761,21 @@ int OplsRun::lay_out_kspace() {
     S.krun = base + 3 * (size_t)S.nk;
     S.kgrp = base + ((4 * (size_t)S.nk + 3) / 4) * 4;
   }
+  if (!L.tl_sp_fits) L.tl.sp_tiles = 0;
+  if (!L.tl_fo_fits) L.tl.fo_tiles = 0;
   if (L.maxgrid > 0) {
     const size_t mg = (size_t)L.maxgrid;
-    HIPCHK(e->d_pppm.ensure((size_t)ns * mg * (4 * sizeof(double2) + sizeof(double))));
+    // (behind the influence function of every simulation, pgstride doubles into its block: the home-tile keys of its atoms, one int each --
+    // k_pppm_keys; md_types.h, whose text the pair kernel's counters are pinned to, keeps its SimDev)
+    const size_t gfs = mg + ((size_t)L.maxatoms + 1) / 2;
+    HIPCHK(e->d_pppm.ensure((size_t)ns * (mg * 4 * sizeof(double2) + gfs * sizeof(double))));
     double *gbase = e->d_pppm.as<double>(), *ebase = gbase + (size_t)ns * mg * 2, *fbase = gbase + (size_t)ns * mg * 8;
     for (int pos = 0; pos < ns; pos++) {
       SimDev &S = e->h_sims[pos];
       S.pgrid = gbase + (size_t)pos * mg * 2;
       S.pfield = ebase + (size_t)pos * mg * 6;
       S.pgstride = (long long)L.maxgrid;
-      S.pgf = fbase + (size_t)pos * mg;
+      S.pgf = fbase + (size_t)pos * gfs;
       L.maxdims = std::max(L.maxdims, S.pg[0] + S.pg[1] + S.pg[2]);
       const bool same = pos > 0 && pos != parts[part_of(parts, pos)].off && std::memcmp(S.pg, e->h_sims[pos - 1].pg, sizeof S.pg) == 0;
       if (same) pppm_runs.back().second += 1;
@@ -795,13 +814,21 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
   if (L.maxgrid <= 0 || na <= 0) return SCEMA_MD_OK;
   const SimDev *Dp = D + pos0;
   bool &clean = pppm_clean[part_of(parts, pos0)];
-  mdk_pppm_spread(st, Dp, na, L.maxgrid, L.maxatoms, clean ? 1 : 0, L.padx_ok ? L.maxgridp : 0);
+  const int maxgridp = L.padx_ok ? L.maxgridp : 0;
+  const int sp_path = mdk_pppm_spread_path(L.maxgrid, maxgridp, &L.tl), fo_path = mdk_pppm_force_path(L.maxgrid, &L.tl);
+  {
+    const int paths[8] = {sp_path, fo_path, sp_path == 1 ? L.tl.sp_ty : 1, sp_path == 1 ? L.tl.sp_tz : 1, fo_path == 1 ? L.tl.fo_ty : 1,
+                          fo_path == 1 ? L.tl.fo_tz : 1, L.tl.budget, L.tl.mode};
+    std::memcpy(e->pppm_paths, paths, sizeof paths);
+  }
+  if (sp_path == 1 || fo_path == 1) mdk_pppm_keys(st, Dp, na, L.maxatoms);   // home tiles from the positions of this step
+  mdk_pppm_spread(st, Dp, na, L.maxgrid, L.maxatoms, clean ? 1 : 0, maxgridp, &L.tl);   // (the tiled kernel stores every point: no zero launch)
   clean = false;
   if (pol.pppm_in_lds) {   // small grids: the whole solve in one launch, in LDS (md_pppm.hip k_pppm_solve); it leaves the charge grids zeroed
     if (new_box) mdk_pppm_gf(st, Dp, na, L.maxgrid);
     mdk_pppm_solve(st, Dp, na, L.maxgrid, L.maxdims);
     clean = true;
-    mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 1);
+    mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 1, &L.tl);
     return SCEMA_MD_OK;
   }
   auto transform = [&](bool fields, int dir) -> int {   // the charge grids forward, or the three field grids of every simulation back
@@ -823,7 +850,7 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
   if (new_box) mdk_pppm_gf(st, Dp, na, L.maxgrid);
   mdk_pppm_poisson(st, Dp, na, L.maxgrid);
   if ((rc = transform(true, HIPFFT_BACKWARD))) return rc;
-  mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add);
+  mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 0, &L.tl);
   return SCEMA_MD_OK;
 }
 

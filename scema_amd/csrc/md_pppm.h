@@ -4,9 +4,23 @@
 #include <hip/hip_runtime.h>
 struct SimDev;
 size_t mdk_pppm_lds_limit();
+// What the tiled kernels of a launch need from the host (engine_run.cpp fills it from the meshes of the batch by md_pppm_tile.h):
+// budget: LDS bytes of the tile rule and of the whole-mesh tests (> 0); mode 0: the kernels without LDS for meshes beyond it, as before;
+// per kernel the largest tile counts of the batch (tiles: largest ty * tz = gridDim.x; 0: a mesh whose smallest brick does not fit, the
+// launch keeps the kernel without LDS) and the largest brick / staged size in bytes.
+struct PppmLaunch {
+  int budget = 0, mode = 1;
+  int sp_ty = 0, sp_tz = 0, sp_tiles = 0, fo_ty = 0, fo_tz = 0, fo_tiles = 0;
+  size_t sp_lds = 0, fo_lds = 0;
+};
+// 0: the whole mesh in LDS, 1: tiled, 2: no LDS (global atomics / unstaged reads) -- what mdk_pppm_spread / mdk_pppm_force take and return
+int mdk_pppm_spread_path(int maxgrid, int maxgridp, const PppmLaunch *tl);
+int mdk_pppm_force_path(int maxgrid, const PppmLaunch *tl);
+// home-tile keys of all atoms from the current positions (one int per atom behind SimDev::pgf, pgstride doubles in): before the first tiled kernel of a step
+void mdk_pppm_keys(hipStream_t st, const SimDev *d, int ns, int maxatoms);
 // charges -> grid 0 (complex, imaginary part 0); maxgrid = largest nx*ny*nz of the batch
 // zeroed != 0: the charge grids are known to hold zeros (k_pppm_solve leaves them so)
-void mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int zeroed, int maxgridp = 0);   // maxgridp: largest grid with 5 more points per x row (0: no padded LDS copy)
+int mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int zeroed, int maxgridp = 0, const PppmLaunch *tl = nullptr);   // maxgridp: largest grid with 5 more points per x row (0: no padded LDS copy)
 // small grids (maxgrid <= mdk_pppm_solve_max()): forward transform, energy / virial / field spectra and the three inverse transforms in one
 // launch, in LDS (replaces the transforms of the engine and mdk_pppm_poisson); maxdims = largest nx + ny + nz of the batch
 int mdk_pppm_solve_max();
@@ -17,4 +31,4 @@ void mdk_pppm_gf(hipStream_t st, const SimDev *d, int ns, int maxgrid);
 void mdk_pppm_poisson(hipStream_t st, const SimDev *d, int ns, int maxgrid);
 // after the inverse transforms of the field grids: forces added to SimDev::f (add != 0) or stored there (the chain runs ahead of
 // the kernel that assembles the force of the step, which then adds them: mdk_ewald_force fkeep)
-void mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int add, int real_fields = 0);   // real_fields: after mdk_pppm_solve
+int mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int add, int real_fields = 0, const PppmLaunch *tl = nullptr);   // real_fields: after mdk_pppm_solve

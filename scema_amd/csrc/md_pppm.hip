@@ -11,11 +11,13 @@
 //   k_pppm_poisson  energy, virial, field spectra -i k G rho(k)
 //   k_pppm_force    per atom: the 125 grid points of three field grids (staged in LDS when they fit), added to the forces the
 //                   other kernels assembled
+//   k_pppm_keys, k_pppm_spread_tiled, k_pppm_force_tiled   meshes beyond the LDS: the two atom kernels over bricks of the mesh (md_pppm_tile.h)
 #include <hip/hip_runtime.h>
 
 #include "md_device.h"
 #include "md_env.h"
 #include "md_pppm.h"
+#include "md_pppm_tile.h"
 #include "md_types.h"
 
 #include <algorithm>
@@ -34,9 +36,10 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // recursion over indicator functions that the oracle walks (oracle: pppm_weights; 330 instructions per dimension, half of the spreading and of
 // the interpolation kernel until round 5).  Same numbers to the last places (the two forms round differently: 1e-16).
 static_assert(PP_ORDER == 5, "the blending polynomials below are those of order 5");
-__device__ __forceinline__ int pppm_weights(double u, double (&w)[PP_ORDER]) {
-  const int i = (int)floor(u + 0.5);
-  const double s = 0.5 - ((double)i - u), r = 1.0 - s;
+// the nearest grid point of u (0 <= u <= n gives 0 .. n): the centre of the stencil, and -- taken mod n -- what decides an atom's home tile
+__device__ __forceinline__ int pppm_nearest(double u) { return (int)floor(u + 0.5); }
+__device__ __forceinline__ void pppm_blend(double s, double (&w)[PP_ORDER]) {
+  const double r = 1.0 - s;
   const double s2 = s * s, r2 = r * r;
   constexpr double q = 1.0 / 24.0;
   w[4] = q * (s2 * s2);
@@ -44,7 +47,16 @@ __device__ __forceinline__ int pppm_weights(double u, double (&w)[PP_ORDER]) {
   w[3] = fma(fma(fma(fma(-4.0 * q, s, 4.0 * q), s, 6.0 * q), s, 4.0 * q), s, q);
   w[2] = fma(fma(fma(fma(6.0 * q, s, -12.0 * q), s, -6.0 * q), s, 12.0 * q), s, 11.0 * q);
   w[1] = fma(fma(fma(fma(-4.0 * q, s, 12.0 * q), s, -6.0 * q), s, -12.0 * q), s, 11.0 * q);
+}
+__device__ __forceinline__ int pppm_weights(double u, double (&w)[PP_ORDER]) {
+  const int i = pppm_nearest(u);
+  pppm_blend(0.5 - ((double)i - u), w);
   return i;
+}
+// the same weights around a nearest point that was decided before (k_pppm_keys) and is known mod n: km == 0 stands for 0 or for n
+__device__ __forceinline__ void pppm_weights_at(double u, int n, int km, double (&w)[PP_ORDER]) {
+  const int i = (km == 0 && u >= 1.0) ? n : km;
+  pppm_blend(0.5 - ((double)i - u), w);
 }
 __device__ __forceinline__ int pmod(int a, int n) { const int r = a % n; return r < 0 ? r + n : r; }
 // the five periodic grid indices i-2 .. i+2 of one dimension (0 <= i <= n); grids of fewer than 4 points wrap more than once
@@ -492,6 +504,7 @@ __global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int spli
         for (int k = 0; k < PP_ORDER; k++) {
           const int g = row + gx[k];
           if (LDS) { rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[NG + g], ry); rz = fma(wx[k], s_grid[2 * NG + g], rz); }
+          else if (REALF) { const double *fr = (const double *)S.pfield; rx = fma(wx[k], fr[g], rx); ry = fma(wx[k], fr[gs + g], ry); rz = fma(wx[k], fr[2 * gs + g], rz); }
           else { rx = fma(wx[k], ex[g].x, rx); ry = fma(wx[k], ey[g].x, ry); rz = fma(wx[k], ez[g].x, rz); }
         }
         fx = fma(zy, rx, fx); fy = fma(zy, ry, fy); fz = fma(zy, rz, fz);
@@ -504,23 +517,269 @@ __global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int spli
 }
 
 
+// ---- tiled charge assignment and interpolation: the LDS formulation of the two kernels above for meshes beyond the LDS ----
+// The mesh is cut into bricks in (y, z) that span whole x rows (md_pppm_tile.h); workgroup (tile, replica).  An atom's HOME tile is the one
+// that owns the (y, z) of its nearest grid point.  It is decided once per step from the current positions by k_pppm_keys (the cell order is
+// stale by up to the list skin between rebuilds) and read from there by both kernels, which also centre their y and z stencils on the key
+// instead of deciding the nearest point again: every atom has exactly one home, and the stencil of an atom lies within two rows of it.
+// key = iy | iz << 16, bit 31: the atom is uncharged.
+#define PP_KEY_Y(key) ((key) & 0xffff)
+#define PP_KEY_Z(key) (((key) >> 16) & 0x7fff)
+// (the keys of a simulation lie behind its influence function, pgstride doubles into the block the engine lays out: engine_run.cpp lay_out_kspace)
+__device__ __forceinline__ int MD_G *pppm_keys_of(const SimDev &S) { return (int MD_G *)(S.pgf + S.pgstride); }
+__global__ __launch_bounds__(256) void k_pppm_keys(const SimDev *sims) {
+  const SimDev &S = sims[blockIdx.y];
+  if (S.pg[0] == 0) return;
+  const int ny = S.pg[1], nz = S.pg[2], a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= S.natoms) return;
+  BoxD b;
+  box_derive(S.sc->box, b);
+  box_uniform(b);
+  double l0, l1, l2;
+  atom_lamda(S, b, a, l0, l1, l2);
+  const int iy = pmod(pppm_nearest(l1 * ny), ny), iz = pmod(pppm_nearest(l2 * nz), nz);
+  pppm_keys_of(S)[a] = iy | (iz << 16) | (S.q[a] == 0.0 ? (int)0x80000000 : 0);
+}
+// the tile of this workgroup: origin and extent of its brick (false: the replica has fewer tiles, or no mesh)
+struct PppmBrick { int y0, z0, byc, bzc, hy, hz; };
+__device__ __forceinline__ bool pppm_brick(int nx, int ny, int nz, int budget, int which, PppmBrick &B) {
+  const PppmTile t = pppm_tile_shape(nx, ny, nz, budget, which);
+  const int tile = (int)blockIdx.x;
+  if (tile >= t.ty * t.tz) return false;
+  const int tzi = tile / t.ty, tyi = tile - tzi * t.ty;
+  B.y0 = tyi * t.by; B.z0 = tzi * t.bz;
+  B.byc = min(t.by, ny - B.y0); B.bzc = min(t.bz, nz - B.z0);
+  B.hy = t.by < ny ? 4 : 0; B.hz = t.bz < nz ? 4 : 0;
+  return true;
+}
+// a - b for mesh indices 0 <= a, b < n, shifted by d (|d| <= 2), taken mod n
+__device__ __forceinline__ int pppm_rel(int a, int b, int d, int n) {
+  const int v = a - b + d;
+  return v < 0 ? v + n : (v >= n ? v - n : v);
+}
+
+// Charge assignment, owner computes: the workgroup keeps its brick in LDS (nx byc bzc doubles), takes every charged atom whose 5 x 5 stencil in
+// (y, z) touches the brick -- home within two rows of it --, adds the stencil points that fall on OWNED rows (ownership is tested per stencil
+// offset: with fewer than five rows in a dimension two offsets of one atom may hit the same row, and an atom near a border is served by up to
+// four tiles, in part by each), and stores the brick with plain stores, zeros included: no global atomics, no k_pppm_zero, and nothing
+// depends on what the charge grid held.  Lanes and waves split the file as in k_pppm_spread (lane l: atoms l rows .. (l + 1) rows - 1, two
+// consecutive ones per turn, merged into one atomic per point where they share their nearest point), but every lane walks to ITS next pair
+// with a candidate on its own: the lanes of a wave stay far apart in the file, and a turn costs 125 atomics only for lanes that have work.
+template <int TPB_>
+__global__ __launch_bounds__(TPB_) void k_pppm_spread_tiled(const SimDev *sims, int budget) {
+  const SimDev &S = sims[blockIdx.y];
+  const int nx = S.pg[0], ny = S.pg[1], nz = S.pg[2];
+  if (nx == 0) return;
+  PppmBrick B;
+  if (!pppm_brick(nx, ny, nz, budget, 0, B)) return;
+  const int y0 = B.y0, z0 = B.z0, byc = B.byc, bzc = B.bzc;
+  const int NG = nx * ny * nz, NB = nx * byc * bzc, T = TPB_;
+  for (int k = threadIdx.x; k < NB; k += T) s_grid[k] = 0.0;
+  __syncthreads();
+  BoxD b;
+  box_derive(S.sc->box, b);
+  box_uniform(b);
+  const double delvolinv = (double)NG / b.vol;
+  const int MD_G *pkey = pppm_keys_of(S);
+  const int natoms = S.natoms, rows = (natoms + 63) >> 6, lane = threadIdx.x & 63, step = 2 * (T >> 6);
+  const int cy = byc + 4, cz = bzc + 4;
+  auto touches = [&](int key) { return key >= 0 && pppm_rel(PP_KEY_Y(key), y0, 2, ny) < cy && pppm_rel(PP_KEY_Z(key), z0, 2, nz) < cz; };
+  int r = 2 * ((int)threadIdx.x >> 6);
+  for (;;) {
+    int aA = 0, kA = 0, kB = 0;
+    bool vB = false, found = false;
+    for (; r < rows; r += step) {
+      const int a = lane * rows + r;
+      if (a >= natoms) { r = rows; break; }
+      const bool hasB = r + 1 < rows && a + 1 < natoms;
+      const int k0 = pkey[a], k1 = hasB ? pkey[a + 1] : -1;
+      const bool c0 = touches(k0), c1 = touches(k1);
+      if (!c0 && !c1) continue;
+      aA = c0 ? a : a + 1; kA = c0 ? k0 : k1;
+      vB = c0 && c1; kB = k1;
+      found = true;
+      r += step;
+      break;
+    }
+    if (!found) break;
+    const int aB = aA + 1;
+    double wxA[PP_ORDER], wyA[PP_ORDER], wzA[PP_ORDER], wxB[PP_ORDER] = {0, 0, 0, 0, 0}, wyB[PP_ORDER] = {0, 0, 0, 0, 0}, wzB[PP_ORDER] = {0, 0, 0, 0, 0};
+    int gxA[PP_ORDER], gyA[PP_ORDER], gzA[PP_ORDER], gxB[PP_ORDER] = {0, 0, 0, 0, 0}, gyB[PP_ORDER] = {0, 0, 0, 0, 0}, gzB[PP_ORDER] = {0, 0, 0, 0, 0};
+    double l0, l1, l2;
+    atom_lamda(S, b, aA, l0, l1, l2);
+    const int ixA = pppm_weights(l0 * nx, wxA);
+    pppm_weights_at(l1 * ny, ny, PP_KEY_Y(kA), wyA); pppm_weights_at(l2 * nz, nz, PP_KEY_Z(kA), wzA);
+    pppm_wrap(ixA, nx, gxA); pppm_wrap(PP_KEY_Y(kA), ny, gyA); pppm_wrap(PP_KEY_Z(kA), nz, gzA);
+    const double zA = delvolinv * S.q[aA];
+    double zB = 0.0;
+    int ixB = -1000;
+    if (vB) {
+      atom_lamda(S, b, aB, l0, l1, l2);
+      ixB = pppm_weights(l0 * nx, wxB);
+      pppm_weights_at(l1 * ny, ny, PP_KEY_Y(kB), wyB); pppm_weights_at(l2 * nz, nz, PP_KEY_Z(kB), wzB);
+      pppm_wrap(ixB, nx, gxB); pppm_wrap(PP_KEY_Y(kB), ny, gyB); pppm_wrap(PP_KEY_Z(kB), nz, gzB);
+      zB = delvolinv * S.q[aB];
+    }
+    const bool merged = vB && ixA == ixB && kA == kB;
+#pragma unroll
+    for (int k = 0; k < PP_ORDER; k++) { wxA[k] *= zA; wxB[k] *= zB; }
+#pragma unroll
+    for (int c = 0; c < PP_ORDER; c++) {
+      const int lz = gzA[c] - z0;
+      if ((unsigned)lz >= (unsigned)bzc) continue;
+#pragma unroll
+      for (int bb = 0; bb < PP_ORDER; bb++) {
+        const int ly = gyA[bb] - y0;
+        if ((unsigned)ly >= (unsigned)byc) continue;
+        const double zyA = wzA[c] * wyA[bb], zyB = merged ? wzB[c] * wyB[bb] : 0.0;
+        double *prow = s_grid + (lz * byc + ly) * nx;
+#pragma unroll
+        for (int k = 0; k < PP_ORDER; k++)
+          (void)__hip_atomic_fetch_add(prow + gxA[k], fma(zyB, wxB[k], zyA * wxA[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    if (vB && !merged) {
+#pragma unroll
+      for (int c = 0; c < PP_ORDER; c++) {
+        const int lz = gzB[c] - z0;
+        if ((unsigned)lz >= (unsigned)bzc) continue;
+#pragma unroll
+        for (int bb = 0; bb < PP_ORDER; bb++) {
+          const int ly = gyB[bb] - y0;
+          if ((unsigned)ly >= (unsigned)byc) continue;
+          const double zyB = wzB[c] * wyB[bb];
+          double *prow = s_grid + (lz * byc + ly) * nx;
+#pragma unroll
+          for (int k = 0; k < PP_ORDER; k++) (void)__hip_atomic_fetch_add(prow + gxB[k], zyB * wxB[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  double2 *rho = (double2 *)S.pgrid;
+  for (int k = threadIdx.x; k < NB; k += T) {
+    const int row = k / nx, x = k - row * nx, lz = row / byc, ly = row - lz * byc;
+    rho[((z0 + lz) * ny + y0 + ly) * nx + x] = make_double2(s_grid[k], 0.0);
+  }
+}
+
+// Interpolation, gather: the workgroup stages the three field grids over its brick and a halo of two rows on each tiled side (staged row
+// i of plane j holds mesh row y0 - 2 + i of plane z0 - 2 + j, wrapped; an axis that is not tiled is staged as it lies) and serves exactly the
+// atoms whose home it is: their stencils need no wrap in a tiled dimension, and each atom is written by one workgroup.  Every thread walks
+// the key list to ITS next home atom on its own (thread t: atoms t, t + T, ...).  add and uncharged atoms as in k_pppm_force.
+template <int TPB_, bool REALF>
+__global__ __launch_bounds__(TPB_) void k_pppm_force_tiled(const SimDev *sims, int budget, int add) {
+  const SimDev &S = sims[blockIdx.y];
+  const int nx = S.pg[0], ny = S.pg[1], nz = S.pg[2];
+  if (nx == 0) return;
+  PppmBrick B;
+  if (!pppm_brick(nx, ny, nz, budget, 1, B)) return;
+  const int y0 = B.y0, z0 = B.z0, byc = B.byc, bzc = B.bzc, hy = B.hy, hz = B.hz;
+  const int sy = byc + hy, sz = bzc + hz, SN = nx * sy * sz, T = TPB_;
+  const size_t gs = (size_t)S.pgstride;
+  const double2 *ex = (const double2 *)S.pfield, *ey = ex + gs, *ez = ey + gs;
+  const double *fr = (const double *)S.pfield;
+  for (int k = threadIdx.x; k < SN; k += T) {
+    const int row = k / nx, x = k - row * nx, j = row / sy, i = row - j * sy;
+    const int g = ((hz ? pmod(z0 - 2 + j, nz) : j) * ny + (hy ? pmod(y0 - 2 + i, ny) : i)) * nx + x;
+    if (REALF) { s_grid[k] = fr[g]; s_grid[SN + k] = fr[gs + g]; s_grid[2 * SN + k] = fr[2 * gs + g]; }
+    else { s_grid[k] = ex[g].x; s_grid[SN + k] = ey[g].x; s_grid[2 * SN + k] = ez[g].x; }
+  }
+  __syncthreads();
+  BoxD b;
+  box_derive(S.sc->box, b);
+  box_uniform(b);
+  const int MD_G *pkey = pppm_keys_of(S);
+  const int natoms = S.natoms;
+  int a = threadIdx.x;
+  for (;;) {
+    int key = 0;
+    for (; a < natoms; a += T) {
+      key = pkey[a];
+      if ((unsigned)(PP_KEY_Y(key) - y0) < (unsigned)byc && (unsigned)(PP_KEY_Z(key) - z0) < (unsigned)bzc) break;
+    }
+    if (a >= natoms) break;
+    const int at = a;
+    a += T;
+    if (key < 0) {
+      if (!add) { S.f[3 * at] = 0.0; S.f[3 * at + 1] = 0.0; S.f[3 * at + 2] = 0.0; }
+      continue;
+    }
+    double l0, l1, l2;
+    atom_lamda(S, b, at, l0, l1, l2);
+    double wx[PP_ORDER], wy[PP_ORDER], wz[PP_ORDER];
+    int gx[PP_ORDER], jy[PP_ORDER], jz[PP_ORDER];
+    const int iy = PP_KEY_Y(key), iz = PP_KEY_Z(key);
+    pppm_wrap(pppm_weights(l0 * nx, wx), nx, gx);
+    pppm_weights_at(l1 * ny, ny, iy, wy); pppm_weights_at(l2 * nz, nz, iz, wz);
+    pppm_wrap(iy, ny, jy); pppm_wrap(iz, nz, jz);
+#pragma unroll
+    for (int k = 0; k < PP_ORDER; k++) { if (hy) jy[k] = iy - y0 + k; if (hz) jz[k] = iz - z0 + k; }
+    double fx = 0.0, fy = 0.0, fz = 0.0;
+#pragma unroll
+    for (int c = 0; c < PP_ORDER; c++) {
+#pragma unroll
+      for (int bb = 0; bb < PP_ORDER; bb++) {
+        const double zy = wz[c] * wy[bb];
+        const int row = (jz[c] * sy + jy[bb]) * nx;
+        double rx = 0.0, ry = 0.0, rz = 0.0;
+#pragma unroll
+        for (int k = 0; k < PP_ORDER; k++) {
+          const int g = row + gx[k];
+          rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[SN + g], ry); rz = fma(wx[k], s_grid[2 * SN + g], rz);
+        }
+        fx = fma(zy, rx, fx); fy = fma(zy, ry, fy); fz = fma(zy, rz, fz);
+      }
+    }
+    const double qf = MD_QQRD2E * S.q[at];
+    if (add) { S.f[3 * at] += qf * fx; S.f[3 * at + 1] += qf * fy; S.f[3 * at + 2] += qf * fz; }
+    else { S.f[3 * at] = qf * fx; S.f[3 * at + 1] = qf * fy; S.f[3 * at + 2] = qf * fz; }
+  }
+}
+
+
 size_t mdk_pppm_lds_limit() { return 144 * 1024; }
 // atom ranges per replica: enough workgroups to fill the 256 CUs several times over, none with fewer than 256 atoms
 static inline int pppm_split(int ns, int maxatoms) {
   // small batches: down to one atom per thread (a single replica: spreading 27 -> 15 us, interpolation 27 -> 20 us)
   return std::max(1, std::min(std::min(ns < 32 ? 64 : 16, cdiv(2048, ns)), maxatoms / 256));
 }
-void mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int zeroed, int maxgridp) {
-  // maxgridp: the largest grid with five more points per x row (0: a grid of the batch has fewer than five points in x): the padded LDS copy
+// which kernel shape a launch takes (md_pppm.h): the budget of the launch stands for mdk_pppm_lds_limit() in the whole-mesh tests
+static inline size_t pppm_budget(const PppmLaunch *tl) { return tl && tl->budget > 0 ? (size_t)tl->budget : mdk_pppm_lds_limit(); }
+static inline bool pppm_padx(int maxgridp, const PppmLaunch *tl) {
   static const bool padx_off = scema_env("SCEMA_MD_PPPM_PADX") && atoi(scema_env("SCEMA_MD_PPPM_PADX")) == 0;
-  const bool padx = maxgridp > 0 && !padx_off && (size_t)maxgridp * sizeof(double) <= 36 * 1024;   // (7 / 19 kB of LDS for 12 x 12 x 12 points: no workgroup fewer)
+  return maxgridp > 0 && !padx_off && (size_t)maxgridp * sizeof(double) <= std::min((size_t)36 * 1024, pppm_budget(tl));   // (7 / 19 kB of LDS for 12 x 12 x 12 points: no workgroup fewer)
+}
+int mdk_pppm_spread_path(int maxgrid, int maxgridp, const PppmLaunch *tl) {
+  const size_t lds = (size_t)(pppm_padx(maxgridp, tl) ? maxgridp : maxgrid) * sizeof(double);
+  if (lds <= pppm_budget(tl)) return 0;
+  return tl && tl->mode != 0 && tl->sp_tiles > 0 ? 1 : 2;
+}
+int mdk_pppm_force_path(int maxgrid, const PppmLaunch *tl) {
+  if (3 * (size_t)maxgrid * sizeof(double) <= pppm_budget(tl)) return 0;
+  return tl && tl->mode != 0 && tl->fo_tiles > 0 ? 1 : 2;
+}
+void mdk_pppm_keys(hipStream_t st, const SimDev *d, int ns, int maxatoms) { hipLaunchKernelGGL(k_pppm_keys, grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d); }
+int mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int zeroed, int maxgridp, const PppmLaunch *tl) {
+  // maxgridp: the largest grid with five more points per x row (0: a grid of the batch has fewer than five points in x): the padded LDS copy
+  const bool padx = pppm_padx(maxgridp, tl);
   const size_t lds = (size_t)(padx ? maxgridp : maxgrid) * sizeof(double);
-  const bool use_lds = lds <= mdk_pppm_lds_limit();
+  const int path = mdk_pppm_spread_path(maxgrid, maxgridp, tl);
+  if (path == 1) {   // bricks of the mesh in LDS, owner computes (the keys of this step are in place: mdk_pppm_keys)
+    const size_t tlds = tl->sp_lds;
+    static size_t optin_tab[16] = {0};
+    size_t &optin = lds_optin_slot(optin_tab);
+    if (tlds > 64 * 1024 && tlds > optin) { (void)hipFuncSetAttribute((const void *)k_pppm_spread_tiled<PP_TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds); optin = tlds; }
+    if (tlds <= 36 * 1024) hipLaunchKernelGGL((k_pppm_spread_tiled<256>), grid2(tl->sp_tiles, ns), dim3(256), tlds, st, d, tl->budget);
+    else hipLaunchKernelGGL((k_pppm_spread_tiled<PP_TPB>), grid2(tl->sp_tiles, ns), dim3(PP_TPB), tlds, st, d, tl->budget);
+    return path;
+  }
+  const bool use_lds = path == 0;
   const int split = pppm_split(ns, maxatoms);
   if ((!use_lds || split > 1) && !zeroed) hipLaunchKernelGGL(k_pppm_zero, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d);
   if (!use_lds) {
     hipLaunchKernelGGL((k_pppm_spread<false, 256>), grid2(split, ns), dim3(256), 0, st, d, split);
-    return;
+    return path;
   }
   static size_t optin_tab[16] = {0};
   size_t &optin = lds_optin_slot(optin_tab);
@@ -529,6 +788,7 @@ void mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int m
   if (padx) hipLaunchKernelGGL((k_pppm_spread<true, 256, true>), grid2(split, ns), dim3(256), lds, st, d, split);
   else if (lds <= 36 * 1024) hipLaunchKernelGGL((k_pppm_spread<true, 256>), grid2(split, ns), dim3(256), lds, st, d, split);
   else hipLaunchKernelGGL((k_pppm_spread<true, PP_TPB>), grid2(split, ns), dim3(PP_TPB), lds, st, d, split);
+  return path;
 }
 int mdk_pppm_solve_max() { return PP_SOLVE_MAX; }
 void mdk_pppm_solve(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxdims) {
@@ -550,11 +810,34 @@ void mdk_pppm_solve(hipStream_t st, const SimDev *d, int ns, int maxgrid, int ma
 }
 void mdk_pppm_gf(hipStream_t st, const SimDev *d, int ns, int maxgrid) { hipLaunchKernelGGL(k_pppm_gf, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d); }
 void mdk_pppm_poisson(hipStream_t st, const SimDev *d, int ns, int maxgrid) { hipLaunchKernelGGL(k_pppm_poisson, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d); }
-void mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int add, int real_fields) {
+int mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int add, int real_fields, const PppmLaunch *tl) {
   const size_t lds = 3 * (size_t)maxgrid * sizeof(double);
-  if (lds > mdk_pppm_lds_limit()) {
-    hipLaunchKernelGGL((k_pppm_force<false, false>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add);
-    return;
+  const int path = mdk_pppm_force_path(maxgrid, tl);
+  if (path == 1) {   // the field grids over a brick and its halo in LDS, every atom served by its home tile (keys: mdk_pppm_keys)
+    const size_t tlds = tl->fo_lds;
+    static size_t optin_tab[16] = {0};
+    size_t &optin = lds_optin_slot(optin_tab);
+    if (tlds > 64 * 1024 && tlds > optin) {
+      (void)hipFuncSetAttribute((const void *)k_pppm_force_tiled<PP_TPB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds);
+      (void)hipFuncSetAttribute((const void *)k_pppm_force_tiled<PP_TPB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds);
+      optin = tlds;
+    }
+    const dim3 g = grid2(tl->fo_tiles, ns);
+    // (a large copy gets the CU to itself and brings its own sixteen waves, as in the spreading kernels)
+    if (tlds <= 36 * 1024) {
+      if (real_fields) hipLaunchKernelGGL((k_pppm_force_tiled<256, true>), g, dim3(256), tlds, st, d, tl->budget, add);
+      else hipLaunchKernelGGL((k_pppm_force_tiled<256, false>), g, dim3(256), tlds, st, d, tl->budget, add);
+    } else {
+      if (real_fields) hipLaunchKernelGGL((k_pppm_force_tiled<PP_TPB, true>), g, dim3(PP_TPB), tlds, st, d, tl->budget, add);
+      else hipLaunchKernelGGL((k_pppm_force_tiled<PP_TPB, false>), g, dim3(PP_TPB), tlds, st, d, tl->budget, add);
+    }
+    return path;
+  }
+  if (path == 2) {
+    // (real field arrays without LDS: only under a forced budget -- a mesh of the in-LDS solve always fits the device's)
+    if (real_fields) hipLaunchKernelGGL((k_pppm_force<false, true>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add);
+    else hipLaunchKernelGGL((k_pppm_force<false, false>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add);
+    return path;
   }
   static size_t optin_tab[16] = {0};
   size_t &optin = lds_optin_slot(optin_tab);
@@ -566,4 +849,5 @@ void mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int ma
   const int split = pppm_split(ns, maxatoms);
   if (real_fields) hipLaunchKernelGGL((k_pppm_force<true, true>), grid2(split, ns), dim3(256), lds, st, d, split, add);
   else hipLaunchKernelGGL((k_pppm_force<true, false>), grid2(split, ns), dim3(256), lds, st, d, split, add);
+  return path;
 }
