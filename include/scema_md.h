@@ -138,6 +138,10 @@ typedef struct {
 int scema_md_probe_lammps_restart(const char *path, scema_lammps_restart_info *info);
 int scema_md_read_lammps_restart_atoms(const char *path, int64_t capacity, int64_t *tag, int32_t *type, int32_t *image,
                                        double *x, double *v);
+/* load: an atom_style full restart of the OPLS styles, or an atom_style atomic one (units real or metal: the reference's
+ * examples/streched_polyhedron/nanoscale_input/init.sic_1.bin), which registers a BARE replica -- types, masses, box, positions,
+ * velocities (A/ps -> A/fs for units metal); no charges, no topology, zero Lennard-Jones coefficients -- for a potential attached to the
+ * material id with scema_md_sw_configure.  convert takes atom_style full files only. */
 int scema_md_load_lammps_restart(scema_md_engine *e, const char *matid, int32_t replica, const char *path);
 int scema_md_convert_lammps_restart(const char *restart_path, const char *replica_path);
 int scema_md_write_lammps_restart(const char *path, const scema_md_system *sys, double cut_lj, double cut_coul,
@@ -369,6 +373,29 @@ int scema_md_reax_debug_compute(scema_md_engine *e, int32_t qp_id, const char *m
  * loop, iterations currently issued as batch launches per solve, evaluations repeated with the Jacobi preconditioner of fix qeq/reax
  * because the charge solve did not converge with the engine's own */
 int scema_md_reax_stats(const scema_md_engine *e, double *out);
+
+/* ---- Stillinger-Weber replicas (`pair_style sw`: the reference's examples/streched_polyhedron, lammps_scripts_sisw) ----
+ * configure = `pair_style sw` + `pair_coeff * * <sw_path> <elements...>` (elements[k] = element of LAMMPS atom type k+1) for the replicas of
+ * ONE material id, registered before or after the call; list skin `neighbor <skin> nsq` (skin < 0: 1.0, the example's), rebuilt by the
+ * engine's displacement test (`neigh_modify every 1 delay 0 check yes`).  energy_unit 0: the file's epsilon is in eV, as the header of the
+ * reference's Si.sw says, and is converted to kcal/mol with 23.060549; 1: epsilon is kcal/mol as written (what LAMMPS 17Nov16 does with
+ * that file under the example's `units real`).  Simulations of such a material take the Stillinger-Weber force stage whatever
+ * MDSim.force_field says (the example's inputs.json says "opls"): no SHAKE, no k-space, no bonded terms.  An update or run that mixes
+ * them with simulations of other materials is refused with SCEMA_MD_ERR_ARG. */
+int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
+                          int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], two-body and three-body energy (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz),
+ * info[4]: longest neighbour row the build asked for, row capacity, pairs inside their cutoff, triplets evaluated */
+int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
+                              double *virial, double *info);
+/* The reader of LAMMPS *.sw files as a pure host function (no GPU, no engine).  `#` starts a comment; an entry is three element names and
+ * eleven numbers (epsilon sigma a lambda gamma costheta0 A B p q tol) on one line or several; the entries whose three elements are all
+ * named are kept.  n_kept: distinct elements named (at most 4, in order of first appearance); type_map[n_elements]: their index per LAMMPS
+ * type; values[n_kept][n_kept][n_kept][11] (room for 4*4*4*11): the numbers of entry i j k, epsilon in kcal/mol.  The pair parameters of
+ * (i, j) are those of entry i j j, as in pair_sw.cpp.  A missing triplet, a non-numeric field, a short or duplicate entry:
+ * SCEMA_MD_ERR_IO with the reason in errbuf. */
+int scema_md_sw_read_params(const char *sw_path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                            int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
 typedef struct {
   int64_t pair_launches;      /* timed pair-kernel launches */

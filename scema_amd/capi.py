@@ -37,6 +37,7 @@ SYMBOLS = [
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
     "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
+    "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -471,6 +472,21 @@ class Engine:
         return dict(f=f, e=dict(zip(REAX_PARTS, e)), w=w, q=q, maxneigh_seen=int(info[0]), maxnb=int(info[1]), maxbd=int(info[2]),
                     qeq_iters=int(info[3]), image_search=int(info[4]), maxbonds_seen=int(info[5]))
 
+    # ---- Stillinger-Weber replicas (pair_style sw) ----
+    def sw_configure(self, matid: str, sw_path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style sw + pair_coeff * * <sw_path> <elements> for the replicas of one material id (lammps_scripts_sisw/in.strain.lammps);
+        energy_unit 0: the file's epsilon is eV, 1: kcal/mol as written"""
+        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+        self._chk(lib().scema_md_sw_configure(self.h, matid.encode(), sw_path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
+                                              C.c_double(skin)))
+
+    def sw_compute(self, matid, replica, qp=QP_NONE):
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); e2 = C.c_double(0.0); e3 = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
+        self._chk(lib().scema_md_sw_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(e2), C.byref(e3), _p(w),
+                                                  _p(info)))
+        return dict(f=f, e2=e2.value, e3=e3.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), ntriplets=int(info[3]))
+
     # ---- init_material's equilibration schedule (in.init.lammps; md_equil.hip) ----
     def minimize(self, matid, replica, qp, etol=1e-7, ftol=1e-11, maxiter=1000, maxeval=50000) -> dict:
         info = np.zeros(5)
@@ -519,6 +535,41 @@ def box_fp64_tflops(device: int = 0) -> float:
     if rc:
         raise EngineError(f"scema_md_box_fma_tflops failed with code {rc} (no HIP device?)")
     return float(out.value)
+
+
+def sw_system(types, x, box, v=None, masses=(28.0855,)) -> dict:
+    """System dict of a Stillinger-Weber replica (atom_style atomic): LAMMPS types (0-based here) and masses only -- no charges, no
+    topology, zero Lennard-Jones coefficients"""
+    n = len(types)
+    nt = len(masses)
+    z2 = np.zeros((0, 2))
+    return dict(natoms=n, ntypes=nt, type=np.asarray(types, np.int32), charge=np.zeros(n), mass=np.array(masses, float),
+                eps=np.zeros((nt, nt)), sigma=np.ones((nt, nt)), bonds=np.zeros((0, 2), np.int32), bond_type=np.zeros(0, np.int32), bond_coeff=z2,
+                angles=np.zeros((0, 3), np.int32), angle_type=np.zeros(0, np.int32), angle_coeff=z2, dihedrals=np.zeros((0, 4), np.int32),
+                dihedral_type=np.zeros(0, np.int32), dihedral_coeff=np.zeros((0, 4)), impropers=np.zeros((0, 4), np.int32),
+                improper_type=np.zeros(0, np.int32), improper_coeff=z2, special_lj=np.zeros(3), special_coul=np.zeros(3),
+                box=np.asarray(box, float), x=np.asarray(x, float), v=np.zeros((n, 3)) if v is None else np.asarray(v, float))
+
+
+SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]
+
+
+def sw_read_params(sw_path: str, elements, energy_unit: int = 0):
+    """(distinct elements kept, type_map, values[n][n][n][11] in the order of SW_FIELDS, epsilon in kcal/mol) of a LAMMPS *.sw file:
+    scema_md_sw_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
+    L = lib()
+    L.scema_md_sw_read_params.restype = C.c_int
+    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+    nk = C.c_int32(0)
+    tmap = np.zeros(len(elements), np.int32)
+    vals = np.zeros(4 * 4 * 4 * 11)
+    err = C.create_string_buffer(512)
+    rc = L.scema_md_sw_read_params(sw_path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(vals), err,
+                                   C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nk.value
+    return n, tmap, vals[:n * n * n * 11].reshape(n, n, n, 11).copy()
 
 
 def kspace_setup(params, box, qsqsum: float, natoms: int):

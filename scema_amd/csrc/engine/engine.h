@@ -6,6 +6,7 @@
 //   engine_kspace.cpp  what a LAMMPS `run` sets up on the host: g_ewald, k-vectors, PPPM grid, the real-space polynomial, fix deform's box path
 //   engine_run.cpp     one run of a batch with the OPLS force stage (run_phase), slots
 //   engine_reax.cpp    the same with the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
+//   engine_sw.cpp      the same with the Stillinger-Weber force stage (run_phase_sw) and the SW entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
 //   engine_state.cpp   state store: branch rule, replica / state files
@@ -37,6 +38,7 @@
 #include "../../../include/scema_md.h"
 #include "host/reax_ffield.h"
 #include "host/sim_plan.h"
+#include "host/sw_params.h"
 #include <hipfft/hipfft.h>
 
 #include "md_kernels.h"
@@ -44,6 +46,7 @@
 #include "md_pppm.h"
 #include "md_pppm_tile.h"
 #include "md_reax.h"
+#include "md_sw.h"
 #include "md_types.h"
 
 namespace scema_eng {
@@ -138,6 +141,9 @@ struct Topo {
   DevBuf d_type, d_q, d_mass, d_lj, d_bt_terms, d_bt_coef, d_ex_start, d_ex_list, d_clus_at, d_clus_n, d_clus_d, d_free_at, d_bt_desc, d_bt_atoms, d_bt_rank;
   int bt_ntile = 0, bt_maxloc = 1, bt_maxchunk = 1, bt_ncoef = 0, bt_cf_off[4] = {0, 0, 0, 0};
   double sp_w[6] = {0, 0, 0, 0, 0, 0};   // special_bonds weights: lj 1-2, 1-3, 1-4, coul 1-2, 1-3, 1-4
+  std::string matid;       // the material the replica was registered under (a Stillinger-Weber potential is attached to a material id)
+  DevBuf d_swtype;         // Stillinger-Weber: element per atom (index into the material's tables), valid for swtype_stamp
+  long long swtype_stamp = 0;
 };
 
 struct State {
@@ -165,6 +171,22 @@ struct RxSlot {
   DevBuf nb_cnt, nb_own0, nbT, hval, hcol, hlen, hown, hownlen, bd_cnt, bd, bd_rev, bd_bop, bd_c, bd_bo, bd_g, bd_cb, deltap, total_bo, cd_delta, hd, q, s, t, s_hist, t_hist, qwork, misc;
 };
 
+// work arrays of the Stillinger-Weber path for one batch position (md_sw.h SwView points into these)
+struct SwSlot {
+  int cap_pad = 0;
+  size_t cap_rows = 0;
+  DevBuf cnt, rows, misc;
+};
+
+// a Stillinger-Weber potential attached to a material id (scema_md_sw_configure)
+struct SwMaterial {
+  SwTable tab;
+  std::vector<int> type_map;   // LAMMPS type - 1 -> element of the tables
+  double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
+  long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
+  DevBuf d_tab;
+};
+
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds
 struct ListSig {
   bool valid = false;
@@ -178,9 +200,11 @@ struct ListSig {
   unsigned long long nentries = 0, nentries_ref = 0, nrowent = 0;
   long long rx_stamp = 0;        // != 0: the rows are ReaxFF rows (RxSlot), built under this force-field stamp; capj holds the near rows' stride
   int rx_mimg[3] = {0, 0, 0};
+  long long sw_stamp = 0;        // != 0: the rows are Stillinger-Weber rows (SwSlot), built under this material stamp; maxneigh holds their capacity, rx_mimg the image search
 };
 struct Slot {
   std::unique_ptr<RxSlot> rx;
+  std::unique_ptr<SwSlot> sw;
   ListSig sig;
   int cap_atoms = 0, cap_pad = 0, cap_neigh = 0, cap_cells = 0, cap_k = 0;
   size_t cap_jtab = 0;
@@ -358,6 +382,12 @@ struct scema_md_engine {
   int rx_qeq_launch_cold = 48;        // the same for the first solves of a run (empty history)
   int rx_qeq_launch = 32;             // conjugate-gradient iterations issued as batch launches per solve (follows what the last run needed)
   bool rx_qeq_launch_pinned = false;  // SCEMA_REAX_QEQ_LAUNCH fixes it (0: every solve runs in the single-workgroup loop)
+  // Stillinger-Weber path: the potentials by material id; simulations of such a material take the SW force stage (run_phase)
+  std::map<std::string, std::unique_ptr<SwMaterial>> sw_mats;
+  long long sw_stamp = 0;
+  DevBuf d_swviews;
+  std::vector<SwView> h_swviews;
+  hipEvent_t sw_fork = nullptr, sw_done = nullptr;   // part batches of an SW run: start and end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
   scema::SimPlan last_plan;
@@ -407,6 +437,11 @@ int settle_pending(scema_md_engine *e, bool failed);
 int ensure_slot(scema_md_engine *e, Slot &sl, int natoms, int maxneigh, int ncells, int nk, int capj);
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
+int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
+// the Stillinger-Weber potential of a material id, or null (engine_sw.cpp)
+SwMaterial *sw_material(scema_md_engine *e, const std::string &matid);
+// a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
+bool sw_bare_replica(const Topo &t);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
 // the batch skeleton both force stages share (engine_run.cpp)

@@ -179,6 +179,8 @@ void scema_md_destroy(scema_md_engine *e) {
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->rx_fork) (void)hipEventDestroy(e->rx_fork);
+  if (e->sw_fork) (void)hipEventDestroy(e->sw_fork);
+  if (e->sw_done) (void)hipEventDestroy(e->sw_done);
   if (e->rx_side1) (void)hipStreamDestroy(e->rx_side1);
   for (int k = 0; k < 4; k++) if (e->rx_side1_ev[k]) (void)hipEventDestroy(e->rx_side1_ev[k]);
   for (hipEvent_t pe : e->md_part_done) (void)hipEventDestroy(pe);
@@ -214,6 +216,7 @@ int scema_md_register_replica(scema_md_engine *e, const char *matid, int32_t rep
     else ++it;
   }
   e->dir.erase_suffix(suffix);
+  t->matid = matid;
   e->topos[topo_key(matid, replica)] = std::move(t);
   return SCEMA_MD_OK;
 }

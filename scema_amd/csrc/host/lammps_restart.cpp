@@ -285,12 +285,19 @@ void decode_image(const Restart &R, int64_t im, int out[3]) {
   else { out[0] = (int)(im & 1023) - 512; out[1] = (int)((im >> 10) & 1023) - 512; out[2] = (int)((im >> 20) & 1023) - 512; }
 }
 
-// atom_style full + the OPLS styles -> scema_md_system (0-based indices in ascending tag order, unwrapped coordinates)
+// atom_style full + the OPLS styles -> scema_md_system (0-based indices in ascending tag order, unwrapped coordinates).
+// allow_atomic: an atom_style atomic file (the reference's examples/streched_polyhedron/nanoscale_input/init.sic_1.bin, units metal) gives a
+// BARE replica -- types, masses, box, x, v; no charges, no topology, zero Lennard-Jones coefficients -- for a potential that is attached to
+// the material afterwards (scema_md_sw_configure); velocities of a units metal file go from A/ps to A/fs.
 template <class Sink>
-int to_system(const Restart &R, std::string &err, Sink sink) {
-  if (R.atom_style != "full") { err = "replica restart must be atom_style full (found " + R.atom_style + ")"; return SCEMA_MD_ERR_ARG; }
-  if (R.pair_style != "lj/cut/coul/long") { err = "replica restart must carry pair_style lj/cut/coul/long"; return SCEMA_MD_ERR_ARG; }
-  if (R.units != "real") { err = "replica restart must be in units real (found " + R.units + ")"; return SCEMA_MD_ERR_ARG; }
+int to_system(const Restart &R, std::string &err, Sink sink, bool allow_atomic = false) {
+  const bool atomic = allow_atomic && R.atom_style == "atomic";
+  if (!atomic) {
+    if (R.atom_style != "full") { err = "replica restart must be atom_style full (found " + R.atom_style + ")"; return SCEMA_MD_ERR_ARG; }
+    if (R.pair_style != "lj/cut/coul/long") { err = "replica restart must carry pair_style lj/cut/coul/long"; return SCEMA_MD_ERR_ARG; }
+    if (R.units != "real") { err = "replica restart must be in units real (found " + R.units + ")"; return SCEMA_MD_ERR_ARG; }
+  } else if (R.units != "real" && R.units != "metal") { err = "an atom_style atomic restart must be in units real or metal (found " + R.units + ")"; return SCEMA_MD_ERR_ARG; }
+  const double vscale = (atomic && R.units == "metal") ? 1.0e-3 : 1.0;
   const size_t n = (size_t)R.natoms;
   const int nt = R.ntypes;
   if ((int)R.mass.size() != nt) { err = "mass array size"; return SCEMA_MD_ERR_IO; }
@@ -307,13 +314,23 @@ int to_system(const Restart &R, std::string &err, Sink sink) {
     const size_t i = order[k];
     if (R.type[i] < 1 || R.type[i] > nt) { err = "atom type out of range"; return SCEMA_MD_ERR_IO; }
     type[k] = R.type[i] - 1;
-    q[k] = R.q[i];
+    q[k] = atomic ? 0.0 : R.q[i];
     int im[3];
     decode_image(R, R.image[i], im);
     x[3 * k] = R.x[3 * i] + im[0] * L[0] + im[1] * R.tilt[0] + im[2] * R.tilt[1];
     x[3 * k + 1] = R.x[3 * i + 1] + im[1] * L[1] + im[2] * R.tilt[2];
     x[3 * k + 2] = R.x[3 * i + 2] + im[2] * L[2];
-    for (int c = 0; c < 3; c++) v[3 * k + c] = R.v[3 * i + c];
+    for (int c = 0; c < 3; c++) v[3 * k + c] = vscale * R.v[3 * i + c];
+  }
+  if (atomic) {
+    std::vector<double> eps0((size_t)nt * nt, 0.0), sig1((size_t)nt * nt, 1.0);
+    scema_md_system s;
+    std::memset(&s, 0, sizeof s);
+    s.natoms = (int32_t)n; s.ntypes = nt;
+    s.type = type.data(); s.charge = q.data(); s.mass = R.mass.data(); s.eps = eps0.data(); s.sigma = sig1.data();
+    for (int k = 0; k < 3; k++) { s.box[k] = R.boxlo[k]; s.box[3 + k] = R.boxhi[k]; s.box[6 + k] = R.tilt[k]; }
+    s.x = x.data(); s.v = v.data();
+    return sink(s);
   }
   // pair coefficients: explicit pairs as stored, the others mixed the way pair lj/cut/coul/long would (mix_flag)
   std::vector<double> eps((size_t)nt * nt), sig((size_t)nt * nt);
@@ -463,7 +480,7 @@ int scema_md_load_lammps_restart(scema_md_engine *e, const char *matid, int32_t 
   Restart R;
   std::string err;
   int rc = parse(path, R, err, true);
-  if (!rc) rc = to_system(R, err, [&](const scema_md_system &s) { return scema_md_register_replica(e, matid, replica, &s); });
+  if (!rc) rc = to_system(R, err, [&](const scema_md_system &s) { return scema_md_register_replica(e, matid, replica, &s); }, true);
   if (rc && !err.empty()) fprintf(stderr, "[scema_md] %s: %s\n", path ? path : "(null)", err.c_str());
   return rc;
 }
