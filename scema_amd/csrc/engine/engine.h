@@ -5,8 +5,9 @@
 //   engine_topo.cpp    topology preprocessing of a registered replica (exclusions, SHAKE clusters, bonded tiles)
 //   engine_kspace.cpp  what a LAMMPS `run` sets up on the host: g_ewald, k-vectors, PPPM grid, the real-space polynomial, fix deform's box path
 //   engine_run.cpp     one run of a batch with the OPLS force stage (run_phase), slots
-//   engine_reax.cpp    the same with the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
-//   engine_sw.cpp      the same with the Stillinger-Weber force stage (run_phase_sw) and the SW entry points
+//   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF or the SW stage
+//   engine_reax.cpp    the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
+//   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
 //   engine_state.cpp   state store: branch rule, replica / state files
@@ -187,20 +188,24 @@ struct SwMaterial {
   DevBuf d_tab;
 };
 
-// what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds
+// what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
+// checks `kind` first and writes every field it checks.
+enum class RowKind { Opls, Reax, Sw };
 struct ListSig {
   bool valid = false;
+  RowKind kind = RowKind::Opls;
   unsigned long long topo = 0;    // Topo::id the rows were built for
   unsigned long long state = 0;   // State::id the rows were last built for (a hint: whether they still hold is decided on the device)
-  int nc[3] = {0, 0, 0}, capj = 0, maxneigh = 0, npad = 0;
-  double rlist = 0.0, cut_lj = 0.0, cut_coul = 0.0;
+  int npad = 0;
+  double rlist = 0.0;
+  int nc[3] = {0, 0, 0}, capj = 0, maxneigh = 0;   // OPLS: cell grid, capacity of a tile's j table and of a cluster row
+  double cut_lj = 0.0, cut_coul = 0.0;
+  long long stamp = 0;                             // rows of RxSlot / SwSlot: the force-field / material stamp they were built under,
+  int mimg[3] = {0, 0, 0}, cap[2] = {0, 0};        // the image search, the row capacities (RowNeed)
   // the list's scalars at the end of the run that left it: what the displacement test of the next run needs, and the statistics
   double corners_hold[24];
   int ago = 0, maxj_seen = 0;
   unsigned long long nentries = 0, nentries_ref = 0, nrowent = 0;
-  long long rx_stamp = 0;        // != 0: the rows are ReaxFF rows (RxSlot), built under this force-field stamp; capj holds the near rows' stride
-  int rx_mimg[3] = {0, 0, 0};
-  long long sw_stamp = 0;        // != 0: the rows are Stillinger-Weber rows (SwSlot), built under this material stamp; maxneigh holds their capacity, rx_mimg the image search
 };
 struct Slot {
   std::unique_ptr<RxSlot> rx;
@@ -340,7 +345,7 @@ struct scema_md_engine {
                                           // exactly four streams in a fixed order of creation -- the runtime deals streams to its four hardware queues in that order,
                                           // and two of these four sharing a queue costs 7 % (bench: a second engine of a process drew such a deal)
   hipEvent_t rx_side1_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t rx_fork = nullptr;           // main stream -> the parts' streams at the start of the step loop
+  hipEvent_t row_fork = nullptr;          // run_rows: main stream -> the parts' streams at the start of the step loop (created on first use)
   std::map<std::string, std::unique_ptr<Topo>> topos;
   std::map<std::string, std::unique_ptr<State>> states;
   std::vector<std::unique_ptr<Slot>> slots;
@@ -362,8 +367,8 @@ struct scema_md_engine {
   std::vector<hipEvent_t> ev_pool;
   Profile prof;
   std::string err;
-  double neigh_grow = 1.0;   // headroom factor of the cluster rows, x1.5 per overflow
-  double jtab_grow = 1.0;    // headroom factor of the tile j tables, x1.25 per overflow (-> smaller cells)
+  double neigh_grow = 1.0;   // headroom factor of the cluster rows, x1.5 and more per overflow (grow_after_overflow)
+  double jtab_grow = 1.0;    // headroom factor of the tile j tables, x1.25 and more per overflow (-> smaller cells)
   int overflow_bits = 0;     // what overflowed in the last run: 4 = a tile's j table, 8 = a cluster row
   double overflow_need_j = 1.0, overflow_need_row = 1.0;   // ... and the largest demand / capacity the run saw (the retry grows by at least that)
   long long unsettled_updates = 0;   // updates of a world > 1 without a communicator that the next call found unsettled and let stand
@@ -387,7 +392,7 @@ struct scema_md_engine {
   long long sw_stamp = 0;
   DevBuf d_swviews;
   std::vector<SwView> h_swviews;
-  hipEvent_t sw_fork = nullptr, sw_done = nullptr;   // part batches of an SW run: start and end of the second part (created on first use)
+  hipEvent_t sw_done = nullptr;   // part batches of an SW run: the end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
   scema::SimPlan last_plan;
@@ -444,7 +449,7 @@ SwMaterial *sw_material(scema_md_engine *e, const std::string &matid);
 bool sw_bare_replica(const Topo &t);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
-// the batch skeleton both force stages share (engine_run.cpp)
+// the batch skeleton every force stage shares (engine_rows.cpp)
 struct Part { int off = 0, n = 0; hipStream_t st = nullptr; };   // a part batch: positions [off, off + n) of the launch order, issued on st
 std::vector<int> batch_order(const std::vector<ActiveSim> &sims, int nparts, const std::function<long(int)> &tie = nullptr);
 std::vector<Part> split_parts(int ns, int nparts);
@@ -467,6 +472,67 @@ int sum_timed_launches(scema_md_engine *e, size_t n, double &ms, long long &laun
 int collect_faults(scema_md_engine *e, int ns);
 void lists_hold(scema_md_engine *e, const std::vector<ActiveSim> &sims, bool valid, bool counts);
 bool keep_list_switch();
+// the run overflowed: its retry runs with capacities grown by the demand the run saw, at least by x1.25 (j tables) / x1.5 (rows)
+void grow_after_overflow(scema_md_engine *e);
+// static evaluation of one state by a run of no steps (the parity hooks), repeated while capacities overflow; the results are in e->h_sc[0], slot 0
+int eval_static(scema_md_engine *e, State *s, const RunSpec &spec);
+
+// A run on per-atom neighbour rows (engine_rows.cpp: RowRun is its driver) and the force stage it is given
+struct RowNeed {   // what the stage needs for one replica
+  double rlist = 0.0, skin = 0.0;
+  long long stamp = 0;          // rows built under another stamp are rebuilt
+  int cap[2] = {0, 0};          // row capacities (ReaxFF: rows and near rows; SW: rows, 0): rows that are kept keep theirs
+  int mimg[3] = {0, 0, 0};      // the image search along each box vector (0: minimum image), filled in by the driver
+};
+struct RowRun;
+struct RowStage {
+  const RowKind kind;
+  const int zero_extra;         // the stage's largest entry of the zero-fill table (32-bit words)
+  RowRun *run = nullptr;        // the run the stage serves (set by the driver)
+  RowStage(RowKind kind_, int zero_extra_) : kind(kind_), zero_extra(zero_extra_) {}
+  virtual ~RowStage() = default;
+  virtual int nparts() const = 0;   // part batches of the run
+  // list radius, skin, stamp and row capacities of a replica of T over the boxes R; the stage's own refusals
+  virtual int rows(Topo &T, const BoxRange &R, RowNeed &need) = 0;
+  // the stage's slot and view of position pos, its zero-fill entries (e->h_zerotab) and batch flags; S and need are final
+  virtual int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) = 0;
+  virtual int upload() = 0;     // the views to the device
+  virtual int setup() = 0;      // what step 0 enqueues before the first force call
+  virtual void forces(hipStream_t st, int pos0, int n, int step, int part) = 0;
+  // streams of the parts beyond the first (parts[k].st) and the events that mark their ends (done[k - 1])
+  virtual int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) = 0;
+  // the read-back of the run's results enqueued on the main stream: RowRun::read_scalars and what the stage puts around it
+  virtual int read_back() = 0;
+  // after the synchronisation: statistics and profile, the stage's fault bits (faults), the largest demand / capacity of its rows
+  virtual int after_read_back(int fault, double &need) = 0;
+  virtual int faults(int fault) = 0;   // the stage's own fault bits of a run or a minimisation -> its error, or 0
+};
+struct RowRun {
+  scema_md_engine *e;
+  std::vector<ActiveSim> &sims;
+  const RunSpec &spec;
+  RowStage &stage;
+  const int ns;
+  std::vector<int> order;
+  std::vector<std::vector<FlipEvent>> flips;   // by position
+  std::vector<Part> parts;
+  std::vector<hipEvent_t> done;                // per part beyond the first: the end of its launches
+  int maxatoms = 0, maxpad = 0, maxsteps = 0;
+  bool any_validate = false;
+  const SimDev *D = nullptr;
+
+  RowRun(scema_md_engine *e_, std::vector<ActiveSim> &sims_, const RunSpec &spec_, RowStage &stage_)
+      : e(e_), sims(sims_), spec(spec_), stage(stage_), ns((int)sims_.size()), flips(sims_.size()) { stage.run = this; }
+  int lay_out();
+  int lay_out_sim(int pos);
+  int setup_step();
+  int minimise();
+  int make_parts(int nparts);
+  void run_steps();
+  int read_scalars();
+  int finish();
+};
+int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

@@ -178,8 +178,7 @@ void scema_md_destroy(scema_md_engine *e) {
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->rx_fork) (void)hipEventDestroy(e->rx_fork);
-  if (e->sw_fork) (void)hipEventDestroy(e->sw_fork);
+  if (e->row_fork) (void)hipEventDestroy(e->row_fork);
   if (e->sw_done) (void)hipEventDestroy(e->sw_done);
   if (e->rx_side1) (void)hipStreamDestroy(e->rx_side1);
   for (int k = 0; k < 4; k++) if (e->rx_side1_ev[k]) (void)hipEventDestroy(e->rx_side1_ev[k]);

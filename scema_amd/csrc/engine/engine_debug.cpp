@@ -78,24 +78,12 @@ int scema_md_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid,
   std::unique_ptr<State> tmp;
   int rc = debug_state(e, qp_id, matid, replica, &s, tmp);
   if (rc) return rc;
-  std::vector<ActiveSim> sims(1);
-  sims[0].st = s;
-  sims[0].nsteps = 0;
-  sims[0].dt = 1.0;
-  sims[0].temperature = 300.0;
-  for (int attempt = 0; attempt < 6; attempt++) {
-    if ((rc = prepare_slots(e, sims))) return rc;
-    RunSpec R;
-    R.use_shake = use_shake;
-    R.ev_always = 1;
-    R.static_only = 1;
-    R.nvt = 0;
-    rc = run_phase(e, sims, R);
-    if (rc != SCEMA_MD_ERR_OVERFLOW) break;
-    if (e->overflow_bits & 4) e->jtab_grow *= 1.25;
-    if ((e->overflow_bits & 8) || !(e->overflow_bits & 4)) e->neigh_grow *= 1.5;
-  }
-  if (rc) return rc;
+  RunSpec R;
+  R.use_shake = use_shake;
+  R.ev_always = 1;
+  R.static_only = 1;
+  R.nvt = 0;
+  if ((rc = eval_static(e, s, R))) return rc;
   const SimScalars &sc = e->h_sc[0];
   if (f) HIPCHK(hipMemcpy(f, e->slots[0]->f.p, 3 * (size_t)s->topo->natoms * 8, hipMemcpyDeviceToHost));
   if (energies) std::memcpy(energies, sc.eng, sizeof sc.eng);

@@ -83,10 +83,6 @@ int equil_restore(EquilCtx &c) {
   HIPCHK(hipMemcpyAsync(c.s->v.p, c.vb.p, bytes, hipMemcpyDeviceToDevice, e->stream));
   return SCEMA_MD_OK;
 }
-void grow_lists(scema_md_engine *e) {
-  if (e->overflow_bits & 4) e->jtab_grow *= 1.25;
-  if ((e->overflow_bits & 8) || !(e->overflow_bits & 4)) e->neigh_grow *= 1.5;
-}
 // min_style sd ; minimize etol ftol maxiter maxeval.  info[4]: iterations, force evaluations, initial and final energy
 int equil_minimize(EquilCtx &c, double etol, double ftol, int maxiter, int maxeval, int *stop, double *info) {
   scema_md_engine *e = c.e;
@@ -104,7 +100,7 @@ int equil_minimize(EquilCtx &c, double etol, double ftol, int maxiter, int maxev
     R.minimize = 1; R.min_etol = etol; R.min_ftol = ftol; R.min_maxiter = maxiter; R.min_maxeval = maxeval;
     rc = run_phase(e, sims, R);
     if (rc != SCEMA_MD_ERR_OVERFLOW) break;
-    grow_lists(e);
+    grow_after_overflow(e);
     if ((rc = equil_restore(c))) return rc;
     rc = SCEMA_MD_ERR_OVERFLOW;
   }
@@ -149,7 +145,7 @@ int equil_run_nh(EquilCtx &c, int nsteps, double dt, double t_start, double t_st
     rc = run_phase(e, sims, R);
     if (rc == SCEMA_MD_ERR_OVERFLOW) {
       if (++failures > 12) return fail(e, SCEMA_MD_ERR_ARG, "equilibration: a run segment kept failing (box leaving its range or lists overflowing)");
-      if (e->overflow_bits & 1) grow_lists(e);
+      if (e->overflow_bits & 1) grow_after_overflow(e);
       else seg = std::max(10, seg / 2);   // the box left the range the segment was laid out for: shorter segments
       if ((rc = equil_restore(c))) return rc;
       if (!first) std::memcpy(c.s->box, carry.box, sizeof carry.box);

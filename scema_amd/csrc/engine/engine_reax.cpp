@@ -4,9 +4,7 @@
 
 namespace scema_eng {
 
-// run_phase_reax is run_phase with another force stage: the same step sequence (k_pre, k_initial_integrate, forces,
-// k_final_integrate, k_post, k_remap), the same batch rules (longest run first, active prefix), the same box flips; no
-// cells, no Ewald tables, no SHAKE (lammps_scripts_reax/in.strain.lammps has no fix shake and no kspace_style).
+// run_phase_reax is the run on per-atom neighbour rows (run_rows, engine_rows.cpp) with the ReaxFF force stage.
 
 // (the pointers of RxView are qualified as global-memory pointers in device code, reax/rx_types.h: a cast in both passes of the compiler)
 #define RXSET(dst, src) dst = (decltype(dst))(src)
@@ -87,177 +85,8 @@ static int ensure_rtype(scema_md_engine *e, Topo &T) {
 
 namespace {
 
-struct RxRun {
-  scema_md_engine *e;
-  std::vector<ActiveSim> &sims;
-  const RunSpec &spec;
-  const int ns;
-  const double rlist;
-  std::vector<int> order;
-  std::vector<std::vector<FlipEvent>> flips;   // by position
-  int maxatoms = 0, maxpad = 0, maxsteps = 0;
-  bool col16 = true;   // columns of the charge-equilibration matrix as 16-bit atom indices (every replica of the batch has at most 65 536 atoms)
-  bool all_sym = false, any_precond = false, any_validate = false, any_cold = false, inject_precond_failure = false;
-  const SimDev *D = nullptr;
-  RxView *VV = nullptr;
-  const RxParams *RP = nullptr;
-  RxSide side = {};
-  const RxSide *sidep = nullptr;
-  std::vector<hipEvent_t> *evp = nullptr;
-  size_t ev_used = 0;
-  std::vector<Part> parts;
-  std::vector<RxSide> sides;     // per part: its side stream for the bond-order chain and the events around it
-  std::vector<hipEvent_t> done;  // per part beyond the first: the end of its launches
-
-  RxRun(scema_md_engine *e_, std::vector<ActiveSim> &sims_, const RunSpec &spec_)
-      : e(e_), sims(sims_), spec(spec_), ns((int)sims_.size()), rlist(e_->rx_host.swb + e_->rx_skin), flips(sims_.size()) {}
-
-  int lay_out();
-  int lay_out_sim(int pos);
-  RxQeqPlan plan_for(int step) const;
-  int setup_step();
-  int minimise();
-  int make_parts(int nparts);
-  void run_steps();
-  int finish();
-};
-
-// The replica at position pos of the launch order: box range, images, row capacities, its slot, its SimDev and RxView
-int RxRun::lay_out_sim(int pos) {
-  const int i = order[pos];
-  ActiveSim &A = sims[i];
-  Topo &T = *A.st->topo;
-  int rc = ensure_rtype(e, T);
-  if (rc) return rc;
-  const SimScalars &hsc = e->h_sc[i];
-  BoxRange R;
-  if (!box_range(spec, A, hsc.box, R, flips[pos]))
-    return fail(e, SCEMA_MD_ERR_BOX, "fix deform is changing yz too much with xy: the strain would tilt yz past half the box");
-  SimDev S;
-  std::memset(&S, 0, sizeof S);
-  RxView V;
-  std::memset(&V, 0, sizeof V);
-  bool small = false;
-  for (int d = 0; d < 3; d++) small = small || R.w[d] < 2.0 * rlist;
-  for (int d = 0; d < 3; d++) {
-    V.mimg[d] = small ? (int)std::ceil(rlist / R.w[d]) : 0;
-    if (V.mimg[d] > 2) return fail(e, SCEMA_MD_ERR_BOX, "box width %.3f < (cutoff+skin)/2 = %.3f in dim %d", R.w[d], 0.5 * rlist, d);
-  }
-  const int n = T.natoms, npad = (n + 63) / 64 * 64;
-  const double rho = n / R.vol_min;
-  int maxnb = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.2 * e->neigh_grow) + 32;
-  maxnb = (maxnb + 7) / 8 * 8;
-  const int maxbd = (int)std::ceil(24 * e->neigh_grow);
-  double rnear = 0.0;   // (the widest near row of the force field sizes the rows)
-  for (int k = 0; k < RX_MAXT * RX_MAXT; k++) rnear = std::max(rnear, std::sqrt(e->rx_host.rnear2[k]));
-  int maxnbn = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rnear * rnear * rnear * 1.5 * e->neigh_grow) + 32;
-  maxnbn = (maxnbn + 7) / 8 * 8;
-  Slot &sl = *e->slots[i];
-  // A run that follows another ReaxFF run of the same state on the same slot (the sampling run behind the straining run of an evaluation; the
-  // straining run of the next update) keeps that run's neighbour rows, as the OPLS path does (run_phase): rows, near rows, reference positions
-  // and the preconditioner live in the slot, the list's scalars come back through the slot's signature (prepare_slots), and k_phase_init /
-  // k_keep_validate decide on the device whether they still hold.  The rows keep the strides they were built with.
-  bool keep = false;
-  {
-    const ListSig &g = sl.sig;
-    if (spec.keep_list && keep_list_switch() && g.valid && g.rx_stamp != 0 && g.rx_stamp == e->rx_stamp && g.topo == T.id && g.rlist == rlist && g.npad == npad &&
-        (spec.keep_list == 1 || g.state == A.st->id) && !hsc.force_rebuild && !hsc.overflow && maxnb <= g.maxneigh && maxnbn <= g.capj &&
-        g.rx_mimg[0] == V.mimg[0] && g.rx_mimg[1] == V.mimg[1] && g.rx_mimg[2] == V.mimg[2] && sl.rx) {
-      keep = true;
-      maxnb = g.maxneigh; maxnbn = g.capj;
-    }
-  }
-  S.keep_list = keep ? spec.keep_list : 0;
-  any_validate = any_validate || S.keep_list == 2;
-  {
-    ListSig &g = sl.sig;   // what this run's rows are built for; valid once the run has ended without a fault
-    g.valid = false;
-    g.rx_stamp = e->rx_stamp;
-    g.topo = T.id;
-    g.rlist = rlist; g.npad = npad; g.maxneigh = maxnb; g.capj = maxnbn;
-    for (int d = 0; d < 3; d++) g.rx_mimg[d] = V.mimg[d];
-  }
-  rc = ensure_slot(e, sl, n, 64, 1, 0, 64);
-  if (rc) return rc;
-  if (!sl.rx) sl.rx.reset(new RxSlot());
-  RxSlot &Rs = *sl.rx;
-  if ((rc = ensure_rx_slot(e, Rs, n, npad, maxnb, maxbd, maxnbn, col16))) return rc;
-  sim_common(S, e->p, spec, A, sl, e->d_sc.as<SimScalars>() + i);
-  S.natoms = n; S.npad = npad; S.ntypes = T.ntypes;
-  S.use_shake = 0;
-  if (spec.minimize) S.min_incremental = 1;   // the neighbour rebuild wraps the atoms into the box: trial points by increments
-  S.neigh_delay = 0;   // neigh_modify every 1 delay 0 (in.set.lammps:32 of the reax scripts); rebuilt when needed, same pairs inside the cutoff
-  S.tdof = 3.0 * n - 3.0;
-  S.skin = e->rx_skin;
-  S.far_band = e->rx_skin;
-  V.n = n; V.npad = npad; V.maxnb = maxnb; V.maxbd = maxbd;
-  RXSET(V.rtype, T.d_rtype.as<int>()); RXSET(V.x, S.x); RXSET(V.q, Rs.q.as<double>());
-  RXSET(V.nbn_cnt, Rs.nbn_cnt.as<int>()); RXSET(V.nbn, Rs.nbn.as<int>()); RXSET(V.nbnT, Rs.nbnT.as<int>()); V.maxnbn = maxnbn; V.rnear2 = rnear * rnear;
-  RXSET(V.qpart, Rs.qpart.as<double>());
-  RXSET(V.nb_cnt, Rs.nb_cnt.as<int>()); RXSET(V.nb, (int *)nullptr); RXSET(V.bd_cnt, Rs.bd_cnt.as<int>()); RXSET(V.bd, Rs.bd.as<int>()); RXSET(V.bd_rev, Rs.bd_rev.as<int>());
-  RXSET(V.bd_bop, Rs.bd_bop.as<double>()); RXSET(V.bd_c, Rs.bd_c.as<double>()); RXSET(V.bd_bo, Rs.bd_bo.as<double>()); RXSET(V.bd_g, Rs.bd_g.as<double>()); RXSET(V.bd_cb, Rs.bd_cb.as<double>());
-  RXSET(V.deltap, Rs.deltap.as<double>()); RXSET(V.total_bo, Rs.total_bo.as<double>()); RXSET(V.cd_delta, Rs.cd_delta.as<double>()); RXSET(V.hd, Rs.hd.as<double>());
-  RXSET(V.f, S.f); RXSET(V.hval, col16 ? nullptr : Rs.hval.as<double>()); RXSET(V.hpk, col16 ? Rs.hval.as<unsigned long long>() : nullptr); RXSET(V.s, Rs.s.as<double>()); RXSET(V.t, Rs.t.as<double>());
-  V.warm = (spec.qeq_continue || A.st->qhist_valid) ? 1 : 0;
-  RXSET(V.hcol16, (unsigned short *)nullptr); RXSET(V.hcol32, col16 ? nullptr : Rs.hcol.as<int>()); RXSET(V.hlen, Rs.hlen.as<int>()); RXSET(V.nbT, Rs.nbT.as<int>());
-  RXSET(V.hown, Rs.hown.as<int>()); RXSET(V.hownlen, Rs.hownlen.as<int>()); RXSET(V.nb_own0, Rs.nb_own0.as<int>());
-  RXSET(V.s_hist, Rs.s_hist.as<double>()); RXSET(V.t_hist, Rs.t_hist.as<double>()); RXSET(V.qwork, Rs.qwork.as<double>());
-  // the bonded-pattern preconditioner needs one image per neighbour (boxes at least two list radii wide: every production replica)
-  V.pm_on = (e->rx_precond && V.mimg[0] == 0 && V.mimg[1] == 0 && V.mimg[2] == 0) ? 1 : 0;
-  if (V.pm_on && scema_env("SCEMA_MD_TEST_QEQ_PRECOND_FAILS")) inject_precond_failure = true;   // test hook: this run reports a solve that did not converge
-  any_precond = any_precond || V.pm_on;
-  // the symmetric form of the solve: rows sorted by partner (one image per neighbour), both vectors of the replica in a workgroup's LDS
-  all_sym = all_sym && V.mimg[0] == 0 && V.mimg[1] == 0 && V.mimg[2] == 0 && 2 * (size_t)npad * 16 + 4096 <= 128 * 1024;
-  RXSET(V.pm_len, Rs.pm_len.as<int>()); RXSET(V.pm_col, Rs.pm_col.as<int>()); RXSET(V.pm_raw, Rs.pm_raw.as<double>()); RXSET(V.pm_val, Rs.pm_val.as<double>());
-  RXSET(V.eparts, Rs.misc.as<double>());                         // [0, 13) doubles
-  RXSET(V.qstat, (int *)(Rs.misc.as<char>() + 128));             // 6 ints
-  RXSET(V.overflow, (int *)(Rs.misc.as<char>() + 160));
-  RXSET(V.sweep_acc, (long long *)(Rs.misc.as<char>() + 168));   // 2 x 8 bytes
-  e->h_zerotab.push_back(MdkZero{sl.wrapn.as<int>(), 3 * (long long)n});
-  e->h_sims[pos] = S;
-  e->h_rxviews[pos] = V;
-  maxatoms = std::max(maxatoms, n); maxpad = std::max(maxpad, npad); maxsteps = std::max(maxsteps, A.nsteps);
-  return SCEMA_MD_OK;
-}
-
-// every replica's layout, and its upload
-int RxRun::lay_out() {
-  e->h_sims.assign(ns, SimDev());
-  e->h_rxviews.assign(ns, RxView());
-  col16 = !(scema_env("SCEMA_MD_RX_COL32") && atoi(scema_env("SCEMA_MD_RX_COL32")) != 0);   // (test switch: 32-bit columns for any size)
-  for (int i = 0; i < ns; i++) col16 = col16 && sims[i].st->topo->natoms <= 65536;
-  e->h_zerotab.clear();
-  all_sym = col16 && e->rx_sym;
-  for (int pos = 0; pos < ns; pos++)
-    if (const int rc = lay_out_sim(pos)) return rc;
-  HIPCHK(e->d_sims.ensure((size_t)ns * sizeof(SimDev)));
-  HIPCHK(e->d_rxviews.ensure((size_t)ns * sizeof(RxView)));
-  HIPCHK(hipMemcpyAsync(e->d_sims.p, e->h_sims.data(), (size_t)ns * sizeof(SimDev), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(e->d_rxviews.p, e->h_rxviews.data(), (size_t)ns * sizeof(RxView), hipMemcpyHostToDevice, e->stream));
-  if (!e->h_zerotab.empty()) {   // the wrap counters of every replica start from zero: one launch
-    HIPCHK(e->d_zerotab.ensure(e->h_zerotab.size() * sizeof(MdkZero)));
-    HIPCHK(hipMemcpyAsync(e->d_zerotab.p, e->h_zerotab.data(), e->h_zerotab.size() * sizeof(MdkZero), hipMemcpyHostToDevice, e->stream));
-    mdk_zero_many(e->stream, e->d_zerotab.as<MdkZero>(), (int)e->h_zerotab.size(), 3 * (long long)maxatoms);
-  }
-  D = e->d_sims.as<SimDev>();
-  VV = e->d_rxviews.as<RxView>();
-  RP = e->d_rxparams.as<RxParams>();
-  return SCEMA_MD_OK;
-}
-
-// how a solve is issued (md_reax.h): as many iterations as the slowest solve of the last run took plus a margin; the first
-// solves of a run that has replicas without a history take longer
-RxQeqPlan RxRun::plan_for(int step) const {
-  RxQeqPlan pl;
-  pl.launch = (step < 4 && any_cold) ? e->rx_qeq_launch_cold : e->rx_qeq_launch;
-  pl.setup = step == 0 ? 1 : 0;
-  pl.precond = any_precond ? 1 : 0;
-  pl.sym = all_sym ? 1 : 0;
-  return pl;
-}
-
 // many device-to-device copies in one launch, from a table that lives on the host only until the launch is issued
-static int copy_many(scema_md_engine *e, const std::vector<MdkCopy> &tab, long long maxn) {
+int copy_many(scema_md_engine *e, const std::vector<MdkCopy> &tab, long long maxn) {
   HIPCHK(e->d_copytab.ensure(tab.size() * sizeof(MdkCopy)));
   HIPCHK(hipMemcpyAsync(e->d_copytab.p, tab.data(), tab.size() * sizeof(MdkCopy), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));   // (the table is a local)
@@ -265,133 +94,170 @@ static int copy_many(scema_md_engine *e, const std::vector<MdkCopy> &tab, long l
   return SCEMA_MD_OK;
 }
 
-// step 0 of the whole batch on the main stream
-int RxRun::setup_step() {
-  hipStream_t st = e->stream;
-  const bool prof = e->p.profile != 0 && !spec.minimize;
-  evp = prof ? &e->ev_pool : nullptr;
-  mdk_phase_init(st, D, ns);
-  if (any_validate) mdk_keep_validate(st, D, ns, maxatoms);
-  // Charge-equilibration history: kept in place when this run follows another one on the same slots; else a state that has run
-  // before brings its own (one copy launch for the batch); the rest start from zeros like a new fix qeq/reax
-  std::vector<MdkCopy> tab;
-  long long maxn = 0;
-  for (int pos = 0; pos < ns; pos++) {
-    ActiveSim &A = sims[order[pos]];
-    const RxView &V = e->h_rxviews[pos];
-    if (!V.warm) any_cold = true;
-    if (spec.qeq_continue || !A.st->qhist_valid) continue;
-    const long long np = V.npad;
-    tab.push_back(MdkCopy{A.st->qhist.as<double>(), V.s_hist, 4 * np});
-    tab.push_back(MdkCopy{A.st->qhist.as<double>() + 4 * np, V.t_hist, 3 * np});
-    maxn = std::max(maxn, 4 * np);
-  }
-  if (!tab.empty())
-    if (const int rc = copy_many(e, tab, maxn)) return rc;
-  // the bond-order chain of the force stage on the engine's side stream, next to the charge chain (md_reax.hip); SCEMA_REAX_OVERLAP=0: one stream
-  side = {e->stream2, e->ev_fork, e->ev_up, e->ev_join};
-  sidep = (e->stream2 && e->ev_up && e->rx_overlap) ? &side : nullptr;
-  mdk_reax_phase_init(st, VV, ns, maxpad);
-  mdk_reax_forces(st, D, VV, RP, ns, maxatoms, rlist, e->rx_qeq_tol, e->rx_qeq_maxiter, plan_for(0), e->rx_terms, col16, evp, &ev_used, sidep);
-  mdk_final_integrate(st, D, ns, maxatoms, 0);
-  if (spec.nh) mdk_setup_post_nh(st, D, ns);
-  else mdk_setup_post(st, D, ns);
-  return SCEMA_MD_OK;
-}
+struct RxStage : RowStage {
+  scema_md_engine *e;
+  const double rlist;
+  double rnear = 0.0;   // the widest near row of the force field sizes the near rows
+  bool col16 = true;    // columns of the charge-equilibration matrix as 16-bit atom indices (every replica of the batch has at most 65 536 atoms)
+  bool all_sym = false, any_precond = false, any_cold = false, inject_precond_failure = false;
+  RxView *VV = nullptr;
+  const RxParams *RP = nullptr;
+  std::vector<hipEvent_t> *evp = nullptr;
+  size_t ev_used = 0;
+  bool overlap = false;
+  std::vector<RxSide> sides;     // per part: its side stream for the bond-order chain and the events around it
 
-// min_style sd (md_equil.hip): the line search of every replica on the device, forces from the ReaxFF stage
-int RxRun::minimise() {
-  auto force = [&] {
-    mdk_reax_forces(e->stream, D, VV, RP, ns, maxatoms, rlist, e->rx_qeq_tol, e->rx_qeq_maxiter, plan_for(1), e->rx_terms, col16, nullptr, nullptr, sidep);
+  RxStage(scema_md_engine *e_, const std::vector<ActiveSim> &sims) : RowStage(RowKind::Reax, 0), e(e_), rlist(e_->rx_host.swb + e_->rx_skin) {
+    e->h_rxviews.assign(sims.size(), RxView());
+    for (int k = 0; k < RX_MAXT * RX_MAXT; k++) rnear = std::max(rnear, std::sqrt(e->rx_host.rnear2[k]));
+    col16 = !(scema_env("SCEMA_MD_RX_COL32") && atoi(scema_env("SCEMA_MD_RX_COL32")) != 0);   // (test switch: 32-bit columns for any size)
+    for (const ActiveSim &A : sims) col16 = col16 && A.st->topo->natoms <= 65536;
+    all_sym = col16 && e->rx_sym;
+  }
+
+  // (From six replicas per part on: 8 / 10 replicas whole 494 / 595 evaluations/s, as two parts 460 / 564; 12 / 16 / 18 replicas 617 / 776 / 847
+  // whole, 661 / 852 / 910 as two.  Three and four parts lose at every size -- each part has a side stream too, and a process has four hardware
+  // queues: 36 replicas 1 171 as two parts, 902 as three.  profiles/r06_x_reax_parts_ab.log)
+  int nparts() const override { return (e->rx_halves >= 2 && run->ns >= 6 * e->rx_halves && !run->spec.minimize) ? e->rx_halves : 1; }
+
+  int rows(Topo &T, const BoxRange &R, RowNeed &need) override {
+    if (const int rc = ensure_rtype(e, T)) return rc;
+    const double rho = T.natoms / R.vol_min;
+    const int maxnb = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.2 * e->neigh_grow) + 32;
+    const int maxnbn = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rnear * rnear * rnear * 1.5 * e->neigh_grow) + 32;
+    need.rlist = rlist; need.skin = e->rx_skin; need.stamp = e->rx_stamp;
+    need.cap[0] = (maxnb + 7) / 8 * 8;
+    need.cap[1] = (maxnbn + 7) / 8 * 8;
     return SCEMA_MD_OK;
-  };
-  auto map_fault = [&](int fault) {
-    if (fault & 32) {
-      e->rx_qeq_failed = true;   // (eval_chunk retries once with the reference's Jacobi preconditioner if the approximate inverse was on)
-      return fail(e, SCEMA_MD_ERR_ARG, "charge equilibration did not converge to %.1e in %d iterations", e->rx_qeq_tol, e->rx_qeq_maxiter);
-    }
-    e->overflow_bits = (fault & 1) ? 8 : 0;
-    return (fault & 1) ? SCEMA_MD_ERR_OVERFLOW : SCEMA_MD_OK;
-  };
-  return run_minimiser(e, order, maxatoms, spec, false, force, map_fault);
-}
-
-// Part batches on as many streams (replicas are independent: each part runs its own sequence of steps, and one part's launch gaps, tails
-// and latency-bound kernels are filled by the other's work), each with its own side stream for the bond-order chain: part 0 on the engine's
-// main and side streams, part 1 on stream3 and the engine's fourth stream, further parts -- a measurement aid, two is the optimum -- on
-// streams of their own (created once, kept).  SCEMA_REAX_HALVES=0: one.
-int RxRun::make_parts(int nparts) {
-  const int pool0 = (e->stream3 && e->rx_side1) ? 2 : 1;   // parts served without the pool
-  while (nparts > pool0 && (int)e->rx_parts.size() < nparts - pool0) {
-    scema_md_engine::RxPart pt;
-    bool ok = hipStreamCreateWithFlags(&pt.main, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&pt.side, hipStreamNonBlocking) == hipSuccess;
-    for (int k = 0; k < 4 && ok; k++) ok = hipEventCreateWithFlags(&pt.ev[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) return fail(e, SCEMA_MD_ERR_DEVICE, "could not create the streams of the ReaxFF part batches");
-    e->rx_parts.push_back(pt);
   }
-  parts = split_parts(ns, nparts);
-  sides.assign(nparts, side);
-  parts[0].st = e->stream;
-  for (int k = 1; k < nparts; k++) {
-    if (k == 1 && pool0 == 2) {
-      parts[k].st = e->stream3;
-      sides[k] = RxSide{e->rx_side1, e->rx_side1_ev[0], e->rx_side1_ev[1], e->rx_side1_ev[2]};
-      done.push_back(e->rx_side1_ev[3]);
-    } else {
-      const auto &pt = e->rx_parts[k - pool0];
-      parts[k].st = pt.main;
-      sides[k] = RxSide{pt.side, pt.ev[0], pt.ev[1], pt.ev[2]};
-      done.push_back(pt.ev[3]);
-    }
-  }
-  if (nparts > 1 && !e->rx_fork) HIPCHK(hipEventCreateWithFlags(&e->rx_fork, hipEventDisableTiming));
-  return fork_parts(e, parts, e->rx_fork);
-}
 
-void RxRun::run_steps() {
-  const FlipSchedule flip_at = flip_schedule(flips, e->h_sims);
-  for (int step = 1; step <= maxsteps; step++) {
-    bool any = false;
-    for (size_t k = 0; k < parts.size(); k++) {
-      const Part &pt = parts[k];
-      const int na = active_prefix(e->h_sims, pt, step);
-      if (na == 0) continue;
-      any = true;
-      const SimDev *Dh = D + pt.off;
-      hipStream_t sh = pt.st;
-      if (spec.nh) { mdk_pre_nh(sh, Dh, na); mdk_initial_integrate_nh(sh, Dh, na, maxatoms); }
-      else { mdk_pre(sh, Dh, na); mdk_initial_integrate(sh, Dh, na, maxatoms); }
-      // the first solves of a run start from an empty history (RX_QEQ_COLD in md_reax.hip: setup is solve 1)
-      mdk_reax_forces(sh, Dh, VV + pt.off, RP, na, maxatoms, rlist, e->rx_qeq_tol, e->rx_qeq_maxiter, plan_for(step), e->rx_terms, col16, evp, &ev_used,
-                      sidep ? &sides[k] : nullptr);
-      mdk_final_integrate(sh, Dh, na, maxatoms, 1);
-      if (spec.nh) mdk_post_nh(sh, Dh, na);
-      else mdk_post(sh, Dh, na);
-      if (spec.deform) mdk_remap(sh, Dh, na, maxatoms);
-      e->prof.md_steps += na;
-    }
-    if (!any) break;
-    auto fl = flip_at.find(step);
-    if (fl != flip_at.end())
-      for (const auto &pk : fl->second) {
-        const FlipEvent &fe = flips[pk.first][pk.second];
-        mdk_flip(parts[part_of(parts, pk.first)].st, D + pk.first, fe.tilt[0], fe.tilt[1], fe.tilt[2]);
-        e->prof.box_flips += 1;
-      }
+  // rows, near rows, reference positions and the preconditioner live in the slot
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
+    const Topo &T = *A.st->topo;
+    const int n = S.natoms, npad = S.npad, maxnb = need.cap[0], maxnbn = need.cap[1];
+    const int maxbd = (int)std::ceil(24 * e->neigh_grow);
+    if (!sl.rx) sl.rx.reset(new RxSlot());
+    RxSlot &Rs = *sl.rx;
+    if (const int rc = ensure_rx_slot(e, Rs, n, npad, maxnb, maxbd, maxnbn, col16)) return rc;
+    RxView V;
+    std::memset(&V, 0, sizeof V);
+    for (int d = 0; d < 3; d++) V.mimg[d] = need.mimg[d];
+    V.n = n; V.npad = npad; V.maxnb = maxnb; V.maxbd = maxbd;
+    RXSET(V.rtype, T.d_rtype.as<int>()); RXSET(V.x, S.x); RXSET(V.q, Rs.q.as<double>());
+    RXSET(V.nbn_cnt, Rs.nbn_cnt.as<int>()); RXSET(V.nbn, Rs.nbn.as<int>()); RXSET(V.nbnT, Rs.nbnT.as<int>()); V.maxnbn = maxnbn; V.rnear2 = rnear * rnear;
+    RXSET(V.qpart, Rs.qpart.as<double>());
+    RXSET(V.nb_cnt, Rs.nb_cnt.as<int>()); RXSET(V.nb, (int *)nullptr); RXSET(V.bd_cnt, Rs.bd_cnt.as<int>()); RXSET(V.bd, Rs.bd.as<int>()); RXSET(V.bd_rev, Rs.bd_rev.as<int>());
+    RXSET(V.bd_bop, Rs.bd_bop.as<double>()); RXSET(V.bd_c, Rs.bd_c.as<double>()); RXSET(V.bd_bo, Rs.bd_bo.as<double>()); RXSET(V.bd_g, Rs.bd_g.as<double>()); RXSET(V.bd_cb, Rs.bd_cb.as<double>());
+    RXSET(V.deltap, Rs.deltap.as<double>()); RXSET(V.total_bo, Rs.total_bo.as<double>()); RXSET(V.cd_delta, Rs.cd_delta.as<double>()); RXSET(V.hd, Rs.hd.as<double>());
+    RXSET(V.f, S.f); RXSET(V.hval, col16 ? nullptr : Rs.hval.as<double>()); RXSET(V.hpk, col16 ? Rs.hval.as<unsigned long long>() : nullptr); RXSET(V.s, Rs.s.as<double>()); RXSET(V.t, Rs.t.as<double>());
+    V.warm = (run->spec.qeq_continue || A.st->qhist_valid) ? 1 : 0;
+    RXSET(V.hcol16, (unsigned short *)nullptr); RXSET(V.hcol32, col16 ? nullptr : Rs.hcol.as<int>()); RXSET(V.hlen, Rs.hlen.as<int>()); RXSET(V.nbT, Rs.nbT.as<int>());
+    RXSET(V.hown, Rs.hown.as<int>()); RXSET(V.hownlen, Rs.hownlen.as<int>()); RXSET(V.nb_own0, Rs.nb_own0.as<int>());
+    RXSET(V.s_hist, Rs.s_hist.as<double>()); RXSET(V.t_hist, Rs.t_hist.as<double>()); RXSET(V.qwork, Rs.qwork.as<double>());
+    // the bonded-pattern preconditioner needs one image per neighbour (boxes at least two list radii wide: every production replica)
+    V.pm_on = (e->rx_precond && V.mimg[0] == 0 && V.mimg[1] == 0 && V.mimg[2] == 0) ? 1 : 0;
+    if (V.pm_on && scema_env("SCEMA_MD_TEST_QEQ_PRECOND_FAILS")) inject_precond_failure = true;   // test hook: this run reports a solve that did not converge
+    any_precond = any_precond || V.pm_on;
+    // the symmetric form of the solve: rows sorted by partner (one image per neighbour), both vectors of the replica in a workgroup's LDS
+    all_sym = all_sym && V.mimg[0] == 0 && V.mimg[1] == 0 && V.mimg[2] == 0 && 2 * (size_t)npad * 16 + 4096 <= 128 * 1024;
+    RXSET(V.pm_len, Rs.pm_len.as<int>()); RXSET(V.pm_col, Rs.pm_col.as<int>()); RXSET(V.pm_raw, Rs.pm_raw.as<double>()); RXSET(V.pm_val, Rs.pm_val.as<double>());
+    RXSET(V.eparts, Rs.misc.as<double>());                         // [0, 13) doubles
+    RXSET(V.qstat, (int *)(Rs.misc.as<char>() + 128));             // 6 ints
+    RXSET(V.overflow, (int *)(Rs.misc.as<char>() + 160));
+    RXSET(V.sweep_acc, (long long *)(Rs.misc.as<char>() + 168));   // 2 x 8 bytes
+    e->h_rxviews[pos] = V;
+    return SCEMA_MD_OK;
   }
-}
 
-// the end of the run: join, charge history back to the states, solver statistics, profile, faults, the signatures of the rows that stand
-int RxRun::finish() {
-  hipStream_t st = e->stream;
-  int rc = join_parts(e, parts, done.data());
-  if (rc) return rc;
-  mdk_phase_end(st, D, ns, maxatoms);
-  {  // the states keep the history for their next run (a failed update drops it: backup_states)
+  int upload() override {
+    const size_t bytes = e->h_rxviews.size() * sizeof(RxView);
+    HIPCHK(e->d_rxviews.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(e->d_rxviews.p, e->h_rxviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    VV = e->d_rxviews.as<RxView>();
+    RP = e->d_rxparams.as<RxParams>();
+    return SCEMA_MD_OK;
+  }
+
+  // how a solve is issued (md_reax.h): as many iterations as the slowest solve of the last run took plus a margin; the first
+  // solves of a run that has replicas without a history take longer
+  RxQeqPlan plan_for(int step) const {
+    RxQeqPlan pl;
+    pl.launch = (step < 4 && any_cold) ? e->rx_qeq_launch_cold : e->rx_qeq_launch;
+    pl.setup = step == 0 ? 1 : 0;
+    pl.precond = any_precond ? 1 : 0;
+    pl.sym = all_sym ? 1 : 0;
+    return pl;
+  }
+
+  int setup() override {
+    const int ns = run->ns;
+    const RunSpec &spec = run->spec;
+    evp = (e->p.profile != 0 && !spec.minimize) ? &e->ev_pool : nullptr;
+    // Charge-equilibration history: kept in place when this run follows another one on the same slots; else a state that has run
+    // before brings its own (one copy launch for the batch); the rest start from zeros like a new fix qeq/reax
     std::vector<MdkCopy> tab;
     long long maxn = 0;
     for (int pos = 0; pos < ns; pos++) {
-      ActiveSim &A = sims[order[pos]];
+      const ActiveSim &A = run->sims[run->order[pos]];
+      const RxView &V = e->h_rxviews[pos];
+      if (!V.warm) any_cold = true;
+      if (spec.qeq_continue || !A.st->qhist_valid) continue;
+      const long long np = V.npad;
+      tab.push_back(MdkCopy{A.st->qhist.as<double>(), V.s_hist, 4 * np});
+      tab.push_back(MdkCopy{A.st->qhist.as<double>() + 4 * np, V.t_hist, 3 * np});
+      maxn = std::max(maxn, 4 * np);
+    }
+    if (!tab.empty())
+      if (const int rc = copy_many(e, tab, maxn)) return rc;
+    // the bond-order chain of the force stage on the engine's side stream, next to the charge chain (md_reax.hip); SCEMA_REAX_OVERLAP=0: one stream
+    sides.assign(1, RxSide{e->stream2, e->ev_fork, e->ev_up, e->ev_join});
+    overlap = e->stream2 && e->ev_up && e->rx_overlap;
+    mdk_reax_phase_init(e->stream, VV, ns, run->maxpad);
+    return SCEMA_MD_OK;
+  }
+
+  // (the first solves of a run start from an empty history: RX_QEQ_COLD in md_reax.hip, setup is solve 1)
+  void forces(hipStream_t st, int pos0, int n, int step, int part) override {
+    mdk_reax_forces(st, run->D + pos0, VV + pos0, RP, n, run->maxatoms, rlist, e->rx_qeq_tol, e->rx_qeq_maxiter, plan_for(step), e->rx_terms, col16, evp, &ev_used,
+                    overlap ? &sides[part] : nullptr);
+  }
+
+  // Each part has its own side stream for the bond-order chain: part 0 on the engine's main and side streams, part 1 on stream3 and the
+  // engine's fourth stream, further parts -- a measurement aid, two is the optimum -- on streams of their own (created once, kept).
+  // SCEMA_REAX_HALVES=0: one.
+  int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) override {
+    const int nparts = (int)parts.size();
+    const int pool0 = (e->stream3 && e->rx_side1) ? 2 : 1;   // parts served without the pool
+    while (nparts > pool0 && (int)e->rx_parts.size() < nparts - pool0) {
+      scema_md_engine::RxPart pt;
+      bool ok = hipStreamCreateWithFlags(&pt.main, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&pt.side, hipStreamNonBlocking) == hipSuccess;
+      for (int k = 0; k < 4 && ok; k++) ok = hipEventCreateWithFlags(&pt.ev[k], hipEventDisableTiming) == hipSuccess;
+      if (!ok) return fail(e, SCEMA_MD_ERR_DEVICE, "could not create the streams of the ReaxFF part batches");
+      e->rx_parts.push_back(pt);
+    }
+    sides.resize(nparts);
+    for (int k = 1; k < nparts; k++) {
+      if (k == 1 && pool0 == 2) {
+        parts[k].st = e->stream3;
+        sides[k] = RxSide{e->rx_side1, e->rx_side1_ev[0], e->rx_side1_ev[1], e->rx_side1_ev[2]};
+        done.push_back(e->rx_side1_ev[3]);
+      } else {
+        const auto &pt = e->rx_parts[k - pool0];
+        parts[k].st = pt.main;
+        sides[k] = RxSide{pt.side, pt.ev[0], pt.ev[1], pt.ev[2]};
+        done.push_back(pt.ev[3]);
+      }
+    }
+    return SCEMA_MD_OK;
+  }
+
+  // charge history back to the states, the scalars, the solver statistics: in this order on the main stream
+  int read_back() override {
+    const int ns = run->ns;
+    std::vector<MdkCopy> tab;   // the states keep the history for their next run (a failed update drops it: backup_states)
+    long long maxn = 0;
+    for (int pos = 0; pos < ns; pos++) {
+      const ActiveSim &A = run->sims[run->order[pos]];
       const RxView &V = e->h_rxviews[pos];
       const long long np = V.npad;
       HIPCHK(A.st->qhist.ensure(7 * (size_t)np * 8));
@@ -400,76 +266,68 @@ int RxRun::finish() {
       maxn = std::max(maxn, 4 * np);
       A.st->qhist_valid = true;
     }
-    if ((rc = copy_many(e, tab, maxn))) return rc;
+    int rc;
+    if ((rc = copy_many(e, tab, maxn)) || (rc = run->read_scalars())) return rc;
+    // (the solver statistics of all replicas in ONE read-back: two small copies per replica were 2 x 72 launch gaps of 24 us per run)
+    HIPCHK(e->d_rxstat.ensure(8 * (size_t)ns * sizeof(long long)));
+    e->h_rxstat.assign(8 * (size_t)ns, 0);
+    mdk_reax_collect_stats(e->stream, VV, ns, e->d_rxstat.as<long long>());
+    HIPCHK(hipMemcpyAsync(e->h_rxstat.data(), e->d_rxstat.p, 8 * (size_t)ns * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    return SCEMA_MD_OK;
   }
-  HIPCHK(hipMemcpyAsync(e->h_sc.data(), e->d_sc.p, (size_t)ns * sizeof(SimScalars), hipMemcpyDeviceToHost, st));
-  // (the solver statistics of all replicas in ONE read-back: two small copies per replica were 2 x 72 launch gaps of 24 us per run)
-  HIPCHK(e->d_rxstat.ensure(8 * (size_t)ns * sizeof(long long)));
-  e->h_rxstat.assign(8 * (size_t)ns, 0);
-  mdk_reax_collect_stats(st, e->d_rxviews.as<RxView>(), ns, e->d_rxstat.as<long long>());
-  HIPCHK(hipMemcpyAsync(e->h_rxstat.data(), e->d_rxstat.p, 8 * (size_t)ns * sizeof(long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
-  const long long *qs = e->h_rxstat.data();
-  if (evp) {
-    // the matrix sweep of the charge equilibration, the HBM-bound kernel of this path: HIP-event time of every launch, and what
-    // the launches read by the algorithm: 8 bytes per stored matrix entry (value and 16-bit column in one word, RxView::hpk; 8 + 4 with 32-bit columns) and RX_SWEEP_ROW_BYTES per row,
-    // for every replica and sweep it took part in (counted on the device, k_rx_qeq_finish)
-    if ((rc = sum_timed_launches(e, ev_used / 2, e->prof.rx_sweep_ms, e->prof.rx_sweep_launches, e->prof.rx_sweep_union_ms))) return rc;
-    for (int pos = 0; pos < ns; pos++) {
-      e->prof.rx_sweep_entries += (double)qs[8 * pos + 6];
-      e->prof.rx_sweep_rows += (double)qs[8 * pos + 7];
+
+  // (the rows' demand is not read back: need stays 1, the retry after an overflow grows by the fixed step)
+  int after_read_back(int fault, double &) override {
+    const int ns = run->ns;
+    const long long *qs = e->h_rxstat.data();
+    if (evp) {
+      // the matrix sweep of the charge equilibration, the HBM-bound kernel of this path: HIP-event time of every launch, and what
+      // the launches read by the algorithm: 8 bytes per stored matrix entry (value and 16-bit column in one word, RxView::hpk; 8 + 4 with 32-bit columns) and RX_SWEEP_ROW_BYTES per row,
+      // for every replica and sweep it took part in (counted on the device, k_rx_qeq_finish)
+      if (const int rc = sum_timed_launches(e, ev_used / 2, e->prof.rx_sweep_ms, e->prof.rx_sweep_launches, e->prof.rx_sweep_union_ms)) return rc;
+      for (int pos = 0; pos < ns; pos++) {
+        e->prof.rx_sweep_entries += (double)qs[8 * pos + 6];
+        e->prof.rx_sweep_rows += (double)qs[8 * pos + 7];
+      }
+      e->prof.rx_sweep_col_bytes = col16 ? 0 : 4;   // (packed entries: the column rides in the value's word)
+      e->prof.rx_sweep_symmetric = all_sym ? 1 : 0;
     }
-    e->prof.rx_sweep_col_bytes = col16 ? 0 : 4;   // (packed entries: the column rides in the value's word)
-    e->prof.rx_sweep_symmetric = all_sym ? 1 : 0;
+    int most = 0, most_cold = 0;
+    for (int i = 0; i < ns; i++) {
+      e->rx_qeq_iters += (int)qs[8 * i];
+      e->rx_qeq_solves += (int)qs[8 * i + 1] - (e->h_rxviews[i].warm ? RX_QEQ_COLD_SOLVES : 0);   // (a warm run starts its solve count past the cold ones)
+      most = std::max(most, (int)qs[8 * i + 2]);
+      most_cold = std::max(most_cold, (int)qs[8 * i + 5]);
+      e->rx_qeq_slow += (int)qs[8 * i + 3];
+    }
+    // iterations issued as launches in the next run: what the slowest solve of this one needed (of all replicas and steps), plus one.  A launch
+    // that finds every replica converged still costs its two kernels and their gaps (28 us); a replica that needs more than was issued
+    // finishes in one workgroup (80 us per iteration).  Scan on the 72-replica set, slowest solve 15: 13 launches 543, 14: 591, 15: 603,
+    // 16: 598, 18: 590 evaluations/s (tools/reax_launch_scan.sh, profiles/r04_zh_launch_scan.txt)
+    if (!e->rx_qeq_launch_pinned) {
+      // (the floor of 8 dated from the Jacobi preconditioner's 11 iterations per solve; with 3.9 per solve -- slowest 5 -- it issued 8: scan
+      // with the round-5 preconditioner, 72 replicas: 3 launches 577, 4: 747, 5: 978, 6: 969, 7: 965, 8: 959 evaluations/s)
+      if (most > 0) e->rx_qeq_launch = std::max(4, most + 1);
+      if (most_cold > 0) e->rx_qeq_launch_cold = std::max(4, most_cold + 1);
+    }
+    return faults(fault | (inject_precond_failure ? 32 : 0));
   }
-  const int fault = collect_faults(e, ns);
-  int most = 0, most_cold = 0;
-  for (int i = 0; i < ns; i++) {
-    e->rx_qeq_iters += (int)qs[8 * i];
-    e->rx_qeq_solves += (int)qs[8 * i + 1] - (e->h_rxviews[i].warm ? RX_QEQ_COLD_SOLVES : 0);   // (a warm run starts its solve count past the cold ones)
-    most = std::max(most, (int)qs[8 * i + 2]);
-    most_cold = std::max(most_cold, (int)qs[8 * i + 5]);
-    e->rx_qeq_slow += (int)qs[8 * i + 3];
+
+  int faults(int fault) override {
+    if (fault & 32) {
+      e->rx_qeq_failed = true;   // (eval_chunk retries once with the reference's Jacobi preconditioner if the approximate inverse was on)
+      return fail(e, SCEMA_MD_ERR_ARG, "charge equilibration did not converge to %.1e in %d iterations", e->rx_qeq_tol, e->rx_qeq_maxiter);
+    }
+    return SCEMA_MD_OK;
   }
-  // iterations issued as launches in the next run: what the slowest solve of this one needed (of all replicas and steps), plus one.  A launch
-  // that finds every replica converged still costs its two kernels and their gaps (28 us); a replica that needs more than was issued
-  // finishes in one workgroup (80 us per iteration).  Scan on the 72-replica set, slowest solve 15: 13 launches 543, 14: 591, 15: 603,
-  // 16: 598, 18: 590 evaluations/s (tools/reax_launch_scan.sh, profiles/r04_zh_launch_scan.txt)
-  if (!e->rx_qeq_launch_pinned) {
-    // (the floor of 8 dated from the Jacobi preconditioner's 11 iterations per solve; with 3.9 per solve -- slowest 5 -- it issued 8: scan
-    // with the round-5 preconditioner, 72 replicas: 3 launches 577, 4: 747, 5: 978, 6: 969, 7: 965, 8: 959 evaluations/s)
-    if (most > 0) e->rx_qeq_launch = std::max(4, most + 1);
-    if (most_cold > 0) e->rx_qeq_launch_cold = std::max(4, most_cold + 1);
-  }
-  if (fault & 16) return fail(e, SCEMA_MD_ERR_ARG, "a simulation became unstable (non-finite or runaway atom positions): overlapping atoms or a time step too long for ReaxFF");
-  if ((fault & 32) || inject_precond_failure) {
-    e->rx_qeq_failed = true;   // (eval_chunk retries once with the reference's Jacobi preconditioner if the approximate inverse was on)
-    return fail(e, SCEMA_MD_ERR_ARG, "charge equilibration did not converge to %.1e in %d iterations", e->rx_qeq_tol, e->rx_qeq_maxiter);
-  }
-  e->overflow_bits = ((fault & 1) ? (1 | 8) : 0) | (fault & 64);
-  if (fault & 1) return SCEMA_MD_ERR_OVERFLOW;
-  if (fault & 64) return SCEMA_MD_ERR_OVERFLOW;   // the barostat took the box out of the range this segment was laid out for
-  lists_hold(e, sims, !spec.minimize, false);
-  return SCEMA_MD_OK;
-}
+};
 
 }  // namespace
 
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec) {
   if (!e->rx_ready) return fail(e, SCEMA_MD_ERR_ARG, "force field 'reax' asked for but no ReaxFF force-field file is loaded (scema_md_reax_configure)");
-  RxRun R(e, sims, spec);
-  // (From six replicas per part on: 8 / 10 replicas whole 494 / 595 evaluations/s, as two parts 460 / 564; 12 / 16 / 18 replicas 617 / 776 / 847
-  // whole, 661 / 852 / 910 as two.  Three and four parts lose at every size -- each part has a side stream too, and a process has four hardware
-  // queues: 36 replicas 1 171 as two parts, 902 as three.  profiles/r06_x_reax_parts_ab.log)
-  const int nparts = (e->rx_halves >= 2 && R.ns >= 6 * e->rx_halves && !spec.minimize) ? e->rx_halves : 1;
-  R.order = batch_order(sims, nparts);
-  int rc;
-  if ((rc = R.lay_out()) || (rc = R.setup_step())) return rc;
-  if (spec.minimize) return R.minimise();
-  if ((rc = R.make_parts(nparts))) return rc;
-  R.run_steps();
-  return R.finish();
+  RxStage stage(e, sims);
+  return run_rows(e, sims, spec, stage);
 }
 
 }  // namespace scema_eng
@@ -609,23 +467,13 @@ int scema_md_reax_debug_compute(scema_md_engine *e, int32_t qp_id, const char *m
   std::unique_ptr<State> tmp;
   int rc = debug_state(e, qp_id, matid, replica, &s, tmp);
   if (rc) return rc;
-  std::vector<ActiveSim> sims(1);
-  sims[0].st = s;
-  sims[0].nsteps = 0;
-  sims[0].dt = 1.0;
-  sims[0].temperature = 300.0;
   const bool saved = e->reax_active;
   e->reax_active = true;
   const long long it0 = e->rx_qeq_iters;
-  for (int attempt = 0; attempt < 6; attempt++) {
-    if ((rc = prepare_slots(e, sims))) break;
-    RunSpec R;
-    R.nvt = 0;
-    R.static_only = 1;
-    rc = run_phase(e, sims, R);
-    if (rc != SCEMA_MD_ERR_OVERFLOW) break;
-    e->neigh_grow *= 1.5;
-  }
+  RunSpec R;
+  R.nvt = 0;
+  R.static_only = 1;
+  rc = eval_static(e, s, R);
   e->reax_active = saved;
   if (rc) return rc;
   const int n = s->topo->natoms;

@@ -1,5 +1,5 @@
-// engine_run.cpp -- one "run" of a batch with the OPLS force stage: slots, launch policy, launch sequence of the MD steps, what comes back;
-// and the batch skeleton the ReaxFF run (engine_reax.cpp) shares with it
+// engine_run.cpp -- one "run" of a batch with the OPLS force stage: slots, launch policy, launch sequence of the MD steps, what comes back
+// (the batch skeleton it shares with the other force stages is in engine_rows.cpp)
 #include "engine.h"
 #include "../md_env.h"
 
@@ -60,225 +60,6 @@ int ensure_slot(scema_md_engine *e, Slot &sl, int natoms, int maxneigh, int ncel
     sl.cap_k = kc;
   }
   return SCEMA_MD_OK;
-}
-
-// -------------------------------------------------------------------------------------------
-// the batch skeleton of both force stages
-// -------------------------------------------------------------------------------------------
-// Launch order: longest run first, so the active simulations are always a prefix (ties broken by `tie`, ascending); dealt round-robin into
-// nparts part batches at consecutive positions: part p takes the ranks p, p + nparts, ... of the length order, so each part is itself sorted
-// longest first and the parts carry the same mix of run lengths
-std::vector<int> batch_order(const std::vector<ActiveSim> &sims, int nparts, const std::function<long(int)> &tie) {
-  const int ns = (int)sims.size();
-  std::vector<int> by_len(ns), order;
-  for (int i = 0; i < ns; i++) by_len[i] = i;
-  std::stable_sort(by_len.begin(), by_len.end(), [&](int a, int b) {
-    if (sims[a].nsteps != sims[b].nsteps) return sims[a].nsteps > sims[b].nsteps;
-    return tie && tie(a) < tie(b);
-  });
-  order.reserve(ns);
-  for (int p = 0; p < nparts; p++)
-    for (int r = p; r < ns; r += nparts) order.push_back(by_len[r]);
-  return order;
-}
-std::vector<Part> split_parts(int ns, int nparts) {
-  std::vector<Part> parts(nparts);
-  for (int p = 0, off = 0; p < nparts; p++) {
-    parts[p].off = off;
-    parts[p].n = (ns - p + nparts - 1) / nparts;
-    off += parts[p].n;
-  }
-  return parts;
-}
-int part_of(const std::vector<Part> &parts, int pos) {
-  int h = 0;
-  while (h + 1 < (int)parts.size() && pos >= parts[h + 1].off) h++;
-  return h;
-}
-int active_prefix(const std::vector<SimDev> &h_sims, const Part &p, int step) {   // (a part is sorted longest first)
-  int na = 0;
-  while (na < p.n && h_sims[p.off + na].nsteps >= step) na++;
-  return na;
-}
-// the parts beyond the first start behind what the main stream has issued so far
-int fork_parts(scema_md_engine *e, const std::vector<Part> &parts, hipEvent_t ev) {
-  if (parts.size() < 2) return SCEMA_MD_OK;
-  HIPCHK(hipEventRecord(ev, e->stream));
-  for (size_t k = 1; k < parts.size(); k++) HIPCHK(hipStreamWaitEvent(parts[k].st, ev, 0));
-  return SCEMA_MD_OK;
-}
-// the main stream waits for the end of every other part (an event of its own per part: done[k - 1] for part k)
-int join_parts(scema_md_engine *e, const std::vector<Part> &parts, const hipEvent_t *done) {
-  for (size_t k = 1; k < parts.size(); k++) {
-    HIPCHK(hipEventRecord(done[k - 1], parts[k].st));
-    HIPCHK(hipStreamWaitEvent(e->stream, done[k - 1], 0));
-  }
-  return SCEMA_MD_OK;
-}
-
-// The boxes a replica passes through in this run: start and end of fix deform's path, with the boxes just before each flip (where the tilt
-// is largest) as extremes, and both ends of the range the barostat may dilate the box to (tilts with it).  False: the path cannot be run.
-bool box_range(const RunSpec &spec, const ActiveSim &A, const double *box, BoxRange &R, std::vector<FlipEvent> &flips) {
-  double box_end[9];
-  std::memcpy(box_end, box, sizeof box_end);
-  R.boxes.assign(2, HostBox());
-  if (spec.deform) {
-    std::vector<HostBox> extremes;
-    if (!deform_trajectory(box, A.rates, A.dt, A.nsteps, box_end, flips, extremes)) return false;
-    R.boxes.insert(R.boxes.end(), extremes.begin(), extremes.end());
-  }
-  box_derive(box, R.boxes[0]);
-  box_derive(box_end, R.boxes[1]);
-  if (spec.nh && spec.npt && spec.box_margin > 0.0)
-    for (int sgn = -1; sgn <= 1; sgn += 2) {
-      double bx[9];
-      const double f = 1.0 + sgn * spec.box_margin;
-      for (int d = 0; d < 3; d++) {
-        const double c = 0.5 * (box[d] + box[3 + d]);
-        bx[d] = c + (box[d] - c) * f;
-        bx[3 + d] = c + (box[3 + d] - c) * f;
-      }
-      for (int k = 6; k < 9; k++) bx[k] = box[k] * f;
-      HostBox hb;
-      box_derive(bx, hb);
-      R.boxes.push_back(hb);
-    }
-  for (const HostBox &hb : R.boxes) {
-    double w[3];
-    perp_widths(hb, w);
-    for (int d = 0; d < 3; d++) R.w[d] = std::min(R.w[d], w[d]);
-    R.vol_min = std::min(R.vol_min, hb.vol);
-    R.vol_max = std::max(R.vol_max, hb.vol);
-  }
-  return true;
-}
-
-// the fields of SimDev that do not depend on the force field (call after the slot's buffers are sized)
-void sim_common(SimDev &S, const scema_md_params &P, const RunSpec &spec, const ActiveSim &A, const Slot &sl, SimScalars *sc) {
-  S.nsteps = A.nsteps;
-  if (spec.sample) {
-    // in.homogenization.lammps:57 (the reax copy is the same): nav = nss/10 (nss/1000 beyond 10000 steps); nss/nav windows
-    S.nav = (A.nsteps > 10000) ? A.nsteps / 1000 : A.nsteps / 10;
-    if (S.nav < 1) S.nav = 1;
-    S.nwin = A.nsteps / S.nav;
-  }
-  S.nvt = spec.nvt;
-  S.deform = spec.deform;
-  if (spec.nh) {
-    S.ramp = 1; S.npt = spec.npt; S.nh_total = std::max(spec.nh_total, 1); S.lavg_nav = spec.lavg_nav;
-    S.t_start = spec.t_start; S.t_stop = spec.t_stop; S.p_target = spec.p_target; S.p_freq = 1.0 / spec.p_period; S.box_margin = spec.box_margin;
-  }
-  if (spec.minimize) {
-    S.min_etol = spec.min_etol; S.min_ftol = spec.min_ftol; S.min_dmax = 0.1; S.min_maxiter = spec.min_maxiter; S.min_maxeval = spec.min_maxeval;
-  }
-  S.t_chain = std::min(P.t_chain, MD_MAXCHAIN);
-  S.dt = A.dt; S.t_target = A.temperature; S.t_freq = 1.0 / P.t_period;
-  for (int k = 0; k < 6; k++) S.rates[k] = A.rates[k];
-  const Topo &T = *A.st->topo;
-  S.type = T.d_type.as<int>(); S.q = T.d_q.as<double>(); S.mass = T.d_mass.as<double>();
-  S.x = A.st->x.as<double>(); S.v = A.st->v.as<double>(); S.f = sl.f.as<double>();
-  S.wrapn = sl.wrapn.as<int>(); S.xhold = sl.xhold.as<double>(); S.sfac = sl.sfac.as<double>(); S.cell_count = sl.cell_count.as<int>();
-  S.sc = sc;
-}
-
-// min_style sd (md_equil.hip): every replica runs its own line search, decided on the device between two force evaluations (`force`); the
-// host only looks every 16 evaluations whether the search is over -- stop_on_any_overflow: once a replica has overflowed or every one has
-// stopped (OPLS); else once every replica has either stopped or overflowed (ReaxFF).  x0 and the search direction live in the slots'
-// backup arrays.  `map_fault` turns the union of the replicas' fault bits into the caller's error (0: none).
-int run_minimiser(scema_md_engine *e, const std::vector<int> &order, int maxatoms, const RunSpec &spec, bool stop_on_any_overflow,
-                  const std::function<int()> &force, const std::function<int(int)> &map_fault) {
-  const int ns = (int)order.size();
-  hipStream_t st = e->stream;
-  const SimDev *D = e->d_sims.as<SimDev>();
-  std::vector<double *> ptrs(2 * (size_t)ns);
-  for (int pos = 0; pos < ns; pos++) {
-    Slot &sl = *e->slots[order[pos]];
-    ptrs[pos] = sl.xbak.as<double>();
-    ptrs[ns + pos] = sl.vbak.as<double>();
-    HIPCHK(hipMemsetAsync(sl.vbak.p, 0, 3 * (size_t)e->h_sims[pos].natoms * 8, st));
-  }
-  HIPCHK(e->d_minptr.ensure(ptrs.size() * sizeof(double *)));
-  HIPCHK(hipMemcpyAsync(e->d_minptr.p, ptrs.data(), ptrs.size() * sizeof(double *), hipMemcpyHostToDevice, st));
-  double *const *x0s = e->d_minptr.as<double *>(), *const *hsd = e->d_minptr.as<double *>() + ns;
-  mdk_min_reduce(st, D, ns, maxatoms, hsd);
-  mdk_min_decide(st, D, ns);
-  const long long cap = (long long)spec.min_maxeval + 2LL * spec.min_maxiter + 8;
-  const auto stopped = [](const SimScalars &c) { return c.min_phase == 4; };
-  const auto overflowed = [](const SimScalars &c) { return c.overflow != 0; };
-  bool done = false;
-  for (long long ev_n = 0; ev_n < cap && !done;) {
-    for (int r = 0; r < 16; r++, ev_n++) {
-      mdk_min_pre(st, D, ns);
-      mdk_min_move(st, D, ns, maxatoms, x0s, hsd);
-      const int rc = force();
-      if (rc) return rc;
-      mdk_min_reduce(st, D, ns, maxatoms, hsd);
-      mdk_min_decide(st, D, ns);
-    }
-    HIPCHK(hipMemcpyAsync(e->h_sc.data(), e->d_sc.p, (size_t)ns * sizeof(SimScalars), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const auto first = e->h_sc.begin(), last = first + ns;
-    done = stop_on_any_overflow ? std::any_of(first, last, overflowed) || std::all_of(first, last, stopped)
-                                : std::all_of(first, last, [&](const SimScalars &c) { return overflowed(c) || stopped(c); });
-  }
-  HIPCHK(hipGetLastError());
-  int fault = 0;
-  for (int i = 0; i < ns; i++) fault |= e->h_sc[i].overflow;
-  if (fault & 16) return fail(e, SCEMA_MD_ERR_ARG, "a simulation became unstable during the minimisation (non-finite positions)");
-  if (const int rc = map_fault(fault)) return rc;
-  if (!done) return fail(e, SCEMA_MD_ERR_ARG, "minimiser did not stop within its evaluation budget");
-  return SCEMA_MD_OK;
-}
-
-// box flips of the run (fix deform, flip yes): step -> (position, flip of that position) that flip after it
-FlipSchedule flip_schedule(const std::vector<std::vector<FlipEvent>> &flips, const std::vector<SimDev> &h_sims) {
-  FlipSchedule at;
-  for (size_t pos = 0; pos < flips.size(); pos++)
-    for (size_t k = 0; k < flips[pos].size(); k++)
-      if (flips[pos][k].step < h_sims[pos].nsteps) at[flips[pos][k].step].push_back({(int)pos, (int)k});
-  return at;
-}
-
-// HIP-event times of the first n timed launches (e->ev_pool: launch l from 2 l to 2 l + 1) into `ms` and `launches`, and the time with at
-// least one of them in flight (the launches of several part batches overlap) into `union_ms`
-int sum_timed_launches(scema_md_engine *e, size_t n, double &ms, long long &launches, double &union_ms) {
-  for (size_t l = 0; l < n; l++) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e->ev_pool[2 * l], e->ev_pool[2 * l + 1]));
-    ms += t;
-    launches += 1;
-  }
-  union_ms += event_union_ms(e->ev_pool, n);
-  return SCEMA_MD_OK;
-}
-
-// the union of the fault bits of the run's replicas; their list builds go to the profile
-int collect_faults(scema_md_engine *e, int ns) {
-  int fault = 0;
-  for (int i = 0; i < ns; i++) {
-    fault |= e->h_sc[i].overflow;
-    e->prof.neigh_builds += e->h_sc[i].nbuilds;
-  }
-  return fault;
-}
-
-// the rows on the device hold for the positions this run ended at (`counts`: with the list's statistics of the OPLS rows)
-void lists_hold(scema_md_engine *e, const std::vector<ActiveSim> &sims, bool valid, bool counts) {
-  for (size_t i = 0; i < sims.size(); i++) {
-    ListSig &g = e->slots[i]->sig;
-    const SimScalars &c = e->h_sc[i];
-    g.valid = valid;
-    g.state = sims[i].st->id;
-    std::memcpy(g.corners_hold, c.corners_hold, sizeof g.corners_hold);
-    g.ago = c.ago;
-    if (counts) { g.maxj_seen = c.maxj_seen; g.nentries = c.nentries; g.nentries_ref = c.nentries_ref; g.nrowent = c.nrowent; }
-  }
-}
-
-// SCEMA_MD_KEEP_LIST=0: every run builds its neighbour rows anew at its start
-bool keep_list_switch() {
-  static const bool on = !(scema_env("SCEMA_MD_KEEP_LIST") && atoi(scema_env("SCEMA_MD_KEEP_LIST")) == 0);
-  return on;
 }
 
 // -------------------------------------------------------------------------------------------
@@ -628,7 +409,7 @@ int OplsRun::lay_out_sim(int pos) {
   // evaluation less.  (Capacities are strides of the stored tables: they stay what they were.)
   Slot &sl = *e->slots[i];
   const ListSig &g = sl.sig;
-  const bool may_keep = spec.keep_list && pol.keep_lists && g.valid && g.rx_stamp == 0 && g.topo == T.id && g.rlist == rlist && g.cut_lj == P.cut_lj &&
+  const bool may_keep = spec.keep_list && pol.keep_lists && g.valid && g.kind == RowKind::Opls && g.topo == T.id && g.rlist == rlist && g.cut_lj == P.cut_lj &&
                         g.cut_coul == P.cut_coul && (spec.keep_list == 1 || g.state == A.st->id) && !hsc.force_rebuild && !hsc.overflow;
   int capj = 0, maxneigh = 0;
   bool keep = false;
@@ -683,7 +464,7 @@ int OplsRun::lay_out_sim(int pos) {
   {
     ListSig &gs = sl.sig;   // what this run's rows are built for; valid once the run has ended without a fault
     gs.valid = false;
-    gs.rx_stamp = 0;
+    gs.kind = RowKind::Opls;
     gs.topo = T.id;
     for (int d = 0; d < 3; d++) gs.nc[d] = S.nc[d];
     gs.capj = capj; gs.maxneigh = maxneigh; gs.npad = S.npad;

@@ -1,6 +1,7 @@
 """The Stillinger-Weber force stage on the GPU (md_sw.hip, engine_sw.cpp) against the independent FP64 numpy restatement tests/sw_numpy.py,
 which tests/test_sw_host.py pins on the CPU: static parity on the shapes at which the kernels take another path, the closed forms of
-silicon, dynamics, the virial -> pressure conversion, whole evaluations, batches, the refusal of mixed updates.
+silicon, dynamics, the virial -> pressure conversion, whole evaluations, batches, box flips inside a split batch, kept neighbour rows,
+the refusal of mixed updates.
 
 Budgets: static parity 1e-10 of the largest force component or term (the project's standing budget: FP64 sums of a few hundred terms in
 another order); NVE positions after 20 steps 1e-9 A; whole evaluations 1e-10 / 1e-9 relative (the same arithmetic in another launch shape).
@@ -275,6 +276,104 @@ def test_batch_of_eleven_equals_each_alone(eleven, split):
         assert err.max() <= 1e-9
     finally:
         e.close()
+
+
+@pytest.fixture(scope="module")
+def sheared():
+    """Eight simulations of a 5 x 2 x 2 diamond cell (160 atoms) written with xy = 2 a = 0.4 lx -- the same unstrained crystal: a shift of a2
+    by two lattice constants along x is a lattice translation -- each sheared by 0.105 to 0.14 lx in xy within 110 to 150 straining steps, so
+    that every one crosses +lx / 2 and flips once; and each one's stress, flips and final box when it runs alone in a fresh engine"""
+    a = swn.si_lattice_constant()
+    x, box = swn.diamond(5, 2, 2, a)
+    box[6] = 2.0 * a
+    t = np.zeros(len(x), int)
+    v = _velocities(len(x), 300.0, 31)
+    lx, ly, lz = box[3:6] - box[:3]
+    # (the tilt xy moves by strain[3] * ly / lz: nts_rule and fix deform's xy rate)
+    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
+    rlist = 1.8 * 2.0951 + 1.0      # a sigma + the skin of sw_configure
+    w_x = lx * ly / math.hypot(ly, 0.5 * lx)     # the narrowest the box gets across its (a2, a3) faces, at xy = lx / 2
+    print(f"sw sheared cell: widths {w_x:.2f} / {ly:.2f} / {lz:.2f} A against two list radii {2 * rlist:.2f} A: image search "
+          f"{'on' if min(w_x, ly, lz) < 2 * rlist else 'off'}")
+
+    def fresh():
+        e = _engine()
+        e.sw_configure("si", SI_SW)
+        e.register_replica("si", 1, capi.sw_system(t, x, box, v=v))
+        return e
+
+    mk = lambda q, s: capi.make_sim(q, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
+    alone, flips, boxes = [], 0, []
+    for q, s in sims:
+        e = fresh()
+        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
+        flips += e.profile()["box_flips"]
+        boxes.append(e.get_state(q, "si", 1)[0])
+        e.close()
+    nts = [_nts_and_rates(s, box, 1.0, 3.4e-3)[0] for _, s in sims]
+    assert len(set(nts)) >= 4 and max(nts) <= 150, nts       # a ragged batch
+    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+
+
+@pytest.mark.parametrize("split", [0, 1])
+def test_box_flips_inside_a_split_batch(sheared, split):
+    """the flips of a batch are enqueued between two steps on the stream of the part that holds the simulation (eight: the smallest batch
+    that runs as two parts): same stresses as each simulation alone, as many flips, every box back inside |xy| <= lx / 2"""
+    fresh, sims, alone, flips, boxes = sheared
+    assert flips >= 8
+    e = fresh()
+    try:
+        e.batch_split(split)
+        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
+        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
+        print(f"sw sheared batch of 8 (split {split}): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
+        assert err.max() <= 1e-9
+        assert e.profile()["box_flips"] == flips
+        for q in range(8):
+            b = e.get_state(q, "si", 1)[0]
+            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
+    finally:
+        e.close()
+
+
+def test_kept_sw_neighbour_rows_equal_rebuilt_ones():
+    """SW rows survive from the straining run to the sampling run and from one update to the next on the same slot where the device finds
+    every atom within the list's displacement bound (as the OPLS and ReaxFF rows do); SCEMA_MD_KEEP_LIST=0 rebuilds at every run start.
+    Two consecutive updates of case (a): same stresses either way, fewer builds."""
+    import json, subprocess, sys
+    code = ("import json, sys, numpy as np\n"
+            "sys.path.insert(0, sys.argv[1])\n"
+            "import sw_numpy as swn\n"
+            "from scema_amd import capi\n"
+            "x, box, t = swn.case_a()\n"
+            "rng = np.random.default_rng(5)\n"
+            "v = rng.normal(size=x.shape) * np.sqrt(swn.BOLTZ * 300.0 / swn.SI_MASS / swn.MVV2E)\n"
+            "v -= v.mean(axis=0)\n"
+            "e = capi.Engine(capi.default_params())\n"
+            "e.sw_configure('si', sys.argv[2])\n"
+            "e.register_replica('si', 1, capi.sw_system(t, x, box, v=v))\n"
+            "L = box[3:6] - box[:3]\n"
+            "st = np.array([1e-3 * L[0], -3e-4 * L[1], -3e-4 * L[2], 2e-4 * L[2], 0, 0])\n"
+            "mk = lambda q, s, recent: capi.make_sim(q, 'si', 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=recent)\n"
+            "out = []\n"
+            "out += [list(o.stress) for o in e.strain_batch([mk(q, st * (1 + 0.5 * q), capi.QP_NONE) for q in (0, 1)])]\n"
+            "out += [list(o.stress) for o in e.strain_batch([mk(q, -st, q) for q in (0, 1)])]\n"
+            "p = e.profile()\n"
+            "print(json.dumps({'s': out, 'builds': p['neigh_builds'], 'steps': p['md_steps']}))\n")
+    res = {}
+    for name, keep in (("keep", None), ("nokeep", "0")):
+        env = {k: w for k, w in os.environ.items() if k != "SCEMA_MD_KEEP_LIST"}
+        if keep is not None:
+            env["SCEMA_MD_KEEP_LIST"] = keep
+        pr = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "tests"), SI_SW], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert pr.returncode == 0, pr.stderr[-2000:]
+        res[name] = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][-1])
+    a, b = np.array(res["keep"]["s"]), np.array(res["nokeep"]["s"])
+    err = (np.abs(a - b).max(axis=1) / np.abs(b).max(axis=1)).max()
+    print(f"sw kept rows: max rel err {err:.2e}, builds {res['keep']['builds']} kept / {res['nokeep']['builds']} rebuilt, steps {res['keep']['steps']}")
+    assert err <= 1e-9
+    assert res["keep"]["steps"] == res["nokeep"]["steps"]
+    assert res["keep"]["builds"] < res["nokeep"]["builds"], (res["keep"]["builds"], res["nokeep"]["builds"])
 
 
 def test_mixed_update_is_refused(small_pe):

@@ -4,7 +4,7 @@ One warm-up update, then the timed ones, each continuing from the states of the 
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/sw_bench.py --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/sw_bench.py [--sims 576] [--updates 5] [--nss 100] [--split 1]
+  python tools/sw_bench.py [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
 """
 import argparse
 import json
@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--updates", type=int, default=5)
     ap.add_argument("--nss", type=int, default=100)
     ap.add_argument("--split", type=int, default=-1, help="scema_md_batch_split: 0 whole, 1 part batches, -1 the default")
+    ap.add_argument("--dump", default=None, metavar="FILE", help="write the stresses of the last update as FILE (.npy, float64, one row of six per quadrature point)")
     a = ap.parse_args()
     gold = os.path.join(ROOT, "tests", "golden")
     e = capi.Engine(capi.default_params())
@@ -52,6 +53,8 @@ def main():
         res = e.strain_batch(batch)
         times.append(time.perf_counter() - t0)
         assert all(o.stress_updated == 1 for o in res)
+    if a.dump:
+        np.save(a.dump, np.array([list(o.stress) for o in res], np.float64))
     prof = e.profile()
     best, med = min(times), sorted(times)[len(times) // 2]
     print(json.dumps({"workload": "sw_si_192", "sims": a.sims, "steps_per_eval": 10 + a.nss, "updates": a.updates, "split": e.concurrency()["split"],
