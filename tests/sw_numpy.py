@@ -285,3 +285,142 @@ Si X  Si 1.9000 0.0    0.0  22.0 0.0  -0.32           0.0         0.0          0
 X  X  Si 1.5000 0.0    0.0  24.0 0.0  -0.28           0.0         0.0          0.0 0.0 0.0
 X  Si X  1.5000 0.0    0.0  24.0 0.0  -0.28           0.0         0.0          0.0 0.0 0.0
 """
+
+
+# ---- inputs for the edges of the kernels (tests/test_sw_edges_host.py, tests/test_gpu_sw_edges.py): generators only ----
+SI_CUT = 1.8 * 2.0951            # a sigma of tests/golden/Si.sw
+SI_RLIST = SI_CUT + 1.0          # + the default skin of sw_configure
+
+
+def widths(box):
+    """perpendicular widths of the box between its three pairs of faces"""
+    H = h_matrix(box)
+    v = volume(box)
+    return np.array([v / np.linalg.norm(np.cross(H[1], H[2])), v / np.linalg.norm(np.cross(H[2], H[0])), v / np.linalg.norm(np.cross(H[0], H[1]))])
+
+
+def check_box(box, cutmax=SI_CUT, rlist=SI_RLIST):
+    """the conditions every input box of the edge tests meets: each perpendicular width is at least cutmax / 1.5 (SW.neighbours searches the
+    fractional minimum image +- 1: |s| <= 1.5 box vectors, complete only above that width) and at least rlist / 2 (below it the engine
+    refuses: it searches at most two images deep)"""
+    w = widths(box)
+    assert (w >= cutmax / 1.5).all() and (w >= rlist / 2.0).all(), w
+    return w
+
+
+def gas(n, box, dmin, seed):
+    """n atoms inserted at random (uniform in the cell, one after the other, a candidate rejected when it comes closer than dmin to an atom
+    placed before, to one of that atom's periodic images, or to a periodic image of itself); deterministic in the seed"""
+    box = np.asarray(box, float)
+    H = h_matrix(box)
+    shifts = np.array(list(itertools.product(range(-3, 4), repeat=3)), float) @ H
+    own = shifts[np.einsum("ij,ij->i", shifts, shifts) > 0.0]
+    assert np.linalg.norm(own, axis=1).min() >= dmin, "an atom's own image is closer than dmin in this box"
+    assert (3.0 * widths(box) > dmin).all()          # (three images deep covers dmin)
+    rng = np.random.default_rng(seed)
+    x = np.zeros((0, 3))
+    for _ in range(100000):
+        if len(x) == n:
+            break
+        c = box[:3] + rng.uniform(size=3) @ H
+        d = (x[:, None, :] - c[None, None, :]) + shifts[None, :, :]
+        if d.size == 0 or np.sqrt(np.einsum("ijk,ijk->ij", d, d)).min() >= dmin:
+            x = np.vstack([x, c])
+    assert len(x) == n, "the box does not hold that many atoms at this distance"
+    return x
+
+
+def truncated(n, seed=15):
+    """the first n atoms of a jittered diamond block large enough to hold them, in the block's box (vacuum where the others were): up to
+    1 200 atoms the 5 x 5 x 6 block of case (g), with its jitter"""
+    nz = 6
+    while 5 * 5 * nz * 8 < n:
+        nz += 1
+    x, box = diamond(5, 5, nz, si_lattice_constant())
+    rng = np.random.default_rng(seed)
+    x = x + rng.uniform(-0.1, 0.1, x.shape)
+    return x[:n].copy(), box, np.zeros(n, int)
+
+
+BIG_BOX = np.array([0.0, 0.0, 0.0, 30.0, 30.0, 30.0, 0.0, 0.0, 0.0])
+
+
+def cluster(k, radius=3.5):
+    """a centre atom and k atoms on a Fibonacci sphere of that radius around it, in a 30 A box"""
+    m = np.arange(k) + 0.5
+    z = 1.0 - 2.0 * m / k
+    phi = m * np.pi * (3.0 - np.sqrt(5.0))
+    s = np.sqrt(1.0 - z * z)
+    shell = radius * np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1)
+    x = np.vstack([np.zeros((1, 3)), shell]) + 15.0
+    return x, BIG_BOX.copy(), np.zeros(k + 1, int)
+
+
+def lone(n):
+    """one atom, or two atoms 2.4 A apart along the body diagonal, in a 30 A box"""
+    u = 2.4 / np.sqrt(3.0)
+    x = np.array([[14.0, 15.0, 16.0], [14.0 + u, 15.0 + u, 16.0 + u]])[:n]
+    return x, BIG_BOX.copy(), np.zeros(n, int)
+
+
+def narrow(name):
+    """boxes narrower than one list radius: the image search two boxes deep, atoms that are their own neighbours
+      N1  24-atom gas, 3.2 x 11 x 12 A orthogonal            N2  5-atom gas, triclinic, lower corner off the origin, widths 8.02 / 2.92 / 3.40 A
+      N3  4-atom gas, 2.6 x 2.7 x 12 A with xy = 0.4 A       N4  one atom in 3.2 x 3.3 x 3.4 A: every neighbour is its own image
+      N5  N1's positions, types alternating (TWO_ELEMENT_SW)
+    The seeds of N2 and N3 are chosen so that a pair inside the cutoff sits two box vectors from its wrapped partner (an atom next to one
+    face, its partner next to the opposite one: rare among seeds).  N1 and N4 cannot have one: at 3.2 A and a distance of 2.1 A to the
+    nearest image, the image two boxes away is beyond the cutoff (3.2^2 + 2.1^2 > 3.77^2); their second images fill the skin only."""
+    if name in ("N1", "N5"):
+        box = np.array([0.0, 0.0, 0.0, 3.2, 11.0, 12.0, 0.0, 0.0, 0.0])
+        x = gas(24, box, 2.1, 101)
+        t = np.zeros(24, int) if name == "N1" else np.arange(24) % 2
+    elif name == "N2":
+        box = np.array([0.5, -1.0, 2.0, 9.5, 2.0, 5.4, 1.1, -0.9, 0.8])
+        x = gas(5, box, 2.1, 136)
+        t = np.zeros(5, int)
+    elif name == "N3":
+        box = np.array([0.0, 0.0, 0.0, 2.6, 2.7, 12.0, 0.4, 0.0, 0.0])
+        x = gas(4, box, 2.1, 106)
+        t = np.zeros(4, int)
+    elif name == "N4":
+        box = np.array([0.0, 0.0, 0.0, 3.2, 3.3, 3.4, 0.0, 0.0, 0.0])
+        x = np.array([[1.1, 2.3, 0.7]])
+        t = np.zeros(1, int)
+    else:
+        raise KeyError(name)
+    check_box(box)
+    return x, box, t
+
+
+def tilted(ncell, seed=17):
+    """jittered diamond, ncell^3 cells of edge L / ncell, tilted by xy = 0.45 L, xz = -0.45 L, yz = 0.45 L: |xy| close to lx / 2, the box a
+    sheared run passes through before it flips.  ncell 3: widths 12.77 / 14.86 / 16.29 A, above two list radii (minimum image); ncell 2:
+    8.51 / 9.91 / 10.86 A (one image deep)"""
+    a = si_lattice_constant()
+    x, box = diamond(ncell, ncell, ncell, a)
+    L = ncell * a
+    F = np.array([[1.0, 0.45, -0.45], [0.0, 1.0, 0.45], [0.0, 0.0, 1.0]])
+    rng = np.random.default_rng(seed)
+    x = (x + rng.uniform(-0.1, 0.1, x.shape)) @ F.T
+    box[6], box[7], box[8] = 0.45 * L, -0.45 * L, 0.45 * L
+    check_box(box)
+    return x, box, np.zeros(len(x), int)
+
+
+def case_a_compressed(frac=0.31):
+    """case (a) compressed by 31 %: 33 neighbours inside the cutoff, one more than the force kernel lists (28 at 25 %)"""
+    x, box, t = case_a()
+    x, box = strained(x, box, -frac * np.eye(3))
+    return x, box, t
+
+
+def supercell(x, box, types, m=3):
+    """the cell repeated m x m x m along its own vectors, the original atoms first"""
+    H = h_matrix(box)
+    box = np.asarray(box, float)
+    sh = np.array(list(itertools.product(range(m), repeat=3)), float) @ H
+    xs = (sh[:, None, :] + np.asarray(x)[None, :, :]).reshape(-1, 3)
+    lo = box[:3]
+    nb = np.array([lo[0], lo[1], lo[2], lo[0] + m * H[0, 0], lo[1] + m * H[1, 1], lo[2] + m * H[2, 2], m * H[1, 0], m * H[2, 0], m * H[2, 1]])
+    return xs, nb, np.tile(np.asarray(types), m ** 3)
