@@ -397,6 +397,34 @@ int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *mat
 int scema_md_sw_read_params(const char *sw_path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                             int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
+/* ---- Tersoff replicas (`pair_style tersoff`; silicon, carbon, silicon carbide) ----
+ * configure = `pair_style tersoff` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1) for the replicas
+ * of ONE material id, registered before or after the call; list skin as for scema_md_sw_configure (skin < 0: 1.0).  energy_unit 0: A and B
+ * of the file are in eV (units metal, as the files LAMMPS ships) and are converted to kcal/mol with 23.060549; 1: kcal/mol as written.
+ * Simulations of such a material take the Tersoff force stage whatever MDSim.force_field says: no SHAKE, no k-space, no bonded terms.  An
+ * update or run that mixes them with simulations of other materials (Stillinger-Weber ones included) is refused with SCEMA_MD_ERR_ARG.  A
+ * material holds ONE attachment: configuring a Tersoff potential for a material that has a Stillinger-Weber one replaces it, and the other
+ * way round.  At most 32 neighbours of an atom may lie inside the cutoff R + D; more is an error of the run, never a truncation.
+ * A bare replica whose material has nothing attached and whose scripts folder holds no Si.sw configures itself at a scema_md_strain_batch
+ * from the line `pair_coeff * * ${locs}/<name>.tersoff <El> ...` of <scripts_folder>/in.strain.lammps (file <scripts_folder>/<name>.tersoff,
+ * energy unit eV); a malformed line of that kind is SCEMA_MD_ERR_ARG. */
+int scema_md_tersoff_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                               int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], the repulsive energy sum 1/2 fC fR and the bond-order energy sum 1/2 fC b fA (kcal/mol), virial[6]
+ * (xx,yy,zz,xy,xz,yz), info[4]: longest neighbour row the build asked for, row capacity, ordered pairs inside their cutoff, ordered (j, k)
+ * evaluated for the bond orders */
+int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep,
+                                   double *e_att, double *virial, double *info);
+/* The reader of LAMMPS *.tersoff files as a pure host function (no GPU, no engine).  `#` starts a comment; an entry is three element names
+ * and fourteen numbers (m gamma lambda3 c d costheta0 n beta lambda2 B R D lambda1 A) on one line or several; the entries whose three
+ * elements are all named are kept.  n_kept, type_map as for scema_md_sw_read_params; values[n_kept][n_kept][n_kept][14] (room for
+ * 4*4*4*14): the numbers of entry i j k, A and B in kcal/mol.  n, beta, lambda2, B, lambda1, A and the pair's R, D are those of entry
+ * i j j; m, gamma, lambda3, c, d, costheta0 and the R, D of the third atom's cutoff those of entry i j k, as in pair_tersoff.cpp.  A missing
+ * triplet, a non-numeric field, a short or duplicate entry, a negative c, d, n, beta, lambda2, B, R, D, lambda1, A or gamma, D > R, m other
+ * than 1 or 3, n = 0 in an entry i j j (the switch points of b(zeta) would not exist): SCEMA_MD_ERR_IO with the reason in errbuf. */
+int scema_md_tersoff_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                 int32_t *type_map, double *values, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;      /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

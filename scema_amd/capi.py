@@ -38,6 +38,7 @@ SYMBOLS = [
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
     "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
+    "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -487,6 +488,21 @@ class Engine:
                                                   _p(info)))
         return dict(f=f, e2=e2.value, e3=e3.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), ntriplets=int(info[3]))
 
+    # ---- Tersoff replicas (pair_style tersoff) ----
+    def tersoff_configure(self, matid: str, path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style tersoff + pair_coeff * * <path> <elements> for the replicas of one material id; energy_unit 0: the file's A and B are
+        eV, 1: kcal/mol as written.  Replaces a Stillinger-Weber potential of the material"""
+        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+        self._chk(lib().scema_md_tersoff_configure(self.h, matid.encode(), path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
+                                                   C.c_double(skin)))
+
+    def tersoff_compute(self, matid, replica, qp=QP_NONE):
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); er = C.c_double(0.0); ea = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
+        self._chk(lib().scema_md_tersoff_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(er), C.byref(ea),
+                                                       _p(w), _p(info)))
+        return dict(f=f, e_rep=er.value, e_att=ea.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), nzeta=int(info[3]))
+
     # ---- init_material's equilibration schedule (in.init.lammps; md_equil.hip) ----
     def minimize(self, matid, replica, qp, etol=1e-7, ftol=1e-11, maxiter=1000, maxeval=50000) -> dict:
         info = np.zeros(5)
@@ -551,6 +567,9 @@ def sw_system(types, x, box, v=None, masses=(28.0855,)) -> dict:
                 box=np.asarray(box, float), x=np.asarray(x, float), v=np.zeros((n, 3)) if v is None else np.asarray(v, float))
 
 
+bare_system = sw_system   # (the same bare replica under a neutral name: what a Tersoff material registers too)
+
+
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]
 
 
@@ -570,6 +589,27 @@ def sw_read_params(sw_path: str, elements, energy_unit: int = 0):
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     n = nk.value
     return n, tmap, vals[:n * n * n * 11].reshape(n, n, n, 11).copy()
+
+
+TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
+
+
+def tersoff_read_params(path: str, elements, energy_unit: int = 0):
+    """(distinct elements kept, type_map, values[n][n][n][14] in the order of TERSOFF_FIELDS, A and B in kcal/mol) of a LAMMPS *.tersoff
+    file: scema_md_tersoff_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
+    L = lib()
+    L.scema_md_tersoff_read_params.restype = C.c_int
+    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+    nk = C.c_int32(0)
+    tmap = np.zeros(len(elements), np.int32)
+    vals = np.zeros(4 * 4 * 4 * 14)
+    err = C.create_string_buffer(512)
+    rc = L.scema_md_tersoff_read_params(path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(vals), err,
+                                        C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nk.value
+    return n, tmap, vals[:n * n * n * 14].reshape(n, n, n, 14).copy()
 
 
 def kspace_setup(params, box, qsqsum: float, natoms: int):

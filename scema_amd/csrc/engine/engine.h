@@ -5,9 +5,10 @@
 //   engine_topo.cpp    topology preprocessing of a registered replica (exclusions, SHAKE clusters, bonded tiles)
 //   engine_kspace.cpp  what a LAMMPS `run` sets up on the host: g_ewald, k-vectors, PPPM grid, the real-space polynomial, fix deform's box path
 //   engine_run.cpp     one run of a batch with the OPLS force stage (run_phase), slots
-//   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF or the SW stage
+//   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF, the SW or the Tersoff stage
 //   engine_reax.cpp    the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
 //   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points
+//   engine_tersoff.cpp the Tersoff force stage (run_phase_tersoff) and the Tersoff entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
 //   engine_state.cpp   state store: branch rule, replica / state files
@@ -40,6 +41,7 @@
 #include "host/reax_ffield.h"
 #include "host/sim_plan.h"
 #include "host/sw_params.h"
+#include "host/tersoff_params.h"
 #include <hipfft/hipfft.h>
 
 #include "md_kernels.h"
@@ -48,6 +50,7 @@
 #include "md_pppm_tile.h"
 #include "md_reax.h"
 #include "md_sw.h"
+#include "md_tersoff.h"
 #include "md_types.h"
 
 namespace scema_eng {
@@ -143,7 +146,7 @@ struct Topo {
   int bt_ntile = 0, bt_maxloc = 1, bt_maxchunk = 1, bt_ncoef = 0, bt_cf_off[4] = {0, 0, 0, 0};
   double sp_w[6] = {0, 0, 0, 0, 0, 0};   // special_bonds weights: lj 1-2, 1-3, 1-4, coul 1-2, 1-3, 1-4
   std::string matid;       // the material the replica was registered under (a Stillinger-Weber potential is attached to a material id)
-  DevBuf d_swtype;         // Stillinger-Weber: element per atom (index into the material's tables), valid for swtype_stamp
+  DevBuf d_swtype;         // Stillinger-Weber and Tersoff: element per atom (index into the material's tables), valid for swtype_stamp
   long long swtype_stamp = 0;
 };
 
@@ -172,7 +175,7 @@ struct RxSlot {
   DevBuf nb_cnt, nb_own0, nbT, hval, hcol, hlen, hown, hownlen, bd_cnt, bd, bd_rev, bd_bop, bd_c, bd_bo, bd_g, bd_cb, deltap, total_bo, cd_delta, hd, q, s, t, s_hist, t_hist, qwork, misc;
 };
 
-// work arrays of the Stillinger-Weber path for one batch position (md_sw.h SwView points into these)
+// work arrays of the Stillinger-Weber and Tersoff paths for one batch position (md_sw.h SwView points into these)
 struct SwSlot {
   int cap_pad = 0;
   size_t cap_rows = 0;
@@ -188,9 +191,19 @@ struct SwMaterial {
   DevBuf d_tab;
 };
 
+// a Tersoff potential attached to a material id (scema_md_tersoff_configure); stamps come from the counter of the SW potentials, so that
+// rows and element arrays never pass from one attachment of a material to another
+struct TsMaterial {
+  TsTable tab;
+  std::vector<int> type_map;   // LAMMPS type - 1 -> element of the tables
+  double skin = 1.0;
+  long long stamp = 0;
+  DevBuf d_tab;
+};
+
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
 // checks `kind` first and writes every field it checks.
-enum class RowKind { Opls, Reax, Sw };
+enum class RowKind { Opls, Reax, Sw, Tersoff };
 struct ListSig {
   bool valid = false;
   RowKind kind = RowKind::Opls;
@@ -392,7 +405,12 @@ struct scema_md_engine {
   long long sw_stamp = 0;
   DevBuf d_swviews;
   std::vector<SwView> h_swviews;
-  hipEvent_t sw_done = nullptr;   // part batches of an SW run: the end of the second part (created on first use)
+  hipEvent_t sw_done = nullptr;   // part batches of an SW or Tersoff run: the end of the second part (created on first use)
+  // Tersoff path: the potentials by material id (a material holds an SW or a Tersoff potential, never both: configuring one replaces the
+  // other); the row part of a run's work sets is h_swviews / d_swviews
+  std::map<std::string, std::unique_ptr<TsMaterial>> ts_mats;
+  DevBuf d_tsviews;
+  std::vector<TsView> h_tsviews;
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
   scema::SimPlan last_plan;
@@ -443,10 +461,19 @@ int ensure_slot(scema_md_engine *e, Slot &sl, int natoms, int maxneigh, int ncel
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
+int run_phase_tersoff(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 // the Stillinger-Weber potential of a material id, or null (engine_sw.cpp)
 SwMaterial *sw_material(scema_md_engine *e, const std::string &matid);
 // a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
 bool sw_bare_replica(const Topo &t);
+// element of every atom of a replica on the device (Topo::d_swtype): the element pair_coeff names for its LAMMPS type; `what` names the
+// potential in the refusal (engine_sw.cpp)
+int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map, long long stamp, const char *what);
+// the Tersoff potential of a material id, or null (engine_tersoff.cpp)
+TsMaterial *ts_material(scema_md_engine *e, const std::string &matid);
+// `pair_coeff * * ${locs}/<name>.tersoff <El> ...` in <folder>/in.strain.lammps: configures the material from that line; no such file or
+// line: nothing happens (0); a malformed line: an error
+int tersoff_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
 // the batch skeleton every force stage shares (engine_rows.cpp)
@@ -533,6 +560,31 @@ struct RowRun {
   int finish();
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
+// What the Stillinger-Weber and the Tersoff stage share (engine_sw.cpp): full neighbour rows inside the material's largest cutoff + skin
+// in the slot's SwSlot, one SwView per position (e->h_swviews / d_swviews; `tab` is the caller's), the row capacity and its growth, part
+// batches on the main and the third stream, the "too many neighbours" fault.  A stage says which material a replica has, adds what its
+// own view needs, and launches.
+struct SwRowsStage : RowStage {
+  struct Mat { double cutmax = 0.0, skin = 0.0; long long stamp = 0; const std::vector<int> *type_map = nullptr; };
+  scema_md_engine *e;
+  const char *what;             // the potential's name in messages
+  SwView *VV = nullptr;         // the views on the device (upload)
+  SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char *what_);
+  // the material of a replica of T, remembered by the stage: bind_view follows for the same one
+  virtual Mat material(const Topo &T) = 0;
+  // what the stage adds to position pos beyond the SwView (its own view, SwView::tab)
+  virtual int bind_view(int pos, SwView &V) = 0;
+  virtual int upload_views() { return SCEMA_MD_OK; }   // the stage's own views to the device
+  int nparts() const override;
+  int rows(Topo &T, const BoxRange &R, RowNeed &need) override;
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override;
+  int upload() override;
+  int setup() override { return SCEMA_MD_OK; }
+  int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) override;
+  int read_back() override;
+  int after_read_back(int fault, double &need) override;
+  int faults(int fault) override;
+};
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

@@ -24,107 +24,122 @@ bool sw_bare_replica(const Topo &t) {
 #define SWSET(dst, src) dst = (decltype(dst))(src)
 
 // element of every atom of a replica: the element pair_coeff names for its LAMMPS type
-static int ensure_swtype(scema_md_engine *e, Topo &T, const SwMaterial &M) {
-  if (T.swtype_stamp == M.stamp && T.d_swtype.p) return SCEMA_MD_OK;
+int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map, long long stamp, const char *what) {
+  if (T.swtype_stamp == stamp && T.d_swtype.p) return SCEMA_MD_OK;
   std::vector<int> st(T.natoms);
   for (int i = 0; i < T.natoms; i++) {
     const int ty = T.original.type[i];   // the registered LAMMPS type (Topo::type holds Lennard-Jones classes)
-    if (ty < 0 || ty >= (int)M.type_map.size())
-      return fail(e, SCEMA_MD_ERR_ARG, "atom %d has type %d but the Stillinger-Weber element list names %zu types (pair_coeff * * file ...)", i, ty + 1, M.type_map.size());
-    st[i] = M.type_map[ty];
+    if (ty < 0 || ty >= (int)type_map.size())
+      return fail(e, SCEMA_MD_ERR_ARG, "atom %d has type %d but the %s element list names %zu types (pair_coeff * * file ...)", i, ty + 1, what, type_map.size());
+    st[i] = type_map[ty];
   }
   int rc = upload(e, T.d_swtype, st);
   if (rc) return rc;
-  T.swtype_stamp = M.stamp;
+  T.swtype_stamp = stamp;
+  return SCEMA_MD_OK;
+}
+
+// ---- the row part the Stillinger-Weber and the Tersoff stage share (engine.h: SwRowsStage) ----
+
+SwRowsStage::SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char *what_) : RowStage(kind_, 16), e(e_), what(what_) {
+  e->h_swviews.assign(ns, SwView());
+}
+
+// Part batches: part 0 on the engine's main stream, part 1 on its third.  The split follows the other paths' shape, SCEMA_MD_SPLIT=0 /
+// scema_md_batch_split(e, 0) runs the batch whole.
+int SwRowsStage::nparts() const { return (e->split_streams && e->stream3 && run->ns >= 8 && !run->spec.minimize) ? 2 : 1; }
+
+int SwRowsStage::rows(Topo &T, const BoxRange &R, RowNeed &need) {
+  const Mat M = material(T);
+  if (const int rc = ensure_swtype(e, T, *M.type_map, M.stamp, what)) return rc;
+  const int n = T.natoms;
+  if (n >= (1 << 24)) return fail(e, SCEMA_MD_ERR_ARG, "a %s replica of %d atoms: row entries hold 24-bit atom indices", what, n);
+  const double rlist = M.cutmax + M.skin;
+  // row capacity: the mean count inside the list radius at the densest box of the run, with headroom (grown after an overflow: grow_after_overflow)
+  const double rho = n / R.vol_min;
+  const int cap = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.5 * e->neigh_grow);
+  need.rlist = rlist; need.skin = M.skin; need.stamp = M.stamp;
+  need.cap[0] = std::max(8, (cap + 7) / 8 * 8);
+  return SCEMA_MD_OK;
+}
+
+int SwRowsStage::bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) {
+  const Topo &T = *A.st->topo;
+  const int npad = S.npad, cap = need.cap[0];
+  if (!sl.sw) sl.sw.reset(new SwSlot());
+  SwSlot &W = *sl.sw;
+  if (npad > W.cap_pad) {
+    HIPCHK(W.cnt.ensure((size_t)npad * 4));
+    HIPCHK(W.misc.ensure(64));
+    W.cap_pad = npad;
+    W.cap_rows = 0;
+  }
+  if ((size_t)npad * cap > W.cap_rows) {
+    HIPCHK(W.rows.ensure((size_t)npad * cap * 4));
+    W.cap_rows = (size_t)npad * cap;
+  }
+  SwView V;
+  std::memset(&V, 0, sizeof V);
+  for (int d = 0; d < 3; d++) V.mimg[d] = need.mimg[d];
+  V.n = S.natoms; V.npad = npad; V.cap = cap; V.rlist = need.rlist;
+  SWSET(V.stype, T.d_swtype.as<int>()); SWSET(V.x, S.x); SWSET(V.f, S.f);
+  SWSET(V.cnt, W.cnt.as<int>()); SWSET(V.rows, W.rows.as<int>());
+  SWSET(V.eacc, W.misc.as<double>());                 // [0, 4) doubles
+  SWSET(V.stat, (int *)(W.misc.as<char>() + 32));     // 2 ints
+  e->h_zerotab.push_back(MdkZero{W.misc.as<int>(), 16});   // (the step sums)
+  if (const int rc = bind_view(pos, V)) return rc;
+  e->h_swviews[pos] = V;
+  return SCEMA_MD_OK;
+}
+
+int SwRowsStage::upload() {
+  const size_t bytes = e->h_swviews.size() * sizeof(SwView);
+  HIPCHK(e->d_swviews.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(e->d_swviews.p, e->h_swviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+  VV = e->d_swviews.as<SwView>();
+  return upload_views();
+}
+
+int SwRowsStage::part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) {
+  if (!e->sw_done) HIPCHK(hipEventCreateWithFlags(&e->sw_done, hipEventDisableTiming));
+  parts[1].st = e->stream3;
+  done.push_back(e->sw_done);
+  return SCEMA_MD_OK;
+}
+
+int SwRowsStage::read_back() { return run->read_scalars(); }
+
+int SwRowsStage::after_read_back(int fault, double &need) {
+  for (int pos = 0; pos < run->ns; pos++)
+    need = std::max(need, (double)e->h_sc[run->order[pos]].maxneigh_seen / (double)std::max(e->h_swviews[pos].cap, 1));
+  return faults(fault);
+}
+
+int SwRowsStage::faults(int fault) {
+  if (fault & 128) return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside the %s cutoff", SW_MAXIN, what);
   return SCEMA_MD_OK;
 }
 
 namespace {
 
-struct SwStage : RowStage {
-  scema_md_engine *e;
-  const SwMaterial *mat = nullptr;   // the material of the replica rows() was last asked about (bind follows for the same one)
-  SwView *VV = nullptr;
+struct SwStage : SwRowsStage {
+  const SwMaterial *mat = nullptr;
 
-  SwStage(scema_md_engine *e_, int ns) : RowStage(RowKind::Sw, 16), e(e_) { e->h_swviews.assign(ns, SwView()); }
+  SwStage(scema_md_engine *e_, int ns) : SwRowsStage(e_, ns, RowKind::Sw, "Stillinger-Weber") {}
 
-  // Part batches: part 0 on the engine's main stream, part 1 on its third.  Not measured yet for this force stage: the split follows the
-  // other paths' shape, SCEMA_MD_SPLIT=0 / scema_md_batch_split(e, 0) runs the batch whole.
-  int nparts() const override { return (e->split_streams && e->stream3 && run->ns >= 8 && !run->spec.minimize) ? 2 : 1; }
-
-  int rows(Topo &T, const BoxRange &R, RowNeed &need) override {
-    const SwMaterial &M = *(mat = sw_material(e, T.matid));
-    if (const int rc = ensure_swtype(e, T, M)) return rc;
-    const int n = T.natoms;
-    if (n >= (1 << 24)) return fail(e, SCEMA_MD_ERR_ARG, "a Stillinger-Weber replica of %d atoms: row entries hold 24-bit atom indices", n);
-    const double rlist = M.tab.cutmax + M.skin;
-    // row capacity: the mean count inside the list radius at the densest box of the run, with headroom (grown after an overflow: grow_after_overflow)
-    const double rho = n / R.vol_min;
-    const int cap = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.5 * e->neigh_grow);
-    need.rlist = rlist; need.skin = M.skin; need.stamp = M.stamp;
-    need.cap[0] = std::max(8, (cap + 7) / 8 * 8);
-    return SCEMA_MD_OK;
+  Mat material(const Topo &T) override {
+    mat = sw_material(e, T.matid);
+    Mat M;
+    M.cutmax = mat->tab.cutmax; M.skin = mat->skin; M.stamp = mat->stamp; M.type_map = &mat->type_map;
+    return M;
   }
 
-  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
-    const Topo &T = *A.st->topo;
-    const int npad = S.npad, cap = need.cap[0];
-    if (!sl.sw) sl.sw.reset(new SwSlot());
-    SwSlot &W = *sl.sw;
-    if (npad > W.cap_pad) {
-      HIPCHK(W.cnt.ensure((size_t)npad * 4));
-      HIPCHK(W.misc.ensure(64));
-      W.cap_pad = npad;
-      W.cap_rows = 0;
-    }
-    if ((size_t)npad * cap > W.cap_rows) {
-      HIPCHK(W.rows.ensure((size_t)npad * cap * 4));
-      W.cap_rows = (size_t)npad * cap;
-    }
-    SwView V;
-    std::memset(&V, 0, sizeof V);
-    for (int d = 0; d < 3; d++) V.mimg[d] = need.mimg[d];
-    V.n = S.natoms; V.npad = npad; V.cap = cap; V.rlist = need.rlist;
-    SWSET(V.stype, T.d_swtype.as<int>()); SWSET(V.tab, mat->d_tab.as<SwTable>()); SWSET(V.x, S.x); SWSET(V.f, S.f);
-    SWSET(V.cnt, W.cnt.as<int>()); SWSET(V.rows, W.rows.as<int>());
-    SWSET(V.eacc, W.misc.as<double>());                 // [0, 4) doubles
-    SWSET(V.stat, (int *)(W.misc.as<char>() + 32));     // 2 ints
-    e->h_zerotab.push_back(MdkZero{W.misc.as<int>(), 16});   // (the step sums)
-    e->h_swviews[pos] = V;
+  int bind_view(int, SwView &V) override {
+    SWSET(V.tab, mat->d_tab.as<SwTable>());
     return SCEMA_MD_OK;
   }
-
-  int upload() override {
-    const size_t bytes = e->h_swviews.size() * sizeof(SwView);
-    HIPCHK(e->d_swviews.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(e->d_swviews.p, e->h_swviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    VV = e->d_swviews.as<SwView>();
-    return SCEMA_MD_OK;
-  }
-
-  int setup() override { return SCEMA_MD_OK; }
 
   void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
-
-  int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) override {
-    if (!e->sw_done) HIPCHK(hipEventCreateWithFlags(&e->sw_done, hipEventDisableTiming));
-    parts[1].st = e->stream3;
-    done.push_back(e->sw_done);
-    return SCEMA_MD_OK;
-  }
-
-  int read_back() override { return run->read_scalars(); }
-
-  int after_read_back(int fault, double &need) override {
-    for (int pos = 0; pos < run->ns; pos++)
-      need = std::max(need, (double)e->h_sc[run->order[pos]].maxneigh_seen / (double)std::max(e->h_swviews[pos].cap, 1));
-    return faults(fault);
-  }
-
-  int faults(int fault) override {
-    if (fault & 128) return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside the Stillinger-Weber cutoff", SW_MAXIN);
-    return SCEMA_MD_OK;
-  }
 };
 
 }  // namespace
@@ -155,6 +170,7 @@ int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_
   HIPCHK(hipMemcpyAsync(M->d_tab.p, &M->tab, sizeof(SwTable), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   e->sw_mats[matid] = std::move(M);   // (a potential it replaces goes with its table: rows and element arrays carry its stamp and are rebuilt)
+  e->ts_mats.erase(matid);            // (a Tersoff potential included: a material holds one attachment)
   return SCEMA_MD_OK;
 }
 

@@ -38,3 +38,6 @@ static_assert(sizeof(double SW_G *) == sizeof(double *), "the qualified pointers
 // the force stage of one step for the first ns replicas: neighbour rows where the rebuild flag of the step is set, pair and triplet
 // terms, forces into SimDev::f, virial (parts P_LJ, P_ANGLE) and energies into SimScalars
 void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms);
+// its first three launches alone (k_sw_prepare, k_sw_wrap, k_sw_rows): the row part of a step, which the Tersoff force stage shares
+// (md_tersoff.hip); the rows cover SwView::rlist and read nothing of SwView::tab
+void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms);

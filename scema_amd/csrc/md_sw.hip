@@ -302,12 +302,18 @@ __global__ void k_sw_finish(const SimDev *sims, const SwView *views) {
 
 static inline int sw_cdv(int a, int b) { return (a + b - 1) / b; }
 
-void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
   if (ns <= 0 || maxatoms <= 0) return;
   const dim3 gt((unsigned)sw_cdv(maxatoms, SW_TILE), (unsigned)ns, 1);
   hipLaunchKernelGGL(k_sw_prepare, dim3(ns), dim3(64), 0, st, d, v);
   hipLaunchKernelGGL(k_sw_wrap, dim3((unsigned)sw_cdv(maxatoms, TPB), (unsigned)ns, 1), dim3(TPB), 0, st, d, v);
   hipLaunchKernelGGL(k_sw_rows, gt, dim3(SW_ROWS_TPB), 0, st, d, v);
+}
+
+void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+  if (ns <= 0 || maxatoms <= 0) return;
+  const dim3 gt((unsigned)sw_cdv(maxatoms, SW_TILE), (unsigned)ns, 1);
+  mdk_sw_rows(st, d, v, ns, maxatoms);
   const int maxpad = (maxatoms + 63) / 64 * 64;
   if (maxpad <= SW_LDS_MAXPAD) hipLaunchKernelGGL(k_sw_force<true>, gt, dim3(SW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v);
   else hipLaunchKernelGGL(k_sw_force<false>, gt, dim3(SW_FORCE_TPB), 0, st, d, v);
