@@ -7,7 +7,7 @@
 //   engine_run.cpp     one run of a batch with the OPLS force stage (run_phase), slots
 //   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF, the SW or the Tersoff stage
 //   engine_reax.cpp    the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
-//   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points
+//   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points; what they share with the Tersoff ones
 //   engine_tersoff.cpp the Tersoff force stage (run_phase_tersoff) and the Tersoff entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
@@ -182,28 +182,21 @@ struct SwSlot {
   DevBuf cnt, rows, misc;
 };
 
-// a Stillinger-Weber potential attached to a material id (scema_md_sw_configure)
-struct SwMaterial {
-  SwTable tab;
+enum class RowKind { Opls, Reax, Sw, Tersoff };
+
+// a Stillinger-Weber or Tersoff potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure).  A material
+// holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
+struct RowMaterial {
+  RowKind kind = RowKind::Sw;
   std::vector<int> type_map;   // LAMMPS type - 1 -> element of the tables
+  double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;
-};
-
-// a Tersoff potential attached to a material id (scema_md_tersoff_configure); stamps come from the counter of the SW potentials, so that
-// rows and element arrays never pass from one attachment of a material to another
-struct TsMaterial {
-  TsTable tab;
-  std::vector<int> type_map;   // LAMMPS type - 1 -> element of the tables
-  double skin = 1.0;
-  long long stamp = 0;
-  DevBuf d_tab;
+  DevBuf d_tab;                // the SwTable / TsTable on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
 // checks `kind` first and writes every field it checks.
-enum class RowKind { Opls, Reax, Sw, Tersoff };
 struct ListSig {
   bool valid = false;
   RowKind kind = RowKind::Opls;
@@ -400,17 +393,13 @@ struct scema_md_engine {
   int rx_qeq_launch_cold = 48;        // the same for the first solves of a run (empty history)
   int rx_qeq_launch = 32;             // conjugate-gradient iterations issued as batch launches per solve (follows what the last run needed)
   bool rx_qeq_launch_pinned = false;  // SCEMA_REAX_QEQ_LAUNCH fixes it (0: every solve runs in the single-workgroup loop)
-  // Stillinger-Weber path: the potentials by material id; simulations of such a material take the SW force stage (run_phase)
-  std::map<std::string, std::unique_ptr<SwMaterial>> sw_mats;
+  // Stillinger-Weber and Tersoff paths: the potentials by material id; simulations of such a material take the force stage of its
+  // potential's kind (run_phase)
+  std::map<std::string, std::unique_ptr<RowMaterial>> row_mats;
   long long sw_stamp = 0;
   DevBuf d_swviews;
   std::vector<SwView> h_swviews;
   hipEvent_t sw_done = nullptr;   // part batches of an SW or Tersoff run: the end of the second part (created on first use)
-  // Tersoff path: the potentials by material id (a material holds an SW or a Tersoff potential, never both: configuring one replaces the
-  // other); the row part of a run's work sets is h_swviews / d_swviews
-  std::map<std::string, std::unique_ptr<TsMaterial>> ts_mats;
-  DevBuf d_tsviews;
-  std::vector<TsView> h_tsviews;
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
   scema::SimPlan last_plan;
@@ -462,15 +451,24 @@ int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &s
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_tersoff(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
-// the Stillinger-Weber potential of a material id, or null (engine_sw.cpp)
-SwMaterial *sw_material(scema_md_engine *e, const std::string &matid);
+// the potential of a material id if it is of that kind, or null (engine_sw.cpp); sw_material, ts_material: the Stillinger-Weber, the
+// Tersoff potential
+RowMaterial *row_material(scema_md_engine *e, const std::string &matid, RowKind kind);
+inline RowMaterial *sw_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Sw); }
+inline RowMaterial *ts_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Tersoff); }
+// what the two configure and the two debug_compute entry points of these potentials share (engine_sw.cpp).  row_configure: `read` fills the
+// caller's host table (tab, bytes; its largest cutoff at *cutmax) and type_map from the file, or err; row_debug_compute: ea, eb are the
+// two energies of the stage
+typedef std::function<bool(const std::vector<std::string> &elements, std::vector<int> &type_map, std::string &err)> RowTableReader;
+int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
+                  const void *tab, size_t bytes, const double *cutmax, const RowTableReader &read);
+int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
+                      double *virial, double *info);
 // a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
 bool sw_bare_replica(const Topo &t);
 // element of every atom of a replica on the device (Topo::d_swtype): the element pair_coeff names for its LAMMPS type; `what` names the
 // potential in the refusal (engine_sw.cpp)
 int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map, long long stamp, const char *what);
-// the Tersoff potential of a material id, or null (engine_tersoff.cpp)
-TsMaterial *ts_material(scema_md_engine *e, const std::string &matid);
 // `pair_coeff * * ${locs}/<name>.tersoff <El> ...` in <folder>/in.strain.lammps: configures the material from that line; no such file or
 // line: nothing happens (0); a malformed line: an error
 int tersoff_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
@@ -561,20 +559,14 @@ struct RowRun {
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // What the Stillinger-Weber and the Tersoff stage share (engine_sw.cpp): full neighbour rows inside the material's largest cutoff + skin
-// in the slot's SwSlot, one SwView per position (e->h_swviews / d_swviews; `tab` is the caller's), the row capacity and its growth, part
-// batches on the main and the third stream, the "too many neighbours" fault.  A stage says which material a replica has, adds what its
-// own view needs, and launches.
+// in the slot's SwSlot, one SwView per position (e->h_swviews / d_swviews; `tab` is the material's table on the device, of the stage's
+// own type), the row capacity and its growth, part batches on the main and the third stream, the "too many neighbours" fault.  A stage
+// names its kind and launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces).
 struct SwRowsStage : RowStage {
-  struct Mat { double cutmax = 0.0, skin = 0.0; long long stamp = 0; const std::vector<int> *type_map = nullptr; };
   scema_md_engine *e;
   const char *what;             // the potential's name in messages
   SwView *VV = nullptr;         // the views on the device (upload)
   SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char *what_);
-  // the material of a replica of T, remembered by the stage: bind_view follows for the same one
-  virtual Mat material(const Topo &T) = 0;
-  // what the stage adds to position pos beyond the SwView (its own view, SwView::tab)
-  virtual int bind_view(int pos, SwView &V) = 0;
-  virtual int upload_views() { return SCEMA_MD_OK; }   // the stage's own views to the device
   int nparts() const override;
   int rows(Topo &T, const BoxRange &R, RowNeed &need) override;
   int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override;

@@ -8,9 +8,9 @@ namespace scema_eng {
 // run_phase_sw is the run on per-atom neighbour rows (run_rows, engine_rows.cpp) with the Stillinger-Weber force stage: no bonded terms either
 // (lammps_scripts_sisw/in.strain.lammps has none).
 
-SwMaterial *sw_material(scema_md_engine *e, const std::string &matid) {
-  auto it = e->sw_mats.find(matid);
-  return it == e->sw_mats.end() ? nullptr : it->second.get();
+RowMaterial *row_material(scema_md_engine *e, const std::string &matid, RowKind kind) {
+  auto it = e->row_mats.find(matid);
+  return it == e->row_mats.end() || it->second->kind != kind ? nullptr : it->second.get();
 }
 
 bool sw_bare_replica(const Topo &t) {
@@ -50,8 +50,8 @@ SwRowsStage::SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char 
 int SwRowsStage::nparts() const { return (e->split_streams && e->stream3 && run->ns >= 8 && !run->spec.minimize) ? 2 : 1; }
 
 int SwRowsStage::rows(Topo &T, const BoxRange &R, RowNeed &need) {
-  const Mat M = material(T);
-  if (const int rc = ensure_swtype(e, T, *M.type_map, M.stamp, what)) return rc;
+  const RowMaterial &M = *row_material(e, T.matid, kind);
+  if (const int rc = ensure_swtype(e, T, M.type_map, M.stamp, what)) return rc;
   const int n = T.natoms;
   if (n >= (1 << 24)) return fail(e, SCEMA_MD_ERR_ARG, "a %s replica of %d atoms: row entries hold 24-bit atom indices", what, n);
   const double rlist = M.cutmax + M.skin;
@@ -87,7 +87,7 @@ int SwRowsStage::bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, co
   SWSET(V.eacc, W.misc.as<double>());                 // [0, 4) doubles
   SWSET(V.stat, (int *)(W.misc.as<char>() + 32));     // 2 ints
   e->h_zerotab.push_back(MdkZero{W.misc.as<int>(), 16});   // (the step sums)
-  if (const int rc = bind_view(pos, V)) return rc;
+  SWSET(V.tab, row_material(e, T.matid, kind)->d_tab.p);
   e->h_swviews[pos] = V;
   return SCEMA_MD_OK;
 }
@@ -97,7 +97,7 @@ int SwRowsStage::upload() {
   HIPCHK(e->d_swviews.ensure(bytes));
   HIPCHK(hipMemcpyAsync(e->d_swviews.p, e->h_swviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
   VV = e->d_swviews.as<SwView>();
-  return upload_views();
+  return SCEMA_MD_OK;
 }
 
 int SwRowsStage::part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) {
@@ -123,22 +123,7 @@ int SwRowsStage::faults(int fault) {
 namespace {
 
 struct SwStage : SwRowsStage {
-  const SwMaterial *mat = nullptr;
-
   SwStage(scema_md_engine *e_, int ns) : SwRowsStage(e_, ns, RowKind::Sw, "Stillinger-Weber") {}
-
-  Mat material(const Topo &T) override {
-    mat = sw_material(e, T.matid);
-    Mat M;
-    M.cutmax = mat->tab.cutmax; M.skin = mat->skin; M.stamp = mat->stamp; M.type_map = &mat->type_map;
-    return M;
-  }
-
-  int bind_view(int, SwView &V) override {
-    SWSET(V.tab, mat->d_tab.as<SwTable>());
-    return SCEMA_MD_OK;
-  }
-
   void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
@@ -149,38 +134,40 @@ int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec
   return run_rows(e, sims, spec, stage);
 }
 
-}  // namespace scema_eng
+// ---- the entry points of the C ABI the two potentials share ----
 
-extern "C" {
-
-int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
-                          int32_t energy_unit, double skin) {
+int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
+                  const void *tab, size_t bytes, const double *cutmax, const RowTableReader &read) {
   if (!e) return SCEMA_MD_ERR_ARG;
-  if (!matid || !*matid || !sw_path || !elements || n_elements <= 0) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  if (!matid || !*matid || !path || !elements || n_elements <= 0) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
   (void)settle_pending(e, false);
   HIPCHK(hipSetDevice(e->p.device));
   std::vector<std::string> el;
   for (int k = 0; k < n_elements; k++) el.push_back(elements[k] ? elements[k] : "");
-  std::unique_ptr<SwMaterial> M(new SwMaterial());
+  std::unique_ptr<RowMaterial> M(new RowMaterial());
   std::string err;
-  if (!scema::read_sw_params(sw_path, el, energy_unit, M->tab, M->type_map, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
+  if (!read(el, M->type_map, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
+  M->kind = kind;
+  M->cutmax = *cutmax;
   M->skin = skin < 0.0 ? 1.0 : skin;
   M->stamp = ++e->sw_stamp;
-  HIPCHK(M->d_tab.ensure(sizeof(SwTable)));
-  HIPCHK(hipMemcpyAsync(M->d_tab.p, &M->tab, sizeof(SwTable), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(M->d_tab.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(M->d_tab.p, tab, bytes, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->sw_mats[matid] = std::move(M);   // (a potential it replaces goes with its table: rows and element arrays carry its stamp and are rebuilt)
-  e->ts_mats.erase(matid);            // (a Tersoff potential included: a material holds one attachment)
+  e->row_mats[matid] = std::move(M);   // (the potential it replaces, of either kind, goes with its table: rows and element arrays carry its stamp and are rebuilt)
   return SCEMA_MD_OK;
 }
 
 // static evaluation of a state (qp_id SCEMA_MD_QP_NONE: the registered replica)
-int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3, double *virial,
-                              double *info) {
+int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
+                      double *virial, double *info) {
   if (!e) return SCEMA_MD_ERR_ARG;
   if (!matid) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
   (void)settle_pending(e, false);
-  if (!sw_material(e, matid)) return fail(e, SCEMA_MD_ERR_ARG, "no Stillinger-Weber potential attached to material %s (scema_md_sw_configure)", matid);
+  if (!row_material(e, matid, kind)) {
+    if (kind == RowKind::Sw) return fail(e, SCEMA_MD_ERR_ARG, "no Stillinger-Weber potential attached to material %s (scema_md_sw_configure)", matid);
+    return fail(e, SCEMA_MD_ERR_ARG, "no Tersoff potential attached to material %s (scema_md_tersoff_configure)", matid);
+  }
   HIPCHK(hipSetDevice(e->p.device));
   State *s = nullptr;
   std::unique_ptr<State> tmp;
@@ -196,8 +183,8 @@ int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *mat
   double acc[4];
   HIPCHK(hipMemcpy(acc, (const void *)V.eacc, sizeof acc, hipMemcpyDeviceToHost));
   if (f) HIPCHK(hipMemcpy(f, e->slots[0]->f.p, 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (e2) *e2 = acc[0];
-  if (e3) *e3 = acc[1];
+  if (ea) *ea = acc[0];
+  if (eb) *eb = acc[1];
   if (virial)
     for (int k = 0; k < 6; k++) {
       virial[k] = 0.0;
@@ -210,6 +197,24 @@ int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *mat
     info[3] = acc[3];
   }
   return SCEMA_MD_OK;
+}
+
+}  // namespace scema_eng
+
+extern "C" {
+
+int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
+                          int32_t energy_unit, double skin) {
+  SwTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, std::string &err) {
+    return scema::read_sw_params(sw_path, el, energy_unit, T, type_map, err);
+  };
+  return row_configure(e, RowKind::Sw, matid, sw_path, elements, n_elements, skin, &T, sizeof T, &T.cutmax, read);
+}
+
+int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3, double *virial,
+                              double *info) {
+  return row_debug_compute(e, RowKind::Sw, qp_id, matid, replica, f, e2, e3, virial, info);
 }
 
 }  // extern "C"

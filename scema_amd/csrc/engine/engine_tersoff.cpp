@@ -11,43 +11,11 @@ namespace scema_eng {
 // replica's work set is an SwView over the slot's SwSlot (SwRowsStage, shared with the Stillinger-Weber stage: the rows are mdk_sw_rows');
 // rows built for the other potential are never kept, the slot's ListSig carries RowKind::Tersoff and the material's stamp.
 
-TsMaterial *ts_material(scema_md_engine *e, const std::string &matid) {
-  auto it = e->ts_mats.find(matid);
-  return it == e->ts_mats.end() ? nullptr : it->second.get();
-}
-
-#define TSSET(dst, src) dst = (decltype(dst))(src)
-
 namespace {
 
-// the row part is SwRowsStage (engine_sw.cpp); the stage adds the TsView of every position and its launch
 struct TsStage : SwRowsStage {
-  const TsMaterial *mat = nullptr;
-  TsView *TT = nullptr;
-
-  TsStage(scema_md_engine *e_, int ns) : SwRowsStage(e_, ns, RowKind::Tersoff, "Tersoff") { e->h_tsviews.assign(ns, TsView()); }
-
-  Mat material(const Topo &T) override {
-    mat = ts_material(e, T.matid);
-    Mat M;
-    M.cutmax = mat->tab.cutmax; M.skin = mat->skin; M.stamp = mat->stamp; M.type_map = &mat->type_map;
-    return M;
-  }
-
-  int bind_view(int pos, SwView &) override {
-    TSSET(e->h_tsviews[pos].tab, mat->d_tab.as<TsTable>());
-    return SCEMA_MD_OK;
-  }
-
-  int upload_views() override {
-    const size_t bytes = e->h_tsviews.size() * sizeof(TsView);
-    HIPCHK(e->d_tsviews.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(e->d_tsviews.p, e->h_tsviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    TT = e->d_tsviews.as<TsView>();
-    return SCEMA_MD_OK;
-  }
-
-  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_ts_forces(st, run->D + pos0, VV + pos0, TT + pos0, n, run->maxatoms); }
+  TsStage(scema_md_engine *e_, int ns) : SwRowsStage(e_, ns, RowKind::Tersoff, "Tersoff") {}
+  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_ts_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
 }  // namespace
@@ -93,61 +61,16 @@ extern "C" {
 
 int scema_md_tersoff_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
                                int32_t energy_unit, double skin) {
-  if (!e) return SCEMA_MD_ERR_ARG;
-  if (!matid || !*matid || !path || !elements || n_elements <= 0) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
-  (void)settle_pending(e, false);
-  HIPCHK(hipSetDevice(e->p.device));
-  std::vector<std::string> el;
-  for (int k = 0; k < n_elements; k++) el.push_back(elements[k] ? elements[k] : "");
-  std::unique_ptr<TsMaterial> M(new TsMaterial());
-  std::string err;
-  if (!scema::read_tersoff_params(path, el, energy_unit, M->tab, M->type_map, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
-  M->skin = skin < 0.0 ? 1.0 : skin;
-  M->stamp = ++e->sw_stamp;
-  HIPCHK(M->d_tab.ensure(sizeof(TsTable)));
-  HIPCHK(hipMemcpyAsync(M->d_tab.p, &M->tab, sizeof(TsTable), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  e->ts_mats[matid] = std::move(M);   // (a potential it replaces goes with its table: rows and element arrays carry its stamp and are rebuilt)
-  e->sw_mats.erase(matid);            // (a Stillinger-Weber potential included: a material holds one attachment)
-  return SCEMA_MD_OK;
+  TsTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, std::string &err) {
+    return scema::read_tersoff_params(path, el, energy_unit, T, type_map, err);
+  };
+  return row_configure(e, RowKind::Tersoff, matid, path, elements, n_elements, skin, &T, sizeof T, &T.cutmax, read);
 }
 
-// static evaluation of a state (qp_id SCEMA_MD_QP_NONE: the registered replica)
 int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
                                    double *virial, double *info) {
-  if (!e) return SCEMA_MD_ERR_ARG;
-  if (!matid) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
-  (void)settle_pending(e, false);
-  if (!ts_material(e, matid)) return fail(e, SCEMA_MD_ERR_ARG, "no Tersoff potential attached to material %s (scema_md_tersoff_configure)", matid);
-  HIPCHK(hipSetDevice(e->p.device));
-  State *s = nullptr;
-  std::unique_ptr<State> tmp;
-  int rc = debug_state(e, qp_id, matid, replica, &s, tmp);
-  if (rc) return rc;
-  RunSpec R;
-  R.nvt = 0;
-  R.static_only = 1;
-  if ((rc = eval_static(e, s, R))) return rc;
-  const int n = s->topo->natoms;
-  const SimScalars &sc = e->h_sc[0];
-  const SwView &V = e->h_swviews[0];
-  double acc[4];
-  HIPCHK(hipMemcpy(acc, (const void *)V.eacc, sizeof acc, hipMemcpyDeviceToHost));
-  if (f) HIPCHK(hipMemcpy(f, e->slots[0]->f.p, 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (e_rep) *e_rep = acc[0];
-  if (e_att) *e_att = acc[1];
-  if (virial)
-    for (int k = 0; k < 6; k++) {
-      virial[k] = 0.0;
-      for (int p = 0; p < MD_NPART; p++) virial[k] += sc.vir[p * 6 + k];
-    }
-  if (info) {
-    info[0] = sc.maxneigh_seen;
-    info[1] = V.cap;
-    info[2] = acc[2];
-    info[3] = acc[3];
-  }
-  return SCEMA_MD_OK;
+  return row_debug_compute(e, RowKind::Tersoff, qp_id, matid, replica, f, e_rep, e_att, virial, info);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 namespace scema {
 
 #define SW_EV_TO_KCALMOL 23.060549
+#define SW_NFIELD 11   /* epsilon sigma a lambda gamma costheta0 A B p q tol */
 
 // elements[k] = element symbol of LAMMPS atom type k + 1.  On success T holds the tables of the distinct elements (compact index =
 // order of first appearance, at most SW_MAXEL) and type_map[k] the compact index of LAMMPS type k + 1.  raw, when given, receives the

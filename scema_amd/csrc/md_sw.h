@@ -24,7 +24,7 @@ typedef struct {
   int mimg[3], pad2_;        // neighbour search: 0 0 0 = minimum image (box at least two list radii wide), else images up to mimg[d] boxes away
   double h[6], lo[3];        // box of the step: lx, ly, lz, yz, xz, xy and origin (k_sw_prepare)
   const int SW_G *stype;     // [n] element of every atom (index into the material's SwTable)
-  const SwTable SW_G *tab;   // the material's parameter tables
+  const void SW_G *tab;      // the material's parameter tables: the stage's own type (SwTable, TsTable), cast once by its force kernel
   const double SW_G *x;      // [n][3]
   double SW_G *f;            // [n][3]
   int SW_G *cnt;             // [npad] entries of a row (clamped to cap)
@@ -41,3 +41,7 @@ void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxat
 // its first three launches alone (k_sw_prepare, k_sw_wrap, k_sw_rows): the row part of a step, which the Tersoff force stage shares
 // (md_tersoff.hip); the rows cover SwView::rlist and read nothing of SwView::tab
 void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms);
+// a force stage on those rows: the row part, then `lacc` (replicas up to SW_LDS_MAXPAD atoms, with the LDS force table) or `direct`, then
+// k_sw_finish.  mdk_sw_forces and mdk_ts_forces (md_tersoff.h) are this with their kernels
+typedef void (*SwForceKernel)(const SimDev *, const SwView *);
+void mdk_row_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms, SwForceKernel lacc, SwForceKernel direct);

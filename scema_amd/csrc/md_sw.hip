@@ -6,24 +6,19 @@
 //   k_sw_wrap ...... zero the forces; at a rebuild wrap the atoms into the box (image counts keep the unwrapped information)
 //   k_sw_rows ...... full neighbour rows inside cutoff + skin, rebuilt when the engine's displacement test says so (`neighbor 1.0 nsq`,
 //                    `neigh_modify every 1 delay 0 check yes`): an N^2 search, the replica's positions streamed through LDS
-//   k_sw_force ..... pair and triplet terms (sw/sw_core.h) around a central atom, forces summed in LDS
-//   k_sw_finish .... energies and fault bits into the engine's scalars
+//   k_sw_force ..... pair and triplet terms (sw/sw_core.h) around a central atom, forces summed in LDS (skeleton: md_rowforce.h)
+//   k_sw_finish .... energies and fault bits into the engine's scalars (the Tersoff stage's too)
 // Row entries carry an image code in the convention of the ReaxFF rows: the shift of an entry is code . h with the box of the STEP, so
 // the rows hold while fix deform remaps the atoms with the box; a box flip forces a rebuild.
 #include <hip/hip_runtime.h>
 
-#include "md_device.h"
 #include "md_kernels.h"
-#include "md_sw.h"
-#include "md_types.h"
+#include "md_rowforce.h"
 
-#define SW_NSHIFT 125
 #define SW_ROWS_TPB 512      /* row build: 8 waves of 8 rows */
 #define SW_NBR 8
 #define SW_JT 512            /* partners staged in LDS per pass of the row build */
-#define SW_FORCE_TPB 256     /* force kernel: 16 groups of 16 lanes, a group per central atom */
-#define SW_NGRP (SW_FORCE_TPB / 16)
-static_assert(SW_TILE == 64 && SW_TILE % SW_NGRP == 0 && SW_ROWS_TPB / 64 * SW_NBR == SW_TILE, "tile shapes of md_sw.hip");
+static_assert(SW_TILE == 64 && SW_ROWS_TPB / 64 * SW_NBR == SW_TILE, "tile shapes of md_sw.hip");
 
 __global__ void k_sw_prepare(const SimDev *sims, SwView *views) {
   const SimDev &S = sims[blockIdx.x];
@@ -158,21 +153,17 @@ __global__ __launch_bounds__(SW_ROWS_TPB) void k_sw_rows(const SimDev *sims, con
   }
 }
 
-// LDS FP64 atomic add without return value (ds_add_f64)
-__device__ __forceinline__ void sw_lds_add(double *p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
 // Forces.  A workgroup owns SW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time.  The group first
 // filters the atom's row to the entries INSIDE their pair cutoff -- vector, distance and the radial factor of a triplet arm, computed once
-// per neighbour -- into LDS (ballot order: the row's order); only these reach an exponential.  Then its lanes take the pairs the atom owns
-// (sw_owns: each pair once) and the triplets (a < b) of the filtered list.  Forces on the partners go into a table of the replica's forces
-// in LDS (LACC; ds_add_f64), flushed with one global FP64 atomic per touched atom and component; replicas beyond SW_LDS_MAXPAD atoms add to
-// global memory directly.  Energies, virial and counts are summed per workgroup.
-extern __shared__ double s_swf[];   // LACC: [3][npad]
+// per neighbour -- into LDS (rowf_filter, md_rowforce.h); only these reach an exponential.  Then its lanes take the pairs the atom owns
+// (sw_owns: each pair once) and the triplets (a < b) of the filtered list.  Forces go into the LDS table or to global memory (LACC,
+// md_rowforce.h).  Energies, virial and counts are summed per workgroup.
 template <bool LACC>
 __global__ __launch_bounds__(SW_FORCE_TPB) void k_sw_force(const SimDev *sims, const SwView *views) {
   const SwView V = views[blockIdx.y];
   const int n = V.n;
   if ((int)(blockIdx.x * SW_TILE) >= n) return;   // (the whole workgroup)
+  const SwTable SW_G *tab = (const SwTable SW_G *)V.tab;
   SimScalars &sc = *sims[blockIdx.y].sc;
   const size_t np = (size_t)V.npad;
   __shared__ double s_sh[3 * SW_NSHIFT];
@@ -181,64 +172,28 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_sw_force(const SimDev *sims, c
   __shared__ double s_nb[6][SW_NGRP][SW_MAXIN];   // d (3), r, arm factor, d(arm exponent)/dr
   __shared__ int s_ent[SW_NGRP][SW_MAXIN], s_tj[SW_NGRP][SW_MAXIN];
   __shared__ double s_red[8 * (SW_FORCE_TPB / 64)];
-  for (int code = threadIdx.x; code < SW_NSHIFT; code += SW_FORCE_TPB) {
-    const int sx = code % 5 - 2, sy = (code / 5) % 5 - 2, sz = code / 25 - 2;
-    s_sh[3 * code] = sx * V.h[0] + sy * V.h[5] + sz * V.h[4];
-    s_sh[3 * code + 1] = sy * V.h[1] + sz * V.h[3];
-    s_sh[3 * code + 2] = sz * V.h[2];
-  }
-  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += SW_FORCE_TPB) ((double *)s_pair)[k] = ((const double SW_G *)&V.tab->pair[0])[k];
-  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += SW_FORCE_TPB) ((double *)s_trip)[k] = ((const double SW_G *)&V.tab->trip[0])[k];
-  if (LACC)
-    for (int k = threadIdx.x; k < 3 * (int)np; k += SW_FORCE_TPB) s_swf[k] = 0.0;
+  rowf_shifts(V, s_sh);
+  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += SW_FORCE_TPB) ((double *)s_pair)[k] = ((const double SW_G *)&tab->pair[0])[k];
+  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += SW_FORCE_TPB) ((double *)s_trip)[k] = ((const double SW_G *)&tab->trip[0])[k];
+  rowf_zero<LACC>(np);
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int shift16 = 16 * (grp & 3);
-  const int cap = V.cap;
   double esum[4] = {0.0, 0.0, 0.0, 0.0};   // e2, e3, pairs, triplets
   double w2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, w3[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  auto add_force = [&](int a, double g0, double g1, double g2) __attribute__((always_inline)) {
-    if (LACC) { sw_lds_add(&s_swf[a], g0); sw_lds_add(&s_swf[np + a], g1); sw_lds_add(&s_swf[2 * np + a], g2); }
-    else { atomicAdd((double *)&V.f[3 * a], g0); atomicAdd((double *)&V.f[3 * a + 1], g1); atomicAdd((double *)&V.f[3 * a + 2], g2); }
-  };
+  auto add_force = [&](int a, double g0, double g1, double g2) __attribute__((always_inline)) { rowf_add<LACC>(V.f, np, a, g0, g1, g2); };
   bool crowded = false;
   for (int it = 0; it < SW_TILE / SW_NGRP; it++) {   // (uniform over the workgroup: the barriers and the group sums below are reached by every lane)
     const int i = blockIdx.x * SW_TILE + it * SW_NGRP + grp;
-    const bool valid = i < n;
-    const int ic = valid ? i : n - 1;
-    const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-    const int ti = V.stype[ic];
-    const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-    const size_t base = (size_t)ic * cap;
-    int nn = 0;
-    for (int c0 = 0; c0 < cnt; c0 += 16) {
-      const int c = c0 + l16;
-      int ent = (c < cnt) ? V.rows[base + c] : -1;
-      bool in = false;
-      double d0 = 0.0, d1 = 0.0, d2 = 0.0, r = 1.0;
-      int tj = 0;
-      if (ent >= 0) {
-        const int j = min(ent & SW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, SW_NSHIFT - 1);
-        ent = j | (code << 24);   // (what the builder wrote; nothing else is ever used as an index)
-        const double *sh = s_sh + 3 * code;
-        d0 = V.x[3 * j] - xi0 + sh[0]; d1 = V.x[3 * j + 1] - xi1 + sh[1]; d2 = V.x[3 * j + 2] - xi2 + sh[2];
-        tj = V.stype[j];
-        const double r2 = d0 * d0 + d1 * d1 + d2 * d2, rc = s_pair[ti * SW_MAXEL + tj].cut;
-        in = r2 < rc * rc && r2 > 0.0;
-        r = sqrt(r2);
-        in = in && r < rc;   // (the test sw_arm and sw_two rely on: a pair at or beyond its cutoff never reaches an exponential)
-      }
-      const unsigned m16 = (unsigned)(__ballot(in) >> shift16) & 0xFFFFu;
-      const int pos = nn + __popc(m16 & ((1u << l16) - 1u));
-      if (in && pos < SW_MAXIN) {
-        double ex, da;
-        sw_arm(s_pair[ti * SW_MAXEL + tj], r, &ex, &da);
-        s_nb[0][grp][pos] = d0; s_nb[1][grp][pos] = d1; s_nb[2][grp][pos] = d2; s_nb[3][grp][pos] = r; s_nb[4][grp][pos] = ex; s_nb[5][grp][pos] = da;
-        s_ent[grp][pos] = ent; s_tj[grp][pos] = tj;
-      }
-      nn += __popc(m16);
-    }
-    if (nn > SW_MAXIN) { crowded = true; nn = SW_MAXIN; }
+    const int ti = V.stype[min(i, n - 1)];
+    const int nn = rowf_filter(
+        V, s_sh, i, ti, l16, shift16, crowded, [&](int a, int b) __attribute__((always_inline)) { return s_pair[a * SW_MAXEL + b].cut; },
+        [&](int pos, int ent, int tj, double d0, double d1, double d2, double r) __attribute__((always_inline)) {
+          double ex, da;
+          sw_arm(s_pair[ti * SW_MAXEL + tj], r, &ex, &da);
+          s_nb[0][grp][pos] = d0; s_nb[1][grp][pos] = d1; s_nb[2][grp][pos] = d2; s_nb[3][grp][pos] = r; s_nb[4][grp][pos] = ex; s_nb[5][grp][pos] = da;
+          s_ent[grp][pos] = ent; s_tj[grp][pos] = tj;
+        });
     __syncthreads();   // the groups' lists are complete
     double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
     for (int m = l16; m < nn; m += 16) {
@@ -271,22 +226,10 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_sw_force(const SimDev *sims, c
       w3[0] += da_[0] * fj[0] + db_[0] * fk[0]; w3[1] += da_[1] * fj[1] + db_[1] * fk[1]; w3[2] += da_[2] * fj[2] + db_[2] * fk[2];
       w3[3] += da_[0] * fj[1] + db_[0] * fk[1]; w3[4] += da_[0] * fj[2] + db_[0] * fk[2]; w3[5] += da_[1] * fj[2] + db_[1] * fk[2];
     }
-    // the central atom's own force: the sum over its group (a row of 16 lanes)
-    fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
-    if (valid && l16 == 0 && (fi0 != 0.0 || fi1 != 0.0 || fi2 != 0.0)) add_force(i, fi0, fi1, fi2);
+    rowf_add_own<LACC>(V, np, i, l16, fi0, fi1, fi2);
     __syncthreads();   // the lists have been read: the next atoms may overwrite them
   }
-  if (LACC) {
-    for (int k = threadIdx.x; k < 3 * n; k += SW_FORCE_TPB) {
-      const int a = k / 3, c = k - 3 * a;
-      const double v = s_swf[(size_t)c * np + a];
-      if (v != 0.0) atomicAdd((double *)&V.f[k], v);
-    }
-  }
-  if (crowded) atomicOr(&V.stat[0], 2);
-  block_atomic_add_n<4, SW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(w2, &sc.vir[P_LJ * 6], s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(w3, &sc.vir[P_ANGLE * 6], s_red);
+  rowf_finish<LACC>(V, sc, np, crowded, esum, w2, w3, s_red);
 }
 
 // energies and fault bits of the step into the engine's scalars: row full -> bit 1 (the host regrows and retries), crowded -> bit 128
@@ -310,12 +253,16 @@ void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatom
   hipLaunchKernelGGL(k_sw_rows, gt, dim3(SW_ROWS_TPB), 0, st, d, v);
 }
 
-void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+void mdk_row_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms, SwForceKernel lacc, SwForceKernel direct) {
   if (ns <= 0 || maxatoms <= 0) return;
   const dim3 gt((unsigned)sw_cdv(maxatoms, SW_TILE), (unsigned)ns, 1);
   mdk_sw_rows(st, d, v, ns, maxatoms);
   const int maxpad = (maxatoms + 63) / 64 * 64;
-  if (maxpad <= SW_LDS_MAXPAD) hipLaunchKernelGGL(k_sw_force<true>, gt, dim3(SW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v);
-  else hipLaunchKernelGGL(k_sw_force<false>, gt, dim3(SW_FORCE_TPB), 0, st, d, v);
+  if (maxpad <= SW_LDS_MAXPAD) hipLaunchKernelGGL(lacc, gt, dim3(SW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v);
+  else hipLaunchKernelGGL(direct, gt, dim3(SW_FORCE_TPB), 0, st, d, v);
   hipLaunchKernelGGL(k_sw_finish, dim3(ns), dim3(64), 0, st, d, v);
+}
+
+void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+  mdk_row_forces(st, d, v, ns, maxatoms, k_sw_force<true>, k_sw_force<false>);
 }

@@ -3,108 +3,64 @@
 // integrator, thermostat, fix deform, pressure sampling and the batch machinery are the ones of the OPLS path.  One launch covers every
 // replica of the batch (blockIdx.y).
 //   k_ts_force ..... pair terms, bond orders and their gradients (tersoff/ts_core.h) around a central atom, forces summed in LDS
-//   k_ts_finish .... energies and fault bits into the engine's scalars
+// on the skeleton of md_rowforce.h; the row part, the launch shape and k_sw_finish (energies and fault bits into the engine's scalars) come
+// with mdk_row_forces (md_sw.hip).
 // Engine parts: the repulsive term 1/2 fC fR and its virial go to P_LJ, everything that carries b_ij (1/2 fC b fA and the gradient of zeta)
 // to P_ANGLE.  Only their sum enters the stress; the split is what scema_md_tersoff_debug_compute reports as e_rep and e_att.
 #include <hip/hip_runtime.h>
 
-#include "md_device.h"
 #include "md_kernels.h"
+#include "md_rowforce.h"
 #include "md_tersoff.h"
-#include "md_types.h"
-
-#define TS_NSHIFT 125
-#define TS_FORCE_TPB 256     /* 16 groups of 16 lanes, a group per central atom */
-#define TS_NGRP (TS_FORCE_TPB / 16)
-static_assert(SW_TILE % TS_NGRP == 0 && TS_MAXIN <= 32, "tile shapes of md_tersoff.hip");
-
-// LDS FP64 atomic add without return value (ds_add_f64)
-__device__ __forceinline__ void ts_lds_add(double *p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // Forces.  A workgroup owns SW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time.  The group first
 // filters the atom's row to the entries INSIDE the cutoff under which the pair (i, k) is used -- vector, distance, fC and fC' of the pair,
-// computed once per neighbour -- into LDS (ballot order: the row's order).  Pass 1, a lane per neighbour j: zeta_ij over the other
+// computed once per neighbour -- into LDS (rowf_filter, md_rowforce.h).  Pass 1, a lane per neighbour j: zeta_ij over the other
 // entries, b and b', the pair term at fixed b and its force, and pref_j = 1/2 fC fA b' left in LDS (in the slot of fC', which nothing reads
 // any more).  The pair term is not owned by one end: V_ij != V_ji, every atom does all of its own ordered pairs.  Pass 2, the lanes over
-// the nn (nn - 1) ordered (j, k): pref_j d zeta_ij / d(x_j, x_k) onto j and k.  Forces on the partners go into a table of the replica's
-// forces in LDS (LACC; ds_add_f64), flushed with one global FP64 atomic per touched atom and component; replicas beyond SW_LDS_MAXPAD atoms
-// add to global memory directly.  Energies, virial and counts are summed per workgroup.
-extern __shared__ double s_tsf[];   // LACC: [3][npad]
+// the nn (nn - 1) ordered (j, k): pref_j d zeta_ij / d(x_j, x_k) onto j and k.  Forces go into the LDS table or to global memory (LACC,
+// md_rowforce.h).  Energies, virial and counts are summed per workgroup.
 template <bool LACC>
-__global__ __launch_bounds__(TS_FORCE_TPB) void k_ts_force(const SimDev *sims, const SwView *views, const TsView *tviews) {
+__global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, const SwView *views) {
   const SwView V = views[blockIdx.y];
   const int n = V.n;
   if ((int)(blockIdx.x * SW_TILE) >= n) return;   // (the whole workgroup)
-  const TsTable SW_G *tab = tviews[blockIdx.y].tab;
+  // (a load of its own, which the compiler may not merge: read as V.tab the pointer joins stype, x, f, cnt, rows, eacc and stat in one
+  // 16-dword scalar load, a tuple this kernel's SGPR spilling then reloads whole around every use -- 312 v_readlane for 200, 1 % of an update)
+  const TsTable SW_G *tab = (const TsTable SW_G *)__atomic_load_n(&views[blockIdx.y].tab, __ATOMIC_RELAXED);
   SimScalars &sc = *sims[blockIdx.y].sc;
   const size_t np = (size_t)V.npad;
-  __shared__ double s_sh[3 * TS_NSHIFT];
+  __shared__ double s_sh[3 * SW_NSHIFT];
   __shared__ TsPairP s_pair[TS_MAXEL * TS_MAXEL];
   __shared__ TsTripP s_trip[TS_MAXEL * TS_MAXEL * TS_MAXEL];
   __shared__ double s_cutin[TS_MAXEL * TS_MAXEL];
-  __shared__ double s_nb[6][TS_NGRP][TS_MAXIN];   // d (3), r, fC of the pair, fC' of the pair -> pref after pass 1
-  __shared__ int s_ent[TS_NGRP][TS_MAXIN], s_tj[TS_NGRP][TS_MAXIN];
-  __shared__ double s_red[8 * (TS_FORCE_TPB / 64)];
-  for (int code = threadIdx.x; code < TS_NSHIFT; code += TS_FORCE_TPB) {
-    const int sx = code % 5 - 2, sy = (code / 5) % 5 - 2, sz = code / 25 - 2;
-    s_sh[3 * code] = sx * V.h[0] + sy * V.h[5] + sz * V.h[4];
-    s_sh[3 * code + 1] = sy * V.h[1] + sz * V.h[3];
-    s_sh[3 * code + 2] = sz * V.h[2];
-  }
-  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += TS_FORCE_TPB) ((double *)s_pair)[k] = ((const double SW_G *)&tab->pair[0])[k];
-  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += TS_FORCE_TPB) ((double *)s_trip)[k] = ((const double SW_G *)&tab->trip[0])[k];
-  for (int k = threadIdx.x; k < TS_MAXEL * TS_MAXEL; k += TS_FORCE_TPB) s_cutin[k] = tab->cutin[k];
-  if (LACC)
-    for (int k = threadIdx.x; k < 3 * (int)np; k += TS_FORCE_TPB) s_tsf[k] = 0.0;
+  __shared__ double s_nb[6][SW_NGRP][SW_MAXIN];   // d (3), r, fC of the pair, fC' of the pair -> pref after pass 1
+  __shared__ int s_ent[SW_NGRP][SW_MAXIN], s_tj[SW_NGRP][SW_MAXIN];
+  __shared__ double s_red[8 * (SW_FORCE_TPB / 64)];
+  rowf_shifts(V, s_sh);
+  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += SW_FORCE_TPB) ((double *)s_pair)[k] = ((const double SW_G *)&tab->pair[0])[k];
+  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += SW_FORCE_TPB) ((double *)s_trip)[k] = ((const double SW_G *)&tab->trip[0])[k];
+  for (int k = threadIdx.x; k < TS_MAXEL * TS_MAXEL; k += SW_FORCE_TPB) s_cutin[k] = tab->cutin[k];
+  rowf_zero<LACC>(np);
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int shift16 = 16 * (grp & 3);
-  const int cap = V.cap;
   double esum[4] = {0.0, 0.0, 0.0, 0.0};   // repulsive, bond-order energy, ordered pairs, ordered (j, k)
   double wr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  auto add_force = [&](int a, double g0, double g1, double g2) __attribute__((always_inline)) {
-    if (LACC) { ts_lds_add(&s_tsf[a], g0); ts_lds_add(&s_tsf[np + a], g1); ts_lds_add(&s_tsf[2 * np + a], g2); }
-    else { atomicAdd((double *)&V.f[3 * a], g0); atomicAdd((double *)&V.f[3 * a + 1], g1); atomicAdd((double *)&V.f[3 * a + 2], g2); }
-  };
+  auto add_force = [&](int a, double g0, double g1, double g2) __attribute__((always_inline)) { rowf_add<LACC>(V.f, np, a, g0, g1, g2); };
   bool crowded = false;
-  for (int it = 0; it < SW_TILE / TS_NGRP; it++) {   // (uniform over the workgroup: the barriers and the group sums below are reached by every lane)
-    const int i = blockIdx.x * SW_TILE + it * TS_NGRP + grp;
-    const bool valid = i < n;
-    const int ic = valid ? i : n - 1;
-    const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-    const int ti = V.stype[ic];
-    const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-    const size_t base = (size_t)ic * cap;
-    int nn = 0;
-    for (int c0 = 0; c0 < cnt; c0 += 16) {
-      const int c = c0 + l16;
-      int ent = (c < cnt) ? V.rows[base + c] : -1;
-      bool in = false;
-      double d0 = 0.0, d1 = 0.0, d2 = 0.0, r = 1.0;
-      int tj = 0;
-      if (ent >= 0) {
-        const int j = min(ent & SW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, TS_NSHIFT - 1);
-        ent = j | (code << 24);   // (what the builder wrote; nothing else is ever used as an index)
-        const double *sh = s_sh + 3 * code;
-        d0 = V.x[3 * j] - xi0 + sh[0]; d1 = V.x[3 * j + 1] - xi1 + sh[1]; d2 = V.x[3 * j + 2] - xi2 + sh[2];
-        tj = V.stype[j];
-        const double r2 = d0 * d0 + d1 * d1 + d2 * d2, rc = s_cutin[ti * TS_MAXEL + tj];
-        in = r2 < rc * rc && r2 > 0.0;
-        r = sqrt(r2);
-        in = in && r < rc;
-      }
-      const unsigned m16 = (unsigned)(__ballot(in) >> shift16) & 0xFFFFu;
-      const int pos = nn + __popc(m16 & ((1u << l16) - 1u));
-      if (in && pos < TS_MAXIN) {
-        const TsPairP &P = s_pair[ti * TS_MAXEL + tj];
-        double fc = 0.0, dfc = 0.0;
-        if (r < P.cut) ts_fc(P.bigr, P.bigd, r, &fc, &dfc);   // (a pair at or beyond its R + D: a third atom only)
-        s_nb[0][grp][pos] = d0; s_nb[1][grp][pos] = d1; s_nb[2][grp][pos] = d2; s_nb[3][grp][pos] = r; s_nb[4][grp][pos] = fc; s_nb[5][grp][pos] = dfc;
-        s_ent[grp][pos] = ent; s_tj[grp][pos] = tj;
-      }
-      nn += __popc(m16);
-    }
-    if (nn > TS_MAXIN) { crowded = true; nn = TS_MAXIN; }
+  for (int it = 0; it < SW_TILE / SW_NGRP; it++) {   // (uniform over the workgroup: the barriers and the group sums below are reached by every lane)
+    const int i = blockIdx.x * SW_TILE + it * SW_NGRP + grp;
+    const int ti = V.stype[min(i, n - 1)];
+    const int nn = rowf_filter(
+        V, s_sh, i, ti, l16, shift16, crowded, [&](int a, int b) __attribute__((always_inline)) { return s_cutin[a * TS_MAXEL + b]; },
+        [&](int pos, int ent, int tj, double d0, double d1, double d2, double r) __attribute__((always_inline)) {
+          const TsPairP &P = s_pair[ti * TS_MAXEL + tj];
+          double fc = 0.0, dfc = 0.0;
+          if (r < P.cut) ts_fc(P.bigr, P.bigd, r, &fc, &dfc);   // (a pair at or beyond its R + D: a third atom only)
+          s_nb[0][grp][pos] = d0; s_nb[1][grp][pos] = d1; s_nb[2][grp][pos] = d2; s_nb[3][grp][pos] = r; s_nb[4][grp][pos] = fc; s_nb[5][grp][pos] = dfc;
+          s_ent[grp][pos] = ent; s_tj[grp][pos] = tj;
+        });
     __syncthreads();   // the groups' lists are complete
     double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
     // pass 1: a lane per neighbour j
@@ -163,41 +119,12 @@ __global__ __launch_bounds__(TS_FORCE_TPB) void k_ts_force(const SimDev *sims, c
       wb[0] += dj[0] * fj[0] + dk[0] * fk[0]; wb[1] += dj[1] * fj[1] + dk[1] * fk[1]; wb[2] += dj[2] * fj[2] + dk[2] * fk[2];
       wb[3] += dj[0] * fj[1] + dk[0] * fk[1]; wb[4] += dj[0] * fj[2] + dk[0] * fk[2]; wb[5] += dj[1] * fj[2] + dk[1] * fk[2];
     }
-    // the central atom's own force: the sum over its group (a row of 16 lanes)
-    fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
-    if (valid && l16 == 0 && (fi0 != 0.0 || fi1 != 0.0 || fi2 != 0.0)) add_force(i, fi0, fi1, fi2);
+    rowf_add_own<LACC>(V, np, i, l16, fi0, fi1, fi2);
     __syncthreads();   // the lists have been read: the next atoms may overwrite them
   }
-  if (LACC) {
-    for (int k = threadIdx.x; k < 3 * n; k += TS_FORCE_TPB) {
-      const int a = k / 3, c = k - 3 * a;
-      const double v = s_tsf[(size_t)c * np + a];
-      if (v != 0.0) atomicAdd((double *)&V.f[k], v);
-    }
-  }
-  if (crowded) atomicOr(&V.stat[0], 2);
-  block_atomic_add_n<4, TS_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
-  block_atomic_add_n<6, TS_FORCE_TPB / 64>(wr, &sc.vir[P_LJ * 6], s_red);
-  block_atomic_add_n<6, TS_FORCE_TPB / 64>(wb, &sc.vir[P_ANGLE * 6], s_red);
+  rowf_finish<LACC>(V, sc, np, crowded, esum, wr, wb, s_red);
 }
 
-// energies and fault bits of the step into the engine's scalars: row full -> bit 1 (the host regrows and retries), crowded -> bit 128
-__global__ void k_ts_finish(const SimDev *sims, const SwView *views) {
-  const SwView &V = views[blockIdx.x];
-  SimScalars &sc = *sims[blockIdx.x].sc;
-  if (threadIdx.x != 0) return;
-  sc.eng[P_LJ] = V.eacc[0];
-  sc.eng[P_ANGLE] = V.eacc[1];
-  const int st = V.stat[0];
-  if (st) atomicOr(&sc.overflow, ((st & 1) ? 1 : 0) | ((st & 2) ? 128 : 0));
-}
-
-void mdk_ts_forces(hipStream_t st, const SimDev *d, SwView *v, const TsView *t, int ns, int maxatoms) {
-  if (ns <= 0 || maxatoms <= 0) return;
-  mdk_sw_rows(st, d, v, ns, maxatoms);
-  const dim3 gt((unsigned)((maxatoms + SW_TILE - 1) / SW_TILE), (unsigned)ns, 1);
-  const int maxpad = (maxatoms + 63) / 64 * 64;
-  if (maxpad <= SW_LDS_MAXPAD) hipLaunchKernelGGL(k_ts_force<true>, gt, dim3(TS_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v, t);
-  else hipLaunchKernelGGL(k_ts_force<false>, gt, dim3(TS_FORCE_TPB), 0, st, d, v, t);
-  hipLaunchKernelGGL(k_ts_finish, dim3(ns), dim3(64), 0, st, d, v);
+void mdk_ts_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+  mdk_row_forces(st, d, v, ns, maxatoms, k_ts_force<true>, k_ts_force<false>);
 }
