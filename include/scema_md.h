@@ -425,8 +425,40 @@ int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char
 int scema_md_tersoff_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                                  int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
+/* ---- embedded-atom replicas (`pair_style eam/alloy`; metals and their alloys) ----
+ * configure = `pair_style eam/alloy` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1, in any order,
+ * repeats allowed, at most 4 distinct) for the replicas of ONE material id, registered before or after the call; <path> is a DYNAMO setfl
+ * file; list skin as for scema_md_sw_configure (skin < 0: 1.0).  energy_unit 0: F and r phi of the file are in eV and eV A (units metal)
+ * and are converted to kcal/mol with 23.060549; 1: as written.  The density has no unit.  The file's masses are read and checked, not
+ * applied: masses come from the replica.  The tables become cubic splines on the file's own knots (seven coefficients per knot, the
+ * derivative exactly that of the cubic: forces are the exact gradient of the energy); above rhomax = (Nrho - 1) drho the embedding energy
+ * continues linearly.  Simulations of such a material take the embedded-atom force stage whatever MDSim.force_field says: no SHAKE, no
+ * k-space, no bonded terms; an atom may have any number of neighbours inside the cutoff.  An update or run that mixes them with
+ * simulations of other materials is refused with SCEMA_MD_ERR_ARG.  A material holds ONE attachment: configuring replaces whatever it
+ * held, of any kind.  A bare replica whose material has nothing attached, whose scripts folder holds no Si.sw and whose in.strain.lammps
+ * names no *.tersoff file configures itself at a scema_md_strain_batch from the line `pair_coeff * * ${locs}/<name>.eam.alloy <El> ...`
+ * of <scripts_folder>/in.strain.lammps (energy unit eV); a malformed line of that kind is SCEMA_MD_ERR_ARG.  Not built: eam/fs, funcfl
+ * `pair_style eam`, tables of different spacing. */
+int scema_md_eam_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                           int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], the pair energy 1/2 sum phi and the embedding energy sum F(rho) (kcal/mol), virial[6]
+ * (xx,yy,zz,xy,xz,yz), info[4]: longest neighbour row the build asked for, row capacity, ordered pairs inside the cutoff, atoms whose
+ * density lies above rhomax */
+int scema_md_eam_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair,
+                               double *e_embed, double *virial, double *info);
+/* The reader of setfl files as a pure host function (no GPU, no engine): three comment lines; `Nelements name ...`; `Nrho drho Nr dr
+ * cutoff`; per element `Z mass a0 lattice`, Nrho values of F, Nr values of rho(r); then for every pair i >= j in file order Nr values of
+ * r phi_ij(r); numbers free-format across lines.  n_kept, type_map as for scema_md_sw_read_params; head[8]: Nrho, drho, Nr, dr, cutoff,
+ * rhomax, the number of doubles of the tables, 0; masses[n_kept] (room for 4); tables (may be NULL; tables_cap doubles of room): per kept
+ * element the records of F ([Nrho][4] value {s3 s4 s5 s6}, then [Nrho][4] derivative {s0 s1 s2 0}) and of rho ([Nr][4] twice), then per
+ * kept pair i >= j those of r phi, F and r phi in kcal/mol.  A short or truncated file, a non-numeric field, Nr or Nrho below 5, dr, drho
+ * or the cutoff not positive, a cutoff beyond (Nr - 1) dr, an element that is not in the file, counts that the file's length cannot hold:
+ * SCEMA_MD_ERR_IO with the reason in errbuf. */
+int scema_md_eam_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                            int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf, int32_t errcap);
+
 typedef struct {
-  int64_t pair_launches;      /* timed pair-kernel launches */
+  int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */
   double pair_alg_bytes;      /* algorithmic bytes of those launches, SURVEY.md 8(d) formula */
   int64_t md_steps;           /* simulation-steps advanced (sum over simulations) */

@@ -39,6 +39,7 @@ SYMBOLS = [
     "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
     "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
+    "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -503,6 +504,21 @@ class Engine:
                                                        _p(w), _p(info)))
         return dict(f=f, e_rep=er.value, e_att=ea.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), nzeta=int(info[3]))
 
+    # ---- embedded-atom replicas (pair_style eam/alloy) ----
+    def eam_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style eam/alloy + pair_coeff * * <path> <elements> for the replicas of one material id (a DYNAMO setfl file); energy_unit 0:
+        the file's F and r phi are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
+        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+        self._chk(lib().scema_md_eam_configure(self.h, matid.encode(), path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
+                                               C.c_double(skin)))
+
+    def eam_compute(self, matid, replica, qp=QP_NONE):
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); ep = C.c_double(0.0); ee = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
+        self._chk(lib().scema_md_eam_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(ep), C.byref(ee),
+                                                   _p(w), _p(info)))
+        return dict(f=f, e_pair=ep.value, e_embed=ee.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), nabove=int(info[3]))
+
     # ---- init_material's equilibration schedule (in.init.lammps; md_equil.hip) ----
     def minimize(self, matid, replica, qp, etol=1e-7, ftol=1e-11, maxiter=1000, maxeval=50000) -> dict:
         info = np.zeros(5)
@@ -567,7 +583,7 @@ def sw_system(types, x, box, v=None, masses=(28.0855,)) -> dict:
                 box=np.asarray(box, float), x=np.asarray(x, float), v=np.zeros((n, 3)) if v is None else np.asarray(v, float))
 
 
-bare_system = sw_system   # (the same bare replica under a neutral name: what a Tersoff material registers too)
+bare_system = sw_system   # (the same bare replica under a neutral name: what a Tersoff or an embedded-atom material registers too)
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]
@@ -610,6 +626,43 @@ def tersoff_read_params(path: str, elements, energy_unit: int = 0):
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     n = nk.value
     return n, tmap, vals[:n * n * n * 14].reshape(n, n, n, 14).copy()
+
+
+def eam_read_setfl(path: str, elements, energy_unit: int = 0):
+    """dict of a DYNAMO setfl file (scema_md_eam_read_setfl, a pure host function, no GPU): n (distinct elements kept), type_map, nrho,
+    drho, nr, dr, cutoff, rhomax, masses[n], and the spline records F[i] (value [nrho][4] {s3 s4 s5 s6}, derivative [nrho][4] {s0 s1 s2
+    0}), rho[i], z[(i, j)] (r phi, i >= j) as pairs of arrays, F and r phi in kcal/mol; raises IOError with the reader's message"""
+    L = lib()
+    L.scema_md_eam_read_setfl.restype = C.c_int
+    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+    nk = C.c_int32(0)
+    tmap = np.zeros(len(elements), np.int32)
+    head, masses = np.zeros(8), np.zeros(4)
+    err = C.create_string_buffer(512)
+    args = (path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(head), _p(masses))
+    rc = L.scema_md_eam_read_setfl(*args, None, C.c_int64(0), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    tab = np.zeros(int(head[6]))
+    rc = L.scema_md_eam_read_setfl(*args, _p(tab), C.c_int64(len(tab)), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n, nrho, nr = nk.value, int(head[0]), int(head[2])
+    pos = 0
+
+    def take(m):
+        nonlocal pos
+        val, der = tab[pos:pos + 4 * m].reshape(m, 4).copy(), tab[pos + 4 * m:pos + 8 * m].reshape(m, 4).copy()
+        pos += 8 * m
+        return val, der
+    F, rho, z = [], [], {}
+    for _ in range(n):
+        F.append(take(nrho))
+        rho.append(take(nr))
+    for i in range(n):
+        for j in range(i + 1):
+            z[(i, j)] = take(nr)
+    return dict(n=n, type_map=tmap, nrho=nrho, drho=head[1], nr=nr, dr=head[3], cutoff=head[4], rhomax=head[5], masses=masses[:n].copy(), F=F, rho=rho, z=z)
 
 
 def kspace_setup(params, box, qsqsum: float, natoms: int):

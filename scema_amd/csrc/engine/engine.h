@@ -9,6 +9,7 @@
 //   engine_reax.cpp    the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
 //   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points; what they share with the Tersoff ones
 //   engine_tersoff.cpp the Tersoff force stage (run_phase_tersoff) and the Tersoff entry points
+//   engine_eam.cpp     the embedded-atom force stage (run_phase_eam) and the EAM entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
 //   engine_state.cpp   state store: branch rule, replica / state files
@@ -41,6 +42,7 @@
 #include "host/reax_ffield.h"
 #include "host/sim_plan.h"
 #include "host/sw_params.h"
+#include "host/eam_setfl.h"
 #include "host/tersoff_params.h"
 #include <hipfft/hipfft.h>
 
@@ -50,6 +52,7 @@
 #include "md_pppm_tile.h"
 #include "md_reax.h"
 #include "md_sw.h"
+#include "md_eam.h"
 #include "md_tersoff.h"
 #include "md_types.h"
 
@@ -180,11 +183,13 @@ struct SwSlot {
   int cap_pad = 0;
   size_t cap_rows = 0;
   DevBuf cnt, rows, misc;
+  DevBuf fp;   // embedded-atom stage: F'(rho) per atom (md_eam.h EamView)
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam };
 
-// a Stillinger-Weber or Tersoff potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure).  A material
+// a Stillinger-Weber, Tersoff or embedded-atom potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure,
+// scema_md_eam_configure).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
 struct RowMaterial {
   RowKind kind = RowKind::Sw;
@@ -192,7 +197,7 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;                // the SwTable / TsTable on the device
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -399,6 +404,8 @@ struct scema_md_engine {
   long long sw_stamp = 0;
   DevBuf d_swviews;
   std::vector<SwView> h_swviews;
+  DevBuf d_eamviews;              // embedded-atom stage: parallel to the views
+  std::vector<EamView> h_eamviews;
   hipEvent_t sw_done = nullptr;   // part batches of an SW or Tersoff run: the end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
@@ -451,17 +458,20 @@ int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &s
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_tersoff(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
+int run_phase_eam(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 // the potential of a material id if it is of that kind, or null (engine_sw.cpp); sw_material, ts_material: the Stillinger-Weber, the
 // Tersoff potential
 RowMaterial *row_material(scema_md_engine *e, const std::string &matid, RowKind kind);
 inline RowMaterial *sw_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Sw); }
 inline RowMaterial *ts_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Tersoff); }
-// what the two configure and the two debug_compute entry points of these potentials share (engine_sw.cpp).  row_configure: `read` fills the
-// caller's host table (tab, bytes; its largest cutoff at *cutmax) and type_map from the file, or err; row_debug_compute: ea, eb are the
-// two energies of the stage
-typedef std::function<bool(const std::vector<std::string> &elements, std::vector<int> &type_map, std::string &err)> RowTableReader;
+inline RowMaterial *eam_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Eam); }
+// what the configure and the debug_compute entry points of these potentials share (engine_sw.cpp).  row_configure: `read` fills type_map
+// from the file and says where its host table stands, how large it is (the reader decides) and its largest cutoff (blk), or err;
+// row_debug_compute: ea, eb are the two energies of the stage
+struct RowTableBlock { const void *p = nullptr; size_t bytes = 0; double cutmax = 0.0; };
+typedef std::function<bool(const std::vector<std::string> &elements, std::vector<int> &type_map, RowTableBlock &blk, std::string &err)> RowTableReader;
 int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
-                  const void *tab, size_t bytes, const double *cutmax, const RowTableReader &read);
+                  const RowTableReader &read);
 int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
                       double *virial, double *info);
 // a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
@@ -472,6 +482,11 @@ int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map,
 // `pair_coeff * * ${locs}/<name>.tersoff <El> ...` in <folder>/in.strain.lammps: configures the material from that line; no such file or
 // line: nothing happens (0); a malformed line: an error
 int tersoff_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
+// the same rule for `pair_coeff * * ${locs}/<name>.eam.alloy <El> ...` (engine_eam.cpp), and what the two share (engine_tersoff.cpp): the
+// line that names a file of extension `ext`, handed to `configure` as (path, elements, n)
+int eam_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
+int pair_coeff_from_scripts(scema_md_engine *e, const std::string &folder, const std::string &ext,
+                            const std::function<int(const char *path, const char *const *elements, int32_t n)> &configure);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
 // the batch skeleton every force stage shares (engine_rows.cpp)
@@ -558,10 +573,10 @@ struct RowRun {
   int finish();
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
-// What the Stillinger-Weber and the Tersoff stage share (engine_sw.cpp): full neighbour rows inside the material's largest cutoff + skin
+// What the Stillinger-Weber, the Tersoff and the embedded-atom stage share (engine_sw.cpp): full neighbour rows inside the material's largest cutoff + skin
 // in the slot's SwSlot, one SwView per position (e->h_swviews / d_swviews; `tab` is the material's table on the device, of the stage's
 // own type), the row capacity and its growth, part batches on the main and the third stream, the "too many neighbours" fault.  A stage
-// names its kind and launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces).
+// names its kind and launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h, with an array of its own beside the views).
 struct SwRowsStage : RowStage {
   scema_md_engine *e;
   const char *what;             // the potential's name in messages

@@ -892,7 +892,7 @@ int OplsRun::finish() {
 // Advance sims[0..ns) (already assigned to slots 0..ns-1, scalars' box valid on the device).
 // On return the per-sim SimScalars are in e->h_sc.
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec) {
-  {   // simulations of a material with a Stillinger-Weber or Tersoff potential attached take that force stage, whichever entry point issued the run
+  {   // simulations of a material with a Stillinger-Weber, Tersoff or EAM potential attached take that force stage, whichever entry point issued the run
     size_t n_sw = 0;
     for (const ActiveSim &A : sims) n_sw += sw_material(e, A.st->topo->matid) ? 1 : 0;
     if (n_sw == sims.size() && n_sw > 0) return run_phase_sw(e, sims, spec);
@@ -901,6 +901,10 @@ int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &s
     for (const ActiveSim &A : sims) n_ts += ts_material(e, A.st->topo->matid) ? 1 : 0;
     if (n_ts == sims.size() && n_ts > 0) return run_phase_tersoff(e, sims, spec);
     if (n_ts) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes Tersoff materials (%zu of %zu simulations) with others", n_ts, sims.size());
+    size_t n_eam = 0;
+    for (const ActiveSim &A : sims) n_eam += eam_material(e, A.st->topo->matid) ? 1 : 0;
+    if (n_eam == sims.size() && n_eam > 0) return run_phase_eam(e, sims, spec);
+    if (n_eam) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes EAM materials (%zu of %zu simulations) with others", n_eam, sims.size());
   }
   if (e->reax_active) return run_phase_reax(e, sims, spec);
   const auto t_enter = Clock::now();

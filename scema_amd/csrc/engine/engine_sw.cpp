@@ -39,7 +39,7 @@ int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map,
   return SCEMA_MD_OK;
 }
 
-// ---- the row part the Stillinger-Weber and the Tersoff stage share (engine.h: SwRowsStage) ----
+// ---- the row part the Stillinger-Weber, the Tersoff and the embedded-atom stage share (engine.h: SwRowsStage) ----
 
 SwRowsStage::SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char *what_) : RowStage(kind_, 16), e(e_), what(what_) {
   e->h_swviews.assign(ns, SwView());
@@ -137,7 +137,7 @@ int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec
 // ---- the entry points of the C ABI the two potentials share ----
 
 int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
-                  const void *tab, size_t bytes, const double *cutmax, const RowTableReader &read) {
+                  const RowTableReader &read) {
   if (!e) return SCEMA_MD_ERR_ARG;
   if (!matid || !*matid || !path || !elements || n_elements <= 0) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
   (void)settle_pending(e, false);
@@ -146,13 +146,14 @@ int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const cha
   for (int k = 0; k < n_elements; k++) el.push_back(elements[k] ? elements[k] : "");
   std::unique_ptr<RowMaterial> M(new RowMaterial());
   std::string err;
-  if (!read(el, M->type_map, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
+  RowTableBlock blk;
+  if (!read(el, M->type_map, blk, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
   M->kind = kind;
-  M->cutmax = *cutmax;
+  M->cutmax = blk.cutmax;
   M->skin = skin < 0.0 ? 1.0 : skin;
   M->stamp = ++e->sw_stamp;
-  HIPCHK(M->d_tab.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(M->d_tab.p, tab, bytes, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(M->d_tab.ensure(blk.bytes));
+  HIPCHK(hipMemcpyAsync(M->d_tab.p, blk.p, blk.bytes, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   e->row_mats[matid] = std::move(M);   // (the potential it replaces, of either kind, goes with its table: rows and element arrays carry its stamp and are rebuilt)
   return SCEMA_MD_OK;
@@ -166,6 +167,7 @@ int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const cha
   (void)settle_pending(e, false);
   if (!row_material(e, matid, kind)) {
     if (kind == RowKind::Sw) return fail(e, SCEMA_MD_ERR_ARG, "no Stillinger-Weber potential attached to material %s (scema_md_sw_configure)", matid);
+    if (kind == RowKind::Eam) return fail(e, SCEMA_MD_ERR_ARG, "no EAM potential attached to material %s (scema_md_eam_configure)", matid);
     return fail(e, SCEMA_MD_ERR_ARG, "no Tersoff potential attached to material %s (scema_md_tersoff_configure)", matid);
   }
   HIPCHK(hipSetDevice(e->p.device));
@@ -206,10 +208,12 @@ extern "C" {
 int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
                           int32_t energy_unit, double skin) {
   SwTable T;
-  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, std::string &err) {
-    return scema::read_sw_params(sw_path, el, energy_unit, T, type_map, err);
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_sw_params(sw_path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
   };
-  return row_configure(e, RowKind::Sw, matid, sw_path, elements, n_elements, skin, &T, sizeof T, &T.cutmax, read);
+  return row_configure(e, RowKind::Sw, matid, sw_path, elements, n_elements, skin, read);
 }
 
 int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3, double *virial,

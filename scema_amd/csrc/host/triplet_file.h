@@ -1,6 +1,7 @@
 // triplet_file.h -- what the readers of LAMMPS many-body parameter files share (host/sw_params.cpp, host/tersoff_params.cpp): a file of
 // entries `El1 El2 El3 <nfield numbers>`, an entry on one line or several, `#` starts a comment.  Header only: whatever compiles one of the
-// readers alone (the host drivers under tests/) has all of it.
+// readers alone (the host drivers under tests/) has all of it.  Its tokeniser and number check (file_tokens, word_number) also serve
+// the setfl reader (host/eam_setfl.cpp), whose file is not made of such entries.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -16,6 +17,30 @@
 
 namespace scema {
 
+// The words of a text file with the line each stands on: the first `skip_lines` lines are left out whole, `#` starts a comment where
+// `hash_comments` says so.  What the readers of parameter files tokenise with (this file's, host/eam_setfl.cpp).
+struct FileTok { std::string s; int line; };
+inline void file_tokens(std::istream &in, int skip_lines, bool hash_comments, std::vector<FileTok> &tok) {
+  std::string line;
+  for (int ln = 1; std::getline(in, line); ln++) {
+    if (ln <= skip_lines) continue;
+    if (hash_comments) {
+      const size_t h = line.find('#');
+      if (h != std::string::npos) line.resize(h);
+    }
+    std::istringstream ss(line);
+    std::string w;
+    while (ss >> w) tok.push_back({w, ln});
+  }
+}
+// the whole word as one finite number
+inline bool word_number(const std::string &s, double &v) {
+  char *end = nullptr;
+  v = std::strtod(s.c_str(), &end);
+  return end != s.c_str() && *end == 0 && std::isfinite(v);
+}
+inline std::string show_word(const std::string &w) { return w.size() > 32 ? w.substr(0, 32) + "..." : w; }
+
 // An entry of three named elements i j k (compact indices), its numbers v[nfield] and " (entry that starts on line N)": checks the numbers,
 // may rescale them in place, returns "" or what is wrong with them (`at` included).
 typedef std::function<std::string(int i, int j, int k, double *v, const std::string &at)> TripletCheck;
@@ -27,7 +52,6 @@ typedef std::function<std::string(int i, int j, int k, double *v, const std::str
 // `check` says, duplicate entry, a triplet of el that the file lacks.
 inline bool read_triplet_file(const std::string &path, const std::vector<std::string> &elements, int maxel, int nfield, const TripletCheck &check,
                               std::vector<std::string> &el, std::vector<int> &type_map, std::vector<double> &val, std::string &err) {
-  struct Tok { std::string s; int line; };
   auto bad = [&](const std::string &m) { err = path + ": " + m; return false; };
   if (elements.empty()) return bad("no elements named");
   // the distinct elements in order of first appearance
@@ -44,16 +68,9 @@ inline bool read_triplet_file(const std::string &path, const std::vector<std::st
   if (ne > maxel) return bad("more than " + std::to_string(maxel) + " distinct elements");
   std::ifstream in(path);
   if (!in) return bad("cannot open");
-  std::vector<Tok> tok;
-  std::string line;
-  for (int ln = 1; std::getline(in, line); ln++) {
-    const size_t h = line.find('#');
-    if (h != std::string::npos) line.resize(h);
-    std::istringstream ss(line);
-    std::string w;
-    while (ss >> w) tok.push_back({w, ln});
-  }
-  auto show = [](const std::string &w) { return w.size() > 32 ? w.substr(0, 32) + "..." : w; };
+  std::vector<FileTok> tok;
+  file_tokens(in, 0, true, tok);
+  auto show = show_word;
   auto index_of = [&](const std::string &s) {
     for (int m = 0; m < ne; m++) if (el[m] == s) return m;
     return -1;
@@ -67,9 +84,7 @@ inline bool read_triplet_file(const std::string &path, const std::vector<std::st
     if (tok.size() - t < nw) return bad("short entry: " + std::to_string(tok.size() - t) + " of " + std::to_string(nw) + " words" + at);
     for (int k = 0; k < nfield; k++) {
       const std::string &s = tok[t + 3 + k].s;
-      char *end = nullptr;
-      v[k] = std::strtod(s.c_str(), &end);
-      if (end == s.c_str() || *end != 0 || !std::isfinite(v[k])) return bad("'" + show(s) + "' on line " + std::to_string(tok[t + 3 + k].line) + " is not a number" + at);
+      if (!word_number(s, v[k])) return bad("'" + show(s) + "' on line " + std::to_string(tok[t + 3 + k].line) + " is not a number" + at);
     }
     for (int k = 0; k < 3; k++) {
       char *end = nullptr;

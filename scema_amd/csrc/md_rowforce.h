@@ -1,6 +1,7 @@
 // md_rowforce.h -- what the force kernels on the rows of mdk_sw_rows share (k_sw_force, md_sw.hip; k_ts_force, md_tersoff.hip): the image
 // shifts, the table of the replica's forces in LDS, the filter of one atom's row and the end of a workgroup.  Device code, included by
-// those two files only.  No helper holds a barrier: a kernel's three barriers per round stand in its own body.
+// those two files and, for the image shifts and the launch shape alone, by md_eam.hip.  No helper holds a barrier: a kernel's three
+// barriers per round stand in its own body.
 #pragma once
 #include "md_device.h"
 #include "md_sw.h"

@@ -24,7 +24,7 @@ typedef struct {
   int mimg[3], pad2_;        // neighbour search: 0 0 0 = minimum image (box at least two list radii wide), else images up to mimg[d] boxes away
   double h[6], lo[3];        // box of the step: lx, ly, lz, yz, xz, xy and origin (k_sw_prepare)
   const int SW_G *stype;     // [n] element of every atom (index into the material's SwTable)
-  const void SW_G *tab;      // the material's parameter tables: the stage's own type (SwTable, TsTable), cast once by its force kernel
+  const void SW_G *tab;      // the material's parameter tables: the stage's own type (SwTable, TsTable, an EamHead block), cast once by its kernels
   const double SW_G *x;      // [n][3]
   double SW_G *f;            // [n][3]
   int SW_G *cnt;             // [npad] entries of a row (clamped to cap)
@@ -38,9 +38,11 @@ static_assert(sizeof(double SW_G *) == sizeof(double *), "the qualified pointers
 // the force stage of one step for the first ns replicas: neighbour rows where the rebuild flag of the step is set, pair and triplet
 // terms, forces into SimDev::f, virial (parts P_LJ, P_ANGLE) and energies into SimScalars
 void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms);
-// its first three launches alone (k_sw_prepare, k_sw_wrap, k_sw_rows): the row part of a step, which the Tersoff force stage shares
-// (md_tersoff.hip); the rows cover SwView::rlist and read nothing of SwView::tab
+// its first three launches alone (k_sw_prepare, k_sw_wrap, k_sw_rows): the row part of a step, which the Tersoff and the embedded-atom
+// force stage share (md_tersoff.hip, md_eam.hip); the rows cover SwView::rlist and read nothing of SwView::tab.  mdk_sw_finish is the last
+// launch of a stage on them (k_sw_finish: eacc[0], eacc[1] and the fault bits into the engine's scalars)
 void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms);
+void mdk_sw_finish(hipStream_t st, const SimDev *d, SwView *v, int ns);
 // a force stage on those rows: the row part, then `lacc` (replicas up to SW_LDS_MAXPAD atoms, with the LDS force table) or `direct`, then
 // k_sw_finish.  mdk_sw_forces and mdk_ts_forces (md_tersoff.h) are this with their kernels
 typedef void (*SwForceKernel)(const SimDev *, const SwView *);

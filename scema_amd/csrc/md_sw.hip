@@ -7,7 +7,7 @@
 //   k_sw_rows ...... full neighbour rows inside cutoff + skin, rebuilt when the engine's displacement test says so (`neighbor 1.0 nsq`,
 //                    `neigh_modify every 1 delay 0 check yes`): an N^2 search, the replica's positions streamed through LDS
 //   k_sw_force ..... pair and triplet terms (sw/sw_core.h) around a central atom, forces summed in LDS (skeleton: md_rowforce.h)
-//   k_sw_finish .... energies and fault bits into the engine's scalars (the Tersoff stage's too)
+//   k_sw_finish .... energies and fault bits into the engine's scalars (the Tersoff and the embedded-atom stage's too)
 // Row entries carry an image code in the convention of the ReaxFF rows: the shift of an entry is code . h with the box of the STEP, so
 // the rows hold while fix deform remaps the atoms with the box; a box flip forces a rebuild.
 #include <hip/hip_runtime.h>
@@ -253,6 +253,10 @@ void mdk_sw_rows(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatom
   hipLaunchKernelGGL(k_sw_rows, gt, dim3(SW_ROWS_TPB), 0, st, d, v);
 }
 
+void mdk_sw_finish(hipStream_t st, const SimDev *d, SwView *v, int ns) {
+  if (ns > 0) hipLaunchKernelGGL(k_sw_finish, dim3(ns), dim3(64), 0, st, d, v);
+}
+
 void mdk_row_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms, SwForceKernel lacc, SwForceKernel direct) {
   if (ns <= 0 || maxatoms <= 0) return;
   const dim3 gt((unsigned)sw_cdv(maxatoms, SW_TILE), (unsigned)ns, 1);
@@ -260,7 +264,7 @@ void mdk_row_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxa
   const int maxpad = (maxatoms + 63) / 64 * 64;
   if (maxpad <= SW_LDS_MAXPAD) hipLaunchKernelGGL(lacc, gt, dim3(SW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v);
   else hipLaunchKernelGGL(direct, gt, dim3(SW_FORCE_TPB), 0, st, d, v);
-  hipLaunchKernelGGL(k_sw_finish, dim3(ns), dim3(64), 0, st, d, v);
+  mdk_sw_finish(st, d, v, ns);
 }
 
 void mdk_sw_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {

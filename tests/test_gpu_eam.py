@@ -1,0 +1,560 @@
+"""The embedded-atom force stage on the GPU (md_eam.hip, engine_eam.cpp) against the independent FP64 numpy restatement
+tests/eam_numpy.py, which tests/test_eam_host.py pins on the CPU (no LAMMPS exists to compare with): static parity on the shapes at which
+the kernels or the driver take another path, forces equal bit for bit between evaluations, dynamics, the virial -> pressure conversion,
+elastic constants, whole evaluations, batches over two materials, box flips inside a split batch, refusals, replaced attachments,
+self-configuration from the scripts folder.
+
+Budgets, those of tests/test_gpu_tersoff.py: static parity 1e-10 of the largest force component, energy term and virial component (FP64
+sums of a few hundred terms in another order); NVE after 20 steps 1e-9 A and 1e-11 A/fs; whole evaluations 1e-10 / 1e-9 relative (the
+same arithmetic in another launch shape).  Forces carry no atomic sum in this stage: where two evaluations see the same state they are
+compared bit for bit.
+
+What the groups catch.  Static parity: F'_i and F'_j swapped or the density taken from the central atom's element (both alloy orders),
+the extrapolation above rhomax (the `rhomax` file), a wrong image shift or a missed self-image (the 4-atom cells, the triclinic box), a
+list cut at 32 (every lattice case has 54 neighbours in range), a short last tile or group (the atom counts), rows that overflow.
+Dynamics and pressure: the sign and the 1/2 of the virial, its split over two engine parts.  Whole evaluations: rows kept or rebuilt
+under the wrong material, part streams, flips.  The wrong builds named first were tried on the CPU driver
+(tests/test_eam_host.py::test_wrong_builds_are_caught says what failed).
+"""
+import math
+import os
+import shutil
+
+import numpy as np
+import pytest
+
+import eam_numpy as en
+import tersoff_numpy as tsn
+from scema_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CUAG = os.path.join(ROOT, "tests", "golden", "CuAg.eam.alloy")
+SIC = os.path.join(ROOT, "tests", "golden", "SiC.tersoff")
+SI_SW = os.path.join(ROOT, "tests", "golden", "Si.sw")
+MASS = (en.CU_MASS,)
+MASS2 = (en.CU_MASS, en.AG_MASS)
+
+
+@pytest.fixture(scope="module")
+def ref_cu():
+    return en.EAM(en.read_setfl(CUAG, ["Cu"])[0])
+
+
+@pytest.fixture(scope="module")
+def ref_cuag():
+    return en.EAM(en.read_setfl(CUAG, ["Cu", "Ag"])[0])
+
+
+@pytest.fixture(scope="module")
+def low_file(tmp_path_factory):
+    """copper with rhomax at 1.1 times the lattice's density: a cell compressed by 5 % passes it"""
+    p = str(tmp_path_factory.mktemp("eam") / "CuLow.eam.alloy")
+    en.write_johnson(p, ["Cu"], rhomax_over_rhoe=1.1)
+    return p
+
+
+def _engine(**kw):
+    return capi.Engine(capi.default_params(**kw))
+
+
+def _static(x, box, t, path=CUAG, elements=("Cu",), masses=MASS):
+    e = _engine()
+    try:
+        e.eam_configure("m", path, elements)
+        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
+        return e.eam_compute("m", 1)
+    finally:
+        e.close()
+
+
+def _check_static(got, ref, tol=1e-10, what="eam static"):
+    assert got["npairs"] == ref["npairs"] and got["nabove"] == ref["nabove"], (got["npairs"], ref["npairs"], got["nabove"], ref["nabove"])
+    assert got["maxrow"] <= got["rowcap"]
+    es = max(abs(ref["e_pair"]), abs(ref["e_embed"]))
+    de = max(abs(got["e_pair"] - ref["e_pair"]), abs(got["e_embed"] - ref["e_embed"]))
+    if ref["npairs"] == 0:      # no pair: the embedding energy of bare atoms, no force at all
+        assert not ref["f"].any() and (got["f"] == 0.0).all() and (got["w"] == 0.0).all() and got["e_pair"] == 0.0 and got["e_embed"] == ref["e_embed"]
+        print(f"{what}: no pairs, forces exactly zero, rows {got['maxrow']}/{got['rowcap']}")
+        return
+    fs = np.abs(ref["f"]).max()
+    df = np.abs(got["f"] - ref["f"]).max()
+    dw = np.abs(got["w"] - ref["w"]).max()
+    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / np.abs(ref['w']).max():.2e}, pairs {got['npairs']}, "
+          f"above rhomax {got['nabove']}, rows {got['maxrow']}/{got['rowcap']}")
+    assert df <= tol * fs and de <= tol * es and dw <= tol * np.abs(ref["w"]).max()
+
+
+# the shapes at which a path changes: no pair; one pair; the image search two boxes deep with an atom's own images, at the example width
+# and just above the width the driver refuses; a triclinic box with atoms outside it; one image deep with 54 neighbours in range (32 and
+# 108 atoms); ragged rows (the gas)
+COPPER = {"single": en.case_single, "dimer": en.case_dimer, "cell4": en.case_cell4, "cell4_narrow": lambda: en.case_cell4(3.26),
+          "triclinic": en.case_triclinic, "j32": lambda: en.case_jitter(2), "j108": lambda: en.case_jitter(3), "gas": en.case_gas}
+
+
+@pytest.mark.parametrize("name", sorted(COPPER))
+def test_static_parity_copper(ref_cu, name):
+    x, box, t = COPPER[name]()
+    ref = ref_cu.compute(x, box, t)
+    if name in ("j32", "j108", "triclinic"):
+        assert ref["maxin"] > 32
+    if name == "cell4":
+        assert box[3] == en.A_CU < 6.5 and ref["maxin"] >= 50
+    if name == "cell4_narrow":
+        assert 3.25 < box[3] and abs(box[3] - 3.26) < 1e-12 and ref["maxin"] > 54
+    if name == "single":
+        assert ref["npairs"] == 0 and ref["e_embed"] == ref_cu.t["F"][0][0]
+    _check_static(_static(x, box, t), ref, what=f"eam static {name}")
+
+
+def test_a_cell_below_the_two_image_limit_is_refused():
+    x, box, t = en.case_cell4(3.24)
+    with pytest.raises(capi.EngineError, match=r"box width 3.240 < \(cutoff\+skin\)/2 = 3.250"):
+        _static(x, box, t)
+
+
+def test_dimer_around_the_cutoff(ref_cu):
+    """at 5.5 A - 1e-6, exactly 5.5 A, and + 1e-6: finite values just inside, no pair from the cutoff on"""
+    for d in (-1e-6, 0.0, 1e-6):
+        x, box, t = en.case_dimer(5.5 + d)
+        assert x[1, 0] - x[0, 0] == 5.5 + d
+        got, ref = _static(x, box, t), ref_cu.compute(x, box, t)
+        assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e_pair"]) and math.isfinite(got["e_embed"])
+        _check_static(got, ref, what=f"eam dimer at the cutoff {d:+.0e}")
+        assert got["npairs"] == (2 if d < 0 else 0)
+
+
+@pytest.mark.parametrize("order", ["Cu Ag", "Ag Cu"])
+def test_static_parity_alloy(ref_cuag, order):
+    """32 atoms, the two elements at random, with both element orders in `elements` (the types swapped with them: the same crystal)"""
+    x, box, t = en.case_alloy()
+    ref = ref_cuag.compute(x, box, t)
+    assert len(set(t)) == 2 and ref["maxin"] > 32
+    got = _static(x, box, t if order == "Cu Ag" else 1 - t, elements=tuple(order.split()), masses=MASS2 if order == "Cu Ag" else MASS2[::-1])
+    _check_static(got, ref, what=f"eam static alloy, elements {order}")
+
+
+def test_static_parity_above_rhomax(low_file):
+    ref_e = en.EAM(en.read_setfl(low_file, ["Cu"])[0])
+    x, box, t = en.case_jitter(2, a=0.95 * en.A_CU)
+    ref = ref_e.compute(x, box, t)
+    assert ref["nabove"] == 32
+    _check_static(_static(x, box, t, path=low_file), ref, what="eam static above rhomax")
+
+
+@pytest.mark.parametrize("n", [63, 65, 1025, 1200])
+def test_atom_count_edges(ref_cu, n):
+    """a partial only tile, a second tile of one atom, 1 025 (a group of the last round alone) and 1 200 atoms (a partial last tile)"""
+    x, box, t = en.case_count(n)
+    _check_static(_static(x, box, t), ref_cu.compute(x, box, t), what=f"eam static n = {n}")
+
+
+def test_row_overflow_regrows_and_retries(ref_cu, monkeypatch):
+    """the 108-atom cell with the row capacity forced low through the overflow test hook: fault bit 1, the retry recovers"""
+    x, box, t = en.case_jitter(3)
+    ref = ref_cu.compute(x, box, t)
+    normal = _static(x, box, t)
+    monkeypatch.setenv("SCEMA_MD_NEIGH_GROW0", "0.05")
+    got = _static(x, box, t)
+    _check_static(got, ref, what="eam static after a row overflow")
+    assert got["rowcap"] < normal["rowcap"]          # it started at 8 entries and grew to what the rows asked for, not to the default
+    assert np.array_equal(got["f"], normal["f"])     # the same rows in the same order: the same bits
+
+
+def test_forces_are_bit_reproducible(ref_cu):
+    """two evaluations of one 256-atom state, in one engine and in a fresh one: neither kernel has an atomic on a force or a density"""
+    x, box, t = en.case_jitter(4)
+    a = _static(x, box, t)
+    e = _engine()
+    try:
+        e.eam_configure("m", CUAG, ("Cu",))
+        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=MASS))
+        b, c = e.eam_compute("m", 1), e.eam_compute("m", 1)
+    finally:
+        e.close()
+    assert np.abs(a["f"]).max() > 0.0 and np.array_equal(a["f"], b["f"]) and np.array_equal(b["f"], c["f"])
+    _check_static(a, ref_cu.compute(x, box, t), what="eam static 256 atoms")
+
+
+def _velocities(n, temp, seed, mass=en.CU_MASS):
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(n, 3)) * math.sqrt(en.BOLTZ * temp / mass / en.MVV2E)
+    return v - v.mean(axis=0)
+
+
+def test_nve_dynamics_and_sampled_pressure(ref_cu):
+    x, box, t = en.case_jitter(2)
+    v = _velocities(len(x), 300.0, 1)
+    e = _engine()
+    try:
+        e.eam_configure("cu", CUAG)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
+        # 20 steps NVE against the numpy velocity-Verlet stepper
+        e.set_state(0, "cu", 1, box, x, v)
+        e.debug_run("cu", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
+        _, xg, vg = e.get_state(0, "cu", 1)
+        xr, vr = ref_cu.nve(x, v, box, t, MASS, 1.0, 20)
+        dx = np.abs(en.minimage_diff(xg, xr, box)).max()
+        print(f"eam nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
+        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
+        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
+        e.set_state(1, "cu", 1, box, x, v)
+        p = e.debug_run("cu", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
+        x1, v1 = ref_cu.nve(x, v, box, t, MASS, 1.0, 1)
+        want = ref_cu.pressure_atm(x1, v1, box, t, MASS)
+        print(f"eam sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
+        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
+    finally:
+        e.close()
+
+
+@pytest.fixture(scope="module")
+def static_constants(ref_cu):
+    """C11, C12 and C44 of the fixture's copper (GPa) from second differences of the numpy energy under +-1e-3 homogeneous strain of the
+    perfect lattice, as slopes of the stress.  The lattice at 3.615 A is not at the fixture's zero of pressure (sigma_0 = 0.5 GPa), and
+    the stress is the energy's strain derivative per CURRENT volume: d sigma_yy / d eps_xx = (1 / V0) d2E / d eps_xx d eps_yy - sigma_0,
+    while the xx and xy slopes carry no such term (the factor 1 + eps_xx of dE / d eps_xx and that of the volume cancel)"""
+    x, box = en.fcc(2, 2, 2, en.A_CU)
+    t = en.zeros(len(x))
+    h, v = 1e-3, en.volume(box)
+    E = lambda eps: ref_cu.energy(*en.strained(x, box, eps), t)
+    d = lambda e1, e2: np.diag([e1, e2, 0.0])
+    s = np.zeros((3, 3))
+    s[0, 1] = h
+    e0 = E(d(0.0, 0.0))
+    c11 = (E(d(h, 0.0)) - 2.0 * e0 + E(d(-h, 0.0))) / h ** 2 / v
+    c12 = (E(d(h, h)) - E(d(h, -h)) - E(d(-h, h)) + E(d(-h, -h))) / (4.0 * h ** 2) / v
+    c44 = (E(s) - 2.0 * e0 + E(-s)) / h ** 2 / v
+    sigma0 = -ref_cu.compute(x, box, t)["w"][1] / v
+    return c11 * en.KCALMOL_A3_TO_GPA, (c12 - sigma0) * en.KCALMOL_A3_TO_GPA, c44 * en.KCALMOL_A3_TO_GPA
+
+
+def test_elastic_constants(static_constants):
+    """C11, C12 and C44 as slopes of the stress from the GPU virials at +-1e-3 strain, through set_state, against second differences of the
+    numpy energy (static_constants) within 0.1 % (both are finite differences with a relative truncation of order h^2 C''' / C ~ 1e-5).  No literature value is asserted."""
+    x, box = en.fcc(2, 2, 2, en.A_CU)
+    t = en.zeros(len(x))
+    e = _engine()
+    try:
+        e.eam_configure("cu", CUAG)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
+        h = 1e-3
+        sig = {}
+        shear = np.zeros((3, 3))
+        shear[0, 1] = h
+        for name, eps in (("n", np.diag([h, 0.0, 0.0])), ("s", shear)):
+            for s in (+1, -1):
+                xs, bs = en.strained(x, box, s * eps)
+                e.set_state(5, "cu", 1, bs, xs, np.zeros_like(xs))
+                sig[name, s] = -e.eam_compute("cu", 1, qp=5)["w"] / en.volume(bs) * en.KCALMOL_A3_TO_GPA
+        c11 = (sig["n", +1][0] - sig["n", -1][0]) / (2 * h)
+        c12 = (sig["n", +1][1] - sig["n", -1][1]) / (2 * h)
+        c44 = (sig["s", +1][3] - sig["s", -1][3]) / (2 * h)
+        print(f"eam elastic constants on the device: C11 {c11:.3f}, C12 {c12:.3f}, C44 {c44:.3f} GPa; numpy energy: "
+              f"{static_constants[0]:.3f}, {static_constants[1]:.3f}, {static_constants[2]:.3f}")
+        for got, want in zip((c11, c12, c44), static_constants):
+            assert abs(got / want - 1.0) < 1e-3
+    finally:
+        e.close()
+
+
+def _nts_and_rates(strain, box, dt, rate):
+    lb = box[3:6] - box[:3]
+    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
+    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
+    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
+    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
+
+
+def test_strain_batch_equals_the_two_runs():
+    """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
+    x, box, t = en.case_jitter(2)
+    v = _velocities(len(x), 300.0, 2)
+    L = box[3:6] - box[:3]
+    s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
+    e, f = _engine(), _engine()
+    try:
+        for g in (e, f):
+            g.eam_configure("cu", CUAG)
+            g.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
+        out = np.array(e.strain_batch([capi.make_sim(0, "cu", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
+        f.set_state(0, "cu", 1, box, x, v)
+        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
+        f.debug_run("cu", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
+        want = -f.debug_run("cu", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
+        print(f"eam strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
+        assert nts == 30 and np.abs(out - want).max() <= 1e-10 * np.abs(want).max()
+        assert e.has_state(0, "cu", 1)
+    finally:
+        e.close()
+        f.close()
+
+
+@pytest.fixture(scope="module")
+def eleven():
+    """11 simulations over two EAM materials (copper, and the alloy with two elements), each one's stress and the forces on its end state
+    alone in a fresh engine"""
+    mats = {"cu": (en.case_jitter(2), ("Cu",), MASS), "cuag": (en.case_alloy(), ("Cu", "Ag"), MASS2)}
+    vel = {m: _velocities(len(c[0][0]), 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
+    rng = np.random.default_rng(21)
+    sims = []
+    for q in range(11):
+        m = "cu" if q % 3 else "cuag"
+        box = mats[m][0][1]
+        L = box[3:6] - box[:3]
+        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
+        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
+
+    def fresh():
+        e = _engine()
+        for m, ((x, box, t), el, masses) in mats.items():
+            e.eam_configure(m, CUAG, el)
+            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
+        return e
+
+    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
+    alone = []
+    for q, m, s in sims:
+        e = fresh()
+        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
+        e.close()
+    return fresh, [mk(*s) for s in sims], np.array(alone), [m for _, m, _ in sims]
+
+
+@pytest.mark.parametrize("split", [0, 1])
+def test_batch_of_eleven_equals_each_alone(eleven, split):
+    """the stresses of the batch against each simulation alone; and the forces on every end state, evaluated in the engine that ran the
+    batch (its slots hold rows and F' of other simulations) and in a fresh engine handed the same state: equal bit for bit"""
+    fresh, sims, alone, mat_of = eleven
+    e, g = fresh(), fresh()
+    try:
+        e.batch_split(split)
+        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
+        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
+        print(f"eam batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
+        assert err.max() <= 1e-9
+        for q, m in enumerate(mat_of):
+            box, x, v = e.get_state(q, m, 1)
+            g.set_state(q, m, 1, box, x, v)
+            a, b = e.eam_compute(m, 1, qp=q), g.eam_compute(m, 1, qp=q)
+            assert np.abs(a["f"]).max() > 0.0 and np.array_equal(a["f"], b["f"]), q
+    finally:
+        e.close()
+        g.close()
+
+
+@pytest.fixture(scope="module")
+def sheared():
+    """Eight simulations of a 5 x 2 x 2 copper cell (80 atoms) written with xy = 2 a = 0.4 lx (the same crystal: a lattice translation),
+    each sheared by 0.105 to 0.14 lx in xy, so that every one crosses +lx / 2 and flips once; each one's stress, flips and box alone"""
+    x, box = en.fcc(5, 2, 2, en.A_CU)
+    box[6] = 2.0 * en.A_CU
+    t = en.zeros(len(x))
+    v = _velocities(len(x), 300.0, 31)
+    lx, ly, lz = box[3:6] - box[:3]
+    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
+
+    def fresh():
+        e = _engine()
+        e.eam_configure("cu", CUAG)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
+        return e
+
+    mk = lambda q, s: capi.make_sim(q, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
+    alone, flips, boxes = [], 0, []
+    for q, s in sims:
+        e = fresh()
+        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
+        flips += e.profile()["box_flips"]
+        boxes.append(e.get_state(q, "cu", 1)[0])
+        e.close()
+    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+
+
+def test_box_flips_inside_a_split_batch(sheared):
+    """eight is the smallest batch that runs as two parts: same stresses as each simulation alone, as many flips, every box back inside"""
+    fresh, sims, alone, flips, boxes = sheared
+    assert flips >= 8
+    e = fresh()
+    try:
+        e.batch_split(1)
+        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
+        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
+        print(f"eam sheared batch of 8 (split): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
+        assert err.max() <= 1e-9
+        assert e.profile()["box_flips"] == flips
+        for q in range(8):
+            b = e.get_state(q, "cu", 1)[0]
+            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
+    finally:
+        e.close()
+
+
+def test_mixed_updates_are_refused(small_pe):
+    """EAM + Stillinger-Weber, EAM + Tersoff and EAM + OPLS in one update: SCEMA_MD_ERR_ARG before anything is planned; each alone runs"""
+    x, box, t = en.case_jitter(2)
+    xs, bs, ts = tsn.case_a()
+    e = _engine(cut_lj=5.0, cut_coul=4.0, skin=1.0, kspace_accuracy=1e-5)
+    try:
+        e.eam_configure("cu", CUAG)
+        e.sw_configure("sw", SI_SW)
+        e.tersoff_configure("ts", SIC)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
+        e.register_replica("sw", 1, capi.bare_system(ts, xs, bs))
+        e.register_replica("ts", 1, capi.bare_system(ts, xs, bs))
+        e.register_replica("pe", 1, small_pe)
+        L = box[3:6] - box[:3]
+        s = np.array([1e-3 * L[0], 0.0, 0.0, 0.0, 0.0, 0.0])
+        mk = lambda q, m: capi.make_sim(q, m, 1, s, nss=10, most_recent=capi.QP_NONE)
+        for other in ("sw", "ts", "pe"):
+            with pytest.raises(capi.EngineError, match="rc=1.*mixes"):
+                e.strain_batch([mk(0, "cu"), mk(1, other)])
+            assert not e.has_state(0, "cu", 1) and not e.has_state(1, other, 1)
+        assert e.strain_batch([mk(0, "cu")])[0].stress_updated == 1
+        for other in ("pe", "sw", "ts"):
+            with pytest.raises(capi.EngineError, match="no EAM potential"):
+                e.eam_compute(other, 1)
+    finally:
+        e.close()
+
+
+def test_configuring_replaces_the_other_attachment(ref_cu):
+    """a material holds one attachment: an EAM potential configured over a Tersoff one replaces it (rows and element arrays are rebuilt: the
+    forces are those of a fresh engine), and the other way round"""
+    x, box, t = en.case_jitter(2)
+    fresh = _static(x, box, t)
+    xs, bs, ts = tsn.case_a()
+    ref_ts = tsn.Tersoff(tsn.read_tersoff(SIC, ["Si"])[0]).compute(xs, bs, ts)
+    e = _engine()
+    try:
+        e.tersoff_configure("m", SIC)
+        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=MASS))
+        e.register_replica("m", 2, capi.bare_system(ts, xs, bs))
+        ts0 = e.tersoff_compute("m", 2)
+        e.eam_configure("m", CUAG)
+        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
+            e.tersoff_compute("m", 2)
+        got = e.eam_compute("m", 1)
+        _check_static(got, ref_cu.compute(x, box, t), what="eam over a Tersoff attachment")
+        assert np.array_equal(got["f"], fresh["f"])
+        e.tersoff_configure("m", SIC)
+        with pytest.raises(capi.EngineError, match="no EAM potential"):
+            e.eam_compute("m", 1)
+        ts1 = e.tersoff_compute("m", 2)
+        assert ts1["npairs"] == ts0["npairs"] == ref_ts["npairs"]
+        assert np.abs(ts1["f"] - ref_ts["f"]).max() <= 1e-10 * np.abs(ref_ts["f"]).max()
+    finally:
+        e.close()
+
+
+def _dimer_update(scripts, configure):
+    """one update of a two-atom replica: every sum of the step has two terms, so its bits do not depend on the order of the atomic sums,
+    and two runs of the same configuration agree bit for bit"""
+    box = np.array([0.0, 0.0, 0.0, 14.0, 14.0, 14.0, 0.0, 0.0, 0.0])
+    x = np.array([[5.0, 6.0, 6.0], [7.4, 6.1, 5.9]])
+    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
+    e = _engine()
+    try:
+        if configure:
+            e.eam_configure("cu", CUAG, ("Cu",))
+        e.register_replica("cu", 1, capi.bare_system(en.zeros(2), x, box, v=v, masses=MASS))
+        s = np.array([1.4e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
+        sim = capi.make_sim(0, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
+                            scripts_folder=str(scripts))
+        out = np.array(e.strain_batch([sim])[0].stress[:])
+        return out, e.get_state(0, "cu", 1)
+    finally:
+        e.close()
+
+
+def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
+    """`pair_coeff * * ${locs}/CuAg.eam.alloy Cu` in in.strain.lammps configures a bare replica whose material has nothing attached; a
+    folder whose script names a Tersoff file, or that holds Si.sw, still takes that potential; a malformed line is an error"""
+    scripts = tmp_path / "lammps_scripts_eam"
+    scripts.mkdir()
+    shutil.copy(CUAG, scripts / "CuAg.eam.alloy")
+    (scripts / "in.strain.lammps").write_text("# straining run\npair_style eam/alloy\n#pair_coeff * * ${locs}/other.eam.alloy Ag\n"
+                                              "pair_coeff * * ${locs}/CuAg.eam.alloy Cu   # the potential\nfix 1 all nvt temp 300 300 100\n")
+    a, sa = _dimer_update(scripts, configure=False)
+    b, sb = _dimer_update(scripts, configure=True)
+    assert np.isfinite(a).all() and np.abs(a).max() > 0.0
+    assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
+    # the update configured the material: static forces of the 32-atom cell against the numpy helper
+    x, box, t = en.case_jitter(2)
+    L = box[3:6] - box[:3]
+    mk = lambda folder: capi.make_sim(0, "cu", 1, np.array([1e-3 * L[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls",
+                                      scripts_folder=str(folder))
+    e = _engine()
+    try:
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3), masses=MASS))
+        with pytest.raises(capi.EngineError, match="no EAM potential"):
+            e.eam_compute("cu", 1)
+        assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
+        _check_static(e.eam_compute("cu", 1), ref_cu.compute(x, box, t), what="eam self-configured")
+    finally:
+        e.close()
+    # a Tersoff line and Si.sw keep their precedence, in that order
+    xs, bs, ts = tsn.case_a()
+    for name, extra, hook in (("tersoff", None, "tersoff_compute"), ("both", SI_SW, "sw_compute")):
+        d = tmp_path / name
+        shutil.copytree(scripts, d)
+        shutil.copy(SIC, d / "SiC.tersoff")
+        (d / "in.strain.lammps").write_text("pair_coeff * * ${locs}/CuAg.eam.alloy Cu\npair_coeff * * ${locs}/SiC.tersoff Si\n")
+        if extra:
+            shutil.copy(extra, d / "Si.sw")
+        e = _engine()
+        try:
+            e.register_replica("cu", 1, capi.bare_system(ts, xs, bs, v=_velocities(len(xs), 300.0, 3, tsn.SI_MASS)))
+            Ls = bs[3:6] - bs[:3]
+            sim = capi.make_sim(0, "cu", 1, np.array([1e-3 * Ls[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls", scripts_folder=str(d))
+            assert e.strain_batch([sim])[0].stress_updated == 1
+            assert getattr(e, hook)("cu", 1)["npairs"] >= 2 * len(xs)
+            with pytest.raises(capi.EngineError, match="no EAM potential"):
+                e.eam_compute("cu", 1)
+        finally:
+            e.close()
+    # malformed lines
+    for k, line in enumerate(["pair_coeff 1 1 ${locs}/CuAg.eam.alloy Cu", "pair_coeff * * CuAg.eam.alloy Cu", "pair_coeff * * ${locs}/CuAg.eam.alloy",
+                              "pair_coeff * * ${locs}/sub/CuAg.eam.alloy Cu"]):
+        badf = tmp_path / f"bad{k}"
+        badf.mkdir()
+        shutil.copy(CUAG, badf / "CuAg.eam.alloy")
+        (badf / "in.strain.lammps").write_text(line + "\n")
+        e = _engine()
+        try:
+            e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
+            with pytest.raises(capi.EngineError, match=r"in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.eam\.alloy"):
+                e.strain_batch([mk(badf)])
+        finally:
+            e.close()
+    # a line that names a file the folder lacks: the reader's message
+    miss = tmp_path / "miss"
+    miss.mkdir()
+    (miss / "in.strain.lammps").write_text("pair_coeff * * ${locs}/CuAg.eam.alloy Cu\n")
+    e = _engine()
+    try:
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
+        with pytest.raises(capi.EngineError, match="CuAg.eam.alloy: cannot open"):
+            e.strain_batch([mk(miss)])
+    finally:
+        e.close()
+
+
+def test_init_material_runs_for_an_eam_material(static_constants):
+    """scema_md_init_material through the same switch: homogenisation run + 12 strained runs of the 32-atom cell, started on the lattice
+    with velocities of 10 K, with 20 sampling steps.  A plumbing check: finite C11 and C12 within 2 % of the static ones (a metal's
+    constants soften by some 3e-4 per kelvin: well below 1 % here; the strained runs continue one state, so their noise is shared)"""
+    x, box = en.fcc(2, 2, 2, en.A_CU)
+    t = en.zeros(len(x))
+    e = _engine()
+    try:
+        e.eam_configure("cu", CUAG)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 10.0, 9), masses=MASS))
+        length, stress, stiff = e.init_material("cu", 1, dt=1.0, temperature=10.0, nss=20, strain_ampl=0.005, strain_rate=1e-4)
+        assert np.allclose(length, box[3:6] - box[:3]) and np.isfinite(stress).all() and np.isfinite(stiff).all()
+        c11, c12 = stiff[0, 0] / 1e9, stiff[0, 3] / 1e9        # file order 00, 01, 02, 11, 12, 22
+        print(f"eam init_material: C11 {c11:.2f} GPa, C12 {c12:.2f} GPa (static lattice: {static_constants[0]:.2f}, {static_constants[1]:.2f})")
+        assert abs(c11 / static_constants[0] - 1.0) < 0.02 and abs(c12 / static_constants[1] - 1.0) < 0.02
+    finally:
+        e.close()
