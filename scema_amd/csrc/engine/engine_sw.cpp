@@ -59,7 +59,10 @@ int SwRowsStage::rows(Topo &T, const BoxRange &R, RowNeed &need) {
   const double rho = n / R.vol_min;
   const int cap = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.5 * e->neigh_grow);
   need.rlist = rlist; need.skin = M.skin; need.stamp = M.stamp;
-  need.cap[0] = std::max(8, (cap + 7) / 8 * 8);
+  // (the floor of 8 entries grows with the same factor: a cluster in a large empty box has a mean density near zero, and a factor that
+  // only multiplied `cap` would be swallowed by the floor -- 17 neighbours in a 30 A box were still not held after six attempts)
+  const int floor8 = (int)std::ceil(8.0 * e->neigh_grow);
+  need.cap[0] = std::max(8, (std::max(cap, floor8) + 7) / 8 * 8);
   return SCEMA_MD_OK;
 }
 

@@ -219,7 +219,10 @@ class EAM:
 # with parameters in the range of his for copper and silver (Ec and phie in eV, re = a / sqrt 2), carried out to the file's cutoff and
 # multiplied there by a switching function; rhoe is the density of the perfect lattice under that cutoff.  Physical accuracy is not claimed.
 JOHNSON = {"Cu": dict(Z=29, mass=63.546, a=3.615, Ec=3.54, fe=0.30, phie=0.59, alpha=5.09, beta=5.85, gamma=8.00),
-           "Ag": dict(Z=47, mass=107.8682, a=4.09, Ec=2.85, fe=0.17, phie=0.48, alpha=5.92, beta=5.96, gamma=8.26)}
+           "Ag": dict(Z=47, mass=107.8682, a=4.09, Ec=2.85, fe=0.17, phie=0.48, alpha=5.92, beta=5.96, gamma=8.26),
+           # two invented elements for the four-element files of the edge tests (numbers of the same range, no metal meant)
+           "X1": dict(Z=28, mass=58.7, a=3.52, Ec=4.45, fe=0.41, phie=0.74, alpha=4.98, beta=6.41, gamma=8.86),
+           "X2": dict(Z=79, mass=197.0, a=4.08, Ec=3.93, fe=0.23, phie=0.65, alpha=6.37, beta=6.67, gamma=8.20)}
 CUTOFF, SWITCH_ON = 5.5, 4.5
 A_CU, A_AG = 3.615, 4.09
 CU_MASS, AG_MASS = 63.546, 107.8682
@@ -363,3 +366,54 @@ def case_count(n, seed=15):
     rng = np.random.default_rng(seed)
     x = x + rng.uniform(-0.1, 0.1, x.shape)
     return x[:n].copy(), box, zeros(n)
+
+
+# ---- inputs for the edges of the kernels (tests/test_row_edges_host.py, tests/test_gpu_eam_edges.py): generators only ----
+FOUR = ["Cu", "X1", "Ag", "X2"]          # the element order of the four-element file: a kept subset (Cu, Ag) skips X1 in the middle
+RLIST = CUTOFF + 1.0                     # + the default skin of eam_configure
+
+
+def check_box(box):
+    """each perpendicular width is at least RLIST / 2 (below it the engine refuses: it searches at most two images deep)"""
+    w = widths(box)
+    assert (w >= RLIST / 2.0).all(), w
+    return w
+
+
+def case_four(ntypes=4, seed=19):
+    """2 x 2 x 2 cells of a = 3.85 A, jitter 0.1 A, `ntypes` LAMMPS types placed at random (each one present)"""
+    x, box, _ = case_jitter(2, seed, 3.85)
+    t = np.random.default_rng(seed + 1).integers(0, ntypes, len(x))
+    assert len(set(int(v) for v in t)) == ntypes
+    return x, box, t
+
+
+def case_partly_above(amp=0.15):
+    """the 32-atom jittered copper cell under the displacement u_x = -amp L / (2 pi) sin(2 pi x / L): compressed by amp along x around
+    x = 0, stretched as much around x = L / 2.  Under a file with rhomax at 1.1 times the lattice's density some atoms lie above it, some below"""
+    x, box, t = case_jitter(2)
+    L = box[3] - box[0]
+    x = x.copy()
+    x[:, 0] -= amp * L / (2.0 * math.pi) * np.sin(2.0 * math.pi * x[:, 0] / L)
+    return x, box, t
+
+
+def case_cell4_tilted(sign=1):
+    """case_cell4 sheared with its box to xy = sign * 0.45 lx: perpendicular widths 3.30 / 3.30 / 3.615 A, above the 3.25 A below which
+    the engine refuses and below the list radius 6.5 A -- two images deep in a tilted cell"""
+    x, box, t = case_cell4()
+    F = np.array([[1.0, sign * 0.45, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
+    box = box.copy()
+    box[6] = sign * 0.45 * (box[4] - box[1])
+    check_box(box)
+    return x @ F.T, box, t
+
+
+HOT_BOX = np.array([0.0, 0.0, 0.0, 3.4, 7.0, 7.6, 0.0, 0.0, 0.0])
+
+
+def case_hot_gas(n=8, dmin=1.65, seed=5):
+    """a small copper gas in a box 3.4 A wide, no two atoms (or images) closer than dmin: far off equilibrium (the lattice's nearest
+    neighbours are 2.556 A apart), so that the atoms move past half a skin within some tens of steps"""
+    check_box(HOT_BOX)
+    return gas(n, HOT_BOX, dmin, seed), HOT_BOX.copy(), zeros(n)

@@ -18,7 +18,8 @@ struct Driver {
   std::vector<int> type_map;
   int wrong;   // deliberately wrong builds, for the tests that show what the suite catches: 1 the pair term owned by the lower index
                // (and doubled), 2 the R, D of fC(r_ik) taken from the pair entry i k k, 3 the same taken from the pair entry i j j (the
-               // pair's own parameter set used where pair_tersoff.cpp uses that of i j k)
+               // pair's own parameter set used where pair_tersoff.cpp uses that of i j k), 4 the neighbour list cut at the pair's own
+               // R + D instead of cutin, so that no entry serves as a third atom only
 };
 struct Nb { int j, tj, code; double d[3], r, fc, dfc, pref; };
 }  // namespace
@@ -96,7 +97,7 @@ int tsh_compute(void *h, int n, const int *types, const double *x, const double 
             Nb q;
             q.d[0] = d[0] + sx * hx + sy * xy + sz * xz; q.d[1] = d[1] + sy * hy + sz * yz; q.d[2] = d[2] + sz * hz;
             q.r = std::sqrt(q.d[0] * q.d[0] + q.d[1] * q.d[1] + q.d[2] * q.d[2]);
-            if (!(q.r < T.cutin[ti * TS_MAXEL + tj])) continue;   // at or beyond every cutoff it could be used under
+            if (!(q.r < (D.wrong == 4 ? P.cut : T.cutin[ti * TS_MAXEL + tj]))) continue;   // at or beyond every cutoff it could be used under
             q.j = j; q.tj = tj; q.code = (sx + 1) + 3 * (sy + 1) + 9 * (sz + 1);
             q.fc = q.dfc = q.pref = 0.0;
             if (q.r < P.cut) ts_fc(P.bigr, P.bigd, q.r, &q.fc, &q.dfc);

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from sw_numpy import (BOLTZ, FTM2V, KCALMOL_A3_TO_GPA, MVV2E, NKTV2P, diamond, gas, h_matrix, minimage_diff, strained,  # noqa: F401
-                      volume, widths)
+                      supercell, volume, widths)
 
 EV_TO_KCALMOL = 23.060549
 FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
@@ -350,3 +350,85 @@ def case_synth(seed=17):
     x, box = diamond(2, 2, 2, A_SI)
     rng = np.random.default_rng(seed)
     return x + rng.uniform(-0.15, 0.15, x.shape), box, rng.integers(0, 2, len(x))
+
+
+# ---- inputs for the edges of the kernel (tests/test_row_edges_host.py, tests/test_gpu_tersoff_edges.py): generators only ----
+SI_CUT = 3.0                     # R + D of silicon in tests/golden/SiC.tersoff
+SI_RLIST = SI_CUT + 1.0          # + the default skin of tersoff_configure
+SYNTH_CUT = 3.1                  # the largest R + D of SYNTH (the pair X X)
+
+
+def check_box(box, cutmax=SI_CUT, rlist=SI_RLIST):
+    """the conditions every input box of the edge tests meets: each perpendicular width is at least cutmax / 1.5 (Tersoff.neighbours
+    searches the fractional minimum image +- 1, complete only above that width) and at least rlist / 2 (below it the engine refuses)"""
+    w = widths(box)
+    assert (w >= cutmax / 1.5).all() and (w >= rlist / 2.0).all(), w
+    return w
+
+
+def case_shell(seed=17):
+    """2 x 2 x 2 diamond cells of 0.78 * 5.432 A (box 8.474 A), the two elements at random, jitter 0.06 A: bonds of 1.83 A and second
+    neighbours around 3.0 A, where the pair cutoffs of SYNTH (2.9 to 3.1 A) and the cutoffs of its i j k entries (2.8 to 3.05 A) cross:
+    entries at or beyond the pair's own R + D that still count as the third atom of another pair's zeta"""
+    x, box = diamond(2, 2, 2, 0.78 * A_SI)
+    rng = np.random.default_rng(seed)
+    return x + rng.uniform(-0.06, 0.06, x.shape), box, rng.integers(0, 2, len(x))
+
+
+def third_only(ref, x, box, types):
+    """the number of row entries (i, k) with R + D of the pair (i, k) <= r < the largest R + D under which k is used around i: the
+    kernel's entries with fC = 0 that serve as third atoms only"""
+    count = 0
+    kinds = sorted(set(int(t) for t in types))
+    for i, row in enumerate(ref.neighbours(x, box, types)):
+        ti = types[i]
+        for k, _, _, rk in row:
+            own = ref.p[(ti, types[k], types[k])]
+            cutin = max([own["R"] + own["D"]] + [ref.p[(ti, tj, types[k])]["R"] + ref.p[(ti, tj, types[k])]["D"] for tj in kinds])
+            count += 1 if own["R"] + own["D"] <= rk < cutin else 0
+    return count
+
+
+NARROW_BOX = np.array([0.0, 0.0, 0.0, 2.45, 2.6, 2.75, 0.0, 0.0, 0.0])
+SLAB_BOX = np.array([0.0, 0.0, 0.0, 2.9, 5.0, 5.6, 0.0, 0.0, 0.0])
+ROD_BOX = np.array([0.0, 0.0, 0.0, 2.45, 4.4, 5.2, 0.0, 0.0, 0.0])
+
+
+def narrow(name):
+    """boxes narrower than one cutoff (3.0 A; the engine refuses below 2.0 A): an atom pairs with its own image, j and k of a zeta term
+    may be two images of one atom, a partner's index may be the central atom's own
+      N1  one atom in 2.45 x 2.6 x 2.75 A: every neighbour is its own image       N2  two atoms, gas(2, ., 1.9, 7), in the same box
+      N3  four atoms, gas(4, ., 2.0, 3), in 2.9 x 5.0 x 5.6 A                      N4  gas(4, ., 2.0, 3) in that box tilted by xy 1.3, xz -1.2,
+      N5  N4 with xy -1.3 (widths 2.79 / 4.65 / 5.6 A)                                 yz 2.2 (widths 2.68 / 4.65 / 5.6 A)
+      N6  gas(4, ., 2.0, 3) in 2.85 x 5.0 x 5.6 A, types alternating (SYNTH): an atom's own image inside the Y Y shell 2.7 .. 2.9 A
+      N7  three atoms, gas(3, ., 2.0, 5), in 2.45 x 4.4 x 5.2 A (dynamics)"""
+    if name == "N1":
+        x, box, t = np.array([[1.0, 1.0, 1.0]]), NARROW_BOX.copy(), zeros(1)
+    elif name == "N2":
+        x, box, t = gas(2, NARROW_BOX, 1.9, 7), NARROW_BOX.copy(), zeros(2)
+    elif name in ("N3", "N4", "N5", "N6"):
+        box = SLAB_BOX.copy()
+        if name == "N6":
+            box[3] = 2.85          # (not 2.9 A: an atom's own image would sit on the Y Y cutoff of SYNTH to the bit)
+        if name in ("N4", "N5"):
+            box[6], box[7], box[8] = (1.3 if name == "N4" else -1.3), -1.2, 2.2
+        x = gas(4, box, 2.0, 3)          # (the same draws: in N4 the fractional coordinates of N3, in N5 its first candidates)
+        t = np.arange(4) % 2 if name == "N6" else zeros(4)
+    elif name == "N7":
+        x, box, t = gas(3, ROD_BOX, 2.0, 5), ROD_BOX.copy(), zeros(3)
+    else:
+        raise KeyError(name)
+    check_box(box, *((SYNTH_CUT, SYNTH_CUT + 1.0) if name == "N6" else ()))
+    return x, box, t
+
+
+def fterm(ref, x, box, types):
+    """the largest pair force at b = 1 among the pairs of a configuration: the size of the terms that cancel in a symmetric one"""
+    out = 0.0
+    for i, row in enumerate(ref.neighbours(x, box, types)):
+        for j, _, _, r in row:
+            p = ref.p[(types[i], types[j], types[j])]
+            fcv, dfc = fc(p, r)
+            fr, fa = p["A"] * math.exp(-p["lambda1"] * r), -p["B"] * math.exp(-p["lambda2"] * r)
+            out = max(out, abs(0.5 * (dfc * (fr + fa) + fcv * (-p["lambda1"] * fr - p["lambda2"] * fa))))
+    return out

@@ -9,11 +9,14 @@ arithmetic in another launch shape).
 
 What the groups catch.  Static parity: a pair term owned by one end only (every jittered case: forces, energies and the count of ordered
 pairs), the cutoff of fC(r_ik) from the wrong entry (from i j j: jittered SiC and the synthetic files; from i k k: the synthetic files, whose
-i j k entries carry their own R, D), a swapped [i][j][k] index (SiC in both element orders), a list that stops at the pair's own cutoff, a wrong image shift (the 8-atom cell, the triclinic box),
+i j k entries carry their own R, D), a swapped [i][j][k] index (SiC in both element orders), a wrong image shift (the 8-atom cell, the triclinic box),
 a force table indexed past the LDS limit or a short last tile (the atom counts), a truncated neighbour list (the crowded cluster must be
 an error).  Dynamics and pressure: the sign and the 1/2 of the virial, its split over two engine parts.  Whole evaluations: rows kept or
 rebuilt under the wrong material, part streams, flips.  The wrong builds named first -- the pair term owned by one end; R, D of fC(r_ik) from entry
 i j j, and from entry i k k -- were tried on the CPU driver (tests/test_tersoff_host.py::test_wrong_builds_are_caught says what failed).
+A list that stops at the pair's own cutoff is NOT caught here: no case of this file has an entry between the pair's R + D and cutin (the
+synthetic cell's bonds end at 2.8 A, its next shell starts at 3.84 A).  The shell case of tests/test_gpu_tersoff_edges.py, with 60 such
+entries, catches it (tests/test_row_edges_host.py::test_list_cut_at_the_pair_cutoff_is_caught).
 """
 import math
 import os

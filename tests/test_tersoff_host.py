@@ -16,7 +16,8 @@ Wrong builds (tsh_create's `wrong`), tried on this driver:
   3  R, D of fC(r_ik) from entry i j j (the pair's own parameter set where pair_tersoff.cpp uses that of i j k): the single-element
      cases pass (one entry); jittered SiC fails -- around Si a carbon third atom is cut at the Si-Si 3.0 A instead of 2.51 A and the
      other way round: another count of (j, k) and forces off by more than their size -- and so does the synthetic file
-test_wrong_builds_are_caught asserts all three.
+test_wrong_builds_are_caught asserts all three.  A fourth, the neighbour list cut at the pair's own R + D instead of cutin, passes every
+input of this file; tests/test_row_edges_host.py has the case that catches it.
 """
 import ctypes as C
 import math
