@@ -474,50 +474,41 @@ class Engine:
         return dict(f=f, e=dict(zip(REAX_PARTS, e)), w=w, q=q, maxneigh_seen=int(info[0]), maxnb=int(info[1]), maxbd=int(info[2]),
                     qeq_iters=int(info[3]), image_search=int(info[4]), maxbonds_seen=int(info[5]))
 
-    # ---- Stillinger-Weber replicas (pair_style sw) ----
+    # ---- replicas under a potential on full neighbour rows: pair_style sw, tersoff, eam/alloy ----
+    def _row_configure(self, symbol, matid, path, elements, energy_unit, skin):
+        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+        self._chk(getattr(lib(), symbol)(self.h, matid.encode(), path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.c_double(skin)))
+
+    def _row_compute(self, symbol, matid, replica, qp, ea_key, eb_key, count_key):
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); ea = C.c_double(0.0); eb = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
+        self._chk(getattr(lib(), symbol)(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(ea), C.byref(eb), _p(w), _p(info)))
+        return {"f": f, ea_key: ea.value, eb_key: eb.value, "w": w, "maxrow": int(info[0]), "rowcap": int(info[1]), "npairs": int(info[2]),
+                count_key: int(info[3])}
+
     def sw_configure(self, matid: str, sw_path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style sw + pair_coeff * * <sw_path> <elements> for the replicas of one material id (lammps_scripts_sisw/in.strain.lammps);
         energy_unit 0: the file's epsilon is eV, 1: kcal/mol as written"""
-        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
-        self._chk(lib().scema_md_sw_configure(self.h, matid.encode(), sw_path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
-                                              C.c_double(skin)))
+        self._row_configure("scema_md_sw_configure", matid, sw_path, elements, energy_unit, skin)
 
     def sw_compute(self, matid, replica, qp=QP_NONE):
-        n = self.natoms(matid, replica)
-        f = np.zeros((n, 3)); e2 = C.c_double(0.0); e3 = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
-        self._chk(lib().scema_md_sw_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(e2), C.byref(e3), _p(w),
-                                                  _p(info)))
-        return dict(f=f, e2=e2.value, e3=e3.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), ntriplets=int(info[3]))
+        return self._row_compute("scema_md_sw_debug_compute", matid, replica, qp, "e2", "e3", "ntriplets")
 
-    # ---- Tersoff replicas (pair_style tersoff) ----
     def tersoff_configure(self, matid: str, path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style tersoff + pair_coeff * * <path> <elements> for the replicas of one material id; energy_unit 0: the file's A and B are
         eV, 1: kcal/mol as written.  Replaces a Stillinger-Weber potential of the material"""
-        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
-        self._chk(lib().scema_md_tersoff_configure(self.h, matid.encode(), path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
-                                                   C.c_double(skin)))
+        self._row_configure("scema_md_tersoff_configure", matid, path, elements, energy_unit, skin)
 
     def tersoff_compute(self, matid, replica, qp=QP_NONE):
-        n = self.natoms(matid, replica)
-        f = np.zeros((n, 3)); er = C.c_double(0.0); ea = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
-        self._chk(lib().scema_md_tersoff_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(er), C.byref(ea),
-                                                       _p(w), _p(info)))
-        return dict(f=f, e_rep=er.value, e_att=ea.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), nzeta=int(info[3]))
+        return self._row_compute("scema_md_tersoff_debug_compute", matid, replica, qp, "e_rep", "e_att", "nzeta")
 
-    # ---- embedded-atom replicas (pair_style eam/alloy) ----
     def eam_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style eam/alloy + pair_coeff * * <path> <elements> for the replicas of one material id (a DYNAMO setfl file); energy_unit 0:
         the file's F and r phi are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
-        arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
-        self._chk(lib().scema_md_eam_configure(self.h, matid.encode(), path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit),
-                                               C.c_double(skin)))
+        self._row_configure("scema_md_eam_configure", matid, path, elements, energy_unit, skin)
 
     def eam_compute(self, matid, replica, qp=QP_NONE):
-        n = self.natoms(matid, replica)
-        f = np.zeros((n, 3)); ep = C.c_double(0.0); ee = C.c_double(0.0); w = np.zeros(6); info = np.zeros(4)
-        self._chk(lib().scema_md_eam_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(ep), C.byref(ee),
-                                                   _p(w), _p(info)))
-        return dict(f=f, e_pair=ep.value, e_embed=ee.value, w=w, maxrow=int(info[0]), rowcap=int(info[1]), npairs=int(info[2]), nabove=int(info[3]))
+        return self._row_compute("scema_md_eam_debug_compute", matid, replica, qp, "e_pair", "e_embed", "nabove")
 
     # ---- init_material's equilibration schedule (in.init.lammps; md_equil.hip) ----
     def minimize(self, matid, replica, qp, etol=1e-7, ftol=1e-11, maxiter=1000, maxeval=50000) -> dict:
@@ -587,45 +578,34 @@ bare_system = sw_system   # (the same bare replica under a neutral name: what a 
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]
+TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
+
+
+def _read_triplet_params(symbol: str, nfields: int, path: str, elements, energy_unit: int):
+    fn = getattr(lib(), symbol)
+    fn.restype = C.c_int
+    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
+    nk = C.c_int32(0)
+    tmap = np.zeros(len(elements), np.int32)
+    vals = np.zeros(4 * 4 * 4 * nfields)
+    err = C.create_string_buffer(512)
+    rc = fn(path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(vals), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nk.value
+    return n, tmap, vals[:n * n * n * nfields].reshape(n, n, n, nfields).copy()
 
 
 def sw_read_params(sw_path: str, elements, energy_unit: int = 0):
     """(distinct elements kept, type_map, values[n][n][n][11] in the order of SW_FIELDS, epsilon in kcal/mol) of a LAMMPS *.sw file:
     scema_md_sw_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
-    L = lib()
-    L.scema_md_sw_read_params.restype = C.c_int
-    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
-    nk = C.c_int32(0)
-    tmap = np.zeros(len(elements), np.int32)
-    vals = np.zeros(4 * 4 * 4 * 11)
-    err = C.create_string_buffer(512)
-    rc = L.scema_md_sw_read_params(sw_path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(vals), err,
-                                   C.c_int32(len(err)))
-    if rc != 0:
-        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
-    n = nk.value
-    return n, tmap, vals[:n * n * n * 11].reshape(n, n, n, 11).copy()
-
-
-TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
+    return _read_triplet_params("scema_md_sw_read_params", len(SW_FIELDS), sw_path, elements, energy_unit)
 
 
 def tersoff_read_params(path: str, elements, energy_unit: int = 0):
     """(distinct elements kept, type_map, values[n][n][n][14] in the order of TERSOFF_FIELDS, A and B in kcal/mol) of a LAMMPS *.tersoff
     file: scema_md_tersoff_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
-    L = lib()
-    L.scema_md_tersoff_read_params.restype = C.c_int
-    arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
-    nk = C.c_int32(0)
-    tmap = np.zeros(len(elements), np.int32)
-    vals = np.zeros(4 * 4 * 4 * 14)
-    err = C.create_string_buffer(512)
-    rc = L.scema_md_tersoff_read_params(path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(vals), err,
-                                        C.c_int32(len(err)))
-    if rc != 0:
-        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
-    n = nk.value
-    return n, tmap, vals[:n * n * n * 14].reshape(n, n, n, 14).copy()
+    return _read_triplet_params("scema_md_tersoff_read_params", len(TERSOFF_FIELDS), path, elements, energy_unit)
 
 
 def eam_read_setfl(path: str, elements, energy_unit: int = 0):

@@ -5,11 +5,10 @@
 //   engine_topo.cpp    topology preprocessing of a registered replica (exclusions, SHAKE clusters, bonded tiles)
 //   engine_kspace.cpp  what a LAMMPS `run` sets up on the host: g_ewald, k-vectors, PPPM grid, the real-space polynomial, fix deform's box path
 //   engine_run.cpp     one run of a batch with the OPLS force stage (run_phase), slots
-//   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF, the SW or the Tersoff stage
+//   engine_rows.cpp    the batch skeleton every stage shares; the run on per-atom neighbour rows (run_rows) that takes the ReaxFF stage or a row potential's
 //   engine_reax.cpp    the ReaxFF force stage (run_phase_reax) and the ReaxFF entry points
-//   engine_sw.cpp      the Stillinger-Weber force stage (run_phase_sw) and the SW entry points; what they share with the Tersoff ones
-//   engine_tersoff.cpp the Tersoff force stage (run_phase_tersoff) and the Tersoff entry points
-//   engine_eam.cpp     the embedded-atom force stage (run_phase_eam) and the EAM entry points
+//   engine_rowpot.cpp  the potentials on full neighbour rows (Stillinger-Weber, Tersoff, eam/alloy): the table that tells them apart (row_pots),
+//                      the stage they share and their own (run_phase_rowpot), self-configuration from the scripts folder, their entry points
 //   engine_batch.cpp   the hot path: scema_md_strain_batch (request checks, plan, chunks, backups, results)
 //   engine_comm.cpp    communicator, handshake, state migration, the stress all-gather, the planner's C face
 //   engine_state.cpp   state store: branch rule, replica / state files
@@ -148,9 +147,9 @@ struct Topo {
   DevBuf d_type, d_q, d_mass, d_lj, d_bt_terms, d_bt_coef, d_ex_start, d_ex_list, d_clus_at, d_clus_n, d_clus_d, d_free_at, d_bt_desc, d_bt_atoms, d_bt_rank;
   int bt_ntile = 0, bt_maxloc = 1, bt_maxchunk = 1, bt_ncoef = 0, bt_cf_off[4] = {0, 0, 0, 0};
   double sp_w[6] = {0, 0, 0, 0, 0, 0};   // special_bonds weights: lj 1-2, 1-3, 1-4, coul 1-2, 1-3, 1-4
-  std::string matid;       // the material the replica was registered under (a Stillinger-Weber potential is attached to a material id)
-  DevBuf d_swtype;         // Stillinger-Weber and Tersoff: element per atom (index into the material's tables), valid for swtype_stamp
-  long long swtype_stamp = 0;
+  std::string matid;       // the material the replica was registered under (a row potential is attached to a material id)
+  DevBuf d_eltype;         // row potentials: element per atom (index into the material's tables), valid for eltype_stamp
+  long long eltype_stamp = 0;
 };
 
 struct State {
@@ -178,8 +177,8 @@ struct RxSlot {
   DevBuf nb_cnt, nb_own0, nbT, hval, hcol, hlen, hown, hownlen, bd_cnt, bd, bd_rev, bd_bop, bd_c, bd_bo, bd_g, bd_cb, deltap, total_bo, cd_delta, hd, q, s, t, s_hist, t_hist, qwork, misc;
 };
 
-// work arrays of the Stillinger-Weber and Tersoff paths for one batch position (md_sw.h SwView points into these)
-struct SwSlot {
+// work arrays of the row potentials' paths for one batch position (md_rows.h RowView points into these)
+struct RowSlot {
   int cap_pad = 0;
   size_t cap_rows = 0;
   DevBuf cnt, rows, misc;
@@ -188,8 +187,7 @@ struct SwSlot {
 
 enum class RowKind { Opls, Reax, Sw, Tersoff, Eam };
 
-// a Stillinger-Weber, Tersoff or embedded-atom potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure,
-// scema_md_eam_configure).  A material
+// a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
 struct RowMaterial {
   RowKind kind = RowKind::Sw;
@@ -211,7 +209,7 @@ struct ListSig {
   double rlist = 0.0;
   int nc[3] = {0, 0, 0}, capj = 0, maxneigh = 0;   // OPLS: cell grid, capacity of a tile's j table and of a cluster row
   double cut_lj = 0.0, cut_coul = 0.0;
-  long long stamp = 0;                             // rows of RxSlot / SwSlot: the force-field / material stamp they were built under,
+  long long stamp = 0;                             // rows of RxSlot / RowSlot: the force-field / material stamp they were built under,
   int mimg[3] = {0, 0, 0}, cap[2] = {0, 0};        // the image search, the row capacities (RowNeed)
   // the list's scalars at the end of the run that left it: what the displacement test of the next run needs, and the statistics
   double corners_hold[24];
@@ -220,7 +218,7 @@ struct ListSig {
 };
 struct Slot {
   std::unique_ptr<RxSlot> rx;
-  std::unique_ptr<SwSlot> sw;
+  std::unique_ptr<RowSlot> row;
   ListSig sig;
   int cap_atoms = 0, cap_pad = 0, cap_neigh = 0, cap_cells = 0, cap_k = 0;
   size_t cap_jtab = 0;
@@ -398,15 +396,15 @@ struct scema_md_engine {
   int rx_qeq_launch_cold = 48;        // the same for the first solves of a run (empty history)
   int rx_qeq_launch = 32;             // conjugate-gradient iterations issued as batch launches per solve (follows what the last run needed)
   bool rx_qeq_launch_pinned = false;  // SCEMA_REAX_QEQ_LAUNCH fixes it (0: every solve runs in the single-workgroup loop)
-  // Stillinger-Weber and Tersoff paths: the potentials by material id; simulations of such a material take the force stage of its
+  // row potentials (Stillinger-Weber, Tersoff, eam/alloy): the potentials by material id; simulations of such a material take the force stage of its
   // potential's kind (run_phase)
   std::map<std::string, std::unique_ptr<RowMaterial>> row_mats;
-  long long sw_stamp = 0;
-  DevBuf d_swviews;
-  std::vector<SwView> h_swviews;
+  long long row_stamp = 0;
+  DevBuf d_rowviews;
+  std::vector<RowView> h_rowviews;
   DevBuf d_eamviews;              // embedded-atom stage: parallel to the views
   std::vector<EamView> h_eamviews;
-  hipEvent_t sw_done = nullptr;   // part batches of an SW or Tersoff run: the end of the second part (created on first use)
+  hipEvent_t row_part_done = nullptr;   // part batches of a row potential's run: the end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
   scema::SimPlan last_plan;
@@ -456,37 +454,6 @@ int settle_pending(scema_md_engine *e, bool failed);
 int ensure_slot(scema_md_engine *e, Slot &sl, int natoms, int maxneigh, int ncells, int nk, int capj);
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
 int run_phase_reax(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
-int run_phase_sw(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
-int run_phase_tersoff(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
-int run_phase_eam(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec);
-// the potential of a material id if it is of that kind, or null (engine_sw.cpp); sw_material, ts_material: the Stillinger-Weber, the
-// Tersoff potential
-RowMaterial *row_material(scema_md_engine *e, const std::string &matid, RowKind kind);
-inline RowMaterial *sw_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Sw); }
-inline RowMaterial *ts_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Tersoff); }
-inline RowMaterial *eam_material(scema_md_engine *e, const std::string &matid) { return row_material(e, matid, RowKind::Eam); }
-// what the configure and the debug_compute entry points of these potentials share (engine_sw.cpp).  row_configure: `read` fills type_map
-// from the file and says where its host table stands, how large it is (the reader decides) and its largest cutoff (blk), or err;
-// row_debug_compute: ea, eb are the two energies of the stage
-struct RowTableBlock { const void *p = nullptr; size_t bytes = 0; double cutmax = 0.0; };
-typedef std::function<bool(const std::vector<std::string> &elements, std::vector<int> &type_map, RowTableBlock &blk, std::string &err)> RowTableReader;
-int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
-                  const RowTableReader &read);
-int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
-                      double *virial, double *info);
-// a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
-bool sw_bare_replica(const Topo &t);
-// element of every atom of a replica on the device (Topo::d_swtype): the element pair_coeff names for its LAMMPS type; `what` names the
-// potential in the refusal (engine_sw.cpp)
-int ensure_swtype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map, long long stamp, const char *what);
-// `pair_coeff * * ${locs}/<name>.tersoff <El> ...` in <folder>/in.strain.lammps: configures the material from that line; no such file or
-// line: nothing happens (0); a malformed line: an error
-int tersoff_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
-// the same rule for `pair_coeff * * ${locs}/<name>.eam.alloy <El> ...` (engine_eam.cpp), and what the two share (engine_tersoff.cpp): the
-// line that names a file of extension `ext`, handed to `configure` as (path, elements, n)
-int eam_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
-int pair_coeff_from_scripts(scema_md_engine *e, const std::string &folder, const std::string &ext,
-                            const std::function<int(const char *path, const char *const *elements, int32_t n)> &configure);
 int prepare_slots(scema_md_engine *e, std::vector<ActiveSim> &sims);
 int reupload_scalars(scema_md_engine *e, int ns);
 // the batch skeleton every force stage shares (engine_rows.cpp)
@@ -521,7 +488,7 @@ int eval_static(scema_md_engine *e, State *s, const RunSpec &spec);
 struct RowNeed {   // what the stage needs for one replica
   double rlist = 0.0, skin = 0.0;
   long long stamp = 0;          // rows built under another stamp are rebuilt
-  int cap[2] = {0, 0};          // row capacities (ReaxFF: rows and near rows; SW: rows, 0): rows that are kept keep theirs
+  int cap[2] = {0, 0};          // row capacities (ReaxFF: rows and near rows; row potentials: rows, 0): rows that are kept keep theirs
   int mimg[3] = {0, 0, 0};      // the image search along each box vector (0: minimum image), filled in by the driver
 };
 struct RowRun;
@@ -573,25 +540,26 @@ struct RowRun {
   int finish();
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
-// What the Stillinger-Weber, the Tersoff and the embedded-atom stage share (engine_sw.cpp): full neighbour rows inside the material's largest cutoff + skin
-// in the slot's SwSlot, one SwView per position (e->h_swviews / d_swviews; `tab` is the material's table on the device, of the stage's
-// own type), the row capacity and its growth, part batches on the main and the third stream, the "too many neighbours" fault.  A stage
-// names its kind and launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h, with an array of its own beside the views).
-struct SwRowsStage : RowStage {
-  scema_md_engine *e;
-  const char *what;             // the potential's name in messages
-  SwView *VV = nullptr;         // the views on the device (upload)
-  SwRowsStage(scema_md_engine *e_, int ns, RowKind kind_, const char *what_);
-  int nparts() const override;
-  int rows(Topo &T, const BoxRange &R, RowNeed &need) override;
-  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override;
-  int upload() override;
-  int setup() override { return SCEMA_MD_OK; }
-  int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) override;
-  int read_back() override;
-  int after_read_back(int fault, double &need) override;
-  int faults(int fault) override;
+// The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM: the order in which
+// a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts folder is searched
+struct RowPot {
+  RowKind kind;
+  const char *name;             // in messages
+  const char *configure_name;   // its configure entry point as messages name it, and (`configure`) the entry point
+  const char *ext;              // extension of the potential file a `pair_coeff * * ${locs}/<name><ext> <El> ...` line of in.strain.lammps names, or null
+  int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
+  RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
+constexpr int ROW_NPOT = 3;
+extern const RowPot row_pots[ROW_NPOT];
+// the entry of the potential attached to a material id, or null
+const RowPot *row_pot_of(scema_md_engine *e, const char *matid);
+int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot);
+// a replica without charges, topology and Lennard-Jones coefficients (what an atom_style atomic restart registers)
+bool bare_replica(const Topo &t);
+// `pair_coeff * * ${locs}/<name><ext> <El> ...` in <folder>/in.strain.lammps, for the extensions of the table in its order: configures the
+// material from the first such line; no such file or line: nothing happens (0); a malformed line: an error
+int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

@@ -233,7 +233,7 @@ int scema_md_strain_batch(scema_md_engine *e, scema_mdsim *sims, int32_t n_sims,
   // all ranks together, before anything is planned or moved ----
   std::vector<std::string> src_keys(n_sims), dst_keys(n_sims);
   std::vector<double> cost(n_sims, 1.0);
-  int n_reax = 0, n_md = 0, n_sw = 0, n_ts = 0, n_eam = 0;
+  int n_reax = 0, n_md = 0, n_pot[ROW_NPOT] = {}, n_rowpot = 0;
   for (int i = 0; i < n_sims; i++) {
     sims[i].stress_updated = 0;
     // stmd_problem.h:462-467
@@ -247,26 +247,26 @@ int scema_md_strain_batch(scema_md_engine *e, scema_mdsim *sims, int32_t n_sims,
     // coefficients: what an atom_style atomic restart registers -- whose material has no potential attached and whose scripts folder holds a
     // Si.sw configures itself from that file, every atom type mapped to Si, as a "reax" update does from ffield.reax.2 below.  Without a
     // Si.sw, the same line of in.strain.lammps written for `pair_style tersoff` (`pair_coeff * * ${locs}/<name>.tersoff <El> ...`) names
-    // the file and the elements of a Tersoff potential (tersoff_from_scripts); where that leaves the material bare, the line written for
-    // `pair_style eam/alloy` (`pair_coeff * * ${locs}/<name>.eam.alloy <El> ...`) those of an embedded-atom potential (eam_from_scripts)
-    if (sims[i].matid && std::strcmp(ff, "reax") != 0 && !sw_material(e, sims[i].matid) && !ts_material(e, sims[i].matid) && !eam_material(e, sims[i].matid)) {
+    // the file and the elements of a Tersoff potential; where that leaves the material bare, the line written for `pair_style eam/alloy`
+    // (`pair_coeff * * ${locs}/<name>.eam.alloy <El> ...`) those of an embedded-atom potential (rowpot_from_scripts: the table's order)
+    if (sims[i].matid && std::strcmp(ff, "reax") != 0 && !row_pot_of(e, sims[i].matid)) {
       const Topo *t = find_topo(e, sims[i].matid, sims[i].replica);
       const std::string folder = sims[i].scripts_folder ? sims[i].scripts_folder : ".";
       const std::string path = folder + "/Si.sw";
       int rc_cfg = SCEMA_MD_OK;
-      if (t && sw_bare_replica(*t) && std::ifstream(path).good()) {
+      if (t && bare_replica(*t) && std::ifstream(path).good()) {
         std::vector<const char *> si((size_t)std::max(t->original.sys.ntypes, 1), "Si");
         rc_cfg = scema_md_sw_configure(e, sims[i].matid, path.c_str(), si.data(), (int32_t)si.size(), 0, -1.0);
-      } else if (t && sw_bare_replica(*t)) {
-        rc_cfg = tersoff_from_scripts(e, sims[i].matid, folder);
-        if (!rc_cfg && !ts_material(e, sims[i].matid)) rc_cfg = eam_from_scripts(e, sims[i].matid, folder);
+      } else if (t && bare_replica(*t)) {
+        rc_cfg = rowpot_from_scripts(e, sims[i].matid, folder);
       }
       if (rc_cfg && !collective_call) return rc_cfg;
       if (rc_cfg && !pre_status) pre_status = rc_cfg;   // (a file one rank cannot read: the others must hear of it)
     }
-    if (sims[i].matid && sw_material(e, sims[i].matid)) n_sw++;   // (whatever force_field says: the example's inputs.json says "opls", its scripts pair_style sw)
-    if (sims[i].matid && ts_material(e, sims[i].matid)) n_ts++;
-    if (sims[i].matid && eam_material(e, sims[i].matid)) n_eam++;
+    if (const RowPot *P = row_pot_of(e, sims[i].matid)) {   // (whatever force_field says: the example's inputs.json says "opls", its scripts pair_style sw)
+      n_pot[P - row_pots]++;
+      n_rowpot++;
+    }
     // requests that cannot be run: LAMMPS would stop while parsing "variable ceeps_.. equal nan" or "timestep 0"
     bool finite = true;
     for (int k = 0; k < 6; k++) finite = finite && std::isfinite(sims[i].strain[k]);
@@ -277,10 +277,10 @@ int scema_md_strain_batch(scema_md_engine *e, scema_mdsim *sims, int32_t n_sims,
     if (sims[i].nsteps_sample < 1) return fail(e, SCEMA_MD_ERR_ARG, "number of sampling steps must be >= 1");
   }
   if (n_reax != 0 && n_reax != n_md) return fail(e, SCEMA_MD_ERR_ARG, "one update mixes force fields (%d of %d simulations ask for 'reax'): md_force_field is one setting per run", n_reax, n_md);
-  if (n_sw != 0 && n_sw != n_md) return fail(e, SCEMA_MD_ERR_ARG, "one update mixes Stillinger-Weber materials (%d of %d simulations) with others", n_sw, n_md);
-  if (n_ts != 0 && n_ts != n_md) return fail(e, SCEMA_MD_ERR_ARG, "one update mixes Tersoff materials (%d of %d simulations) with others", n_ts, n_md);
-  if (n_eam != 0 && n_eam != n_md) return fail(e, SCEMA_MD_ERR_ARG, "one update mixes EAM materials (%d of %d simulations) with others", n_eam, n_md);
-  if (n_reax && !n_sw && !n_ts && !n_eam && !e->rx_ready) {
+  for (int k = 0; k < ROW_NPOT; k++)   // (the first kind of the table that is present is the one named)
+    if (n_pot[k] != 0 && n_pot[k] != n_md)
+      return fail(e, SCEMA_MD_ERR_ARG, "one update mixes %s materials (%d of %d simulations) with others", row_pots[k].name, n_pot[k], n_md);
+  if (n_reax && !n_rowpot && !e->rx_ready) {
     // the reference's scripts name the file and the elements: pair_coeff * * ${locs}/ffield.reax.2 H C N O
     // (lammps_scripts_reax/in.strain.lammps:11, locs = MDSim.scripts_folder, stmd_problem.h:163)
     static const char *hcno[4] = {"H", "C", "N", "O"};

@@ -179,7 +179,7 @@ void scema_md_destroy(scema_md_engine *e) {
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_join) (void)hipEventDestroy(e->ev_join);
   if (e->row_fork) (void)hipEventDestroy(e->row_fork);
-  if (e->sw_done) (void)hipEventDestroy(e->sw_done);
+  if (e->row_part_done) (void)hipEventDestroy(e->row_part_done);
   if (e->rx_side1) (void)hipStreamDestroy(e->rx_side1);
   for (int k = 0; k < 4; k++) if (e->rx_side1_ev[k]) (void)hipEventDestroy(e->rx_side1_ev[k]);
   for (hipEvent_t pe : e->md_part_done) (void)hipEventDestroy(pe);

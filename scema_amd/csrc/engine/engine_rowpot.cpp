@@ -1,0 +1,381 @@
+// engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
+// `pair_style tersoff`; `pair_style eam/alloy`): the stage they share, the table that tells them apart (row_pots), their three stages
+// and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
+#include "engine.h"
+#include "../md_env.h"
+
+#include <fstream>
+#include <sstream>
+
+namespace scema_eng {
+
+// run_phase_rowpot is the run on per-atom neighbour rows (run_rows, engine_rows.cpp) with the force stage of one of these potentials: no
+// bonded terms (lammps_scripts_sisw/in.strain.lammps has none).  The row part of a replica's work set is a RowView over the slot's RowSlot;
+// rows built for another potential are never kept: the slot's ListSig carries the stage's RowKind and the material's stamp.
+
+// the potential of a material id if it is of that kind, or null
+static RowMaterial *row_material(scema_md_engine *e, const std::string &matid, RowKind kind) {
+  auto it = e->row_mats.find(matid);
+  return it == e->row_mats.end() || it->second->kind != kind ? nullptr : it->second.get();
+}
+
+const RowPot *row_pot_of(scema_md_engine *e, const char *matid) {
+  if (!matid) return nullptr;
+  auto it = e->row_mats.find(matid);
+  if (it == e->row_mats.end()) return nullptr;
+  for (const RowPot &P : row_pots)
+    if (P.kind == it->second->kind) return &P;
+  return nullptr;
+}
+
+bool bare_replica(const Topo &t) {
+  const scema_md_system &s = t.original.sys;
+  if (s.nbonds || s.nangles || s.ndihedrals || s.nimpropers) return false;
+  for (double q : t.original.q) if (q != 0.0) return false;
+  for (double v : t.original.eps) if (v != 0.0) return false;
+  return true;
+}
+
+#define ROWSET(dst, src) dst = (decltype(dst))(src)
+
+// element of every atom of a replica on the device (Topo::d_eltype): the element pair_coeff names for its LAMMPS type; `what` names the
+// potential in the refusal
+static int ensure_eltype(scema_md_engine *e, Topo &T, const std::vector<int> &type_map, long long stamp, const char *what) {
+  if (T.eltype_stamp == stamp && T.d_eltype.p) return SCEMA_MD_OK;
+  std::vector<int> st(T.natoms);
+  for (int i = 0; i < T.natoms; i++) {
+    const int ty = T.original.type[i];   // the registered LAMMPS type (Topo::type holds Lennard-Jones classes)
+    if (ty < 0 || ty >= (int)type_map.size())
+      return fail(e, SCEMA_MD_ERR_ARG, "atom %d has type %d but the %s element list names %zu types (pair_coeff * * file ...)", i, ty + 1, what, type_map.size());
+    st[i] = type_map[ty];
+  }
+  int rc = upload(e, T.d_eltype, st);
+  if (rc) return rc;
+  T.eltype_stamp = stamp;
+  return SCEMA_MD_OK;
+}
+
+// ---- the stage the three potentials share: full neighbour rows inside the material's largest cutoff + skin in the slot's RowSlot, one
+// RowView per position (e->h_rowviews / d_rowviews; `tab` is the material's table on the device, of the stage's own type), the row
+// capacity and its growth, part batches on the main and the third stream, the "too many neighbours" fault ----
+
+struct RowPotStage : RowStage {
+  scema_md_engine *e;
+  const char *what;             // the potential's name in messages
+  RowView *VV = nullptr;        // the views on the device (upload)
+  RowPotStage(scema_md_engine *e_, int ns, const RowPot &pot);
+  int nparts() const override;
+  int rows(Topo &T, const BoxRange &R, RowNeed &need) override;
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override;
+  int upload() override;
+  int setup() override { return SCEMA_MD_OK; }
+  int part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) override;
+  int read_back() override;
+  int after_read_back(int fault, double &need) override;
+  int faults(int fault) override;
+};
+
+RowPotStage::RowPotStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowStage(pot.kind, 16), e(e_), what(pot.name) {
+  e->h_rowviews.assign(ns, RowView());
+}
+
+// Part batches: part 0 on the engine's main stream, part 1 on its third.  The split follows the other paths' shape, SCEMA_MD_SPLIT=0 /
+// scema_md_batch_split(e, 0) runs the batch whole.
+int RowPotStage::nparts() const { return (e->split_streams && e->stream3 && run->ns >= 8 && !run->spec.minimize) ? 2 : 1; }
+
+int RowPotStage::rows(Topo &T, const BoxRange &R, RowNeed &need) {
+  const RowMaterial &M = *row_material(e, T.matid, kind);
+  if (const int rc = ensure_eltype(e, T, M.type_map, M.stamp, what)) return rc;
+  const int n = T.natoms;
+  if (n >= (1 << 24)) return fail(e, SCEMA_MD_ERR_ARG, "a %s replica of %d atoms: row entries hold 24-bit atom indices", what, n);
+  const double rlist = M.cutmax + M.skin;
+  // row capacity: the mean count inside the list radius at the densest box of the run, with headroom (grown after an overflow: grow_after_overflow)
+  const double rho = n / R.vol_min;
+  const int cap = (int)std::ceil(rho * 4.0 / 3.0 * MD_PI * rlist * rlist * rlist * 1.5 * e->neigh_grow);
+  need.rlist = rlist; need.skin = M.skin; need.stamp = M.stamp;
+  // (the floor of 8 entries grows with the same factor: a cluster in a large empty box has a mean density near zero, and a factor that
+  // only multiplied `cap` would be swallowed by the floor -- 17 neighbours in a 30 A box were still not held after six attempts)
+  const int floor8 = (int)std::ceil(8.0 * e->neigh_grow);
+  need.cap[0] = std::max(8, (std::max(cap, floor8) + 7) / 8 * 8);
+  return SCEMA_MD_OK;
+}
+
+int RowPotStage::bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) {
+  const Topo &T = *A.st->topo;
+  const int npad = S.npad, cap = need.cap[0];
+  if (!sl.row) sl.row.reset(new RowSlot());
+  RowSlot &W = *sl.row;
+  if (npad > W.cap_pad) {
+    HIPCHK(W.cnt.ensure((size_t)npad * 4));
+    HIPCHK(W.misc.ensure(64));
+    W.cap_pad = npad;
+    W.cap_rows = 0;
+  }
+  if ((size_t)npad * cap > W.cap_rows) {
+    HIPCHK(W.rows.ensure((size_t)npad * cap * 4));
+    W.cap_rows = (size_t)npad * cap;
+  }
+  RowView V;
+  std::memset(&V, 0, sizeof V);
+  for (int d = 0; d < 3; d++) V.mimg[d] = need.mimg[d];
+  V.n = S.natoms; V.npad = npad; V.cap = cap; V.rlist = need.rlist;
+  ROWSET(V.stype, T.d_eltype.as<int>()); ROWSET(V.x, S.x); ROWSET(V.f, S.f);
+  ROWSET(V.cnt, W.cnt.as<int>()); ROWSET(V.rows, W.rows.as<int>());
+  ROWSET(V.eacc, W.misc.as<double>());                 // [0, 4) doubles
+  ROWSET(V.stat, (int *)(W.misc.as<char>() + 32));     // 2 ints
+  e->h_zerotab.push_back(MdkZero{W.misc.as<int>(), 16});   // (the step sums)
+  ROWSET(V.tab, row_material(e, T.matid, kind)->d_tab.p);
+  e->h_rowviews[pos] = V;
+  return SCEMA_MD_OK;
+}
+
+int RowPotStage::upload() {
+  const size_t bytes = e->h_rowviews.size() * sizeof(RowView);
+  HIPCHK(e->d_rowviews.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(e->d_rowviews.p, e->h_rowviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+  VV = e->d_rowviews.as<RowView>();
+  return SCEMA_MD_OK;
+}
+
+int RowPotStage::part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> &done) {
+  if (!e->row_part_done) HIPCHK(hipEventCreateWithFlags(&e->row_part_done, hipEventDisableTiming));
+  parts[1].st = e->stream3;
+  done.push_back(e->row_part_done);
+  return SCEMA_MD_OK;
+}
+
+int RowPotStage::read_back() { return run->read_scalars(); }
+
+int RowPotStage::after_read_back(int fault, double &need) {
+  for (int pos = 0; pos < run->ns; pos++)
+    need = std::max(need, (double)e->h_sc[run->order[pos]].maxneigh_seen / (double)std::max(e->h_rowviews[pos].cap, 1));
+  return faults(fault);
+}
+
+int RowPotStage::faults(int fault) {
+  if (fault & 128) return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside the %s cutoff", ROW_MAXIN, what);
+  return SCEMA_MD_OK;
+}
+
+// ---- the three stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h) ----
+
+namespace {
+
+struct SwStage : RowPotStage {
+  using RowPotStage::RowPotStage;
+  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+};
+
+struct TsStage : RowPotStage {
+  using RowPotStage::RowPotStage;
+  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_ts_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+};
+
+// What the two passes of the embedded-atom stage hand from one to the other, F'(rho) per atom, lives in the slot too and reaches the
+// kernels through an array of EamView parallel to the views.
+struct EamStage : RowPotStage {
+  EamView *AA = nullptr;   // on the device (upload)
+  EamStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowPotStage(e_, ns, pot) { e->h_eamviews.assign(ns, EamView()); }
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
+    if (const int rc = RowPotStage::bind(pos, A, sl, S, need)) return rc;
+    HIPCHK(sl.row->fp.ensure((size_t)S.npad * sizeof(double)));
+    e->h_eamviews[pos].fp = (decltype(EamView::fp))sl.row->fp.as<double>();
+    return SCEMA_MD_OK;
+  }
+  int upload() override {
+    if (const int rc = RowPotStage::upload()) return rc;
+    const size_t bytes = e->h_eamviews.size() * sizeof(EamView);
+    HIPCHK(e->d_eamviews.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(e->d_eamviews.p, e->h_eamviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    AA = e->d_eamviews.as<EamView>();
+    return SCEMA_MD_OK;
+  }
+  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_eam_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
+  int faults(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
+};
+
+template <class Stage>
+RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
+
+}  // namespace
+
+// the order is the precedence of the refusals (run_phase, scema_md_strain_batch) and of self-configuration (rowpot_from_scripts)
+const RowPot row_pots[ROW_NPOT] = {
+    {RowKind::Sw, "Stillinger-Weber", "scema_md_sw_configure", nullptr, scema_md_sw_configure, make_stage<SwStage>},
+    {RowKind::Tersoff, "Tersoff", "scema_md_tersoff_configure", ".tersoff", scema_md_tersoff_configure, make_stage<TsStage>},
+    {RowKind::Eam, "EAM", "scema_md_eam_configure", ".eam.alloy", scema_md_eam_configure, make_stage<EamStage>},
+};
+
+int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
+  const std::unique_ptr<RowStage> stage(pot.stage(e, (int)sims.size(), pot));
+  return run_rows(e, sims, spec, *stage);
+}
+
+// The one line of in.strain.lammps that names a potential file of extension `ext` -- `pair_coeff * * ${locs}/<name><ext> <El> ...`, ${locs}
+// being the scripts folder -- parsed as LAMMPS would: words separated by blanks, `#` starts a comment.  Nothing else of the script is read.
+// The line goes to `configure` as (path, elements, n); no such file or line: nothing happens (0); a malformed line: an error
+static int pair_coeff_from_scripts(scema_md_engine *e, const std::string &folder, const std::string &ext,
+                                   const std::function<int(const char *path, const char *const *elements, int32_t n)> &configure) {
+  const std::string script = folder + "/in.strain.lammps";
+  std::ifstream in(script);
+  if (!in) return SCEMA_MD_OK;
+  std::string line;
+  for (int ln = 1; std::getline(in, line); ln++) {
+    const size_t h = line.find('#');
+    if (h != std::string::npos) line.resize(h);
+    std::istringstream ss(line);
+    std::vector<std::string> w;
+    for (std::string s; ss >> s;) w.push_back(s);
+    if (w.empty() || w[0] != "pair_coeff") continue;
+    const std::string locs = "${locs}/";
+    bool names = false;
+    for (const std::string &s : w) names = names || (s.size() > ext.size() && s.compare(s.size() - ext.size(), ext.size(), ext) == 0);
+    if (!names) continue;
+    const bool ok = w.size() >= 5 && w[1] == "*" && w[2] == "*" && w[3].compare(0, locs.size(), locs) == 0 && w[3].size() > locs.size() + ext.size() &&
+                    w[3].compare(w[3].size() - ext.size(), ext.size(), ext) == 0 && w[3].find('/', locs.size()) == std::string::npos;
+    if (!ok)
+      return fail(e, SCEMA_MD_ERR_ARG, "%s line %d: expected `pair_coeff * * ${locs}/<name>%s <element> ...`", script.c_str(), ln, ext.c_str());
+    const std::string path = folder + "/" + w[3].substr(locs.size());
+    std::vector<const char *> el;
+    for (size_t k = 4; k < w.size(); k++) el.push_back(w[k].c_str());
+    return configure(path.c_str(), el.data(), (int32_t)el.size());
+  }
+  return SCEMA_MD_OK;
+}
+
+int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+  for (const RowPot &P : row_pots) {
+    if (!P.ext) continue;
+    const int rc = pair_coeff_from_scripts(e, folder, P.ext, [&](const char *path, const char *const *el, int32_t n) {
+      return P.configure(e, matid, path, el, n, 0, -1.0);
+    });
+    if (rc || row_pot_of(e, matid)) return rc;
+  }
+  return SCEMA_MD_OK;
+}
+
+// ---- what the entry points of the C ABI share.  row_configure: `read` fills type_map from the file and says where its host table
+// stands, how large it is (the reader decides) and its largest cutoff (blk), or err; row_debug_compute: ea, eb are the two energies of the
+// stage ----
+
+struct RowTableBlock { const void *p = nullptr; size_t bytes = 0; double cutmax = 0.0; };
+typedef std::function<bool(const std::vector<std::string> &elements, std::vector<int> &type_map, RowTableBlock &blk, std::string &err)> RowTableReader;
+
+static int row_configure(scema_md_engine *e, RowKind kind, const char *matid, const char *path, const char *const *elements, int32_t n_elements, double skin,
+                         const RowTableReader &read) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (!matid || !*matid || !path || !elements || n_elements <= 0) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  (void)settle_pending(e, false);
+  HIPCHK(hipSetDevice(e->p.device));
+  std::vector<std::string> el;
+  for (int k = 0; k < n_elements; k++) el.push_back(elements[k] ? elements[k] : "");
+  std::unique_ptr<RowMaterial> M(new RowMaterial());
+  std::string err;
+  RowTableBlock blk;
+  if (!read(el, M->type_map, blk, err)) return fail(e, SCEMA_MD_ERR_IO, "%s", err.c_str());
+  M->kind = kind;
+  M->cutmax = blk.cutmax;
+  M->skin = skin < 0.0 ? 1.0 : skin;
+  M->stamp = ++e->row_stamp;
+  HIPCHK(M->d_tab.ensure(blk.bytes));
+  HIPCHK(hipMemcpyAsync(M->d_tab.p, blk.p, blk.bytes, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->row_mats[matid] = std::move(M);   // (the potential it replaces, of either kind, goes with its table: rows and element arrays carry its stamp and are rebuilt)
+  return SCEMA_MD_OK;
+}
+
+// static evaluation of a state (qp_id SCEMA_MD_QP_NONE: the registered replica)
+static int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
+                             double *virial, double *info) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (!matid) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  (void)settle_pending(e, false);
+  if (!row_material(e, matid, kind)) {
+    for (const RowPot &P : row_pots)
+      if (P.kind == kind) return fail(e, SCEMA_MD_ERR_ARG, "no %s potential attached to material %s (%s)", P.name, matid, P.configure_name);
+    return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  }
+  HIPCHK(hipSetDevice(e->p.device));
+  State *s = nullptr;
+  std::unique_ptr<State> tmp;
+  int rc = debug_state(e, qp_id, matid, replica, &s, tmp);
+  if (rc) return rc;
+  RunSpec R;
+  R.nvt = 0;
+  R.static_only = 1;
+  if ((rc = eval_static(e, s, R))) return rc;
+  const int n = s->topo->natoms;
+  const SimScalars &sc = e->h_sc[0];
+  const RowView &V = e->h_rowviews[0];
+  double acc[4];
+  HIPCHK(hipMemcpy(acc, (const void *)V.eacc, sizeof acc, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(hipMemcpy(f, e->slots[0]->f.p, 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (ea) *ea = acc[0];
+  if (eb) *eb = acc[1];
+  if (virial)
+    for (int k = 0; k < 6; k++) {
+      virial[k] = 0.0;
+      for (int p = 0; p < MD_NPART; p++) virial[k] += sc.vir[p * 6 + k];
+    }
+  if (info) {
+    info[0] = sc.maxneigh_seen;
+    info[1] = V.cap;
+    info[2] = acc[2];
+    info[3] = acc[3];
+  }
+  return SCEMA_MD_OK;
+}
+
+}  // namespace scema_eng
+
+extern "C" {
+
+int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
+                          int32_t energy_unit, double skin) {
+  SwTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_sw_params(sw_path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::Sw, matid, sw_path, elements, n_elements, skin, read);
+}
+
+int scema_md_sw_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3, double *virial,
+                              double *info) {
+  return row_debug_compute(e, RowKind::Sw, qp_id, matid, replica, f, e2, e3, virial, info);
+}
+
+int scema_md_tersoff_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                               int32_t energy_unit, double skin) {
+  TsTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_tersoff_params(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::Tersoff, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
+                                   double *virial, double *info) {
+  return row_debug_compute(e, RowKind::Tersoff, qp_id, matid, replica, f, e_rep, e_att, virial, info);
+}
+
+int scema_md_eam_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                           int32_t energy_unit, double skin) {
+  std::vector<double> block;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_eam_setfl(path, el, energy_unit, block, type_map, err)) return false;
+    blk = RowTableBlock{block.data(), block.size() * sizeof(double), scema::eam_head(block).cutoff};
+    return true;
+  };
+  return row_configure(e, RowKind::Eam, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_eam_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_embed,
+                               double *virial, double *info) {
+  return row_debug_compute(e, RowKind::Eam, qp_id, matid, replica, f, e_pair, e_embed, virial, info);
+}
+
+}  // extern "C"

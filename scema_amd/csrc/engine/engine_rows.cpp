@@ -1,5 +1,5 @@
 // engine_rows.cpp -- the batch skeleton every force stage shares (launch order, part batches, box range, minimiser, flips, what a run leaves
-// behind), the growth rule after an overflow, and the run of a batch on per-atom neighbour rows that the ReaxFF and Stillinger-Weber stages share
+// behind), the growth rule after an overflow, and the run of a batch on per-atom neighbour rows that the ReaxFF stage and the row potentials' stages share
 #include "engine.h"
 #include "../md_env.h"
 
@@ -249,7 +249,7 @@ int eval_static(scema_md_engine *e, State *s, const RunSpec &spec) {
 }
 
 // -------------------------------------------------------------------------------------------
-// the run of a batch on per-atom neighbour rows: run_phase with the ReaxFF or the Stillinger-Weber force stage
+// the run of a batch on per-atom neighbour rows: run_phase with the ReaxFF force stage or a row potential's
 // -------------------------------------------------------------------------------------------
 // The same step sequence as the OPLS run (k_pre, k_initial_integrate, forces, k_final_integrate, k_post, k_remap), the same batch rules
 // (longest run first, active prefix, part batches), the same box flips; no cells, no k-space, no SHAKE (neither lammps_scripts_reax nor

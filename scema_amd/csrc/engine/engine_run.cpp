@@ -893,18 +893,13 @@ int OplsRun::finish() {
 // On return the per-sim SimScalars are in e->h_sc.
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec) {
   {   // simulations of a material with a Stillinger-Weber, Tersoff or EAM potential attached take that force stage, whichever entry point issued the run
-    size_t n_sw = 0;
-    for (const ActiveSim &A : sims) n_sw += sw_material(e, A.st->topo->matid) ? 1 : 0;
-    if (n_sw == sims.size() && n_sw > 0) return run_phase_sw(e, sims, spec);
-    if (n_sw) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes Stillinger-Weber materials (%zu of %zu simulations) with others", n_sw, sims.size());
-    size_t n_ts = 0;
-    for (const ActiveSim &A : sims) n_ts += ts_material(e, A.st->topo->matid) ? 1 : 0;
-    if (n_ts == sims.size() && n_ts > 0) return run_phase_tersoff(e, sims, spec);
-    if (n_ts) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes Tersoff materials (%zu of %zu simulations) with others", n_ts, sims.size());
-    size_t n_eam = 0;
-    for (const ActiveSim &A : sims) n_eam += eam_material(e, A.st->topo->matid) ? 1 : 0;
-    if (n_eam == sims.size() && n_eam > 0) return run_phase_eam(e, sims, spec);
-    if (n_eam) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes EAM materials (%zu of %zu simulations) with others", n_eam, sims.size());
+    size_t n_pot[ROW_NPOT] = {};
+    for (const ActiveSim &A : sims)
+      if (const RowPot *P = row_pot_of(e, A.st->topo->matid.c_str())) n_pot[P - row_pots]++;
+    for (int k = 0; k < ROW_NPOT; k++) {   // (the first kind of the table that is present takes the run or is named in the refusal)
+      if (n_pot[k] == sims.size() && n_pot[k] > 0) return run_phase_rowpot(e, sims, spec, row_pots[k]);
+      if (n_pot[k]) return fail(e, SCEMA_MD_ERR_ARG, "one run mixes %s materials (%zu of %zu simulations) with others", row_pots[k].name, n_pot[k], sims.size());
+    }
   }
   if (e->reax_active) return run_phase_reax(e, sims, spec);
   const auto t_enter = Clock::now();

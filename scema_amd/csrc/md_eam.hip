@@ -1,10 +1,10 @@
 // md_eam.hip -- gfx950 kernels of the embedded-atom force stage (`pair_style eam/alloy`).  The neighbour rows are those of the
-// Stillinger-Weber stage (mdk_sw_rows, md_sw.hip: full rows inside cutoff + skin, sorted by partner, image codes in the convention of the
+// row part (mdk_rows_build, md_rows.hip: full rows inside cutoff + skin, sorted by partner, image codes in the convention of the
 // ReaxFF rows); the integrator, thermostat, fix deform, pressure sampling and the batch machinery are the ones of the OPLS path.  One
 // launch covers every replica of the batch (blockIdx.y).
 //   k_eam_density .. rho_i over the entries of atom i's row inside the cutoff, F(rho_i) into the step's energy, F'(rho_i) into fp[i]
 //   k_eam_force .... the same walk with the full pair term (eam/eam_core.h): every F' exists before any force is formed
-// between the row part and k_sw_finish (md_sw.hip).  With full rows every atom sums its own force: neither kernel has an atomic on a
+// between the row part and k_row_finish (md_rows.hip).  With full rows every atom sums its own force: neither kernel has an atomic on a
 // force or a density, rows are sorted and the sum over a group has a fixed order, so forces do not depend on the schedule.
 // Engine parts: phi and the virial of phi' go to P_LJ, the embedding energy and the virial of the F' terms to P_ANGLE.  Only their sum
 // enters the stress; the split is what scema_md_eam_debug_compute reports as e_pair and e_embed.
@@ -14,13 +14,13 @@
 #include "md_kernels.h"
 #include "md_rowforce.h"
 
-typedef const double SW_G *EamTab;
+typedef const double ROW_G *EamTab;
 
 // A group of 16 lanes walks the row of atom i, a lane per entry: entries with 0 < r^2 < cutoff^2 go to term(j, d0, d1, d2, r2), d = x_j
 // - x_i with the entry's image shift.  Index and image code are clamped to what the builder can have written.  A group past the
 // replica's last atom (i >= n) walks nothing; no lane leaves, so the group sums that follow see whole waves.
 template <class Term>
-__device__ __forceinline__ void eam_walk(const SwView &V, const double *s_sh, double cut2, int i, int l16, Term term) {
+__device__ __forceinline__ void eam_walk(const RowView &V, const double *s_sh, double cut2, int i, int l16, Term term) {
   const int n = V.n, cap = V.cap;
   const bool valid = i < n;
   const int ic = valid ? i : n - 1;
@@ -29,7 +29,7 @@ __device__ __forceinline__ void eam_walk(const SwView &V, const double *s_sh, do
   const size_t base = (size_t)ic * cap;
   for (int c = l16; c < cnt; c += 16) {
     const int ent = V.rows[base + c];
-    const int j = min(ent & SW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, SW_NSHIFT - 1);
+    const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
     const double *sh = s_sh + 3 * code;
     const double d0 = V.x[3 * j] - xi0 + sh[0], d1 = V.x[3 * j + 1] - xi1 + sh[1], d2 = V.x[3 * j + 2] - xi2 + sh[2];
     const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
@@ -39,20 +39,20 @@ __device__ __forceinline__ void eam_walk(const SwView &V, const double *s_sh, do
 
 // the material's head into LDS (offsets are read per lane, by the partner's element)
 __device__ __forceinline__ void eam_head_to_lds(EamTab blk, EamHead *s_hd) {
-  for (int k = threadIdx.x; k < (int)(sizeof(EamHead) / 4); k += SW_FORCE_TPB) ((int *)s_hd)[k] = ((const int SW_G *)blk)[k];
+  for (int k = threadIdx.x; k < (int)(sizeof(EamHead) / 4); k += ROW_FORCE_TPB) ((int *)s_hd)[k] = ((const int ROW_G *)blk)[k];
 }
 
-// Densities.  A workgroup owns SW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time; the group's
+// Densities.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time; the group's
 // first lane evaluates F and F'.  Value records only (eam_core.h).
-__global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_density(const SimDev *sims, const SwView *views, const EamView *aux) {
-  const SwView V = views[blockIdx.y];
+__global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_density(const SimDev *sims, const RowView *views, const EamView *aux) {
+  const RowView V = views[blockIdx.y];
   const int n = V.n;
-  if ((int)(blockIdx.x * SW_TILE) >= n) return;   // (the whole workgroup)
+  if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
   const EamTab blk = (EamTab)V.tab;
-  double SW_G *fp = aux[blockIdx.y].fp;
-  __shared__ double s_sh[3 * SW_NSHIFT];
+  double ROW_G *fp = aux[blockIdx.y].fp;
+  __shared__ double s_sh[3 * ROW_NSHIFT];
   __shared__ EamHead s_hd;
-  __shared__ double s_red[8 * (SW_FORCE_TPB / 64)];
+  __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
   eam_head_to_lds(blk, &s_hd);
   __syncthreads();
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_density(const SimDev *sims
   const int nr = s_hd.nr;
   const double rdr = s_hd.rdr, cut2 = s_hd.cut2;
   double esum[4] = {0.0, 0.0, 0.0, 0.0};   // pair energy (the force pass), embedding energy, ordered pairs, atoms above rhomax
-  for (int it = 0; it < SW_TILE / SW_NGRP; it++) {   // (uniform over the workgroup)
-    const int i = blockIdx.x * SW_TILE + it * SW_NGRP + grp;
+  for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup)
+    const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const int ti = V.stype[min(i, n - 1)];
     double rho = 0.0;
     eam_walk(V, s_sh, cut2, i, l16, [&](int j, double, double, double, double r2) __attribute__((always_inline)) {
@@ -81,21 +81,21 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_density(const SimDev *sims
       if (rho > s_hd.rhomax) esum[3] += 1.0;
     }
   }
-  block_atomic_add_n<4, SW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
+  block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
 }
 
 // Forces: the same walk; a lane's entry takes the derivative records of the two densities and both records of r phi, and F' of both
 // ends.  The group's sum is the atom's force, stored once.  Half of a pair's phi and half of its virial go to each end.
-__global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_force(const SimDev *sims, const SwView *views, const EamView *aux) {
-  const SwView V = views[blockIdx.y];
+__global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims, const RowView *views, const EamView *aux) {
+  const RowView V = views[blockIdx.y];
   const int n = V.n;
-  if ((int)(blockIdx.x * SW_TILE) >= n) return;   // (the whole workgroup)
+  if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
   const EamTab blk = (EamTab)V.tab;
-  const double SW_G *fp = aux[blockIdx.y].fp;
+  const double ROW_G *fp = aux[blockIdx.y].fp;
   SimScalars &sc = *sims[blockIdx.y].sc;
-  __shared__ double s_sh[3 * SW_NSHIFT];
+  __shared__ double s_sh[3 * ROW_NSHIFT];
   __shared__ EamHead s_hd;
-  __shared__ double s_red[8 * (SW_FORCE_TPB / 64)];
+  __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
   eam_head_to_lds(blk, &s_hd);
   __syncthreads();
@@ -105,8 +105,8 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_force(const SimDev *sims, 
   const double rdr = s_hd.rdr, cut2 = s_hd.cut2;
   double esum[4] = {0.0, 0.0, 0.0, 0.0};
   double wa[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int it = 0; it < SW_TILE / SW_NGRP; it++) {   // (uniform over the workgroup)
-    const int i = blockIdx.x * SW_TILE + it * SW_NGRP + grp;
+  for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup)
+    const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const int ic = min(i, n - 1);
     const int ti = V.stype[ic];
     const double fpi = fp[ic];
@@ -133,16 +133,16 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_eam_force(const SimDev *sims, 
     fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
     if (i < n && l16 == 0) { V.f[3 * i] = fi0; V.f[3 * i + 1] = fi1; V.f[3 * i + 2] = fi2; }
   }
-  block_atomic_add_n<4, SW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(wa, &sc.vir[P_LJ * 6], s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(wb, &sc.vir[P_ANGLE * 6], s_red);
+  block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
+  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wa, &sc.vir[P_LJ * 6], s_red);
+  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wb, &sc.vir[P_ANGLE * 6], s_red);
 }
 
-void mdk_eam_forces(hipStream_t st, const SimDev *d, SwView *v, const EamView *a, int ns, int maxatoms) {
+void mdk_eam_forces(hipStream_t st, const SimDev *d, RowView *v, const EamView *a, int ns, int maxatoms) {
   if (ns <= 0 || maxatoms <= 0) return;
-  const dim3 gt((unsigned)((maxatoms + SW_TILE - 1) / SW_TILE), (unsigned)ns, 1);
-  mdk_sw_rows(st, d, v, ns, maxatoms);
-  hipLaunchKernelGGL(k_eam_density, gt, dim3(SW_FORCE_TPB), 0, st, d, v, a);
-  hipLaunchKernelGGL(k_eam_force, gt, dim3(SW_FORCE_TPB), 0, st, d, v, a);
-  mdk_sw_finish(st, d, v, ns);
+  const dim3 gt((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1);
+  mdk_rows_build(st, d, v, ns, maxatoms);
+  hipLaunchKernelGGL(k_eam_density, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+  hipLaunchKernelGGL(k_eam_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+  mdk_rows_finish(st, d, v, ns);
 }

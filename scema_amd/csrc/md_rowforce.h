@@ -1,22 +1,21 @@
-// md_rowforce.h -- what the force kernels on the rows of mdk_sw_rows share (k_sw_force, md_sw.hip; k_ts_force, md_tersoff.hip): the image
+// md_rowforce.h -- what the force kernels on the rows of mdk_rows_build share (k_sw_force, md_sw.hip; k_ts_force, md_tersoff.hip): the image
 // shifts, the table of the replica's forces in LDS, the filter of one atom's row and the end of a workgroup.  Device code, included by
-// those two files and, for the image shifts and the launch shape alone, by md_eam.hip.  No helper holds a barrier: a kernel's three
-// barriers per round stand in its own body.
+// those two files, for the image shifts and the launch shape alone by md_eam.hip, and for the launch shape by md_rows.hip.  No helper
+// holds a barrier: a kernel's three barriers per round stand in its own body.
 #pragma once
 #include "md_device.h"
-#include "md_sw.h"
+#include "md_rows.h"
 #include "md_types.h"
 
-#define SW_NSHIFT 125
-#define SW_FORCE_TPB 256     /* force kernels: 16 groups of 16 lanes, a group per central atom */
-#define SW_NGRP (SW_FORCE_TPB / 16)
-static_assert(SW_TILE % SW_NGRP == 0 && SW_MAXIN <= 32, "tile shapes of the force kernels");
+#define ROW_FORCE_TPB 256    /* force kernels: 16 groups of 16 lanes, a group per central atom */
+#define ROW_NGRP (ROW_FORCE_TPB / 16)
+static_assert(ROW_TILE % ROW_NGRP == 0 && ROW_MAXIN <= 32, "tile shapes of the force kernels");
 
 extern __shared__ double s_rowf[];   // LACC: [3][npad]
 
 // shift of every image code: code . h
-__device__ __forceinline__ void rowf_shifts(const SwView &V, double *s_sh) {
-  for (int code = threadIdx.x; code < SW_NSHIFT; code += SW_FORCE_TPB) {
+__device__ __forceinline__ void rowf_shifts(const RowView &V, double *s_sh) {
+  for (int code = threadIdx.x; code < ROW_NSHIFT; code += ROW_FORCE_TPB) {
     const int sx = code % 5 - 2, sy = (code / 5) % 5 - 2, sz = code / 25 - 2;
     s_sh[3 * code] = sx * V.h[0] + sy * V.h[5] + sz * V.h[4];
     s_sh[3 * code + 1] = sy * V.h[1] + sz * V.h[3];
@@ -28,23 +27,23 @@ __device__ __forceinline__ void rowf_shifts(const SwView &V, double *s_sh) {
 __device__ __forceinline__ void rowf_lds_add(double *p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // Forces on partners go into a table of the replica's forces in LDS (LACC; ds_add_f64), flushed with one global FP64 atomic per touched
-// atom and component; replicas beyond SW_LDS_MAXPAD atoms add to global memory directly.
+// atom and component; replicas beyond ROW_LDS_MAXPAD atoms add to global memory directly.
 template <bool LACC>
 __device__ __forceinline__ void rowf_zero(size_t np) {
   if (LACC)
-    for (int k = threadIdx.x; k < 3 * (int)np; k += SW_FORCE_TPB) s_rowf[k] = 0.0;
+    for (int k = threadIdx.x; k < 3 * (int)np; k += ROW_FORCE_TPB) s_rowf[k] = 0.0;
 }
 template <bool LACC>
-__device__ __forceinline__ void rowf_add(double SW_G *f, size_t np, int a, double g0, double g1, double g2) {
+__device__ __forceinline__ void rowf_add(double ROW_G *f, size_t np, int a, double g0, double g1, double g2) {
   if (LACC) { rowf_lds_add(&s_rowf[a], g0); rowf_lds_add(&s_rowf[np + a], g1); rowf_lds_add(&s_rowf[2 * np + a], g2); }
   else { atomicAdd((double *)&f[3 * a], g0); atomicAdd((double *)&f[3 * a + 1], g1); atomicAdd((double *)&f[3 * a + 2], g2); }
 }
 
 // One group of 16 lanes filters the row of atom i (element ti) to the entries INSIDE their cutoff, in the row's order (ballot order): an
-// accepted entry goes to keep(pos, ent, tj, d0, d1, d2, r) with pos < SW_MAXIN, cut(ti, tj) is the cutoff of a pair of elements.  Returns
-// the entries kept; more than SW_MAXIN inside set `crowded`.  A group past the replica's last atom (i >= n) filters nothing.
+// accepted entry goes to keep(pos, ent, tj, d0, d1, d2, r) with pos < ROW_MAXIN, cut(ti, tj) is the cutoff of a pair of elements.  Returns
+// the entries kept; more than ROW_MAXIN inside set `crowded`.  A group past the replica's last atom (i >= n) filters nothing.
 template <class Cut, class Keep>
-__device__ __forceinline__ int rowf_filter(const SwView &V, const double *s_sh, int i, int ti, int l16, int shift16, bool &crowded, Cut cut, Keep keep) {
+__device__ __forceinline__ int rowf_filter(const RowView &V, const double *s_sh, int i, int ti, int l16, int shift16, bool &crowded, Cut cut, Keep keep) {
   const int n = V.n, cap = V.cap;
   const bool valid = i < n;
   const int ic = valid ? i : n - 1;
@@ -59,7 +58,7 @@ __device__ __forceinline__ int rowf_filter(const SwView &V, const double *s_sh, 
     double d0 = 0.0, d1 = 0.0, d2 = 0.0, r = 1.0;
     int tj = 0;
     if (ent >= 0) {
-      const int j = min(ent & SW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, SW_NSHIFT - 1);
+      const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
       ent = j | (code << 24);   // (what the builder wrote; nothing else is ever used as an index)
       const double *sh = s_sh + 3 * code;
       d0 = V.x[3 * j] - xi0 + sh[0]; d1 = V.x[3 * j + 1] - xi1 + sh[1]; d2 = V.x[3 * j + 2] - xi2 + sh[2];
@@ -71,16 +70,16 @@ __device__ __forceinline__ int rowf_filter(const SwView &V, const double *s_sh, 
     }
     const unsigned m16 = (unsigned)(__ballot(in) >> shift16) & 0xFFFFu;
     const int pos = nn + __popc(m16 & ((1u << l16) - 1u));
-    if (in && pos < SW_MAXIN) keep(pos, ent, tj, d0, d1, d2, r);
+    if (in && pos < ROW_MAXIN) keep(pos, ent, tj, d0, d1, d2, r);
     nn += __popc(m16);
   }
-  if (nn > SW_MAXIN) { crowded = true; nn = SW_MAXIN; }
+  if (nn > ROW_MAXIN) { crowded = true; nn = ROW_MAXIN; }
   return nn;
 }
 
 // the central atom's own force: the sum over its group (a row of 16 lanes), added by the group's first lane
 template <bool LACC>
-__device__ __forceinline__ void rowf_add_own(const SwView &V, size_t np, int i, int l16, double fi0, double fi1, double fi2) {
+__device__ __forceinline__ void rowf_add_own(const RowView &V, size_t np, int i, int l16, double fi0, double fi1, double fi2) {
   fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
   if (i < V.n && l16 == 0 && (fi0 != 0.0 || fi1 != 0.0 || fi2 != 0.0)) rowf_add<LACC>(V.f, np, i, fi0, fi1, fi2);
 }
@@ -88,16 +87,16 @@ __device__ __forceinline__ void rowf_add_own(const SwView &V, size_t np, int i, 
 // end of a workgroup, after the last round's closing barrier: the LDS table to global memory (zeros skipped), the crowded bit, and the
 // step's sums (esum -> eacc, wa -> virial part P_LJ, wb -> P_ANGLE), one atomic per value and workgroup
 template <bool LACC>
-__device__ __forceinline__ void rowf_finish(const SwView &V, SimScalars &sc, size_t np, bool crowded, double (&esum)[4], double (&wa)[6], double (&wb)[6], double *s_red) {
+__device__ __forceinline__ void rowf_finish(const RowView &V, SimScalars &sc, size_t np, bool crowded, double (&esum)[4], double (&wa)[6], double (&wb)[6], double *s_red) {
   if (LACC) {
-    for (int k = threadIdx.x; k < 3 * V.n; k += SW_FORCE_TPB) {
+    for (int k = threadIdx.x; k < 3 * V.n; k += ROW_FORCE_TPB) {
       const int a = k / 3, c = k - 3 * a;
       const double v = s_rowf[(size_t)c * np + a];
       if (v != 0.0) atomicAdd((double *)&V.f[k], v);
     }
   }
   if (crowded) atomicOr(&V.stat[0], 2);
-  block_atomic_add_n<4, SW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(wa, &sc.vir[P_LJ * 6], s_red);
-  block_atomic_add_n<6, SW_FORCE_TPB / 64>(wb, &sc.vir[P_ANGLE * 6], s_red);
+  block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
+  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wa, &sc.vir[P_LJ * 6], s_red);
+  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wb, &sc.vir[P_ANGLE * 6], s_red);
 }

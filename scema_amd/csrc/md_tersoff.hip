@@ -1,10 +1,10 @@
-// md_tersoff.hip -- gfx950 kernels of the Tersoff force stage (`pair_style tersoff`).  The neighbour rows are those of the Stillinger-Weber
-// stage (mdk_sw_rows, md_sw.hip: full rows inside the largest R + D + skin, image codes in the convention of the ReaxFF rows); the
+// md_tersoff.hip -- gfx950 kernels of the Tersoff force stage (`pair_style tersoff`).  The neighbour rows are those of the row part
+// (mdk_rows_build, md_rows.hip: full rows inside the largest R + D + skin, image codes in the convention of the ReaxFF rows); the
 // integrator, thermostat, fix deform, pressure sampling and the batch machinery are the ones of the OPLS path.  One launch covers every
 // replica of the batch (blockIdx.y).
 //   k_ts_force ..... pair terms, bond orders and their gradients (tersoff/ts_core.h) around a central atom, forces summed in LDS
-// on the skeleton of md_rowforce.h; the row part, the launch shape and k_sw_finish (energies and fault bits into the engine's scalars) come
-// with mdk_row_forces (md_sw.hip).
+// on the skeleton of md_rowforce.h; the row part, the launch shape and k_row_finish (energies and fault bits into the engine's scalars) come
+// with mdk_row_forces (md_rows.hip).
 // Engine parts: the repulsive term 1/2 fC fR and its virial go to P_LJ, everything that carries b_ij (1/2 fC b fA and the gradient of zeta)
 // to P_ANGLE.  Only their sum enters the stress; the split is what scema_md_tersoff_debug_compute reports as e_rep and e_att.
 #include <hip/hip_runtime.h>
@@ -13,7 +13,7 @@
 #include "md_rowforce.h"
 #include "md_tersoff.h"
 
-// Forces.  A workgroup owns SW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time.  The group first
+// Forces.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time.  The group first
 // filters the atom's row to the entries INSIDE the cutoff under which the pair (i, k) is used -- vector, distance, fC and fC' of the pair,
 // computed once per neighbour -- into LDS (rowf_filter, md_rowforce.h).  Pass 1, a lane per neighbour j: zeta_ij over the other
 // entries, b and b', the pair term at fixed b and its force, and pref_j = 1/2 fC fA b' left in LDS (in the slot of fC', which nothing reads
@@ -21,26 +21,26 @@
 // the nn (nn - 1) ordered (j, k): pref_j d zeta_ij / d(x_j, x_k) onto j and k.  Forces go into the LDS table or to global memory (LACC,
 // md_rowforce.h).  Energies, virial and counts are summed per workgroup.
 template <bool LACC>
-__global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, const SwView *views) {
-  const SwView V = views[blockIdx.y];
+__global__ __launch_bounds__(ROW_FORCE_TPB) void k_ts_force(const SimDev *sims, const RowView *views) {
+  const RowView V = views[blockIdx.y];
   const int n = V.n;
-  if ((int)(blockIdx.x * SW_TILE) >= n) return;   // (the whole workgroup)
+  if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
   // (a load of its own, which the compiler may not merge: read as V.tab the pointer joins stype, x, f, cnt, rows, eacc and stat in one
   // 16-dword scalar load, a tuple this kernel's SGPR spilling then reloads whole around every use -- 312 v_readlane for 200, 1 % of an update)
-  const TsTable SW_G *tab = (const TsTable SW_G *)__atomic_load_n(&views[blockIdx.y].tab, __ATOMIC_RELAXED);
+  const TsTable ROW_G *tab = (const TsTable ROW_G *)__atomic_load_n(&views[blockIdx.y].tab, __ATOMIC_RELAXED);
   SimScalars &sc = *sims[blockIdx.y].sc;
   const size_t np = (size_t)V.npad;
-  __shared__ double s_sh[3 * SW_NSHIFT];
+  __shared__ double s_sh[3 * ROW_NSHIFT];
   __shared__ TsPairP s_pair[TS_MAXEL * TS_MAXEL];
   __shared__ TsTripP s_trip[TS_MAXEL * TS_MAXEL * TS_MAXEL];
   __shared__ double s_cutin[TS_MAXEL * TS_MAXEL];
-  __shared__ double s_nb[6][SW_NGRP][SW_MAXIN];   // d (3), r, fC of the pair, fC' of the pair -> pref after pass 1
-  __shared__ int s_ent[SW_NGRP][SW_MAXIN], s_tj[SW_NGRP][SW_MAXIN];
-  __shared__ double s_red[8 * (SW_FORCE_TPB / 64)];
+  __shared__ double s_nb[6][ROW_NGRP][ROW_MAXIN];   // d (3), r, fC of the pair, fC' of the pair -> pref after pass 1
+  __shared__ int s_ent[ROW_NGRP][ROW_MAXIN], s_tj[ROW_NGRP][ROW_MAXIN];
+  __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
-  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += SW_FORCE_TPB) ((double *)s_pair)[k] = ((const double SW_G *)&tab->pair[0])[k];
-  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += SW_FORCE_TPB) ((double *)s_trip)[k] = ((const double SW_G *)&tab->trip[0])[k];
-  for (int k = threadIdx.x; k < TS_MAXEL * TS_MAXEL; k += SW_FORCE_TPB) s_cutin[k] = tab->cutin[k];
+  for (int k = threadIdx.x; k < (int)(sizeof(s_pair) / 8); k += ROW_FORCE_TPB) ((double *)s_pair)[k] = ((const double ROW_G *)&tab->pair[0])[k];
+  for (int k = threadIdx.x; k < (int)(sizeof(s_trip) / 8); k += ROW_FORCE_TPB) ((double *)s_trip)[k] = ((const double ROW_G *)&tab->trip[0])[k];
+  for (int k = threadIdx.x; k < TS_MAXEL * TS_MAXEL; k += ROW_FORCE_TPB) s_cutin[k] = tab->cutin[k];
   rowf_zero<LACC>(np);
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
@@ -49,8 +49,8 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, c
   double wr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   auto add_force = [&](int a, double g0, double g1, double g2) __attribute__((always_inline)) { rowf_add<LACC>(V.f, np, a, g0, g1, g2); };
   bool crowded = false;
-  for (int it = 0; it < SW_TILE / SW_NGRP; it++) {   // (uniform over the workgroup: the barriers and the group sums below are reached by every lane)
-    const int i = blockIdx.x * SW_TILE + it * SW_NGRP + grp;
+  for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup: the barriers and the group sums below are reached by every lane)
+    const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const int ti = V.stype[min(i, n - 1)];
     const int nn = rowf_filter(
         V, s_sh, i, ti, l16, shift16, crowded, [&](int a, int b) __attribute__((always_inline)) { return s_cutin[a * TS_MAXEL + b]; },
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, c
         pref = 0.5 * fc * fa * db;
         const double fp = fprep + fpatt;
         const double g0 = fp * dj[0], g1 = fp * dj[1], g2 = fp * dj[2];   // force on the partner
-        add_force(s_ent[grp][m] & SW_JMASK, g0, g1, g2);
+        add_force(s_ent[grp][m] & ROW_JMASK, g0, g1, g2);
         fi0 -= g0; fi1 -= g1; fi2 -= g2;
         esum[0] += erep; esum[1] += eatt; esum[2] += 1.0;
         const double q0 = fprep * dj[0], q1 = fprep * dj[1], q2 = fprep * dj[2];
@@ -113,8 +113,8 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, c
       const double dj[3] = {s_nb[0][grp][j], s_nb[1][grp][j], s_nb[2][grp][j]}, dk[3] = {s_nb[0][grp][k], s_nb[1][grp][k], s_nb[2][grp][k]};
       double fj[3], fk[3];
       ts_zeta_force(Q, pref, dj, r1, dk, r2, fj, fk);
-      add_force(s_ent[grp][j] & SW_JMASK, fj[0], fj[1], fj[2]);
-      add_force(s_ent[grp][k] & SW_JMASK, fk[0], fk[1], fk[2]);
+      add_force(s_ent[grp][j] & ROW_JMASK, fj[0], fj[1], fj[2]);
+      add_force(s_ent[grp][k] & ROW_JMASK, fk[0], fk[1], fk[2]);
       fi0 -= fj[0] + fk[0]; fi1 -= fj[1] + fk[1]; fi2 -= fj[2] + fk[2];
       wb[0] += dj[0] * fj[0] + dk[0] * fk[0]; wb[1] += dj[1] * fj[1] + dk[1] * fk[1]; wb[2] += dj[2] * fj[2] + dk[2] * fk[2];
       wb[3] += dj[0] * fj[1] + dk[0] * fk[1]; wb[4] += dj[0] * fj[2] + dk[0] * fk[2]; wb[5] += dj[1] * fj[2] + dk[1] * fk[2];
@@ -125,6 +125,6 @@ __global__ __launch_bounds__(SW_FORCE_TPB) void k_ts_force(const SimDev *sims, c
   rowf_finish<LACC>(V, sc, np, crowded, esum, wr, wb, s_red);
 }
 
-void mdk_ts_forces(hipStream_t st, const SimDev *d, SwView *v, int ns, int maxatoms) {
+void mdk_ts_forces(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms) {
   mdk_row_forces(st, d, v, ns, maxatoms, k_ts_force<true>, k_ts_force<false>);
 }

@@ -19,9 +19,10 @@
 #define SW_HD inline
 #endif
 
+#include "../md_row_entry.h"   /* the row entries sw_owns reads: ROW_JMASK, ROW_CODE0 */
+
 #define SW_MAXEL 4           /* elements kept (named by pair_coeff) */
-#define SW_CODE0 62          /* row entry: [23:0] atom, [30:24] image code (sx+2) + 5 (sy+2) + 25 (sz+2), as the ReaxFF rows (RX_JMASK); 62 = no shift */
-#define SW_JMASK 0x00FFFFFF
+#define SW_JMASK ROW_JMASK   /* the entry's atom field under this header's own name, for code written against it (tests/sw_host_driver.cpp) */
 
 typedef struct {
   double aeps;     // A eps
@@ -45,8 +46,8 @@ typedef struct {
 // does row entry `ent` of atom i name a pair that i evaluates?  Every pair (i, j, image) is listed at both ends: the lower index owns it; an
 // atom's pair with its own image is listed twice in its own row, under a code and under the mirrored one: the upper code owns it.
 SW_HD bool sw_owns(int i, int ent) {
-  const int j = ent & SW_JMASK;
-  return j > i || (j == i && ((ent >> 24) & 0x7F) > SW_CODE0);
+  const int j = ent & ROW_JMASK;
+  return j > i || (j == i && ((ent >> 24) & 0x7F) > ROW_CODE0);
 }
 
 // (sigma/r)^p and (sigma/r)^q

@@ -1,4 +1,4 @@
-"""The embedded-atom force stage on the GPU (md_eam.hip, engine_eam.cpp) against the independent FP64 numpy restatement
+"""The embedded-atom force stage on the GPU (md_eam.hip, engine_rowpot.cpp) against the independent FP64 numpy restatement
 tests/eam_numpy.py, which tests/test_eam_host.py pins on the CPU (no LAMMPS exists to compare with): static parity on the shapes at which
 the kernels or the driver take another path, forces equal bit for bit between evaluations, dynamics, the virial -> pressure conversion,
 elastic constants, whole evaluations, batches over two materials, box flips inside a split batch, refusals, replaced attachments,

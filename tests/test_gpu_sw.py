@@ -1,4 +1,4 @@
-"""The Stillinger-Weber force stage on the GPU (md_sw.hip, engine_sw.cpp) against the independent FP64 numpy restatement tests/sw_numpy.py,
+"""The Stillinger-Weber force stage on the GPU (md_rows.hip, md_sw.hip, engine_rowpot.cpp) against the independent FP64 numpy restatement tests/sw_numpy.py,
 which tests/test_sw_host.py pins on the CPU: static parity on the shapes at which the kernels take another path, the closed forms of
 silicon, dynamics, the virial -> pressure conversion, whole evaluations, batches, box flips inside a split batch, kept neighbour rows,
 the refusal of mixed updates.

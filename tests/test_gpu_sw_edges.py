@@ -1,4 +1,4 @@
-"""The Stillinger-Weber kernels (md_sw.hip) where tests/test_gpu_sw.py does not take them, against the numpy reference tests/sw_numpy.py, which
+"""The Stillinger-Weber kernels (md_rows.hip, md_sw.hip) where tests/test_gpu_sw.py does not take them, against the numpy reference tests/sw_numpy.py, which
 tests/test_sw_edges_host.py licenses on these inputs (supercell identity, central differences, pinned counts):
 
   1  boxes narrower than one list radius: the image search two boxes deep, an atom's pair with its own image (sw_owns with j == i), triplets

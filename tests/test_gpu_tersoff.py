@@ -1,4 +1,4 @@
-"""The Tersoff force stage on the GPU (md_tersoff.hip, engine_tersoff.cpp) against the independent FP64 numpy restatement
+"""The Tersoff force stage on the GPU (md_tersoff.hip, engine_rowpot.cpp) against the independent FP64 numpy restatement
 tests/tersoff_numpy.py, which tests/test_tersoff_host.py pins on the CPU (no LAMMPS and no reference Tersoff file exist to compare with):
 static parity on the shapes at which the kernels take another path, dynamics, the virial -> pressure conversion, elastic constants, whole
 evaluations, batches over two materials, box flips inside a split batch, refusals, self-configuration from the scripts folder.

@@ -1,0 +1,108 @@
+"""Throughput of a force stage on full neighbour rows: N quadrature points (default 576) x one replica, 10 straining + 100 sampling steps
+per evaluation at 1 fs.  The replica per potential:
+  sw ....... the 192-atom silicon replica of the reference's example (tests/golden/lammps_17Nov16_init.sic_1.bin with tests/golden/Si.sw)
+  tersoff .. 192 atoms of diamond silicon (3 x 2 x 4 cells of 5.432 A, thermal velocities at 300 K, tests/golden/SiC.tersoff)
+  eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
+             tests/golden/CuAg.eam.alloy)
+One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
+in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
+tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
+
+  python tools/rowpot_bench.py --potential sw|tersoff|eam [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
+"""
+import argparse
+import itertools
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from scema_amd import capi  # noqa: E402
+
+GOLD = os.path.join(ROOT, "tests", "golden")
+BOLTZ, MVV2E = 0.0019872067, 48.88821291 ** 2
+DIAMOND = [[0, 0, 0], [0, 2, 2], [2, 0, 2], [2, 2, 0], [1, 1, 1], [1, 3, 3], [3, 1, 3], [3, 3, 1]]
+FCC = DIAMOND[:4]
+
+
+def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1):
+    """a cubic lattice of that basis (in quarters of the cell) with thermal velocities, as a bare replica"""
+    nx, ny, nz = cells
+    grid = np.array(list(itertools.product(range(nx), range(ny), range(nz))), float)
+    x = (grid[:, None, :] + np.array(basis, float)[None, :, :] * 0.25).reshape(-1, 3) * a
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=x.shape) * math.sqrt(BOLTZ * temp / mass / MVV2E)
+    box = np.array([0.0, 0.0, 0.0, nx * a, ny * a, nz * a, 0.0, 0.0, 0.0])
+    e.register_replica(matid, 1, capi.bare_system(np.zeros(len(x), np.int32), x, box, v=v - v.mean(axis=0), masses=(mass,)))
+
+
+def make_sw(e):
+    e.load_lammps_restart("sic", 1, os.path.join(GOLD, "lammps_17Nov16_init.sic_1.bin"), 192)
+    e.sw_configure("sic", os.path.join(GOLD, "Si.sw"))
+
+
+def make_tersoff(e):
+    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.432, 28.0855)
+    e.tersoff_configure("si", os.path.join(GOLD, "SiC.tersoff"), ("Si",))
+
+
+def make_eam(e):
+    register_lattice(e, "cu", FCC, (4, 4, 4), 3.615, 63.546)
+    e.eam_configure("cu", os.path.join(GOLD, "CuAg.eam.alloy"), ("Cu",))
+
+
+# potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
+POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--potential", required=True, choices=sorted(POTENTIALS))
+    ap.add_argument("--sims", type=int, default=576)
+    ap.add_argument("--updates", type=int, default=5)
+    ap.add_argument("--nss", type=int, default=100)
+    ap.add_argument("--split", type=int, default=-1, help="scema_md_batch_split: 0 whole, 1 part batches, -1 the default")
+    ap.add_argument("--dump", default=None, metavar="FILE", help="write the stresses of the last update as FILE (.npy, float64, one row of six per quadrature point)")
+    a = ap.parse_args()
+    workload, mat, make = POTENTIALS[a.potential]
+    e = capi.Engine(capi.default_params())
+    make(e)
+    e.batch_split(a.split)
+    box, _, _ = e.get_state(capi.QP_NONE, mat, 1)
+    L = box[3:6] - box[:3]
+    rng = np.random.default_rng(1)
+
+    def sims(first):
+        out = []
+        for q in range(a.sims):
+            ezz = rng.uniform(4e-4, 9e-4)      # 10 straining steps at 1e-4 per fs, dt 1 fs
+            s = np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.1 * ezz * L[2], 0.0, 0.0])
+            out.append(capi.make_sim(q, mat, 1, s, nss=a.nss, dt=1.0, temperature=300.0, strain_rate=1e-4,
+                                     most_recent=capi.QP_NONE if first else q))
+        return out
+
+    e.strain_batch(sims(True))                 # warm-up: code objects, slots, rows
+    times = []
+    for _ in range(a.updates):
+        batch = sims(False)
+        t0 = time.perf_counter()
+        res = e.strain_batch(batch)
+        times.append(time.perf_counter() - t0)
+        assert all(o.stress_updated == 1 for o in res)
+    if a.dump:
+        np.save(a.dump, np.array([list(o.stress) for o in res], np.float64))
+    prof = e.profile()
+    best, med = min(times), sorted(times)[len(times) // 2]
+    print(json.dumps({"workload": workload, "sims": a.sims, "steps_per_eval": 10 + a.nss, "updates": a.updates, "split": e.concurrency()["split"],
+                      "evals_per_s_median": a.sims / med, "evals_per_s_best": a.sims / best, "update_s": times,
+                      "replica_steps_per_s_median": a.sims * (10 + a.nss) / med, "neigh_builds": prof["neigh_builds"], "md_steps": prof["md_steps"]}))
+    e.close()
+
+
+if __name__ == "__main__":
+    main()
