@@ -425,6 +425,33 @@ int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char
 int scema_md_tersoff_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                                  int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
+/* ---- the Tersoff forms `pair_style tersoff/mod`, `tersoff/mod/c` (Kumagai et al.: Si.tersoff.mod, Si.tersoff.modc) and `tersoff/zbl`
+ * (Devanathan et al.: SiC.tersoff.zbl) ----
+ * Each is a kind of its own on the same stage, with everything said of scema_md_tersoff_configure: one attachment per material (configuring
+ * replaces a plain Tersoff one and the other way round), the limit of 32 neighbours inside R + D, the refusal of updates and runs that mix
+ * kinds (a Tersoff/mod material with a plain Tersoff one included), the energy unit (ZBL: energy_unit 1 also takes the Coulomb constant of
+ * `units real`, K / 0.043365121).  One entry point serves tersoff/mod and tersoff/mod/c: a file whose first entry carries 18 numbers is
+ * mod/c (the 18th is c0), otherwise c0 = 0.  A bare replica configures itself from `pair_coeff * * ${locs}/<name>.tersoff.mod`, `.tersoff.modc`
+ * or `.tersoff.zbl` of in.strain.lammps, searched after *.tersoff and *.eam.alloy.  debug_compute: e_rep is everything without b_ij (the c0
+ * term and the ZBL repulsion included), e_att everything that carries it. */
+int scema_md_tersoff_mod_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin);
+int scema_md_tersoff_mod_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep,
+                                       double *e_att, double *virial, double *info);
+int scema_md_tersoff_zbl_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin);
+int scema_md_tersoff_zbl_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep,
+                                       double *e_att, double *virial, double *info);
+/* The readers as pure host functions, as scema_md_tersoff_read_params: values[n_kept][n_kept][n_kept][18] for both forms (room for
+ * 4*4*4*18).  mod: beta alpha h eta beta_ters lambda2 B R D lambda1 A n c1 c2 c3 c4 c5 c0, with c0 = 0 for a 17-column file, A, B and c0
+ * in kcal/mol; refused: beta_ters other than 1, beta other than 1 or 3, a negative alpha, eta, lambda2, B, R, D, lambda1, A, n, c2, c3, c4
+ * or c5, D > R, n = 0 or eta = 0 in an entry i j j, c3 = 0 with -1 <= h <= 1.  zbl: the fourteen numbers of a plain entry, then Z_i Z_j
+ * ZBLcut ZBLexpscale; refused: what the plain reader refuses, Z <= 0, a negative ZBLcut or ZBLexpscale. */
+int scema_md_tersoff_mod_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                     int32_t *type_map, double *values, char *errbuf, int32_t errcap);
+int scema_md_tersoff_zbl_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                     int32_t *type_map, double *values, char *errbuf, int32_t errcap);
+
 /* ---- embedded-atom replicas (`pair_style eam/alloy`; metals and their alloys) ----
  * configure = `pair_style eam/alloy` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1, in any order,
  * repeats allowed, at most 4 distinct) for the replicas of ONE material id, registered before or after the call; <path> is a DYNAMO setfl

@@ -40,6 +40,8 @@ SYMBOLS = [
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
     "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
     "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
+    "scema_md_tersoff_mod_configure", "scema_md_tersoff_mod_debug_compute", "scema_md_tersoff_mod_read_params",
+    "scema_md_tersoff_zbl_configure", "scema_md_tersoff_zbl_debug_compute", "scema_md_tersoff_zbl_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -502,6 +504,22 @@ class Engine:
     def tersoff_compute(self, matid, replica, qp=QP_NONE):
         return self._row_compute("scema_md_tersoff_debug_compute", matid, replica, qp, "e_rep", "e_att", "nzeta")
 
+    def tersoff_mod_configure(self, matid: str, path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style tersoff/mod or tersoff/mod/c (a file whose first entry has 18 numbers) + pair_coeff * * <path> <elements>; energy_unit
+        as for tersoff_configure.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_tersoff_mod_configure", matid, path, elements, energy_unit, skin)
+
+    def tersoff_mod_compute(self, matid, replica, qp=QP_NONE):
+        return self._row_compute("scema_md_tersoff_mod_debug_compute", matid, replica, qp, "e_rep", "e_att", "nzeta")
+
+    def tersoff_zbl_configure(self, matid: str, path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style tersoff/zbl + pair_coeff * * <path> <elements>; energy_unit 0: A, B in eV, 1: kcal/mol as written, with the Coulomb
+        constant of `units real`.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_tersoff_zbl_configure", matid, path, elements, energy_unit, skin)
+
+    def tersoff_zbl_compute(self, matid, replica, qp=QP_NONE):
+        return self._row_compute("scema_md_tersoff_zbl_debug_compute", matid, replica, qp, "e_rep", "e_att", "nzeta")
+
     def eam_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style eam/alloy + pair_coeff * * <path> <elements> for the replicas of one material id (a DYNAMO setfl file); energy_unit 0:
         the file's F and r phi are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -579,6 +597,8 @@ bare_system = sw_system   # (the same bare replica under a neutral name: what a 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]
 TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
+TERSOFF_MOD_FIELDS = ["beta", "alpha", "h", "eta", "beta_ters", "lambda2", "B", "R", "D", "lambda1", "A", "n", "c1", "c2", "c3", "c4", "c5", "c0"]
+TERSOFF_ZBL_FIELDS = TERSOFF_FIELDS + ["Z_i", "Z_j", "ZBLcut", "ZBLexpscale"]
 
 
 def _read_triplet_params(symbol: str, nfields: int, path: str, elements, energy_unit: int):
@@ -606,6 +626,17 @@ def tersoff_read_params(path: str, elements, energy_unit: int = 0):
     """(distinct elements kept, type_map, values[n][n][n][14] in the order of TERSOFF_FIELDS, A and B in kcal/mol) of a LAMMPS *.tersoff
     file: scema_md_tersoff_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
     return _read_triplet_params("scema_md_tersoff_read_params", len(TERSOFF_FIELDS), path, elements, energy_unit)
+
+
+def tersoff_mod_read_params(path: str, elements, energy_unit: int = 0):
+    """as tersoff_read_params for a *.tersoff.mod or *.tersoff.modc file: values[n][n][n][18] in the order of TERSOFF_MOD_FIELDS (c0 = 0
+    for a 17-column file), A, B and c0 in kcal/mol: scema_md_tersoff_mod_read_params"""
+    return _read_triplet_params("scema_md_tersoff_mod_read_params", len(TERSOFF_MOD_FIELDS), path, elements, energy_unit)
+
+
+def tersoff_zbl_read_params(path: str, elements, energy_unit: int = 0):
+    """as tersoff_read_params for a *.tersoff.zbl file: values[n][n][n][18] in the order of TERSOFF_ZBL_FIELDS: scema_md_tersoff_zbl_read_params"""
+    return _read_triplet_params("scema_md_tersoff_zbl_read_params", len(TERSOFF_ZBL_FIELDS), path, elements, energy_unit)
 
 
 def eam_read_setfl(path: str, elements, energy_unit: int = 0):

@@ -185,9 +185,9 @@ struct RowSlot {
   DevBuf fp;   // embedded-atom stage: F'(rho) per atom (md_eam.h EamView)
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff, Eam };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl };
 
-// a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure).  A material
+// a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure, ...: row_pots).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
 struct RowMaterial {
   RowKind kind = RowKind::Sw;
@@ -195,7 +195,7 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) on the device
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -540,17 +540,18 @@ struct RowRun {
   int finish();
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
-// The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM: the order in which
-// a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts folder is searched
+// The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM, Tersoff/mod,
+// Tersoff/ZBL: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
+// folder is searched
 struct RowPot {
   RowKind kind;
   const char *name;             // in messages
   const char *configure_name;   // its configure entry point as messages name it, and (`configure`) the entry point
-  const char *ext;              // extension of the potential file a `pair_coeff * * ${locs}/<name><ext> <El> ...` line of in.strain.lammps names, or null
+  const char *ext[2];           // extensions of the potential file a `pair_coeff * * ${locs}/<name><ext> <El> ...` line of in.strain.lammps names (null: none, no further one)
   int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
   RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
-constexpr int ROW_NPOT = 3;
+constexpr int ROW_NPOT = 5;
 extern const RowPot row_pots[ROW_NPOT];
 // the entry of the potential attached to a material id, or null
 const RowPot *row_pot_of(scema_md_engine *e, const char *matid);

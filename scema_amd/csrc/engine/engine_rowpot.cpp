@@ -1,6 +1,6 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`): the stage they share, the table that tells them apart (row_pots), their three stages
-// and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`): the stage they
+// share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
 
@@ -55,7 +55,7 @@ static int ensure_eltype(scema_md_engine *e, Topo &T, const std::vector<int> &ty
   return SCEMA_MD_OK;
 }
 
-// ---- the stage the three potentials share: full neighbour rows inside the material's largest cutoff + skin in the slot's RowSlot, one
+// ---- the stage the potentials share: full neighbour rows inside the material's largest cutoff + skin in the slot's RowSlot, one
 // RowView per position (e->h_rowviews / d_rowviews; `tab` is the material's table on the device, of the stage's own type), the row
 // capacity and its growth, part batches on the main and the third stream, the "too many neighbours" fault ----
 
@@ -157,7 +157,7 @@ int RowPotStage::faults(int fault) {
   return SCEMA_MD_OK;
 }
 
-// ---- the three stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h) ----
+// ---- the stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h) ----
 
 namespace {
 
@@ -166,9 +166,11 @@ struct SwStage : RowPotStage {
   void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
+// (Tersoff and its forms tersoff/mod(/c) and tersoff/zbl: one stage, the form's launch wrapper)
+template <void (*Launch)(hipStream_t, const SimDev *, RowView *, int, int)>
 struct TsStage : RowPotStage {
   using RowPotStage::RowPotStage;
-  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_ts_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+  void forces(hipStream_t st, int pos0, int n, int, int) override { Launch(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
 // What the two passes of the embedded-atom stage hand from one to the other, F'(rho) per atom, lives in the slot too and reaches the
@@ -201,9 +203,13 @@ RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new
 
 // the order is the precedence of the refusals (run_phase, scema_md_strain_batch) and of self-configuration (rowpot_from_scripts)
 const RowPot row_pots[ROW_NPOT] = {
-    {RowKind::Sw, "Stillinger-Weber", "scema_md_sw_configure", nullptr, scema_md_sw_configure, make_stage<SwStage>},
-    {RowKind::Tersoff, "Tersoff", "scema_md_tersoff_configure", ".tersoff", scema_md_tersoff_configure, make_stage<TsStage>},
-    {RowKind::Eam, "EAM", "scema_md_eam_configure", ".eam.alloy", scema_md_eam_configure, make_stage<EamStage>},
+    {RowKind::Sw, "Stillinger-Weber", "scema_md_sw_configure", {nullptr, nullptr}, scema_md_sw_configure, make_stage<SwStage>},
+    {RowKind::Tersoff, "Tersoff", "scema_md_tersoff_configure", {".tersoff", nullptr}, scema_md_tersoff_configure, make_stage<TsStage<mdk_ts_forces>>},
+    {RowKind::Eam, "EAM", "scema_md_eam_configure", {".eam.alloy", nullptr}, scema_md_eam_configure, make_stage<EamStage>},
+    {RowKind::TersoffMod, "Tersoff/mod", "scema_md_tersoff_mod_configure", {".tersoff.mod", ".tersoff.modc"}, scema_md_tersoff_mod_configure,
+     make_stage<TsStage<mdk_ts_mod_forces>>},
+    {RowKind::TersoffZbl, "Tersoff/ZBL", "scema_md_tersoff_zbl_configure", {".tersoff.zbl", nullptr}, scema_md_tersoff_zbl_configure,
+     make_stage<TsStage<mdk_ts_zbl_forces>>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -244,13 +250,14 @@ static int pair_coeff_from_scripts(scema_md_engine *e, const std::string &folder
 }
 
 int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
-  for (const RowPot &P : row_pots) {
-    if (!P.ext) continue;
-    const int rc = pair_coeff_from_scripts(e, folder, P.ext, [&](const char *path, const char *const *el, int32_t n) {
-      return P.configure(e, matid, path, el, n, 0, -1.0);
-    });
-    if (rc || row_pot_of(e, matid)) return rc;
-  }
+  for (const RowPot &P : row_pots)
+    for (const char *ext : P.ext) {
+      if (!ext) break;
+      const int rc = pair_coeff_from_scripts(e, folder, ext, [&](const char *path, const char *const *el, int32_t n) {
+        return P.configure(e, matid, path, el, n, 0, -1.0);
+      });
+      if (rc || row_pot_of(e, matid)) return rc;
+    }
   return SCEMA_MD_OK;
 }
 
@@ -360,6 +367,38 @@ int scema_md_tersoff_configure(scema_md_engine *e, const char *matid, const char
 int scema_md_tersoff_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
                                    double *virial, double *info) {
   return row_debug_compute(e, RowKind::Tersoff, qp_id, matid, replica, f, e_rep, e_att, virial, info);
+}
+
+int scema_md_tersoff_mod_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin) {
+  TsModTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_tersoff_mod_params(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::TersoffMod, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_tersoff_mod_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
+                                       double *virial, double *info) {
+  return row_debug_compute(e, RowKind::TersoffMod, qp_id, matid, replica, f, e_rep, e_att, virial, info);
+}
+
+int scema_md_tersoff_zbl_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin) {
+  TsZblTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_tersoff_zbl_params(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::TersoffZbl, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_tersoff_zbl_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
+                                       double *virial, double *info) {
+  return row_debug_compute(e, RowKind::TersoffZbl, qp_id, matid, replica, f, e_rep, e_att, virial, info);
 }
 
 int scema_md_eam_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,

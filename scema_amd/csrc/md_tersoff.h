@@ -13,3 +13,7 @@
 // terms and bond orders, forces into SimDev::f, virial (parts P_LJ: the repulsive term, P_ANGLE: everything that carries b_ij) and
 // energies into SimScalars
 void mdk_ts_forces(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms);
+// the same stage for `pair_style tersoff/mod` and `tersoff/mod/c` (`tab` points to a TsModTable) and for `tersoff/zbl` (a TsZblTable): the
+// kernel's instances for those forms
+void mdk_ts_mod_forces(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms);
+void mdk_ts_zbl_forces(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms);

@@ -2,13 +2,14 @@
 per evaluation at 1 fs.  The replica per potential:
   sw ....... the 192-atom silicon replica of the reference's example (tests/golden/lammps_17Nov16_init.sic_1.bin with tests/golden/Si.sw)
   tersoff .. 192 atoms of diamond silicon (3 x 2 x 4 cells of 5.432 A, thermal velocities at 300 K, tests/golden/SiC.tersoff)
+  tersoff_mod, tersoff_zbl .. the same 192 silicon atoms under tests/golden/Si.tersoff.mod (a = 5.429 A) and tests/golden/SiC.tersoff.zbl
   eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
              tests/golden/CuAg.eam.alloy)
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|tersoff|eam [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -51,13 +52,24 @@ def make_tersoff(e):
     e.tersoff_configure("si", os.path.join(GOLD, "SiC.tersoff"), ("Si",))
 
 
+def make_tersoff_mod(e):
+    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.429, 28.0855)
+    e.tersoff_mod_configure("si", os.path.join(GOLD, "Si.tersoff.mod"), ("Si",))
+
+
+def make_tersoff_zbl(e):
+    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.432, 28.0855)
+    e.tersoff_zbl_configure("si", os.path.join(GOLD, "SiC.tersoff.zbl"), ("Si",))
+
+
 def make_eam(e):
     register_lattice(e, "cu", FCC, (4, 4, 4), 3.615, 63.546)
     e.eam_configure("cu", os.path.join(GOLD, "CuAg.eam.alloy"), ("Cu",))
 
 
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
-POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam)}
+POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
+              "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl)}
 
 
 def main():
