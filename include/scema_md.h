@@ -484,6 +484,37 @@ int scema_md_eam_debug_compute(scema_md_engine *e, int32_t qp_id, const char *ma
 int scema_md_eam_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                             int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf, int32_t errcap);
 
+/* ---- Vashishta replicas (`pair_style vashishta`; SiC, SiO2, Al2O3, InP) ----
+ * configure = `pair_style vashishta` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1, at most 4
+ * distinct) for the replicas of ONE material id, registered before or after the call; list skin as for scema_md_sw_configure (skin < 0:
+ * 1.0).  energy_unit 0: H, D, W and B of the file are eV-based (units metal), the Coulomb constant K is 14.399645 eV A, and everything is
+ * converted to kcal/mol with 23.060549; 1: the numbers as written and K = 332.06371 (units real).  The form:
+ *   U(r) = H r^-eta + K Zi Zj exp(-r/lambda1)/r - D exp(-r/lambda4)/r^4 - W/r^6,  E2(r) = U(r) - U(rc) - (r - rc) U'(rc) for r < rc;
+ *   E3 = B dc^2/(1 + C dc^2) exp(gamma_ij/(r_ij - r0_ij) + gamma_ik/(r_ik - r0_ik)), dc = cos theta - costheta0, for r_ij < r0_ij, r_ik < r0_ik.
+ * Simulations of such a material take the Vashishta force stage whatever MDSim.force_field says: no SHAKE, no k-space, no bonded terms.
+ * The pair term takes any number of neighbours inside rc; at most 32 neighbours of an atom may lie inside r0, the three-body range: more
+ * is an error of the run, never a truncation.  An update or run that mixes them with simulations of other materials is refused with
+ * SCEMA_MD_ERR_ARG.  A material holds ONE attachment: configuring replaces whatever it held, of any kind.  A bare replica whose material
+ * has nothing attached configures itself at a scema_md_strain_batch from the line `pair_coeff * * ${locs}/<name>.vashishta <El> ...` of
+ * <scripts_folder>/in.strain.lammps (energy unit eV), searched after every other extension; a malformed line of that kind is
+ * SCEMA_MD_ERR_ARG.  Not built: vashishta/table. */
+int scema_md_vashishta_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                 int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], two-body and three-body energy (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz), info[4]: longest neighbour row
+ * the build asked for, row capacity, ordered pairs inside rc (each pair counts at both ends), pairs (a, b) of the lists inside r0 */
+int scema_md_vashishta_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
+                                     double *virial, double *info);
+/* The reader of LAMMPS *.vashishta files as a pure host function (no GPU, no engine).  `#` starts a comment; an entry is three element
+ * names and fourteen numbers (H eta Zi Zj lambda1 D lambda4 W rc B gamma r0 C costheta0) on one line or several; the entries whose three
+ * elements are all named are kept.  n_kept, type_map as for scema_md_sw_read_params; values[n_kept][n_kept][n_kept][14] (room for
+ * 4*4*4*14): the numbers of entry i j k, H, D, W and B in kcal/mol.  H eta Zi Zj lambda1 D lambda4 W rc and the arm's gamma, r0 of a pair
+ * (i, j) are those of entry i j j; B, C, costheta0 of a triplet those of entry i j k, as in pair_vashishta.cpp.  A lambda of 0 means
+ * exp(...) = 1.  A missing triplet, a non-numeric field, a short or duplicate entry; in an entry i j j: rc <= 0, eta <= 0 with H != 0, a
+ * negative lambda1, lambda4, gamma or r0, r0 > rc; a negative C in any entry; entries i j j and j i i whose rc or r0 differ (a pair has
+ * one cutoff at both ends): SCEMA_MD_ERR_IO with the reason in errbuf. */
+int scema_md_vashishta_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                   int32_t *type_map, double *values, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
     "scema_md_tersoff_mod_configure", "scema_md_tersoff_mod_debug_compute", "scema_md_tersoff_mod_read_params",
     "scema_md_tersoff_zbl_configure", "scema_md_tersoff_zbl_debug_compute", "scema_md_tersoff_zbl_read_params",
+    "scema_md_vashishta_configure", "scema_md_vashishta_debug_compute", "scema_md_vashishta_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -520,6 +521,17 @@ class Engine:
     def tersoff_zbl_compute(self, matid, replica, qp=QP_NONE):
         return self._row_compute("scema_md_tersoff_zbl_debug_compute", matid, replica, qp, "e_rep", "e_att", "nzeta")
 
+    def vashishta_configure(self, matid: str, path: str, elements=("Si", "C"), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style vashishta + pair_coeff * * <path> <elements> for the replicas of one material id; energy_unit 0: H, D, W and B are
+        eV-based with K = 14.399645 eV A, 1: kcal/mol as written with K = 332.06371.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_vashishta_configure", matid, path, elements, energy_unit, skin)
+
+    def vashishta_compute(self, matid, replica, qp=QP_NONE):
+        """npairs: ordered pairs inside rc; ntriplets: pairs (a, b) of the lists inside r0"""
+        return self._row_compute("scema_md_vashishta_debug_compute", matid, replica, qp, "e2", "e3", "ntriplets")
+
+    vashishta_debug_compute = vashishta_compute
+
     def eam_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style eam/alloy + pair_coeff * * <path> <elements> for the replicas of one material id (a DYNAMO setfl file); energy_unit 0:
         the file's F and r phi are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -599,6 +611,7 @@ SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", 
 TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
 TERSOFF_MOD_FIELDS = ["beta", "alpha", "h", "eta", "beta_ters", "lambda2", "B", "R", "D", "lambda1", "A", "n", "c1", "c2", "c3", "c4", "c5", "c0"]
 TERSOFF_ZBL_FIELDS = TERSOFF_FIELDS + ["Z_i", "Z_j", "ZBLcut", "ZBLexpscale"]
+VASHISHTA_FIELDS = ["H", "eta", "Zi", "Zj", "lambda1", "D", "lambda4", "W", "rc", "B", "gamma", "r0", "C", "costheta0"]
 
 
 def _read_triplet_params(symbol: str, nfields: int, path: str, elements, energy_unit: int):
@@ -637,6 +650,12 @@ def tersoff_mod_read_params(path: str, elements, energy_unit: int = 0):
 def tersoff_zbl_read_params(path: str, elements, energy_unit: int = 0):
     """as tersoff_read_params for a *.tersoff.zbl file: values[n][n][n][18] in the order of TERSOFF_ZBL_FIELDS: scema_md_tersoff_zbl_read_params"""
     return _read_triplet_params("scema_md_tersoff_zbl_read_params", len(TERSOFF_ZBL_FIELDS), path, elements, energy_unit)
+
+
+def vashishta_read_params(path: str, elements, energy_unit: int = 0):
+    """(distinct elements kept, type_map, values[n][n][n][14] in the order of VASHISHTA_FIELDS, H, D, W and B in kcal/mol) of a LAMMPS
+    *.vashishta file: scema_md_vashishta_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
+    return _read_triplet_params("scema_md_vashishta_read_params", len(VASHISHTA_FIELDS), path, elements, energy_unit)
 
 
 def eam_read_setfl(path: str, elements, energy_unit: int = 0):

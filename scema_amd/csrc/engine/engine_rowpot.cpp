@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -196,6 +196,18 @@ struct EamStage : RowPotStage {
   int faults(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
 };
 
+// Vashishta: the list of ROW_MAXIN entries holds the neighbours inside r0, the three-body range, alone; the pair term takes any number
+// inside rc (158 in SiC), so the refusal names r0
+struct VsStage : TsStage<mdk_vs_forces> {
+  using TsStage<mdk_vs_forces>::TsStage;
+  int faults(int fault) override {
+    if (fault & 128)
+      return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside r0, the three-body range of the %s potential (inside rc any number is taken)",
+                  ROW_MAXIN, what);
+    return SCEMA_MD_OK;
+  }
+};
+
 template <class Stage>
 RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
 
@@ -210,6 +222,7 @@ const RowPot row_pots[ROW_NPOT] = {
      make_stage<TsStage<mdk_ts_mod_forces>>},
     {RowKind::TersoffZbl, "Tersoff/ZBL", "scema_md_tersoff_zbl_configure", {".tersoff.zbl", nullptr}, scema_md_tersoff_zbl_configure,
      make_stage<TsStage<mdk_ts_zbl_forces>>},
+    {RowKind::Vashishta, "Vashishta", "scema_md_vashishta_configure", {".vashishta", nullptr}, scema_md_vashishta_configure, make_stage<VsStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -399,6 +412,22 @@ int scema_md_tersoff_zbl_configure(scema_md_engine *e, const char *matid, const 
 int scema_md_tersoff_zbl_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_rep, double *e_att,
                                        double *virial, double *info) {
   return row_debug_compute(e, RowKind::TersoffZbl, qp_id, matid, replica, f, e_rep, e_att, virial, info);
+}
+
+int scema_md_vashishta_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                 int32_t energy_unit, double skin) {
+  VsTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_vashishta_params(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::Vashishta, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_vashishta_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
+                                     double *virial, double *info) {
+  return row_debug_compute(e, RowKind::Vashishta, qp_id, matid, replica, f, e2, e3, virial, info);
 }
 
 int scema_md_eam_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,

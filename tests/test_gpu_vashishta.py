@@ -1,0 +1,486 @@
+"""The Vashishta force stage on the GPU (md_vashishta.hip, engine_rowpot.cpp) against the independent FP64 numpy restatement
+tests/vashishta_numpy.py, which tests/test_vashishta_host.py pins on the CPU (no LAMMPS exists to compare with): static parity on the
+smallest shapes at which the kernel takes another path, dynamics, the virial -> pressure conversion, elastic constants, whole
+evaluations, batches over two materials, refusals, replaced attachments, self-configuration from the scripts folder.
+
+Budgets, the standing ones: static parity 1e-10 of the largest force component, 1e-9 of the largest energy term and virial component
+(FP64 sums of a few hundred terms in another order); NVE after 20 steps 1e-9 A and 1e-11 A/fs; whole evaluations and a batch against each
+simulation alone 1e-9 relative (the triplet forces go through atomics).  The perfect 8-atom cell sits at the potential's own minimum
+(forces of 1e-14, a virial that is 1e-4 of its terms), so its forces and virial are measured on the scale of its jittered twin.
+
+What the groups catch.  The 8-atom cell and every lattice: a list cut at 32 (158 neighbours inside rc), a wrong image shift two images
+deep.  The clusters: the ballot rank across a trip of 16 and the limit of 32 inside r0, counted apart from the 32 * 33 pairs inside rc.
+Atom counts: a short last tile, the force table past the LDS limit.  Element orders: a swapped [i][j][k] index.  The synthetic file:
+arm numbers from the wrong entry, pow for a non-integer eta, lambda = 0, C = 0.  Dynamics and pressure: the sign and the 1/2 of the
+virial at each end.  Whole evaluations: rows kept or rebuilt under the wrong material, part streams.
+"""
+import math
+import os
+import shutil
+
+import numpy as np
+import pytest
+
+import sw_numpy as swn
+import vashishta_numpy as vn
+from scema_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIC = os.path.join(ROOT, "tests", "golden", "SiC.vashishta")
+SIC_TERSOFF = os.path.join(ROOT, "tests", "golden", "SiC.tersoff")
+SI_SW = os.path.join(ROOT, "tests", "golden", "Si.sw")
+EL = ("Si", "C")
+MASS2 = (vn.SI_MASS, vn.C_MASS)
+SYNTH_EL, SYNTH_MASS = ("X", "Y"), (28.0, 20.0)
+
+
+@pytest.fixture(scope="module")
+def ref_sic():
+    p, _, K = vn.read_vashishta(SIC, list(EL))
+    return vn.Vashishta(p, K)
+
+
+@pytest.fixture(scope="module")
+def synth(tmp_path_factory):
+    """(file, numpy object) of the synthetic two-element potential"""
+    path = tmp_path_factory.mktemp("vashishta") / "synth.vashishta"
+    path.write_text(vn.SYNTH)
+    p, _, K = vn.read_vashishta(str(path), list(SYNTH_EL))
+    return str(path), vn.Vashishta(p, K)
+
+
+def _engine(**kw):
+    return capi.Engine(capi.default_params(**kw))
+
+
+def _static(x, box, t, path=SIC, elements=EL, masses=MASS2):
+    e = _engine()
+    try:
+        e.vashishta_configure("m", path, elements)
+        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
+        return e.vashishta_compute("m", 1)
+    finally:
+        e.close()
+
+
+def _check_static(got, ref, what, scale=None):
+    scale = scale or ref
+    assert (got["npairs"], got["ntriplets"]) == (ref["npairs"], ref["ntriplets"]), (got["npairs"], ref["npairs"], got["ntriplets"], ref["ntriplets"])
+    assert got["maxrow"] <= got["rowcap"]
+    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e2"]) and math.isfinite(got["e3"])
+    if ref["npairs"] == 0:      # no pair, so no term at all: everything is exactly zero, and there is no scale to divide by
+        assert ref["e"] == 0.0 and not ref["f"].any() and not ref["w"].any()
+        assert got["e2"] == 0.0 and got["e3"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
+        print(f"{what}: no pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
+        return
+    fs, ws = np.abs(scale["f"]).max(), np.abs(scale["w"]).max()
+    es = max(abs(scale["e2"]), abs(scale["e3"]))
+    df = np.abs(got["f"] - ref["f"]).max()
+    de = max(abs(got["e2"] - ref["e2"]), abs(got["e3"] - ref["e3"]))
+    dw = np.abs(got["w"] - ref["w"]).max()
+    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']}, "
+          f"triplets {got['ntriplets']}, rows {got['maxrow']}/{got['rowcap']}")
+    assert df <= 1e-10 * fs and de <= 1e-9 * es and dw <= 1e-9 * ws
+
+
+PAIRS = {"SiSi": (0, 0), "CC": (1, 1), "SiC": (0, 1)}
+
+
+@pytest.mark.parametrize("pair", sorted(PAIRS))
+def test_dimers(ref_sic, pair):
+    """each pair inside r0, between r0 and rc, next to rc (0.05 A inside: tests/test_vashishta_host.py says why not closer), and exactly at rc
+    and beyond, where the result is exactly zero and the pair is not counted"""
+    a, b = PAIRS[pair]
+    for r in (2.0, 4.0, vn.RC_SIC - 0.05, vn.RC_SIC, vn.RC_SIC + 1e-9):
+        x, box, t = vn.case_dimer(a, b, r)
+        assert x[1, 0] - x[0, 0] == r
+        got, ref = _static(x, box, t), ref_sic.compute(x, box, t)
+        assert ref["npairs"] == (2 if r < vn.RC_SIC else 0) and ref["ntriplets"] == 0
+        _check_static(got, ref, f"vashishta dimer {pair} at {r}")
+
+
+def test_trimer_next_to_r0(ref_sic):
+    """C - Si - C with one arm at r0 - 1e-6: exp(-1e6) = 0 times a derivative of -1e12 stays finite; and with that arm well inside"""
+    for r1 in (vn.R0_SIC - 1e-6, vn.R0_SIC, 2.1):
+        x, box, t = vn.case_trimer(r1=r1)
+        ref = ref_sic.compute(x, box, t)
+        assert ref["ntriplets"] == (1 if r1 < vn.R0_SIC else 0) and ref["npairs"] == 6
+        _check_static(_static(x, box, t), ref, f"vashishta trimer, arm at {r1}")
+
+
+def test_the_eight_atom_cell(ref_sic):
+    """two images deep at 4.3581 A, 158 neighbours inside rc and 4 inside r0: the case no other kernel of the row driver takes.  Pinned
+    (most inside r0, ordered pairs inside rc, triplets) = (4, 8 x 158, 8 x 6); a cell of 4.0 A is refused by the driver's two-image rule"""
+    x, box, t = vn.case_cell8()
+    ref = ref_sic.compute(x, box, t)
+    xj, _, _ = vn.case_cell8_jittered()
+    refj = ref_sic.compute(xj, box, t)
+    for r in (ref, refj):
+        assert (r["maxin"], r["npairs"], r["ntriplets"], r["maxrc"]) == (4, 8 * 158, 8 * 6, 158)
+    assert box[3] == 4.3581 and box[3] < vn.RC_SIC + 1.0
+    got = _static(x, box, t)
+    assert got["maxrow"] > 32
+    _check_static(got, ref, "vashishta 8-atom cell", scale=refj)
+    _check_static(_static(xj, box, t), refj, "vashishta 8-atom cell, jittered")
+    x4, box4, _ = vn.case_cell8(4.0)
+    with pytest.raises(capi.EngineError, match="box width"):
+        _static(x4, box4, t)
+
+
+@pytest.mark.parametrize("m", [15, 16, 17, 31, 32])
+def test_short_list_lengths(ref_sic, m):
+    """a silicon atom inside m carbon atoms on a sphere of 2.5 A: the centre's list inside r0 holds m entries (one trip of 16, one more, two
+    trips to the last slot), the carbon atoms' lists one; all m + 1 atoms lie inside rc of each other"""
+    x, box, t = vn.case_cluster(m)
+    ref = ref_sic.compute(x, box, t)
+    assert (ref["maxin"], ref["npairs"], ref["ntriplets"]) == (m, m * (m + 1), m * (m - 1) // 2 + 0)
+    _check_static(_static(x, box, t), ref, f"vashishta cluster of {m}")
+
+
+def test_more_than_32_inside_r0_is_an_error(ref_sic):
+    x, box, t = vn.case_cluster(33)
+    ref = ref_sic.compute(x, box, t)
+    assert ref["maxin"] == 33 and ref["npairs"] == 33 * 34
+    with pytest.raises(capi.EngineError, match="more than 32 neighbours inside r0"):
+        _static(x, box, t)
+
+
+@pytest.mark.parametrize("name", ["cluster32", "jitter64"])
+def test_rows_regrown_after_an_overflow(ref_sic, monkeypatch, name):
+    """the row capacity forced low through the overflow hook: fault bit 1, the retry recovers the same forces (the cluster in its empty box
+    starts below its 32 entries in any case; the lattice, with 238 entries a row, only under the hook)"""
+    x, box, t = vn.case_cluster(32) if name == "cluster32" else vn.case_jitter(2, 1)
+    ref = ref_sic.compute(x, box, t)
+    normal = _static(x, box, t)
+    monkeypatch.setenv("SCEMA_MD_NEIGH_GROW0", "0.05")
+    got = _static(x, box, t)
+    _check_static(got, ref, f"vashishta {name} after a row overflow")
+    assert got["rowcap"] >= got["maxrow"] and np.abs(got["f"] - normal["f"]).max() <= 1e-10 * np.abs(ref["f"]).max()
+    if name == "jitter64":
+        assert got["rowcap"] < normal["rowcap"]          # it started low and grew to what the rows asked for, not to the default
+
+
+@pytest.mark.parametrize("n", [63, 65, 1000, 1440])
+def test_atom_count_edges(ref_sic, n):
+    """a partial only tile, a second tile of one atom, and 1 000 / 1 440 atoms on either side of the LDS force table (1 024): both instances"""
+    x, box, t = vn.case_count(n)
+    assert len(x) == n
+    _check_static(_static(x, box, t), ref_sic.compute(x, box, t), f"vashishta n = {n}")
+
+
+def test_triclinic_box_with_atoms_outside(ref_sic):
+    x, box, t = vn.case_triclinic()
+    H = vn.h_matrix(box)
+    s = (x - box[:3]) @ np.linalg.inv(H)
+    assert ((s < 0.0) | (s >= 1.0)).any(axis=1).sum() > 10 and box[6] != 0.0 and box[7] != 0.0 and box[8] != 0.0
+    _check_static(_static(x, box, t), ref_sic.compute(x, box, t), "vashishta triclinic")
+
+
+def _velocities(t, masses, temp, seed):
+    rng = np.random.default_rng(seed)
+    m = np.asarray(masses, float)[np.asarray(t)][:, None]
+    v = rng.normal(size=(len(t), 3)) * np.sqrt(vn.BOLTZ * temp / m / vn.MVV2E)
+    return v - (m * v).sum(axis=0) / m.sum()
+
+
+def test_static_parity_of_a_flipped_state(ref_sic):
+    """a 5 x 2 x 2 cell written with xy = 2 a = 0.4 lx (a lattice translation: the same crystal), sheared by 0.12 lx so that it passes
+    lx / 2 and flips; the forces on the state it leaves, in the box it leaves, against numpy"""
+    x, box, t = vn.zincblende(5, 2, 2)
+    box[6] = 2.0 * vn.A_SIC
+    lx, ly, lz = box[3:6] - box[:3]
+    e = _engine()
+    try:
+        e.vashishta_configure("sic", SIC, EL)
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS2, 300.0, 31), masses=MASS2))
+        s = np.array([0.0, 0.0, 0.0, 0.12 * lx * lz / ly, 0.0, 0.0])
+        e.strain_batch([capi.make_sim(0, "sic", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)])
+        flips = e.profile()["box_flips"]
+        b, xs, _ = e.get_state(0, "sic", 1)
+        print(f"vashishta flipped state: {flips} flip(s), xy {box[6]:.3f} -> {b[6]:.3f} A of lx {b[3] - b[0]:.3f} A")
+        assert flips >= 1 and abs(b[6]) <= 0.5 * (b[3] - b[0]) and b[6] < 0.0
+        _check_static(e.vashishta_compute("sic", 1, qp=0), ref_sic.compute(xs, b, t), "vashishta flipped state")
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("order", ["Si C", "C Si", "Si C Si"])
+def test_element_orders_and_a_many_to_one_type_map(ref_sic, order):
+    """the jittered 64-atom cell under both element orders of pair_coeff (the types swapped with them: the same crystal), and with three
+    LAMMPS types of which the first and the third are silicon"""
+    x, box, t = vn.case_jitter(2, 1)
+    ref = ref_sic.compute(x, box, t)
+    if order == "Si C":
+        types, masses = t, MASS2
+    elif order == "C Si":
+        types, masses = 1 - t, MASS2[::-1]
+    else:
+        types, masses = np.where((t == 0) & (np.arange(len(t)) % 3 == 0), 2, t), (vn.SI_MASS, vn.C_MASS, vn.SI_MASS)
+        assert set(types) == {0, 1, 2}
+    _check_static(_static(x, box, types, elements=tuple(order.split()), masses=masses), ref, f"vashishta elements {order}")
+
+
+def test_synthetic_file(synth):
+    """every triplet live, r0 and gamma of their own per pair, eta = 7.5, one lambda1 = 0, C = 0 in one entry"""
+    path, ref_vs = synth
+    x, box, t = vn.case_synth()
+    ref = ref_vs.compute(x, box, t)
+    assert len(set(t)) == 2 and ref["ntriplets"] >= 64 * 6 and ref["e3"] > 0.0
+    _check_static(_static(x, box, t, path=path, elements=SYNTH_EL, masses=SYNTH_MASS), ref, "vashishta synthetic file")
+
+
+def test_nve_dynamics_and_sampled_pressure(ref_sic):
+    x, box, t = vn.case_jitter(2, 1)
+    v = _velocities(t, MASS2, 300.0, 1)
+    e = _engine()
+    try:
+        e.vashishta_configure("sic", SIC, EL)
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=v, masses=MASS2))
+        # 20 steps NVE against the numpy velocity-Verlet stepper
+        e.set_state(0, "sic", 1, box, x, v)
+        e.debug_run("sic", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
+        _, xg, vg = e.get_state(0, "sic", 1)
+        xr, vr = ref_sic.nve(x, v, box, t, MASS2, 1.0, 20)
+        dx = np.abs(vn.minimage_diff(xg, xr, box)).max()
+        print(f"vashishta nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
+        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
+        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
+        e.set_state(1, "sic", 1, box, x, v)
+        p = e.debug_run("sic", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
+        x1, v1 = ref_sic.nve(x, v, box, t, MASS2, 1.0, 1)
+        want = ref_sic.pressure_atm(x1, v1, box, t, MASS2)
+        print(f"vashishta sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
+        assert np.abs(p - want).max() <= 1e-9 * np.abs(want).max()
+    finally:
+        e.close()
+
+
+def _shear(h):
+    e = np.zeros((3, 3))
+    e[1, 2] = h
+    return e
+
+
+@pytest.fixture(scope="module")
+def static_constants(ref_sic):
+    """C11, C12 and C44 (unrelaxed: homogeneous strain of every atom) of zincblende SiC in GPa from second differences of the numpy energy
+    under +-1e-3 strain of the perfect 2 x 2 x 2 cell"""
+    x, box, t = vn.zincblende(2, 2, 2)
+    h, v = 1e-3, vn.volume(box)
+    E = lambda eps: ref_sic.energy(*vn.strained(x, box, eps), t)
+    E0 = E(np.zeros((3, 3)))
+    c11 = (E(np.diag([h, 0.0, 0.0])) - 2.0 * E0 + E(np.diag([-h, 0.0, 0.0]))) / h ** 2 / v
+    c12 = (E(np.diag([h, h, 0.0])) - E(np.diag([h, -h, 0.0])) - E(np.diag([-h, h, 0.0])) + E(np.diag([-h, -h, 0.0]))) / (4.0 * h ** 2) / v
+    c44 = (E(_shear(h)) - 2.0 * E0 + E(_shear(-h))) / h ** 2 / v
+    return np.array([c11, c12, c44]) * vn.KCALMOL_A3_TO_GPA
+
+
+def test_elastic_constants(static_constants):
+    """C11, C12 and C44 from the GPU virials at +-1e-3 strain, through set_state, against second differences of the numpy energy within
+    0.1 % (both are finite differences with a relative truncation of order h^2 C''' / C ~ 1e-5).  No literature value is asserted."""
+    x, box, t = vn.zincblende(2, 2, 2)
+    e = _engine()
+    try:
+        e.vashishta_configure("sic", SIC, EL)
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, masses=MASS2))
+        h = 1e-3
+
+        def stress(eps):
+            xs, bs = vn.strained(x, box, eps)
+            e.set_state(5, "sic", 1, bs, xs, np.zeros_like(xs))
+            return -e.vashishta_compute("sic", 1, qp=5)["w"] / vn.volume(bs) * vn.KCALMOL_A3_TO_GPA
+
+        sp, sm = stress(np.diag([h, 0.0, 0.0])), stress(np.diag([-h, 0.0, 0.0]))
+        c11, c12 = (sp[0] - sm[0]) / (2 * h), (sp[1] - sm[1]) / (2 * h)
+        c44 = (stress(_shear(h))[5] - stress(_shear(-h))[5]) / (2 * h)
+        got = np.array([c11, c12, c44])
+        print(f"vashishta elastic constants on the device: C11 {c11:.3f}, C12 {c12:.3f}, C44 (unrelaxed) {c44:.3f} GPa; numpy energy: {static_constants}")
+        assert (np.abs(got / static_constants - 1.0) < 1e-3).all()
+    finally:
+        e.close()
+
+
+def _nts_and_rates(strain, box, dt, rate):
+    lb = box[3:6] - box[:3]
+    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
+    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
+    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
+    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
+
+
+def test_strain_batch_equals_the_two_runs():
+    """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
+    x, box, t = vn.case_jitter(2, 1)
+    v = _velocities(t, MASS2, 300.0, 2)
+    L = box[3:6] - box[:3]
+    s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
+    e, f = _engine(), _engine()
+    try:
+        for g in (e, f):
+            g.vashishta_configure("sic", SIC, EL)
+            g.register_replica("sic", 1, capi.bare_system(t, x, box, v=v, masses=MASS2))
+        out = np.array(e.strain_batch([capi.make_sim(0, "sic", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
+        f.set_state(0, "sic", 1, box, x, v)
+        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
+        f.debug_run("sic", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
+        want = -f.debug_run("sic", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
+        print(f"vashishta strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
+        assert nts == 30 and np.abs(out - want).max() <= 1e-9 * np.abs(want).max()
+        assert e.has_state(0, "sic", 1)
+    finally:
+        e.close()
+        f.close()
+
+
+@pytest.fixture(scope="module")
+def eleven(synth):
+    """11 simulations over the fixture material and the synthetic one, and each one's stress alone in a fresh engine"""
+    mats = {"sic": (vn.case_jitter(2, 1), SIC, EL, MASS2), "xy": (vn.case_synth(), synth[0], SYNTH_EL, SYNTH_MASS)}
+    vel = {m: _velocities(c[0][2], c[3], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
+    rng = np.random.default_rng(21)
+    sims = []
+    for q in range(11):
+        m = "sic" if q % 3 else "xy"
+        box = mats[m][0][1]
+        L = box[3:6] - box[:3]
+        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
+        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
+
+    def fresh():
+        e = _engine()
+        for m, ((x, box, t), path, el, masses) in mats.items():
+            e.vashishta_configure(m, path, el)
+            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
+        return e
+
+    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
+    alone = []
+    for q, m, s in sims:
+        e = fresh()
+        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
+        e.close()
+    return fresh, [mk(*s) for s in sims], np.array(alone)
+
+
+@pytest.mark.parametrize("split", [0, 1])
+def test_batch_of_eleven_equals_each_alone(eleven, split):
+    fresh, sims, alone = eleven
+    e = fresh()
+    try:
+        e.batch_split(split)
+        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
+        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
+        print(f"vashishta batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
+        assert err.max() <= 1e-9
+    finally:
+        e.close()
+
+
+def _dimer_update(scripts, configure):
+    """one update of a two-atom replica (Si, C): no triplet, and each atom sums its own pair force, so two runs of the same configuration
+    agree bit for bit"""
+    box = np.array([0.0, 0.0, 0.0, 12.0, 12.0, 12.0, 0.0, 0.0, 0.0])
+    x = np.array([[5.0, 6.0, 6.0], [6.9, 6.1, 5.9]])
+    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
+    e = _engine()
+    try:
+        if configure:
+            e.vashishta_configure("sic", SIC, EL)
+        e.register_replica("sic", 1, capi.bare_system(np.array([0, 1]), x, box, v=v, masses=MASS2))
+        s = np.array([1.2e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
+        sim = capi.make_sim(0, "sic", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
+                            scripts_folder=str(scripts))
+        out = np.array(e.strain_batch([sim])[0].stress[:])
+        return out, e.get_state(0, "sic", 1)
+    finally:
+        e.close()
+
+
+def test_self_configuration_from_the_scripts_folder(ref_sic, tmp_path):
+    """`pair_coeff * * ${locs}/SiC.vashishta Si C` in in.strain.lammps configures a bare replica whose material has nothing attached, bit
+    for bit as the configured run; a malformed line of that kind is SCEMA_MD_ERR_ARG"""
+    scripts = tmp_path / "lammps_scripts_vashishta"
+    scripts.mkdir()
+    shutil.copy(SIC, scripts / "SiC.vashishta")
+    (scripts / "in.strain.lammps").write_text("# straining run\npair_style vashishta\n#pair_coeff * * ${locs}/other.vashishta C\n"
+                                              "pair_coeff * * ${locs}/SiC.vashishta Si C   # the potential\nfix 1 all nvt temp 300 300 100\n")
+    a, sa = _dimer_update(scripts, configure=False)
+    b, sb = _dimer_update(scripts, configure=True)
+    assert np.isfinite(a).all() and np.abs(a).max() > 0.0
+    assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
+    # the update configured the material: static forces of the 64-atom cell against the numpy helper
+    x, box, t = vn.case_jitter(2, 1)
+    L = box[3:6] - box[:3]
+    mk = lambda folder: capi.make_sim(0, "sic", 1, np.array([1e-3 * L[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls",
+                                      scripts_folder=str(folder))
+    e = _engine()
+    try:
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS2, 300.0, 3), masses=MASS2))
+        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
+            e.vashishta_compute("sic", 1)
+        assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
+        _check_static(e.vashishta_compute("sic", 1), ref_sic.compute(x, box, t), "vashishta self-configured")
+    finally:
+        e.close()
+    for k, line in enumerate(["pair_coeff 1 1 ${locs}/SiC.vashishta Si C", "pair_coeff * * SiC.vashishta Si C", "pair_coeff * * ${locs}/SiC.vashishta",
+                              "pair_coeff * * ${locs}/sub/SiC.vashishta Si C"]):
+        badf = tmp_path / f"bad{k}"
+        badf.mkdir()
+        shutil.copy(SIC, badf / "SiC.vashishta")
+        (badf / "in.strain.lammps").write_text(line + "\n")
+        e = _engine()
+        try:
+            e.register_replica("sic", 1, capi.bare_system(t, x, box, masses=MASS2))
+            with pytest.raises(capi.EngineError, match=r"rc=1: .*in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.vashishta"):
+                e.strain_batch([mk(badf)])
+        finally:
+            e.close()
+
+
+def test_configuring_replaces_a_tersoff_attachment_and_back(ref_sic):
+    """a material holds one attachment: Vashishta configured over Tersoff replaces it (rows and element arrays are rebuilt: the forces are
+    those of a fresh engine), and the other way round"""
+    x, box, t = vn.case_jitter(2, 1)
+    ref = ref_sic.compute(x, box, t)
+    e = _engine()
+    try:
+        e.tersoff_configure("sic", SIC_TERSOFF, EL)
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, masses=MASS2))
+        ts0 = e.tersoff_compute("sic", 1)
+        e.vashishta_configure("sic", SIC, EL)
+        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
+            e.tersoff_compute("sic", 1)
+        _check_static(e.vashishta_compute("sic", 1), ref, "vashishta over a Tersoff attachment")
+        e.tersoff_configure("sic", SIC_TERSOFF, EL)
+        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
+            e.vashishta_compute("sic", 1)
+        ts1 = e.tersoff_compute("sic", 1)
+        assert ts1["npairs"] == ts0["npairs"] > 0 and np.abs(ts1["f"] - ts0["f"]).max() <= 1e-10 * np.abs(ts0["f"]).max()
+    finally:
+        e.close()
+
+
+def test_an_update_mixed_with_stillinger_weber_is_refused():
+    """Vashishta + Stillinger-Weber in one update: SCEMA_MD_ERR_ARG before anything is planned, naming the earlier kind of the table; no
+    state is left behind; each alone runs"""
+    x, box, t = vn.case_jitter(2, 1)
+    xs, boxs, ts = swn.case_a()
+    e = _engine()
+    try:
+        e.vashishta_configure("vs", SIC, EL)
+        e.sw_configure("sw", SI_SW)
+        e.register_replica("vs", 1, capi.bare_system(t, x, box, masses=MASS2))
+        e.register_replica("sw", 1, capi.bare_system(ts, xs, boxs))
+        mk = lambda q, m, b: capi.make_sim(q, m, 1, np.array([1e-3 * (b[3] - b[0]), 0.0, 0.0, 0.0, 0.0, 0.0]), nss=10, most_recent=capi.QP_NONE)
+        for sims in ([mk(0, "vs", box), mk(1, "sw", boxs)], [mk(1, "sw", boxs), mk(0, "vs", box)]):
+            with pytest.raises(capi.EngineError, match="rc=1: .*mixes Stillinger-Weber materials"):
+                e.strain_batch(sims)
+            assert not e.has_state(0, "vs", 1) and not e.has_state(1, "sw", 1)
+        assert e.strain_batch([mk(0, "vs", box)])[0].stress_updated == 1
+        assert e.strain_batch([mk(1, "sw", boxs)])[0].stress_updated == 1
+        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
+            e.vashishta_compute("sw", 1)
+    finally:
+        e.close()

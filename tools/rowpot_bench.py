@@ -5,16 +5,17 @@ per evaluation at 1 fs.  The replica per potential:
   tersoff_mod, tersoff_zbl .. the same 192 silicon atoms under tests/golden/Si.tersoff.mod (a = 5.429 A) and tests/golden/SiC.tersoff.zbl
   eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
              tests/golden/CuAg.eam.alloy)
+  vashishta  512 atoms of zincblende SiC (4 x 4 x 4 cells of 4.3581 A: the box of 17.43 A is at least twice rc + skin = 8.35 A, so the rows
+             are built by minimum image; masses 28.0855 and 12.011, thermal velocities at 300 K, tests/golden/SiC.vashishta)
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
 """
 import argparse
 import itertools
 import json
-import math
 import os
 import sys
 import time
@@ -29,17 +30,21 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 BOLTZ, MVV2E = 0.0019872067, 48.88821291 ** 2
 DIAMOND = [[0, 0, 0], [0, 2, 2], [2, 0, 2], [2, 2, 0], [1, 1, 1], [1, 3, 3], [3, 1, 3], [3, 3, 1]]
 FCC = DIAMOND[:4]
+ZINCBLENDE = FCC + [[1, 1, 1], [1, 3, 3], [3, 1, 3], [3, 3, 1]]          # (the diamond sites: the fcc ones, then those a quarter diagonal further)
 
 
-def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1):
-    """a cubic lattice of that basis (in quarters of the cell) with thermal velocities, as a bare replica"""
+def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1, basis_types=None):
+    """a cubic lattice of that basis (in quarters of the cell) with thermal velocities, as a bare replica; mass: one number, or with
+    basis_types (the LAMMPS type, from 0, of every basis site) one per type"""
     nx, ny, nz = cells
     grid = np.array(list(itertools.product(range(nx), range(ny), range(nz))), float)
     x = (grid[:, None, :] + np.array(basis, float)[None, :, :] * 0.25).reshape(-1, 3) * a
+    masses = (mass,) if basis_types is None else tuple(mass)
+    types = np.tile(np.zeros(len(basis), np.int32) if basis_types is None else np.array(basis_types, np.int32), len(grid))
     rng = np.random.default_rng(seed)
-    v = rng.normal(size=x.shape) * math.sqrt(BOLTZ * temp / mass / MVV2E)
+    v = rng.normal(size=x.shape) * np.sqrt(BOLTZ * temp / np.array(masses)[types] / MVV2E)[:, None]
     box = np.array([0.0, 0.0, 0.0, nx * a, ny * a, nz * a, 0.0, 0.0, 0.0])
-    e.register_replica(matid, 1, capi.bare_system(np.zeros(len(x), np.int32), x, box, v=v - v.mean(axis=0), masses=(mass,)))
+    e.register_replica(matid, 1, capi.bare_system(types, x, box, v=v - v.mean(axis=0), masses=masses))
 
 
 def make_sw(e):
@@ -67,9 +72,15 @@ def make_eam(e):
     e.eam_configure("cu", os.path.join(GOLD, "CuAg.eam.alloy"), ("Cu",))
 
 
+def make_vashishta(e):
+    register_lattice(e, "sic", ZINCBLENDE, (4, 4, 4), 4.3581, (28.0855, 12.011), basis_types=[0, 0, 0, 0, 1, 1, 1, 1])
+    e.vashishta_configure("sic", os.path.join(GOLD, "SiC.vashishta"), ("Si", "C"))
+
+
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
-              "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl)}
+              "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
+              "vashishta": ("vashishta_sic_512", "sic", make_vashishta)}
 
 
 def main():
