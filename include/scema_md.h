@@ -515,6 +515,32 @@ int scema_md_vashishta_debug_compute(scema_md_engine *e, int32_t qp_id, const ch
 int scema_md_vashishta_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                                    int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
+/* ---- Angular-dependent potential (`pair_style adp`; Mishin, Mehl and Papaconstantopoulos, Acta Mater. 53, 4029 (2005): Cu-Ta, Al-Cu,
+ * U-Mo, Fe-Ni, bcc metals) ----
+ * configure = `pair_style adp` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1, at most 4 distinct)
+ * for the replicas of ONE material id; list skin and energy_unit as for scema_md_eam_configure, u and w being converted with the square
+ * root of 23.060549 at energy_unit 0.  The form, with d = x_j - x_i over 0 < r^2 < cutoff^2:
+ *   rho_i = sum_j rho_{el(j)}(r),  mu_i[a] = sum_j u_{el(i)el(j)}(r) d[a],  lam_i[ab] = sum_j w_{el(i)el(j)}(r) d[a] d[b],  nu_i = tr lam_i
+ *   E = sum_i [F(rho_i) + 1/2 |mu_i|^2 + 1/2 sum_ab lam_i[ab]^2 - nu_i^2 / 6] + 1/2 sum_i sum_j phi(r)
+ * with F continued linearly above rhomax as for eam/alloy.  Any number of neighbours is taken.  Simulations of such a material take the
+ * ADP force stage whatever MDSim.force_field says.  An update or run that mixes them with simulations of other materials is refused with
+ * SCEMA_MD_ERR_ARG.  A material holds ONE attachment: configuring replaces whatever it held, of any kind.  A bare replica whose material
+ * has nothing attached configures itself at a scema_md_strain_batch from the line `pair_coeff * * ${locs}/<name>.adp <El> ...` of
+ * <scripts_folder>/in.strain.lammps (energy unit eV), searched after every other extension. */
+int scema_md_adp_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                           int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], pair energy (1/2 sum phi) and many-body energy (embedding plus the angular terms; kcal/mol), virial[6]
+ * (xx,yy,zz,xy,xz,yz), info[4]: longest neighbour row the build asked for, row capacity, ordered pairs inside the cutoff, atoms whose
+ * density lies above rhomax */
+int scema_md_adp_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_manybody,
+                               double *virial, double *info);
+/* The reader of extended setfl files (*.adp) as a pure host function: the arguments of scema_md_eam_read_setfl.  The file is a setfl file
+ * through its r phi tables; then follow, for every pair i >= j in file order, Nr values of u_ij(r), then in the same order Nr values of
+ * w_ij(r), as written (not multiplied by r).  In `tables` the records of u (kept pairs i >= j), then those of w, follow the r phi
+ * records; head[6] counts them.  The refusals of scema_md_eam_read_setfl, and a file that ends inside the u or the w tables. */
+int scema_md_adp_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                            int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

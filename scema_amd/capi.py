@@ -43,6 +43,7 @@ SYMBOLS = [
     "scema_md_tersoff_mod_configure", "scema_md_tersoff_mod_debug_compute", "scema_md_tersoff_mod_read_params",
     "scema_md_tersoff_zbl_configure", "scema_md_tersoff_zbl_debug_compute", "scema_md_tersoff_zbl_read_params",
     "scema_md_vashishta_configure", "scema_md_vashishta_debug_compute", "scema_md_vashishta_read_params",
+    "scema_md_adp_configure", "scema_md_adp_debug_compute", "scema_md_adp_read_setfl",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -540,6 +541,15 @@ class Engine:
     def eam_compute(self, matid, replica, qp=QP_NONE):
         return self._row_compute("scema_md_eam_debug_compute", matid, replica, qp, "e_pair", "e_embed", "nabove")
 
+    def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
+        and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_adp_configure", matid, path, elements, energy_unit, skin)
+
+    def adp_compute(self, matid, replica, qp=QP_NONE):
+        """e_pair: 1/2 sum phi; e_manybody: the embedding energy plus the angular terms; nabove: atoms above rhomax"""
+        return self._row_compute("scema_md_adp_debug_compute", matid, replica, qp, "e_pair", "e_manybody", "nabove")
+
     # ---- init_material's equilibration schedule (in.init.lammps; md_equil.hip) ----
     def minimize(self, matid, replica, qp, etol=1e-7, ftol=1e-11, maxiter=1000, maxeval=50000) -> dict:
         info = np.zeros(5)
@@ -662,19 +672,30 @@ def eam_read_setfl(path: str, elements, energy_unit: int = 0):
     """dict of a DYNAMO setfl file (scema_md_eam_read_setfl, a pure host function, no GPU): n (distinct elements kept), type_map, nrho,
     drho, nr, dr, cutoff, rhomax, masses[n], and the spline records F[i] (value [nrho][4] {s3 s4 s5 s6}, derivative [nrho][4] {s0 s1 s2
     0}), rho[i], z[(i, j)] (r phi, i >= j) as pairs of arrays, F and r phi in kcal/mol; raises IOError with the reader's message"""
+    return _read_setfl("scema_md_eam_read_setfl", False, path, elements, energy_unit)
+
+
+def adp_read_setfl(path: str, elements, energy_unit: int = 0):
+    """the dict of eam_read_setfl for an extended setfl file of pair_style adp (scema_md_adp_read_setfl), with u[(i, j)] and w[(i, j)],
+    i >= j, besides: the records of the dipole and quadrupole functions, in the square root of kcal/mol per A and per A^2"""
+    return _read_setfl("scema_md_adp_read_setfl", True, path, elements, energy_unit)
+
+
+def _read_setfl(symbol: str, adp: bool, path: str, elements, energy_unit: int):
     L = lib()
-    L.scema_md_eam_read_setfl.restype = C.c_int
+    read = getattr(L, symbol)
+    read.restype = C.c_int
     arr = (C.c_char_p * len(elements))(*[e.encode() for e in elements])
     nk = C.c_int32(0)
     tmap = np.zeros(len(elements), np.int32)
     head, masses = np.zeros(8), np.zeros(4)
     err = C.create_string_buffer(512)
     args = (path.encode(), arr, C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(head), _p(masses))
-    rc = L.scema_md_eam_read_setfl(*args, None, C.c_int64(0), err, C.c_int32(len(err)))
+    rc = read(*args, None, C.c_int64(0), err, C.c_int32(len(err)))
     if rc != 0:
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     tab = np.zeros(int(head[6]))
-    rc = L.scema_md_eam_read_setfl(*args, _p(tab), C.c_int64(len(tab)), err, C.c_int32(len(err)))
+    rc = read(*args, _p(tab), C.c_int64(len(tab)), err, C.c_int32(len(err)))
     if rc != 0:
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     n, nrho, nr = nk.value, int(head[0]), int(head[2])
@@ -692,7 +713,12 @@ def eam_read_setfl(path: str, elements, energy_unit: int = 0):
     for i in range(n):
         for j in range(i + 1):
             z[(i, j)] = take(nr)
-    return dict(n=n, type_map=tmap, nrho=nrho, drho=head[1], nr=nr, dr=head[3], cutoff=head[4], rhomax=head[5], masses=masses[:n].copy(), F=F, rho=rho, z=z)
+    out = dict(n=n, type_map=tmap, nrho=nrho, drho=head[1], nr=nr, dr=head[3], cutoff=head[4], rhomax=head[5], masses=masses[:n].copy(), F=F, rho=rho, z=z)
+    if adp:
+        for key in ("u", "w"):
+            out[key] = {(i, j): take(nr) for i in range(n) for j in range(i + 1)}
+    assert pos == len(tab)
+    return out
 
 
 def kspace_setup(params, box, qsqsum: float, natoms: int):

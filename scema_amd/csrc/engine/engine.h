@@ -53,6 +53,7 @@
 #include "md_reax.h"
 #include "md_sw.h"
 #include "md_eam.h"
+#include "md_adp.h"
 #include "md_tersoff.h"
 #include "md_vashishta.h"
 #include "md_types.h"
@@ -185,9 +186,10 @@ struct RowSlot {
   size_t cap_rows = 0;
   DevBuf cnt, rows, misc;
   DevBuf fp;   // embedded-atom stage: F'(rho) per atom (md_eam.h EamView)
+  DevBuf adp;  // angular-dependent stage: the record {F', mu, lam} per atom (md_adp.h AdpView)
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp };
 
 // a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure, ...: row_pots).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
@@ -197,7 +199,7 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable on the device
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -406,6 +408,8 @@ struct scema_md_engine {
   std::vector<RowView> h_rowviews;
   DevBuf d_eamviews;              // embedded-atom stage: parallel to the views
   std::vector<EamView> h_eamviews;
+  DevBuf d_adpviews;              // angular-dependent stage: parallel to the views
+  std::vector<AdpView> h_adpviews;
   hipEvent_t row_part_done = nullptr;   // part batches of a row potential's run: the end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
@@ -543,7 +547,7 @@ struct RowRun {
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM, Tersoff/mod,
-// Tersoff/ZBL, Vashishta: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
+// Tersoff/ZBL, Vashishta, ADP: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
 // folder is searched
 struct RowPot {
   RowKind kind;
@@ -553,7 +557,7 @@ struct RowPot {
   int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
   RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
-constexpr int ROW_NPOT = 6;
+constexpr int ROW_NPOT = 7;
 extern const RowPot row_pots[ROW_NPOT];
 // the entry of the potential attached to a material id, or null
 const RowPot *row_pot_of(scema_md_engine *e, const char *matid);

@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -157,7 +157,7 @@ int RowPotStage::faults(int fault) {
   return SCEMA_MD_OK;
 }
 
-// ---- the stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h) ----
+// ---- the stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h; md_adp.h) ----
 
 namespace {
 
@@ -196,6 +196,28 @@ struct EamStage : RowPotStage {
   int faults(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
 };
 
+// The angular-dependent stage hands ten doubles per atom from its first pass to its second (md_adp.h AdpView): the slot's own array again
+struct AdpStage : RowPotStage {
+  AdpView *AA = nullptr;   // on the device (upload)
+  AdpStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowPotStage(e_, ns, pot) { e->h_adpviews.assign(ns, AdpView()); }
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
+    if (const int rc = RowPotStage::bind(pos, A, sl, S, need)) return rc;
+    HIPCHK(sl.row->adp.ensure((size_t)S.npad * ADP_REC * sizeof(double)));
+    e->h_adpviews[pos].rec = (decltype(AdpView::rec))sl.row->adp.as<double>();
+    return SCEMA_MD_OK;
+  }
+  int upload() override {
+    if (const int rc = RowPotStage::upload()) return rc;
+    const size_t bytes = e->h_adpviews.size() * sizeof(AdpView);
+    HIPCHK(e->d_adpviews.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(e->d_adpviews.p, e->h_adpviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    AA = e->d_adpviews.as<AdpView>();
+    return SCEMA_MD_OK;
+  }
+  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_adp_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
+  int faults(int) override { return SCEMA_MD_OK; }   // (as for EAM: no list of 32)
+};
+
 // Vashishta: the list of ROW_MAXIN entries holds the neighbours inside r0, the three-body range, alone; the pair term takes any number
 // inside rc (158 in SiC), so the refusal names r0
 struct VsStage : TsStage<mdk_vs_forces> {
@@ -223,6 +245,7 @@ const RowPot row_pots[ROW_NPOT] = {
     {RowKind::TersoffZbl, "Tersoff/ZBL", "scema_md_tersoff_zbl_configure", {".tersoff.zbl", nullptr}, scema_md_tersoff_zbl_configure,
      make_stage<TsStage<mdk_ts_zbl_forces>>},
     {RowKind::Vashishta, "Vashishta", "scema_md_vashishta_configure", {".vashishta", nullptr}, scema_md_vashishta_configure, make_stage<VsStage>},
+    {RowKind::Adp, "ADP", "scema_md_adp_configure", {".adp", nullptr}, scema_md_adp_configure, make_stage<AdpStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -444,6 +467,22 @@ int scema_md_eam_configure(scema_md_engine *e, const char *matid, const char *pa
 int scema_md_eam_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_embed,
                                double *virial, double *info) {
   return row_debug_compute(e, RowKind::Eam, qp_id, matid, replica, f, e_pair, e_embed, virial, info);
+}
+
+int scema_md_adp_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                           int32_t energy_unit, double skin) {
+  std::vector<double> block;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_adp_setfl(path, el, energy_unit, block, type_map, err)) return false;
+    blk = RowTableBlock{block.data(), block.size() * sizeof(double), scema::eam_head(block).cutoff};
+    return true;
+  };
+  return row_configure(e, RowKind::Adp, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_adp_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_manybody,
+                               double *virial, double *info) {
+  return row_debug_compute(e, RowKind::Adp, qp_id, matid, replica, f, e_pair, e_manybody, virial, info);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// eam_setfl.cpp -- reader of DYNAMO setfl files (host/eam_setfl.h) and its face in the C ABI
+// eam_setfl.cpp -- reader of DYNAMO setfl files, plain and with the u and w tables of `pair_style adp` (host/eam_setfl.h), and its faces
+// in the C ABI
 #include "eam_setfl.h"
 
 #include <algorithm>
@@ -10,8 +11,9 @@
 
 namespace scema {
 
-bool read_eam_setfl(const std::string &path, const std::vector<std::string> &elements, int energy_unit, std::vector<double> &block, std::vector<int> &type_map,
-                    std::string &err, std::vector<double> *masses) {
+// the one parse: adp says that Nr values of u and of w per pair follow the r phi tables (AdpHead at the start of the block, else EamHead)
+static bool read_setfl(const std::string &path, const std::vector<std::string> &elements, int energy_unit, bool adp, std::vector<double> &block,
+                       std::vector<int> &type_map, std::string &err, std::vector<double> *masses) {
   auto bad = [&](const std::string &m) { err = path + ": " + m; return false; };
   if (energy_unit != 0 && energy_unit != 1) return bad("energy unit " + std::to_string(energy_unit) + " (0: F and r phi in eV, 1: in kcal/mol)");
   if (elements.empty()) return bad("no elements named");
@@ -60,17 +62,24 @@ bool read_eam_setfl(const std::string &path, const std::vector<std::string> &ele
   if (!(drho > 0.0) || !(dr > 0.0) || !(cutoff > 0.0)) return bad("drho, dr and the cutoff must be positive");
   if (cutoff > (nr - 1) * dr) return bad("the cutoff " + std::to_string(cutoff) + " lies beyond the last knot (Nr - 1) dr = " + std::to_string((nr - 1) * dr));
   // what the counts announce against what the file holds, before anything is sized by them
-  const double words = (double)nfile * (4.0 + nrho + nr) + 0.5 * nfile * (nfile + 1.0) * nr;
+  const double npairs = 0.5 * nfile * (nfile + 1.0);
+  const double words_eam = (double)nfile * (4.0 + nrho + nr) + npairs * nr, words = words_eam + (adp ? 2.0 * npairs * nr : 0.0);
+  if (adp && words_eam <= (double)(tok.size() - t) && words > (double)(tok.size() - t))
+    return bad(std::string("truncated file: it ends inside the ") + (words_eam + npairs * nr > (double)(tok.size() - t) ? "u" : "w") + " tables of an ADP file (" +
+               std::to_string(nfile * (nfile + 1) / 2) + " pairs of Nr " + std::to_string(nr) + " values of u, then as many of w, after r phi): its counts announce " +
+               std::to_string((long long)words) + " numbers, it holds " + std::to_string(tok.size() - t));
   if (words > (double)(tok.size() - t))
     return bad("truncated file: its counts (" + std::to_string(nfile) + " elements, Nrho " + std::to_string(nrho) + ", Nr " + std::to_string(nr) + ") announce " +
                std::to_string((long long)words) + " numbers, it holds " + std::to_string(tok.size() - t));
   const double escale = energy_unit == 0 ? EAM_EV_TO_KCALMOL : 1.0;
   // the block: head, then per kept element F and rho, then per kept pair i >= j r phi; each function 8 n doubles
-  const size_t ndoubles = EAM_HEAD_DOUBLES + (size_t)ne * 8 * ((size_t)nrho + nr) + (size_t)ne * (ne + 1) / 2 * 8 * nr;
+  // (ADP: then per kept pair u, then per kept pair w)
+  const size_t ndoubles = EAM_HEAD_DOUBLES + (size_t)ne * 8 * ((size_t)nrho + nr) + (size_t)ne * (ne + 1) / 2 * 8 * nr * (adp ? 3 : 1);
   if (ndoubles > (size_t)0x7FFFFFFF) return bad("tables of more than 2^31 numbers: the block's offsets are 32-bit");
   block.assign(ndoubles, 0.0);
-  EamHead H;
-  std::memset(&H, 0, sizeof H);
+  AdpHead A;
+  std::memset(&A, 0, sizeof A);
+  EamHead &H = A.eam;
   H.nelem = ne; H.nrho = nrho; H.nr = nr;
   H.drho = drho; H.dr = dr; H.rdrho = 1.0 / drho; H.rdr = 1.0 / dr;
   H.cutoff = cutoff; H.cut2 = cutoff * cutoff; H.rhomax = (nrho - 1) * drho;
@@ -83,6 +92,10 @@ bool read_eam_setfl(const std::string &path, const std::vector<std::string> &ele
     for (int j = 0; j < ne; j++) H.off_rho[i * EAM_MAXEL + j] = off_src[j];
   for (int i = 0; i < ne; i++)
     for (int j = 0; j <= i; j++) H.off_z[i * EAM_MAXEL + j] = H.off_z[j * EAM_MAXEL + i] = place(nr);
+  if (adp)
+    for (int *o : {A.off_u, A.off_w})
+      for (int i = 0; i < ne; i++)
+        for (int j = 0; j <= i; j++) o[i * EAM_MAXEL + j] = o[j * EAM_MAXEL + i] = place(nr);
   std::vector<double> f((size_t)std::max(nrho, nr));
   auto table = [&](const char *what, int n, double delta, double scale, int where) {
     for (int k = 0; k < n; k++) {
@@ -111,15 +124,37 @@ bool read_eam_setfl(const std::string &path, const std::vector<std::string> &ele
       while (b < ne && src[b] != j) b++;
       if (!table("r phi(r)", nr, dr, escale, a < ne && b < ne ? H.off_z[a * EAM_MAXEL + b] : -1)) return false;
     }
-  std::memcpy(block.data(), &H, sizeof H);
+  if (adp) {
+    // u and w as written, not multiplied by r; mu^2 and lam^2 are energies: the square root of the unit's factor
+    const double ascale = std::sqrt(escale);
+    for (int pass = 0; pass < 2; pass++)
+      for (int i = 0; i < nfile; i++)
+        for (int j = 0; j <= i; j++) {
+          int a = 0, b = 0;
+          while (a < ne && src[a] != i) a++;
+          while (b < ne && src[b] != j) b++;
+          const int *o = pass ? A.off_w : A.off_u;
+          if (!table(pass ? "w(r)" : "u(r)", nr, dr, ascale, a < ne && b < ne ? o[a * EAM_MAXEL + b] : -1)) return false;
+        }
+  }
+  std::memcpy(block.data(), &A, adp ? sizeof A : sizeof H);
   return true;
+}
+
+bool read_eam_setfl(const std::string &path, const std::vector<std::string> &elements, int energy_unit, std::vector<double> &block, std::vector<int> &type_map,
+                    std::string &err, std::vector<double> *masses) {
+  return read_setfl(path, elements, energy_unit, false, block, type_map, err, masses);
+}
+
+bool read_adp_setfl(const std::string &path, const std::vector<std::string> &elements, int energy_unit, std::vector<double> &block, std::vector<int> &type_map,
+                    std::string &err, std::vector<double> *masses) {
+  return read_setfl(path, elements, energy_unit, true, block, type_map, err, masses);
 }
 
 }  // namespace scema
 
-extern "C" int scema_md_eam_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
-                                       int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf,
-                                       int32_t errcap) {
+static int read_setfl_c(bool adp, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept, int32_t *type_map,
+                        double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf, int32_t errcap) {
   auto say = [&](const std::string &m) {
     if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
   };
@@ -130,7 +165,7 @@ extern "C" int scema_md_eam_read_setfl(const char *path, const char *const *elem
   std::vector<double> block, mass;
   std::vector<int> map;
   std::string err;
-  if (!scema::read_eam_setfl(path, el, energy_unit, block, map, err, &mass)) { say(err); return SCEMA_MD_ERR_IO; }
+  if (!scema::read_setfl(path, el, energy_unit, adp, block, map, err, &mass)) { say(err); return SCEMA_MD_ERR_IO; }
   const EamHead &H = scema::eam_head(block);
   if (n_kept) *n_kept = H.nelem;
   if (type_map) for (int k = 0; k < n_elements; k++) type_map[k] = map[k];
@@ -144,4 +179,16 @@ extern "C" int scema_md_eam_read_setfl(const char *path, const char *const *elem
     std::memcpy(tables, block.data() + EAM_HEAD_DOUBLES, (size_t)(H.ndoubles - EAM_HEAD_DOUBLES) * sizeof(double));
   }
   return SCEMA_MD_OK;
+}
+
+extern "C" int scema_md_eam_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                       int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf,
+                                       int32_t errcap) {
+  return read_setfl_c(false, path, elements, n_elements, energy_unit, n_kept, type_map, head, masses, tables, tables_cap, errbuf, errcap);
+}
+
+extern "C" int scema_md_adp_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                       int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf,
+                                       int32_t errcap) {
+  return read_setfl_c(true, path, elements, n_elements, energy_unit, n_kept, type_map, head, masses, tables, tables_cap, errbuf, errcap);
 }

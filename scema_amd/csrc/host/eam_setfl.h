@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "../eam/adp_core.h"
 #include "../eam/eam_core.h"
 
 namespace scema {
@@ -25,5 +26,16 @@ bool read_eam_setfl(const std::string &path, const std::vector<std::string> &ele
                     std::string &err, std::vector<double> *masses = nullptr);
 
 inline const EamHead &eam_head(const std::vector<double> &block) { return *(const EamHead *)block.data(); }
+
+// The same for the extended setfl files of `pair_style adp` (`pair_coeff * * CuAg.adp Cu Ag`): after the r phi tables come, for every
+// pair i >= j in file order, Nr values of u_ij(r), then in the same order Nr values of w_ij(r), as written (not multiplied by r).  The
+// block starts with an AdpHead (eam/adp_core.h): its EAM part is laid out exactly as read_eam_setfl lays it out, the u records and then
+// the w records of the kept pairs follow the r phi records.  energy_unit 0 converts F and r phi with 23.060549 and u and w with its
+// square root (mu^2 and lam^2 are energies); 1: everything as written.  The refusals are those of read_eam_setfl; a file that ends
+// inside the u or the w tables (a plain eam/alloy file among them) is refused by its counts before anything is sized.
+bool read_adp_setfl(const std::string &path, const std::vector<std::string> &elements, int energy_unit, std::vector<double> &block, std::vector<int> &type_map,
+                    std::string &err, std::vector<double> *masses = nullptr);
+
+inline const AdpHead &adp_head(const std::vector<double> &block) { return *(const AdpHead *)block.data(); }
 
 }  // namespace scema

@@ -5,13 +5,14 @@ per evaluation at 1 fs.  The replica per potential:
   tersoff_mod, tersoff_zbl .. the same 192 silicon atoms under tests/golden/Si.tersoff.mod (a = 5.429 A) and tests/golden/SiC.tersoff.zbl
   eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
              tests/golden/CuAg.eam.alloy)
+  adp ...... the same 256 copper atoms under tests/golden/CuAg.adp (pair_style adp: the embedded-atom terms plus dipoles and quadrupoles)
   vashishta  512 atoms of zincblende SiC (4 x 4 x 4 cells of 4.3581 A: the box of 17.43 A is at least twice rc + skin = 8.35 A, so the rows
              are built by minimum image; masses 28.0855 and 12.011, thermal velocities at 300 K, tests/golden/SiC.vashishta)
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -72,6 +73,11 @@ def make_eam(e):
     e.eam_configure("cu", os.path.join(GOLD, "CuAg.eam.alloy"), ("Cu",))
 
 
+def make_adp(e):
+    register_lattice(e, "cu", FCC, (4, 4, 4), 3.615, 63.546)
+    e.adp_configure("cu", os.path.join(GOLD, "CuAg.adp"), ("Cu",))
+
+
 def make_vashishta(e):
     register_lattice(e, "sic", ZINCBLENDE, (4, 4, 4), 4.3581, (28.0855, 12.011), basis_types=[0, 0, 0, 0, 1, 1, 1, 1])
     e.vashishta_configure("sic", os.path.join(GOLD, "SiC.vashishta"), ("Si", "C"))
@@ -80,7 +86,7 @@ def make_vashishta(e):
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
-              "vashishta": ("vashishta_sic_512", "sic", make_vashishta)}
+              "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp)}
 
 
 def main():
