@@ -312,6 +312,10 @@ int scema_md_debug_run_nh(scema_md_engine *e, int32_t qp_id, const char *matid, 
  * init state): forces [natoms*3], energies[SCEMA_MD_NPART], virials[SCEMA_MD_NPART*6] (kcal/mol). */
 int scema_md_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, int32_t use_shake,
                            double *f, double *energies, double *virials, double *info /* [8]: g_ewald,nk,npairs,tdof,... */);
+/* Diagnostics of the skin bands of the pair rows: for the replica at position pos of the last run, as the next pair launch
+ * would walk its rows: out[0] = K (bands), then K skin entries listed per band, K walked per band, rows with skin entries, rows with a band
+ * open, rows with every band open.  cap >= 2 K + 4. */
+int scema_md_debug_skin_bands(scema_md_engine *e, int32_t pos, uint64_t *out, int32_t cap);
 /* One "run": nsteps of Verlet + SHAKE + NVT (+deform if rates) (+pressure average if press_avg). */
 int scema_md_debug_run(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, int32_t nsteps,
                        double dt, double temperature, int32_t nvt, int32_t use_shake, const double *rates,

@@ -31,7 +31,7 @@ SYMBOLS = [
     "scema_md_strain_batch", "scema_md_strain", "scema_md_local_stress_device_ptr",
     "scema_md_local_stress_count", "scema_md_local_result_doubles", "scema_md_copy_local_stress", "scema_md_scatter_gathered", "scema_md_settle_update", "scema_md_has_state", "scema_md_get_state",
     "scema_md_set_state", "scema_md_drop_state", "scema_md_save_state_file", "scema_md_load_state_file", "scema_md_save_state_lammps",
-    "scema_md_init_material", "scema_md_debug_compute", "scema_md_debug_run", "scema_md_get_profile", "scema_md_env_overrides",
+    "scema_md_init_material", "scema_md_debug_compute", "scema_md_debug_run", "scema_md_debug_skin_bands", "scema_md_get_profile", "scema_md_env_overrides",
     "scema_md_comm_unique_id", "scema_md_comm_init_rccl", "scema_md_comm_init_host", "scema_md_comm_destroy",
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
@@ -415,6 +415,15 @@ class Engine:
                                            C.c_double(dt), C.c_double(temperature), C.c_int32(1 if nvt else 0),
                                            C.c_int32(1 if use_shake else 0), _p(r), _p(pavg)))
         return pavg
+
+    def debug_skin_bands(self, pos=0):
+        """Skin bands of the pair rows of the replica at position `pos` of the last run, as its next pair launch would walk them:
+        dict(K, listed[K], walked[K], rows, rows_open, rows_all_open) (skin entries per band; rows with skin entries)."""
+        out = np.zeros(64, np.uint64)
+        self._chk(lib().scema_md_debug_skin_bands(self.h, C.c_int32(pos), out.ctypes.data_as(C.c_void_p), C.c_int32(out.size)))
+        k = int(out[0])
+        return dict(K=k, listed=[int(v) for v in out[1:1 + k]], walked=[int(v) for v in out[1 + k:1 + 2 * k]],
+                    rows=int(out[1 + 2 * k]), rows_open=int(out[2 + 2 * k]), rows_all_open=int(out[3 + 2 * k]))
 
     def init_material(self, matid, replica, dt=2.0, temperature=300.0, nss=100, strain_ampl=0.005, strain_rate=1e-4):
         """EQMDProblem::lammps_equilibration for an equilibrated replica (init_material_problem.h:196-300): returns

@@ -227,7 +227,7 @@ struct Slot {
   int cap_atoms = 0, cap_pad = 0, cap_neigh = 0, cap_cells = 0, cap_k = 0;
   size_t cap_jtab = 0;
   DevBuf virp, virb, fb, fs, slot_of, tile_nj, tile_jtab, tile_order, tile_wstart;
-    DevBuf f, xq, stype, perm, slot_tmp, wrapn, xhold, cell_of, ckey, cell_count, cell_start, cell_fill, numneigh, neigh, sfac, kvec,
+    DevBuf f, xq, stype, perm, slot_tmp, wrapn, xhold, cell_of, ckey, cell_count, cell_start, cell_fill, numneigh, dslot, neigh, sfac, kvec,
       xbak, vbak;
 };
 
@@ -485,6 +485,7 @@ int sum_timed_launches(scema_md_engine *e, size_t n, double &ms, long long &laun
 int collect_faults(scema_md_engine *e, int ns);
 void lists_hold(scema_md_engine *e, const std::vector<ActiveSim> &sims, bool valid, bool counts);
 bool keep_list_switch();
+bool skin_bands_switch();
 // the run overflowed: its retry runs with capacities grown by the demand the run saw, at least by x1.25 (j tables) / x1.5 (rows)
 void grow_after_overflow(scema_md_engine *e);
 // static evaluation of one state by a run of no steps (the parity hooks), repeated while capacities overflow; the results are in e->h_sc[0], slot 0

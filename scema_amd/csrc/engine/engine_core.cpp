@@ -49,6 +49,7 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_PARTS", "2-4: this many part batches for every launch group that is split, if it has 2 replicas per part (default: by the size of the group, engine_run.cpp)"},
     {"SCEMA_MD_ONE_STREAM", "no side stream (bonded / k-space chain beside the pair kernel)"},
     {"SCEMA_MD_KEEP_LIST", "0: the sampling run of an evaluation rebuilds its neighbour rows at its start even where those of the straining run still hold"},
+    {"SCEMA_MD_SKIN_BANDS", "0: the pair kernel walks every listed entry of a row on every step (default: the skin part of a row only as far as its cluster's and the replica's displacement bounds allow a pair inside the cutoff; results do not depend on it)"},
     {"SCEMA_MD_SKIN_EXTRA", "list skin = params.skin + this many Angstrom (results do not depend on it)"},
     {"SCEMA_MD_SKIN_ADAPT", "1: per-state adaptation of the extra skin from the rebuild interval (round-1 behaviour)"},
     {"SCEMA_MD_PPPM_SOLVE_WIDE", "1 / 0: the in-LDS PPPM solve with 1 024 threads and three LDS grids / 512 threads and two (default: by batch size)"},

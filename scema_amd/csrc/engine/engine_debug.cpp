@@ -4,6 +4,23 @@
 
 namespace scema_eng {
 
+// The skin bands of the replica at position pos of the last run, as its next pair launch would walk them (md_skin_bands.h): out[2 K + 3] =
+// skin entries listed per band, walked per band, rows with skin entries, rows with a band open, rows with every band open.  A launch and a
+// copy of its own: diagnostics, never part of a step.
+int skin_band_stats(const scema_md_engine *e, int pos, unsigned long long *out) {
+  const int n = 2 * MD_SKIN_BANDS + 3;
+  unsigned long long *d = nullptr;
+  if (hipMalloc(&d, n * sizeof *d) != hipSuccess) return SCEMA_MD_ERR_DEVICE;
+  hipError_t err = hipMemsetAsync(d, 0, n * sizeof *d, e->stream);
+  if (err == hipSuccess) {
+    mdk_band_stats(e->stream, e->d_sims.as<SimDev>() + pos, d);
+    err = hipMemcpyAsync(out, d, n * sizeof *d, hipMemcpyDeviceToHost, e->stream);
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  (void)hipFree(d);
+  return err == hipSuccess ? SCEMA_MD_OK : SCEMA_MD_ERR_DEVICE;
+}
+
 // SCEMA_MD_TIMING: the lists of the first replica of the run that just ended, the host time of its layout, and the counters of a build
 // with PAIR_COUNT / PAIR_TIMING
 void print_run_timing(const scema_md_engine *e, int ns, double layout_ms, double kspace_ms, double box_ms, double grid_ms, double rest_ms) {
@@ -15,7 +32,14 @@ void print_run_timing(const scema_md_engine *e, int ns, double layout_ms, double
           (double)c.nentries / S0.natoms, c.nbuilds);
   fprintf(stderr, "[scema_md] host: %.2f ms laying out %d simulations before the first launch of this run (k-space set-up on host threads %.2f, box range %.2f, cell grid %.2f, rest of the loop %.2f)\n",
           layout_ms, ns, kspace_ms, box_ms, grid_ms, rest_ms);
-  fprintf(stderr, "[scema_md] sim 0: far skin band walked on %d of %d steps; list skin %.2f A\n", c.nfar_steps, c.step, S0.skin);
+  if (S0.dslot) {
+    unsigned long long bs[2 * MD_SKIN_BANDS + 3];
+    if (skin_band_stats(e, 0, bs) == SCEMA_MD_OK) {
+      fprintf(stderr, "[scema_md] sim 0 after %d steps, list skin %.2f A: skin entries walked / listed per band:", c.step, S0.skin);
+      for (int b = 0; b < MD_SKIN_BANDS; b++) fprintf(stderr, " %llu / %llu", bs[MD_SKIN_BANDS + b], bs[b]);
+      fprintf(stderr, "; rows with skin entries %llu, with a band open %llu, with all open %llu\n", bs[2 * MD_SKIN_BANDS], bs[2 * MD_SKIN_BANDS + 1], bs[2 * MD_SKIN_BANDS + 2]);
+    }
+  }
 #ifdef PAIR_COUNT
   fprintf(stderr, "[scema_md] k_pair lanes (sim 0, this run): %llu wave-chunks (%llu with work); atom blocks run %llu = %.2f per working chunk, %.1f lanes of 64 in them; "
           "LJ block run in %llu of them with %.1f lanes; coulomb block in %llu with %.1f lanes; pairs inside the LJ cutoff %llu, inside the coulomb cutoff %llu\n",
@@ -99,6 +123,17 @@ int scema_md_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid,
     info[6] = e->h_sims[0].maxneigh;
     info[7] = s->topo->nclus;
   }
+  return SCEMA_MD_OK;
+}
+
+int scema_md_debug_skin_bands(scema_md_engine *e, int32_t pos, uint64_t *out, int32_t cap) {
+  if (!e || !out || pos < 0 || pos >= (int)e->h_sims.size() || cap < 2 * MD_SKIN_BANDS + 4) return SCEMA_MD_ERR_ARG;
+  if (!e->h_sims[pos].dslot) return fail(e, SCEMA_MD_ERR_ARG, "the last run kept no cluster rows with skin bands");
+  HIPCHK(hipSetDevice(e->p.device));
+  unsigned long long bs[2 * MD_SKIN_BANDS + 3];
+  if (skin_band_stats(e, pos, bs)) return fail(e, SCEMA_MD_ERR_DEVICE, "the statistics launch of the skin bands failed");
+  out[0] = MD_SKIN_BANDS;
+  for (int k = 0; k < 2 * MD_SKIN_BANDS + 3; k++) out[1 + k] = bs[k];
   return SCEMA_MD_OK;
 }
 

@@ -225,6 +225,12 @@ bool keep_list_switch() {
   return on;
 }
 
+// SCEMA_MD_SKIN_BANDS=0: k_pair walks every listed entry of a row on every step (the reference behaviour of the skin bands, md_skin_bands.h)
+bool skin_bands_switch() {
+  static const bool on = !(scema_env("SCEMA_MD_SKIN_BANDS") && atoi(scema_env("SCEMA_MD_SKIN_BANDS")) == 0);
+  return on;
+}
+
 // by the demand the failed run saw where that is more than the fixed step: a capacity far too small is found in one retry, not six
 void grow_after_overflow(scema_md_engine *e) {
   if (e->overflow_bits & 4) e->jtab_grow *= std::max(1.25, std::min(8.0, 1.1 * e->overflow_need_j));
@@ -305,7 +311,6 @@ int RowRun::lay_out_sim(int pos) {
   S.neigh_delay = 0;   // neigh_modify every 1 delay 0 check yes (in.set.lammps of both script sets); rebuilt when needed, same pairs inside the cutoff
   S.tdof = 3.0 * n - 3.0;
   S.skin = N.skin;
-  S.far_band = N.skin;
   e->h_zerotab.push_back(MdkZero{sl.wrapn.as<int>(), 3 * (long long)n});
   if ((rc = stage.bind(pos, A, sl, S, N))) return rc;
   e->h_sims[pos] = S;

@@ -30,7 +30,8 @@ int ensure_slot(scema_md_engine *e, Slot &sl, int natoms, int maxneigh, int ncel
     HIPCHK(sl.xq.ensure((size_t)npad * 32));
     HIPCHK(sl.stype.ensure((size_t)npad * 4));
     HIPCHK(sl.perm.ensure((size_t)npad * 4));
-    HIPCHK(sl.numneigh.ensure((size_t)npad * 4));
+    HIPCHK(sl.numneigh.ensure((size_t)(npad / MD_CLUSTER) * MD_BAND_CNT * 2));   // 16-bit cumulative counts per cluster (md_skin_bands.h)
+    HIPCHK(sl.dslot.ensure((size_t)npad * 4));
     sl.cap_atoms = natoms;
     sl.cap_pad = npad;
     sl.cap_neigh = 0;
@@ -448,11 +449,17 @@ int OplsRun::lay_out_sim(int pos) {
     const double m = 0.1 * P.skin;   // margin of the row segments over the cutoffs (scan 0 .. 0.6 skin: flat optimum at 0.05-0.15)
     S.seg_a2 = (P.cut_coul + m) * (P.cut_coul + m);
     S.seg_b2 = (P.cut_lj + m) * (P.cut_lj + m);
-    // skin pairs listed beyond cutmax + far_band sit at the back of the rows and are skipped until an atom has moved far_band/2
-    double frac = 0.65;   // scan 0.25 .. 0.85 on PE-10k (rebuild every ~33 steps, the largest displacement passes 0.5 A after ~8): optimum 0.65-0.75
-    S.far_band = frac * skin_i;
-    const double cm = std::max(P.cut_coul, P.cut_lj) + S.far_band;
-    S.seg_c2 = cm * cm;
+    // the skin pairs -- listed beyond cutmax + m -- sit at the back of the rows in MD_SKIN_BANDS bands of equal width by build-time distance; a row is
+    // walked into band b only once its cluster's and the replica's displacement bounds and the corner motion add up to w[b] (md_skin_bands.h)
+    const double cmax = std::max(P.cut_coul, P.cut_lj);
+    for (int b = 0; b < MD_SKIN_BANDS; b++) {
+      const double w = m + b * (skin_i - m) / MD_SKIN_BANDS;
+      S.band_e2[b] = (cmax + w) * (cmax + w);
+      S.band_w[b] = skin_down(w);
+    }
+    S.dquant = (float)(skin_i / MD_DLEVELS);
+    S.dquant_inv = (float)(MD_DLEVELS / skin_i);
+    S.skin_bands = skin_bands_switch() ? 1 : 0;
   }
   S.natoms = T.natoms;
   S.npad = padded_slots(T.natoms, S.ncells);
@@ -493,7 +500,7 @@ int OplsRun::lay_out_sim(int pos) {
   S.free_at = T.d_free_at.as<int>(); S.nfree = T.nfree;
   S.xq = sl.xq.as<double4>(); S.stype = sl.stype.as<int>(); S.perm = sl.perm.as<int>(); S.slot_tmp = sl.slot_tmp.as<int>();
   S.cell_of = sl.cell_of.as<int>(); S.ckey = sl.ckey.as<int>(); S.cell_start = sl.cell_start.as<int>();
-  S.cell_fill = sl.cell_fill.as<int>(); S.numneigh = sl.numneigh.as<int>(); S.neigh = sl.neigh.as<int>();
+  S.cell_fill = sl.cell_fill.as<int>(); S.numneigh = sl.numneigh.as<int>(); S.neigh = sl.neigh.as<int>(); S.dslot = sl.dslot.as<float>();
   S.fs = sl.fs.as<double>(); S.fb = sl.fb.as<double>(); S.slot_of = sl.slot_of.as<int>(); S.tile_nj = sl.tile_nj.as<int>(); S.tile_jtab = sl.tile_jtab.as<int>(); S.tile_order = sl.tile_order.as<int>(); S.tile_wstart = sl.tile_wstart.as<int>(); S.virp = sl.virp.as<double>(); S.virb = sl.virb.as<double>();
   S.kvec = sl.kvec.as<double>();
   if (S.nk > 0) {

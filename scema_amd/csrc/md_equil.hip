@@ -140,9 +140,8 @@ __global__ void k_pre_nh(const SimDev *sims) {
     }
     const double delta = 0.5 * (S.skin - (d1 + d2));
     sc.deltasq = (delta > 0.0) ? delta * delta : -1.0;
-    const double far = 0.5 * (S.far_band - (d1 + d2));
-    sc.far_dsq = (far > 0.0) ? far * far * (1.0 - 1.0e-9) : -1.0;
-    sc.need_far = 0;
+    sc.corner = d1 + d2;
+    sc.walk_all = 1;   // (this integrator keeps no displacement bounds: whole rows but for the step of a build, which clears the flag)
     for (int k = 0; k < 6; k++) sc.ke[k] = 0.0;
     for (int k = 0; k < MD_NPART * 6; k++) sc.vir[k] = 0.0;
     for (int k = 0; k < MD_NPART; k++) sc.eng[k] = 0.0;
@@ -182,7 +181,6 @@ __global__ __launch_bounds__(TPB) void k_initial_integrate_nh(const SimDev *sims
     dsq += d * d;
   }
   if (sc.check && dsq > sc.deltasq) sc.rebuild = 1;
-  if (dsq >= sc.far_dsq) sc.need_far = 1;
 }
 
 // end of a step: barostat kick of the velocities, temperature, omega_dot, both chains, box-length averages, grid guard
@@ -190,7 +188,6 @@ __global__ void k_post_nh(const SimDev *sims) {
   const SimDev &S = sims[blockIdx.x];
   SimScalars &sc = *S.sc;
   if (threadIdx.x != 0) return;
-  sc.nfar_steps += sc.need_far;
   double f2 = 1.0;
   if (S.npt) {
     const double fp = exp(-0.25 * S.dt * (sc.omega_dot + sc.mtk_term2));
@@ -242,9 +239,8 @@ __global__ void k_min_pre(const SimDev *sims) {
     sc.check = 1;
     const double delta = 0.5 * S.skin;
     sc.deltasq = delta * delta;
-    const double far = 0.5 * S.far_band;
-    sc.far_dsq = far * far * (1.0 - 1.0e-9);
-    sc.need_far = 0;
+    sc.corner = 0.0;
+    sc.walk_all = 1;   // (the moves of the line search keep no displacement bounds: whole rows but for the evaluation of a build)
     for (int k = 0; k < 6; k++) sc.ke[k] = 0.0;
     for (int k = 0; k < MD_NPART * 6; k++) sc.vir[k] = 0.0;
     for (int k = 0; k < MD_NPART; k++) sc.eng[k] = 0.0;
@@ -276,7 +272,6 @@ __global__ __launch_bounds__(TPB) void k_min_move(const SimDev *sims, double *co
     dsq += d * d;
   }
   if (dsq > sc.deltasq) sc.rebuild = 1;
-  if (dsq >= sc.far_dsq) sc.need_far = 1;
 }
 // after a force evaluation: f.h, f.f, max |f|
 __global__ __launch_bounds__(TPB) void k_min_reduce(const SimDev *sims, double *const *hs) {

@@ -11,6 +11,7 @@ void mdk_neighbor(hipStream_t st, const SimDev *d, int ns, int maxatoms, int max
 void mdk_neigh_build(hipStream_t st, const SimDev *d, int ns, int maxcells, int maxrow, int capj);
 // dynamic LDS of the tile kernels for a j-table capacity (the engine sizes the cell grid so that these fit)
 size_t mdk_pair_lds_bytes(int capj);
+void mdk_band_stats(hipStream_t st, const SimDev *d, unsigned long long *out);   // diagnostics: [2 K + 3] counters of the skin bands of ONE replica (md_pair.hip), added to out
 size_t mdk_neigh_lds_bytes(int capj, int maxrow);
 // vir: accumulate the pair virial (needed when the pressure is sampled); eng: also energies (parity hook)
 void mdk_pair(hipStream_t st, const SimDev *d, int ns, int maxcells, int capj, int vir, int eng, int npoly, int cle = 0);   // cle: cut_coul <= cut_lj for the whole batch

@@ -49,7 +49,7 @@ __global__ void k_phase_init(const SimDev *sims) {
     // per step at the reference's strain rate, 0.3 A at a rate of 1e-2 per fs), so they stand where the list's own test says so for the
     // positions and the box the run starts from -- the same test as for rows kept from the update before (below), with the rows' age and
     // reference positions.  (Until round 6 they stood unchecked: a sheared replica at a rate of 1e-2 lost pairs in the set-up evaluation
-    // of its sampling run, 1e-7 of the stress.)  The far band is walked in the set-up evaluation (what moved since the build is only looked at from step 1 on).  A box flip that
+    // of its sampling run, 1e-7 of the stress.)  The set-up evaluation walks whole rows (walk_all: the displacement bounds of the skin bands are only taken from step 1 on).  A box flip that
     // is still pending forces the build as it would between two steps.  Results do not depend on when a list is built.
     int keep = S.keep_list && !sc.force_rebuild;
     sc.deltasq = 0.0;
@@ -74,9 +74,8 @@ __global__ void k_phase_init(const SimDev *sims) {
     sc.check = 1;
     sc.rebuild = keep ? 0 : 1;
     sc.force_rebuild = 0;
-    sc.far_dsq = 1.0e300;
-    sc.need_far = keep ? 1 : 0;
-    sc.nfar_steps = 0;
+    sc.corner = 0.0;
+    sc.walk_all = keep ? 1 : 0;   // (a build clears it again: a fresh row is walked as far as segment B)
 #if defined(PAIR_TIMING) || defined(PAIR_COUNT)
     for (int k = 0; k < 20; k++) sc.dbg[k] = 0;
     for (int k = 0; k < 8; k++) sc.dbg2[k] = 0;
@@ -152,11 +151,9 @@ __device__ __forceinline__ void pre_scalars(const SimDev &S, SimScalars &sc, dou
     // triggers -- LAMMPS squares the negative difference and tests against that)
     const double delta = 0.5 * (S.skin - (d1 + d2));
     sc.deltasq = delta > 0.0 ? delta * delta : 0.0;
-    // far skin band: a pair listed at r0 >= cutmax + far_band is inside the cutoff only after
-    // 2 dmax + (d1 + d2) >= far_band
-    const double far = 0.5 * (S.far_band - (d1 + d2));
-    sc.far_dsq = (far > 0.0) ? far * far * (1.0 - 1.0e-9) : -1.0;
-    sc.need_far = 0;
+    // skin bands (md_skin_bands.h): the box term of the rule; the displacement bounds come from k_initial_integrate
+    sc.corner = d1 + d2;
+    sc.walk_all = 0;
     if (S.nvt) sc.vscale *= nhc_half(S, sc);
     for (int k = 0; k < 6; k++) sc.ke[k] = 0.0;
     for (int k = 0; k < MD_NPART * 6; k++) sc.vir[k] = 0.0;
@@ -214,7 +211,15 @@ __global__ __launch_bounds__(TPB) void k_initial_integrate(const SimDev *sims) {
     dsq += d * d;
   }
   if (sc.check && dsq > sc.deltasq) sc.rebuild = 1;
-  if (dsq >= sc.far_dsq) sc.need_far = 1;
+  // Skin bands: the atom's displacement as an FP32 upper bound at its slot, and the replica's level flag of it (a plain store of the same
+  // value by whoever gets there, like the rebuild flag; the flag is read first, so that a level is written by its first few atoms only).
+  // On a step that rebuilds, the kernels that deal the slots anew clear both.
+  if (S.dslot) {
+    const float dup = sqrtf((float)dsq) * 1.00001f;
+    S.dslot[S.slot_of[i]] = dup;
+    const int lev = skin_level(dup, S.dquant_inv);
+    if (sc.dflag[lev] == 0) sc.dflag[lev] = 1;
+  }
   // The slot-ordered record of the atom for k_pair (what k_pack does for the flows without this kernel): wrapped position at the
   // atom's slot, its pair-force accumulator cleared.  On a step that rebuilds, the slots are dealt anew afterwards and k_cell_sort
   // writes all records of its cell, so what is stored here is then simply overwritten.
@@ -253,9 +258,10 @@ __global__ __launch_bounds__(TPB) void k_bin(const SimDev *sims) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     box_corners(sc.box, sc.corners_hold);
     sc.force_rebuild = 0;
-    sc.far_dsq = 1.0e300;   // fresh list: every listed skin pair is outside the cutoff
-    sc.need_far = 0;
+    sc.corner = 0.0;   // fresh list: every listed skin pair is outside the cutoff (no band open until something has moved)
+    sc.walk_all = 0;
   }
+  if (blockIdx.x == 0 && threadIdx.x < MD_DLEVELS) sc.dflag[threadIdx.x] = 0;
   BoxD b;
   box_derive(sc.box, b);
   int nsub[3];
@@ -399,6 +405,7 @@ __device__ __forceinline__ void pack_slot(const SimDev &S, int s, int a, double 
   if (a < 0) { xy[0] = 1.0e15 + 1.0e6 * (double)s; xy[1] = 1.0e15; zq[0] = 1.0e15; zq[1] = 0.0; S.stype[s] = 0; }
   else { xy[0] = x; xy[1] = y; zq[0] = z; zq[1] = S.q[a]; S.stype[s] = S.type[a]; }
   S.fs[s] = 0.0; S.fs[(size_t)S.npad + s] = 0.0; S.fs[2 * (size_t)S.npad + s] = 0.0;
+  if (S.dslot) S.dslot[s] = 0.0f;   // (skin bands: nothing has moved since this build; a pad never does)
 }
 
 // k_cell_build : k_bin + k_cell_scan + k_cell_fill in ONE launch for replicas of up to CB_MAXATOMS atoms and BIN_MAXCELLS cells: one
@@ -431,9 +438,10 @@ __global__ __launch_bounds__(CB_TPB) void k_cell_build(const SimDev *sims, int c
   if (threadIdx.x == 0) {
     box_corners(sc.box, sc.corners_hold);
     sc.force_rebuild = 0;
-    sc.far_dsq = 1.0e300;   // fresh list: every listed skin pair is outside the cutoff
-    sc.need_far = 0;
+    sc.corner = 0.0;   // fresh list: every listed skin pair is outside the cutoff (no band open until something has moved)
+    sc.walk_all = 0;
   }
+  if (threadIdx.x < MD_DLEVELS) sc.dflag[threadIdx.x] = 0;
   BoxD b;
   box_derive(sc.box, b);
   int nsub[3];
@@ -1291,7 +1299,6 @@ __global__ void k_post(const SimDev *sims, int next_pre) {
   for (int k = threadIdx.x; k < S.ncells; k += blockDim.x) S.cell_count[k] = 0;
 }
 __device__ __forceinline__ void post_scalars(const SimDev &S, SimScalars &sc) {
-  sc.nfar_steps += sc.need_far;
   sc.t_current = (sc.ke[0] + sc.ke[1] + sc.ke[2]) / (S.tdof * MD_BOLTZ);
   double f2 = 1.0;
   if (S.nvt) f2 = nhc_half(S, sc);

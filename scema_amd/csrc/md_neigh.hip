@@ -42,7 +42,7 @@ struct ClusterI {
 };
 
 extern __shared__ int s_build[];  // [3][capj + 64] FP32 records of the j table (x, y, z relative to the tile's origin; entry capj: a far dummy), then
-                                  // [TW][capB] per-wave lists (segment B from the front, the skin band from the back), then
+                                  // [TW][capB] per-wave lists (segment B and the skin bands, two lists per region: k_neigh_build), then
                                   // [NQ][qcap] 16-bit table indices: the part of the table each group (quarter) of the cell's clusters can reach
 #define NQ 4      // groups of a cell's clusters with their own candidate list (<= TW: one wave takes each group's bounding box)
 #define NB_MAXRUN 128    // slot runs of one tile's candidates (own cell + half stencil; 20 for PE-10k)
@@ -61,6 +61,12 @@ extern __shared__ int s_build[];  // [3][capj + 64] FP32 records of the j table 
 __device__ __forceinline__ float nb_eps(double M, double r2) {
   const double r = sqrt(r2);
   return (float)(1.0001 * 5.9604644775390625e-8 * (96.0 * M * r + 8.0 * r2));
+}
+// the cumulative 16-bit counts of a cluster's row (md_skin_bands.h): [A|B], then + each skin band in turn
+__device__ __forceinline__ void nb_store_counts(const SimDev &S, int cl, const int *cum) {
+  unsigned short *c = (unsigned short *)S.numneigh + (size_t)MD_BAND_CNT * cl;
+#pragma unroll
+  for (int k = 0; k <= MD_SKIN_BANDS; k++) c[k] = (unsigned short)(cum ? cum[k] : 0);
 }
 // v < t, rounded so that the FP32 test can only err towards "inside"
 __device__ __forceinline__ float nb_up(double t, float eps) { return (float)(t * (1.0 + 2.4e-7)) + eps; }
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
   // per cell.  A denser cell is reported like a table overflow (the engine retries with smaller cells), never dropped.
   if (!runs_ok || nj > capjs || nown / NI > 64 * TW) {   // uniform: table overflow -> the engine regrows and retries
     if (threadIdx.x == 0) { S.tile_nj[cell] = 0; atomicOr(&sc.overflow, 1 | 4); atomicMax(&sc.maxj_seen, runs_ok ? nj : 2 * S.capj); }   // 4: table
-    for (int cl = cs / NI + threadIdx.x; cl < ce / NI; cl += TT) { S.numneigh[2 * cl] = 0; S.numneigh[2 * cl + 1] = 0; }
+    for (int cl = cs / NI + threadIdx.x; cl < ce / NI; cl += TT) nb_store_counts(S, cl, nullptr);
     return;
   }
   if (threadIdx.x == 0) { S.tile_nj[cell] = nj; atomicMax(&sc.maxj_seen, nj); }
@@ -336,7 +342,14 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
   const unsigned long long tb1 = __builtin_readcyclecounter();
 #endif
   const int maxrow = S.maxneigh;
-  const double ra2 = S.seg_a2, rb2 = fmax(S.seg_a2, S.seg_b2), rc2 = fmax(rb2, S.seg_c2), excl2 = S.excl_cut2;
+  const double ra2 = S.seg_a2, rb2 = fmax(S.seg_a2, S.seg_b2), excl2 = S.excl_cut2;
+  // Skin bands (md_skin_bands.h): lists 0 .. K of a row behind segment A are B and the K bands; list t >= 1 holds the entries whose nearest
+  // build-time distance lies in [eb2[t - 1], eb2[t]), eb2[0] = rb2.  (No edge below the one before it, whatever the parameters.)
+  constexpr int KB = MD_SKIN_BANDS, NR = (KB + 2) / 2;
+  double eb2[KB];
+  eb2[0] = rb2;
+#pragma unroll
+  for (int b = 1; b < KB; b++) eb2[b] = fmax(eb2[b - 1], S.band_e2[b]);
   unsigned int npairs = 0, npairs_ref = 0;   // per lane and tile: far below 2^32
   unsigned long long nrowent = 0;
   // The first build of a run is the exact one (header).  Only a list wider than the reference's needs the second count (uniform),
@@ -345,11 +358,29 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
   const bool wider = S.rlist_ref2 < S.rlist2;
   const bool exact = exact_mode == 1 || (exact_mode != 0 && sc.step == 0);
   const bool count_ref = wider && exact && sc.step == 0;
-  const float ra2e = nb_up(ra2, eps), rb2e = nb_up(rb2, eps), rc2e = nb_up(rc2, eps), excl2e = nb_up(excl2, eps);
+  const float ra2e = nb_up(ra2, eps), excl2e = nb_up(excl2, eps);
+  // (every edge widened like the list radius: an FP32 distance at or beyond a widened edge is an exact one at or beyond the edge itself, so
+  // no entry lands in a farther band than its exact distance allows)
+  float eb2e[KB];
+#pragma unroll
+  for (int b = 0; b < KB; b++) eb2e[b] = nb_up(eb2[b], eps);
   const GLOBAL_AS int *gjr = (const GLOBAL_AS int *)gj;
-  // The wave's staging list, 16-bit entries (position in the group's list | i-mask << 12): segment B from the front of [0, capBC),
-  // the near skin band C1 from its back, the far band C2 in [capBC, capB).  (32-bit entries were 41 KB of LDS for the eight waves.)
-  const int capD = capB >> 2, capBC = capB - capD;
+  // The wave's staging list, 16-bit entries (position in the group's list | i-mask << 12), in NR regions of two lists each: list 2 g from
+  // the front of region g, list 2 g + 1 from its back (K even: the last band has the last region to itself).  A region's share of the list
+  // is its share of the shell volume between the edge of segment A and the list radius, which is what its lists hold of a row at uniform
+  // density.  (32-bit entries were 41 KB of LDS for the eight waves.)
+  int rbnd[NR + 1];
+  {
+    const double v0 = ra2 * sqrt(ra2), vt = rl2 * sqrt(rl2) - v0;
+    rbnd[0] = 0;
+#pragma unroll
+    for (int g = 1; g < NR; g++) {
+      const double e2 = eb2[2 * g - 1];   // lower edge of list 2 g (band 2 g - 1)
+      const double share = (vt > 0.0) ? (e2 * sqrt(e2) - v0) / vt : (double)g / NR;
+      rbnd[g] = __builtin_amdgcn_readfirstlane(min(max((int)(share * capB), rbnd[g - 1]), capB));
+    }
+    rbnd[NR] = capB;
+  }
   int nmax = 0, over = 0;
   for (int cl = cs / NI + wave; cl < ce / NI; cl += TW) {
     const int s0slot = cl * NI;
@@ -364,7 +395,7 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
       ci.x[a] = XQ_X(S, s0slot + a); ci.y[a] = XQ_Y(S, s0slot + a); ci.z[a] = XQ_Z(S, s0slot + a);
     }
     if (ci.atom[0] < 0) {  // empty cluster (pad only)
-      if (lane == 0) { S.numneigh[2 * cl] = 0; S.numneigh[2 * cl + 1] = 0; }
+      if (lane == 0) nb_store_counts(S, cl, nullptr);
       continue;
     }
     GLOBAL_AS int *row = as_global_w(S.neigh) + (size_t)cl * maxrow;
@@ -388,7 +419,9 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
     }
     const unsigned long long exvalid = __ballot(exv >= 0);
     const bool exlong = max(max(exn[0], exn[1]), max(exn[2], exn[3])) > 16;   // (uniform)
-    int nA = 0, nB = 0, nC = 0, nD = 0;   // segments A, B, C1 (near skin band), C2 (far skin band)
+    int nA = 0, nL[KB + 1];   // segment A; the lists behind it: B, then the skin bands
+#pragma unroll
+    for (int t = 0; t <= KB; t++) nL[t] = 0;
     // the part of the table this cluster's quarter can reach (or the whole table if that list overflowed)
     int qq = 0;   // quarter q holds the clusters [q n / NQ, (q + 1) n / NQ) of the cell, as its bounding box was taken
 #pragma unroll
@@ -421,7 +454,7 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
     int posA_prev = dump, entA_prev = 0;
     // What both row loops do with a chunk once the i-mask of every candidate is known: own-cell rule, exclusions, segments, stores.
     // (lt: list entry; jt: table entry)
-#define NB_CHUNK_TAIL(RMIN, RA, RB, RC, EXCL)                                                                                            \
+#define NB_CHUNK_TAIL(RMIN, RA, EB, EXCL)                                                                                                \
       const int l = lt & 0xFFF;                                                                                                           \
       const int j = jt & MD_JMASK;                                                                                                        \
       if (own_chunks) {   /* (wave-uniform: the entries of the own cell come first in the table and in every list) */                     \
@@ -456,25 +489,36 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
               if (S.slot_of[S.ex_list[exb[a] + e]] == j) { mask &= ~(1 << a); refm &= ~(1 << a); }                                        \
         }                                                                                                                                 \
       }                                                                                                                                   \
-      /* Segments: A straight into the row (the store itself at the top of the next turn); B, C1, C2 into the wave's staging list with ONE store. */ \
-      /* Lanes without an entry get a distance beyond every threshold, so that the four class masks are four plain compares (a ballot of a */      \
+      /* Segments: A straight into the row (the store itself at the top of the next turn); B and the skin bands into the wave's staging list with ONE store. */ \
+      /* Lanes without an entry get a distance beyond every threshold, so that the class masks are plain compares (a ballot of a */                \
       /* composed condition costs two more vector instructions each), and the staging index is selected, clamped into the list (an index that */  \
-      /* leaves its region means an overflow, which `bad` reports below) and used by one predicated store instead of three. */                    \
+      /* leaves its region means an overflow, which `bad` reports below) and used by one predicated store instead of one per list. */             \
       {                                                                                                                                   \
         typedef decltype(RMIN) nb_rm_t;                                                                                                   \
         const nb_rm_t rmx = mask ? RMIN : (nb_rm_t)3.0e38f;                                                                               \
-        const bool inA = rmx < RA, inAB = rmx < RB, inABC = rmx < RC, inAll = mask != 0;                                                  \
-        const unsigned long long mA = __ballot(inA), mAB = __ballot(inAB), mABC = __ballot(inABC), mAll = __ballot(inAll);                \
-        const unsigned long long mB = mAB & ~mA, mC = mABC & ~mAB, mD = mAll & ~mABC;                                                     \
-        const int pB = nB + popc_below(mB), pC = capBC - 1 - (nC + popc_below(mC)), pD = capBC + nD + popc_below(mD);                     \
-        const int idx = min(max(inAB ? pB : (inABC ? pC : pD), 0), capB - 1);                                                             \
+        const bool inA = rmx < RA, inAll = mask != 0;                                                                                     \
+        const unsigned long long mA = __ballot(inA), mAll = __ballot(inAll);                                                              \
+        /* below[t]: nearer than the upper edge of list t (the last list: every entry) */                                                 \
+        bool below[KB + 1];                                                                                                               \
+        unsigned long long mbelow[KB + 1];                                                                                                \
+        _Pragma("unroll") for (int t = 0; t < KB; t++) { below[t] = rmx < EB[t]; mbelow[t] = __ballot(below[t]); }                         \
+        below[KB] = inAll; mbelow[KB] = mAll;                                                                                             \
+        int idx = 0;                                                                                                                      \
+        _Pragma("unroll") for (int t = KB; t >= 0; t--) {                                                                                 \
+          const unsigned long long mt = mbelow[t] & ~(t ? mbelow[t - 1] : mA);                                                            \
+          const int pt = nL[t] + popc_below(mt);                                                                                          \
+          const int it = (t & 1) ? rbnd[(t >> 1) + 1] - 1 - pt : rbnd[t >> 1] + pt;                                                       \
+          idx = (t == KB || below[t]) ? it : idx;                                                                                         \
+          nL[t] += __popcll(mt);                                                                                                          \
+        }                                                                                                                                 \
+        idx = min(max(idx, 0), capB - 1);                                                                                                 \
         if (inAll && !inA) lb[idx] = (unsigned short)((base + lane) | (mask << 12));                                                      \
         if (inA) {                                                                                                                        \
           const int pos = nA + popc_below(mA);                                                                                            \
           const int ty = qall ? (int)((unsigned)jt >> 28) : (lt >> 12);                                                                   \
           if (pos < maxrow - 64) { posA_prev = pos; entA_prev = l | (ty << E_TYPE_SHIFT) | (mask << E_MASK_SHIFT); }                      \
         }                                                                                                                                 \
-        nA += __popcll(mA); nB += __popcll(mB); nC += __popcll(mC); nD += __popcll(mD);                                                   \
+        nA += __popcll(mA);                                                                                                               \
       }                                                                                                                                   \
       npairs += __popc(mask);
 
@@ -525,7 +569,7 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
           }
           const double rmin = vmin_f64(vmin_f64(r2a[0], r2a[1]), vmin_f64(r2a[2], r2a[3]));
           if (!in) { mask = 0; refm = 0; }
-          NB_CHUNK_TAIL(rmin, ra2, rb2, rc2, excl2)
+          NB_CHUNK_TAIL(rmin, ra2, eb2, excl2)
           if (CREF) npairs_ref += __popc(refm);
         }
       };
@@ -558,7 +602,7 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
           r2a[a] = r2;
         }
         const float rmin = vmin3_f32(vmin_f32(r2a[0], r2a[1]), r2a[2], r2a[3]);
-        NB_CHUNK_TAIL(rmin, ra2e, rb2e, rc2e, excl2e)
+        NB_CHUNK_TAIL(rmin, ra2e, eb2e, excl2e)
       };
       // The pipeline: list entries two chunks ahead, record and table entry one chunk ahead (a record's address needs its list entry:
       // that is there when the requests of the next chunk go out).  The loop body is TWO chunks with two register sets, each loaded
@@ -585,28 +629,34 @@ __global__ __launch_bounds__(TT, 4) void k_neigh_build(const SimDev *__restrict_
 #ifdef PAIR_TIMING
     const unsigned long long tr2 = __builtin_readcyclecounter();
 #endif
-    const int n = nA + nB + nC + nD;
-    const bool bad = nB + nC > capBC || nD > capD || n > maxrow - 64;   // (the row's last 64 words are the loop's dump zone)
+    int cum[KB + 1];   // entries up to and including list t
+    bool bad = false;
+#pragma unroll
+    for (int t = 0; t <= KB; t++) cum[t] = (t ? cum[t - 1] : nA) + nL[t];
+#pragma unroll
+    for (int g = 0; g < NR; g++) bad = bad || nL[2 * g] + ((2 * g + 1 <= KB) ? nL[2 * g + 1] : 0) > rbnd[g + 1] - rbnd[g];
+    const int n = cum[KB];
+    bad = bad || n > maxrow - 64;   // (the row's last 64 words are the loop's dump zone)
     if (bad) over = 1;
-    // B, C1, C2: staging list -> behind A, with the table index and the type of j back in place (same-wave LDS traffic is processed in order)
+    // B and the bands: staging list -> behind A, with the table index and the type of j back in place (same-wave LDS traffic is processed in order)
     if (!bad) {
       auto expand = [&](int e16) -> int {
         const int lt = list_at(e16 & 0xFFF), l = lt & 0xFFF;
         const int ty = qall ? (int)((unsigned)gjr[l] >> 28) : (lt >> 12);
         return l | (ty << E_TYPE_SHIFT) | ((e16 >> 12) << E_MASK_SHIFT);
       };
-      for (int k = lane; k < nB; k += 64) row[nA + k] = expand(lb[k]);
-      for (int k = lane; k < nC; k += 64) row[nA + nB + k] = expand(lb[capBC - 1 - k]);
-      for (int k = lane; k < nD; k += 64) row[nA + nB + nC + k] = expand(lb[capBC + k]);
+#pragma unroll
+      for (int t = 0; t <= KB; t++) {
+        const int off = t ? cum[t - 1] : nA;
+        for (int k = lane; k < nL[t]; k += 64) row[off + k] = expand(lb[(t & 1) ? rbnd[(t >> 1) + 1] - 1 - k : rbnd[t >> 1] + k]);
+      }
       // the row's last chunk is filled up with empty entries (mask 0): k_pair reads whole chunks and masks no lane.  (maxrow is a
-      // multiple of 64.)  On steps without the far band it reads up to the end of the chunk that holds the last C1 entry: what
-      // follows there are C2 entries, whose pairs are outside the cutoff on such a step -- evaluated to nothing in lanes that
-      // would otherwise idle
+      // multiple of 64.)  A row that is not walked to its end is read up to the end of the chunk that holds its last open entry:
+      // what follows there are entries of closed bands, whose pairs are outside the cutoff on such a step -- evaluated to nothing
+      // in lanes that would otherwise idle
       if (n + lane < ((n + 63) & ~63)) row[n + lane] = 0;
     }
-    if (lane == 0) {
-      S.numneigh[2 * cl] = bad ? 0 : nA + nB + nC; S.numneigh[2 * cl + 1] = bad ? 0 : nD;
-    }
+    if (lane == 0) nb_store_counts(S, cl, bad ? nullptr : cum);
     nmax = max(nmax, n);
     nrowent += n;
 #ifdef PAIR_TIMING

@@ -15,9 +15,10 @@
 //     neighbours, each entry carrying a 4-bit mask of which i atoms list that j.
 //   * ONE WAVE PER CLUSTER, the 64 lanes span the row (contiguous 256 B per wave instruction); a lane
 //     gathers its j record once and evaluates it against up to 4 i atoms held in scalar registers.
-//   * rows keep table order inside three segments by build-time distance (A: may need coulomb,
-//     B: LJ only, C: skin), so the three regimes are wave-uniform branches.  Every lane still tests
-//     r^2 against the cutoffs: results never depend on the segments or on the cluster grouping.
+//   * rows keep table order inside segments by build-time distance (A: may need coulomb, B: LJ only,
+//     then the skin in MD_SKIN_BANDS bands), so the regimes are wave-uniform branches, and a row is
+//     walked only as far into its skin bands as its atoms have moved (md_skin_bands.h).  Every lane
+//     still tests r^2 against the cutoffs: results never depend on the segments or on the cluster grouping.
 //   entry = i-mask [20:17] | type of j [16:13] | index into the tile's j table [12:0]
 //   j table entry = image code [27:23] | j slot [22:0]
 //
@@ -81,8 +82,17 @@ __global__ __launch_bounds__(TT, 4) void k_pair(const SimDev *__restrict__ sims,
   const int lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int maxrow = S.maxneigh;
-  // far skin band: walked only on steps where some atom of the replica has moved far enough for such a pair to reach the cutoff
-  const int need_far = __builtin_amdgcn_readfirstlane(S.sc->need_far);
+  // Skin bands (md_skin_bands.h): a row is walked into its skin part only as far as its own cluster's displacement bound, the replica's and
+  // the motion of the box corners allow a pair inside the cutoff.  The replica's bound is the highest level flag raised since the build
+  // (lane l reads flag l); whole rows where the flow keeps no bounds (walk_all) or the switch says so.
+  // One wave-uniform number carries all of it: the replica's bound plus the corner term, rounded up, or a bound beyond every band.
+  float d_gc;
+  {
+    const unsigned long long dflags = __ballot(sc.dflag[lane] != 0);
+    const float d_g = skin_level_bound(dflags ? 63 - __builtin_clzll(dflags) : 0, S.dquant), d_c = skin_up(sc.corner);
+    const bool banded = S.skin_bands != 0 && sc.walk_all == 0;
+    d_gc = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(banded ? (d_g + d_c) * 1.000001f : 3.0e38f)));
+  }
   // Row headers of this wave and the first two chunks of its entry stream are requested before the tile's table is
   // staged: none of that needs the LDS, so their latency runs under the table load and the barrier.
   const int p_begin = S.tile_wstart[(size_t)cell * (TW + 1) + wave], p_end = S.tile_wstart[(size_t)cell * (TW + 1) + wave + 1];
@@ -94,7 +104,13 @@ __global__ __launch_bounds__(TT, 4) void k_pair(const SimDev *__restrict__ sims,
     // an entry of the schedule: cluster | a << 20 | b << 25 = the chunks [C a / 16, C b / 16) of that cluster's row (k_neigh_build)
     const int ent = S.tile_order[2 * (cs / NI) + p_begin + lane];
     h_cl = ent & 0xFFFFF;
-    const int n = S.numneigh[2 * h_cl] + (need_far ? S.numneigh[2 * h_cl + 1] : 0);   // [A|B|C1], then C2
+    // [A|B], then the open bands: the row's cumulative counts, and the bound of the cluster's four slots
+    const unsigned short *cnt = (const unsigned short *)S.numneigh + (size_t)MD_BAND_CNT * h_cl;
+    const float4 dv = *(const float4 *)(S.dslot + (size_t)NI * h_cl);
+    const int nopen = skin_bands_open(fmaxf(fmaxf(dv.x, dv.y), fmaxf(dv.z, dv.w)), d_gc, 0.0f, S.band_w);
+    int n = cnt[0];
+#pragma unroll
+    for (int b = 0; b < MD_SKIN_BANDS; b++) n = (nopen > b) ? (int)cnt[b + 1] : n;
     const int C = (n + 63) >> 6, pa = (ent >> 20) & 31, pb = (ent >> 25) & 31;
     const int kb = 64 * ((C * pa) >> 4), ke = 64 * ((C * pb) >> 4);   // whole chunks: the row's last one is padded with empty entries
     h_nn = (max(ke, kb) << 16) | kb;
@@ -425,6 +441,34 @@ __global__ __launch_bounds__(TT, 4) void k_pair(const SimDev *__restrict__ sims,
   }
 }
 
+
+// k_band_stats : diagnostics only (SCEMA_MD_TIMING, scema_md_debug_skin_bands; never part of a step): what the next k_pair launch on this
+// replica would walk of the skin part of its rows, by the rule its header lanes apply.  out: [K] skin entries listed per band, [K] walked,
+// rows with skin entries, rows with a band open, rows with every band open
+__global__ __launch_bounds__(256) void k_band_stats(const SimDev *sim, unsigned long long *out) {
+  const SimDev &S = *sim;
+  const SimScalars &sc = *S.sc;
+  const bool banded = S.skin_bands != 0 && sc.walk_all == 0;
+  int lev = 0;
+  for (int l = 0; l < MD_DLEVELS; l++) if (sc.dflag[l] != 0) lev = l;
+  const float d_g = skin_level_bound(lev, S.dquant), d_c = skin_up(sc.corner);
+  const int nclus = S.cell_start[S.ncells] / NI;
+  for (int cl = blockIdx.x * blockDim.x + threadIdx.x; cl < nclus; cl += gridDim.x * blockDim.x) {
+    const unsigned short *cnt = (const unsigned short *)S.numneigh + (size_t)MD_BAND_CNT * cl;
+    const float4 dv = *(const float4 *)(S.dslot + (size_t)NI * cl);
+    const int nopen = banded ? skin_bands_open(fmaxf(fmaxf(dv.x, dv.y), fmaxf(dv.z, dv.w)), d_g, d_c, S.band_w) : MD_SKIN_BANDS;
+    if (cnt[MD_SKIN_BANDS] == cnt[0]) continue;
+    for (int b = 0; b < MD_SKIN_BANDS; b++) {
+      const unsigned long long nb = (unsigned long long)(cnt[b + 1] - cnt[b]);
+      atomicAdd(&out[b], nb);
+      if (nopen > b) atomicAdd(&out[MD_SKIN_BANDS + b], nb);
+    }
+    atomicAdd(&out[2 * MD_SKIN_BANDS], 1ull);
+    if (nopen > 0) atomicAdd(&out[2 * MD_SKIN_BANDS + 1], 1ull);
+    if (nopen == MD_SKIN_BANDS) atomicAdd(&out[2 * MD_SKIN_BANDS + 2], 1ull);
+  }
+}
+void mdk_band_stats(hipStream_t st, const SimDev *d, unsigned long long *out) { hipLaunchKernelGGL(k_band_stats, dim3(16), dim3(256), 0, st, d, out); }
 
 size_t mdk_pair_lds_bytes(int capj) { return (size_t)capj * (3 * sizeof(double) + sizeof(int)); }
 template <bool VIR, bool ENG, int NP, bool CLE = false>

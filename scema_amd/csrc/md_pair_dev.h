@@ -11,7 +11,6 @@
 #define E_LMASK 0x1FFF
 #define E_TYPE_SHIFT 13
 #define E_MASK_SHIFT 17
-#define E_FAR (1 << 21)    // (inside k_neigh_build only: a skin-band entry of the far part, C2)
 #define CODE_HOME 13       // image code of (0,0,0)
 
 // slot records are stored as two arrays of 16-byte halves, (x,y)[npad] then (z,q)[npad]: a wave's gather

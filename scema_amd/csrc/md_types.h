@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "md_skin_bands.h"
+
 #define MD_MAXCHAIN 8
 #define MD_NPART 8
 #define MD_MAXTYPES 16
@@ -55,7 +57,7 @@ struct SimScalars {
   double vscale;       // deferred Nose-Hoover velocity scale, applied by the next kick
   double psum[6];      // running sum of the sampled pressure tensor (atm)
   double deltasq;      // neighbour trigger: (skin - corner motion)^2 / 4
-  double far_dsq;      // squared atom displacement from which the far skin band (segment C2) can reach the cutoff
+  double corner;       // motion of the two fastest box corners since the rows were built (d1 + d2 of pre_scalars): the box term of the skin-band rule
   double corners_hold[24];
   unsigned long long nentries;  // (i,j) pairs listed at the last build (= entries of a full per-atom list)
   unsigned long long nentries_ref;  // the same count inside the reference's list radius (cutoff + params.skin)
@@ -68,8 +70,8 @@ struct SimScalars {
   int force_rebuild;   // set by a box flip: the next step rebuilds whatever the displacements
   int overflow;
   int maxneigh_seen;
-  int nfar_steps;      // steps of this phase on which the far skin band was walked (SCEMA_MD_TIMING)
-  int need_far;        // this step some atom moved >= sqrt(far_dsq): k_pair walks segment C2 too
+  int walk_all;        // k_pair walks whole rows: the set-up evaluation on kept rows, and every flow that does not produce the displacement bounds
+  int pad_walk_;
   int maxj_seen;       // largest tile j table at the last builds
   int nbuilds;
   // ---- init_material's equilibration schedule only (md_equil.hip): fix npt ... iso, temperature ramps, min_style sd ----
@@ -89,6 +91,9 @@ struct SimScalars {
   double min_alpha_now, min_alpha_next;   // where x sits on the current search line before / after the move of this evaluation (min_incremental)
   double min_alpha, min_alphamax, min_fdothall, min_eorig, min_eprev, min_fhprev, min_engprev, min_alphaprev, min_fh_trial, min_ecur, min_einit;
   double min_dots[4];  // f.h, f.f, max |f| of the last evaluation (+ spare)
+  // the replica's displacement bound since the rows were built, as level flags (md_skin_bands.h): raised by plain stores of k_initial_integrate,
+  // cleared by the kernels that reset xhold; outside the part of the structure that k_post carries through LDS
+  int dflag[MD_DLEVELS];
 #if defined(PAIR_TIMING) || defined(PAIR_COUNT)
   unsigned long long dbg[20];   // [12..17]: k_neigh_build per row: set-up, chunk loop, row end (cycles); chunks through the exclusion walk, own-cell chunks, chunks
   unsigned long long dbg2[8];   // k_pppm_solve phase clocks
@@ -137,8 +142,12 @@ struct SimDev {
   int keep_list;            // this run continues one that has just ended on the same slot: its cell grid and neighbour rows stand (k_phase_init)
   double rlist_ref2;      // (cutoff + the reference's skin)^2: pairs inside it are what the roofline accounting prices
   double seg_a2, seg_b2;  // row segments by build-time distance: (cut_coul+m)^2, (cut_lj+m)^2
-  double far_band;        // width (A) of the near skin band C1
-  double seg_c2;          // skin band split: (cutmax + skin/2)^2, beyond it segment C2 (skipped while nothing moved far enough)
+  // the skin part of a row in K bands by build-time distance (md_skin_bands.h): band b holds r0^2 >= band_e2[b]; band_e2[0] = max(seg_a2, seg_b2)
+  double band_e2[MD_SKIN_BANDS];
+  float band_w[MD_SKIN_BANDS];   // band_e2 as distances beyond the larger cutoff, rounded down
+  float dquant, dquant_inv;      // quantum of the replica's displacement levels (skin / MD_DLEVELS) and its inverse
+  int skin_bands;                // 0: k_pair walks every listed entry on every step (SCEMA_MD_SKIN_BANDS=0)
+  int pad_bands_;
   // topology (shared by all simulations of one (material, replica))
   const int MD_G *type;
   const double MD_G *q, *mass;       // per atom
@@ -174,7 +183,8 @@ struct SimDev {
   int MD_G *wrapn;       // atom -> integer wrap (3)
   double MD_G *xhold;
   int MD_G *cell_of, *ckey, *cell_count, *cell_start, *cell_fill;
-  int MD_G *numneigh, *neigh;  // per cluster: {entries in segments A+B+C1 (front), entries in segment C2 (back)}; rows of maxneigh entries
+  int MD_G *numneigh, *neigh;  // per cluster: MD_BAND_CNT 16-bit cumulative counts (A+B, then + each skin band in turn); rows of maxneigh entries
+  float MD_G *dslot;           // per slot: upper bound of the atom's displacement since the rows were built (pads 0); null in the flows without slots
   // ewald
   const int MD_G *kn;    // 3 ints per k
   const int MD_G *krun;  // per k: +-(number of following k-vectors that continue its row: same n1, n2; n3 + 1 or n3 - 1 each), sign = direction
