@@ -316,6 +316,12 @@ int scema_md_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid,
  * would walk its rows: out[0] = K (bands), then K skin entries listed per band, K walked per band, rows with skin entries, rows with a band
  * open, rows with every band open.  cap >= 2 K + 4. */
 int scema_md_debug_skin_bands(scema_md_engine *e, int32_t pos, uint64_t *out, int32_t cap);
+/* The neighbour rows of a row potential (Stillinger-Weber ... ADP) for the replica at position pos of the last run or
+ * static evaluation of such a potential, as its last list build left them: info[6] = atoms n, row capacity, 1 if the rows were built
+ * through cells (0: the N^2 build), the cell grid ncell[3] (0 0 0 on the N^2 build).  With cnt and rows non-NULL: cnt[n] entries per row
+ * and rows[n][capacity], an entry = atom | image code << 24, ascending by atom; rows_cap (in entries) < n * capacity, or no such run, is
+ * an error with a message.  Both builds write the same rows: SCEMA_MD_ROW_CELLS chooses between them (performance only). */
+int scema_md_debug_rows(scema_md_engine *e, int32_t pos, int32_t *cnt, int32_t *rows, int64_t rows_cap, int32_t *info);
 /* One "run": nsteps of Verlet + SHAKE + NVT (+deform if rates) (+pressure average if press_avg). */
 int scema_md_debug_run(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, int32_t nsteps,
                        double dt, double temperature, int32_t nvt, int32_t use_shake, const double *rates,
@@ -569,6 +575,7 @@ typedef struct {
   double rx_sweep_union_ms;
   int64_t rx_sweep_symmetric; /* 1: the timed sweeps ran in the symmetric form (each pair of the matrix stored once, in its owner's row: rx_sweep_entries
                                * counts stored entries, half of the full rows'); 0: full rows */
+  int64_t row_cell_builds;    /* row potentials: the neighbour-list builds (part of neigh_builds) of replicas whose rows are built through cells */
 } scema_md_profile;
 int scema_md_get_profile(scema_md_engine *e, scema_md_profile *out, int32_t reset);
 

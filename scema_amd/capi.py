@@ -31,7 +31,7 @@ SYMBOLS = [
     "scema_md_strain_batch", "scema_md_strain", "scema_md_local_stress_device_ptr",
     "scema_md_local_stress_count", "scema_md_local_result_doubles", "scema_md_copy_local_stress", "scema_md_scatter_gathered", "scema_md_settle_update", "scema_md_has_state", "scema_md_get_state",
     "scema_md_set_state", "scema_md_drop_state", "scema_md_save_state_file", "scema_md_load_state_file", "scema_md_save_state_lammps",
-    "scema_md_init_material", "scema_md_debug_compute", "scema_md_debug_run", "scema_md_debug_skin_bands", "scema_md_get_profile", "scema_md_env_overrides",
+    "scema_md_init_material", "scema_md_debug_compute", "scema_md_debug_run", "scema_md_debug_skin_bands", "scema_md_debug_rows", "scema_md_get_profile", "scema_md_env_overrides",
     "scema_md_comm_unique_id", "scema_md_comm_init_rccl", "scema_md_comm_init_host", "scema_md_comm_destroy",
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
@@ -100,7 +100,8 @@ class Profile(C.Structure):
                 ("md_steps", C.c_int64), ("neigh_builds", C.c_int64), ("unique_pairs_per_sim", C.c_double),
                 ("evals", C.c_int64), ("list_skin_mean", C.c_double), ("pair_sims", C.c_int64), ("box_flips", C.c_int64),
                 ("rx_sweep_launches", C.c_int64), ("rx_sweep_ms", C.c_double), ("rx_sweep_entries", C.c_double), ("rx_sweep_rows", C.c_double), ("rx_sweep_col_bytes", C.c_int64),
-                ("pair_union_ms", C.c_double), ("rx_sweep_union_ms", C.c_double), ("rx_sweep_symmetric", C.c_int64)]
+                ("pair_union_ms", C.c_double), ("rx_sweep_union_ms", C.c_double), ("rx_sweep_symmetric", C.c_int64),
+                ("row_cell_builds", C.c_int64)]
 
 
 _lib = None
@@ -424,6 +425,21 @@ class Engine:
         k = int(out[0])
         return dict(K=k, listed=[int(v) for v in out[1:1 + k]], walked=[int(v) for v in out[1 + k:1 + 2 * k]],
                     rows=int(out[1 + 2 * k]), rows_open=int(out[2 + 2 * k]), rows_all_open=int(out[3 + 2 * k]))
+
+    def debug_rows(self, pos=0, rows=True):
+        """Neighbour rows of the replica at position `pos` of the last run or static evaluation of a row potential: dict(n, cap, cells
+        (1: built through cells), ncell[3], and with `rows` cnt[n] and rows[n, cap]: atom | image code << 24, ascending by atom)."""
+        info = np.zeros(6, np.int32)
+        f = lib().scema_md_debug_rows
+        f.argtypes = [_P, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        self._chk(f(self.h, pos, None, None, 0, info.ctypes.data))
+        out = dict(n=int(info[0]), cap=int(info[1]), cells=int(info[2]), ncell=[int(v) for v in info[3:6]])
+        if rows:
+            cnt = np.zeros(out["n"], np.int32)
+            tab = np.zeros((out["n"], out["cap"]), np.int32)
+            self._chk(f(self.h, pos, cnt.ctypes.data, tab.ctypes.data, tab.size, info.ctypes.data))
+            out.update(cnt=cnt, rows=tab)
+        return out
 
     def init_material(self, matid, replica, dt=2.0, temperature=300.0, nss=100, strain_ampl=0.005, strain_rate=1e-4):
         """EQMDProblem::lammps_equilibration for an equilibrated replica (init_material_problem.h:196-300): returns

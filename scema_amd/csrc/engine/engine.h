@@ -56,6 +56,7 @@
 #include "md_adp.h"
 #include "md_tersoff.h"
 #include "md_vashishta.h"
+#include "md_rowcells.h"
 #include "md_types.h"
 
 namespace scema_eng {
@@ -187,6 +188,9 @@ struct RowSlot {
   DevBuf cnt, rows, misc;
   DevBuf fp;   // embedded-atom stage: F'(rho) per atom (md_eam.h EamView)
   DevBuf adp;  // angular-dependent stage: the record {F', mu, lam} per atom (md_adp.h AdpView)
+  // rows built through cells (md_rows.h RowCells; md_rowcells.h has the rule): cell starts, counts / fill cursors, atoms by cell, cell of an atom
+  int cap_cellpad = 0, cap_ncells = 0;
+  DevBuf cstart, ccur, clist, cellof;
 };
 
 enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp };
@@ -284,6 +288,7 @@ struct Profile {
   double pair_union_ms = 0.0, rx_sweep_union_ms = 0.0;   // time with at least one timed launch in flight (launches of two half batches overlap)
   long long box_flips = 0;   // triclinic box flips applied (fix deform, flip yes)
   long long md_steps = 0, neigh_builds = 0, evals = 0;
+  long long row_cell_builds = 0;   // row potentials: the list builds of replicas whose rows are built through cells (md_rowcells.h)
   double unique_pairs_sum = 0;
   long long unique_pairs_n = 0;
   double skin_sum = 0;
@@ -410,6 +415,11 @@ struct scema_md_engine {
   std::vector<EamView> h_eamviews;
   DevBuf d_adpviews;              // angular-dependent stage: parallel to the views
   std::vector<AdpView> h_adpviews;
+  DevBuf d_rowcells;              // rows built through cells: parallel to the views (all zero for a replica on the N^2 build)
+  std::vector<RowCells> h_rowcells;
+  std::vector<unsigned char> h_rowcells_on;
+  int rows_run_ns = 0;            // replicas of the last run of a row potential if it ended well, else 0 (scema_md_debug_rows)
+  int row_cells_mode = 2;         // SCEMA_MD_ROW_CELLS 0 / 1 / unset: ROWCELL_OFF, ROWCELL_FORCE, ROWCELL_AUTO (md_rowcells.h)
   hipEvent_t row_part_done = nullptr;   // part batches of a row potential's run: the end of the second part (created on first use)
   Comm comm;
   scema::OwnerDirectory dir;   // state key -> owning rank, identical on every rank (host/sim_plan.h)
@@ -497,6 +507,7 @@ struct RowNeed {   // what the stage needs for one replica
   long long stamp = 0;          // rows built under another stamp are rebuilt
   int cap[2] = {0, 0};          // row capacities (ReaxFF: rows and near rows; row potentials: rows, 0): rows that are kept keep theirs
   int mimg[3] = {0, 0, 0};      // the image search along each box vector (0: minimum image), filled in by the driver
+  double w[3] = {0.0, 0.0, 0.0};   // row potentials: the narrowest perpendicular widths over the run (BoxRange::w), for the cell grid
 };
 struct RowRun;
 struct RowStage {

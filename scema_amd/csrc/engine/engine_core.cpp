@@ -61,6 +61,7 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_SMALL_BATCH_MAX", "largest batch that takes the cell grid with the most cells instead of the largest cells (default: launch groups of up to 31 replicas that run whole, i.e. not as part batches)"},
     {"SCEMA_MD_REBUILD_TOGETHER", "0 / 1: every replica rebuilds its neighbour rows on its own trigger / the replicas of a launch rebuild together as soon as one asks for it (default: together in launches of fewer than 128 replicas)"},
     {"SCEMA_MD_CELL_BUILD", "0: cell binning as k_bin + k_cell_scan + k_cell_fill instead of the one-launch k_cell_build"},
+    {"SCEMA_MD_ROW_CELLS", "0 / 1: the neighbour rows of the row potentials never through cells (the N^2 build for every replica) / through cells wherever the geometry allows it, whatever the size (default: for no replica -- no measured size gains in the update time, DESIGN.md 7m; rows and results do not depend on it)"},
     {"SCEMA_MD_POLY_TOL", "fit target of the real-space Ewald polynomial (default 2e-13); parity tolerances assume the default"},
     {"SCEMA_REAX_DROP_DSBO2", "ReaxFF valence-angle gradient without the dSBO2 term, as USER-REAXC is believed to compute it"},
     {"SCEMA_MD_RX_ITEM_LDS", "0 (test hook): the ReaxFF angle and torsion items add forces and dE/dDelta to the work set with device-wide atomics instead of through a workgroup's LDS tables (replicas too large for the tables do)"},
@@ -164,6 +165,7 @@ int scema_md_create(const scema_md_params *p, scema_md_engine **out) {
   }
   // test hook: start with undersized neighbour capacities, so that the overflow -> restore -> regrow path runs
   if (const char *g0 = scema_env("SCEMA_MD_NEIGH_GROW0")) e->neigh_grow = e->jtab_grow = std::max(0.05, atof(g0));
+  if (const char *rc = scema_env("SCEMA_MD_ROW_CELLS")) e->row_cells_mode = atoi(rc) != 0 ? ROWCELL_FORCE : ROWCELL_OFF;
   *out = e;
   return SCEMA_MD_OK;
 }
@@ -230,6 +232,7 @@ int scema_md_get_profile(scema_md_engine *e, scema_md_profile *out, int32_t rese
   out->pair_alg_bytes = e->prof.pair_alg_bytes;
   out->md_steps = e->prof.md_steps;
   out->neigh_builds = e->prof.neigh_builds;
+  out->row_cell_builds = e->prof.row_cell_builds;
   out->unique_pairs_per_sim = e->prof.unique_pairs_n ? e->prof.unique_pairs_sum / e->prof.unique_pairs_n : 0.0;
   out->evals = e->prof.evals;
   out->list_skin_mean = e->prof.evals ? e->prof.skin_sum / (double)e->prof.evals : 0.0;

@@ -73,10 +73,18 @@ struct RowPotStage : RowStage {
   int read_back() override;
   int after_read_back(int fault, double &need) override;
   int faults(int fault) override;
+  // the stage's kernels for the positions [pos0, pos0 + n) (every stage reaches the row build through mdk_rows_build), and its own
+  // "too many neighbours" fault
+  virtual void launch(hipStream_t st, int pos0, int n) = 0;
+  virtual int crowded(int fault);
+  void forces(hipStream_t st, int pos0, int n, int step, int part) override;
+  long cells_missed = 0;        // launch groups whose cell launch did not match their replicas' paths (forces)
 };
 
 RowPotStage::RowPotStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowStage(pot.kind, 16), e(e_), what(pot.name) {
   e->h_rowviews.assign(ns, RowView());
+  e->h_rowcells.assign(ns, RowCells());
+  e->h_rowcells_on.assign(ns, 0);
 }
 
 // Part batches: part 0 on the engine's main stream, part 1 on its third.  The split follows the other paths' shape, SCEMA_MD_SPLIT=0 /
@@ -97,6 +105,7 @@ int RowPotStage::rows(Topo &T, const BoxRange &R, RowNeed &need) {
   // only multiplied `cap` would be swallowed by the floor -- 17 neighbours in a 30 A box were still not held after six attempts)
   const int floor8 = (int)std::ceil(8.0 * e->neigh_grow);
   need.cap[0] = std::max(8, (std::max(cap, floor8) + 7) / 8 * 8);
+  for (int d = 0; d < 3; d++) need.w[d] = R.w[d];   // (the cell grid of the replica: bind, once the driver has set the image search)
   return SCEMA_MD_OK;
 }
 
@@ -125,7 +134,31 @@ int RowPotStage::bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, co
   ROWSET(V.stat, (int *)(W.misc.as<char>() + 32));     // 2 ints
   e->h_zerotab.push_back(MdkZero{W.misc.as<int>(), 16});   // (the step sums)
   ROWSET(V.tab, row_material(e, T.matid, kind)->d_tab.p);
+  // Rows through cells (md_rowcells.h: minimum image, 3 cells and more per dimension over the whole run, a capacity the build kernel
+  // stages, the size threshold or SCEMA_MD_ROW_CELLS).  The grid is this run's: it is rebuilt with the rows at every rebuild and nothing
+  // of it outlives the run, and the rows are those of k_row_build entry for entry, so rows kept from a run on the other path hold
+  // (the slot's ListSig has no field for the path).
+  RowCells G;
+  std::memset(&G, 0, sizeof G);
+  if (rowcell_grid(need.w, need.rlist, need.mimg, cap, V.n, npad, e->row_cells_mode, G.nc)) {
+    G.ncells = G.nc[0] * G.nc[1] * G.nc[2];
+    if (npad > W.cap_cellpad) {
+      HIPCHK(W.clist.ensure((size_t)npad * 4));
+      HIPCHK(W.cellof.ensure((size_t)npad * 4));
+      W.cap_cellpad = npad;
+    }
+    if (G.ncells > W.cap_ncells) {
+      HIPCHK(W.cstart.ensure(((size_t)G.ncells + 1) * 4));
+      HIPCHK(W.ccur.ensure((size_t)G.ncells * 4));
+      W.cap_ncells = G.ncells;
+    }
+    ROWSET(G.cstart, W.cstart.as<int>()); ROWSET(G.ccur, W.ccur.as<int>());
+    ROWSET(G.clist, W.clist.as<int>()); ROWSET(G.cellof, W.cellof.as<int>());
+    V.cells = 1;
+  }
   e->h_rowviews[pos] = V;
+  e->h_rowcells[pos] = G;
+  e->h_rowcells_on[pos] = V.cells ? 1 : 0;
   return SCEMA_MD_OK;
 }
 
@@ -134,6 +167,14 @@ int RowPotStage::upload() {
   HIPCHK(e->d_rowviews.ensure(bytes));
   HIPCHK(hipMemcpyAsync(e->d_rowviews.p, e->h_rowviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
   VV = e->d_rowviews.as<RowView>();
+  // the cell arrays travel only where a replica uses them; the launches of this thread learn either way which positions do (md_rows.h)
+  const bool any = std::any_of(e->h_rowcells_on.begin(), e->h_rowcells_on.end(), [](unsigned char c) { return c != 0; });
+  if (any) {
+    const size_t cb = e->h_rowcells.size() * sizeof(RowCells);
+    HIPCHK(e->d_rowcells.ensure(cb));
+    HIPCHK(hipMemcpyAsync(e->d_rowcells.p, e->h_rowcells.data(), cb, hipMemcpyHostToDevice, e->stream));
+  }
+  mdk_rows_cells(VV, any ? e->d_rowcells.as<RowCells>() : nullptr, e->h_rowcells_on.data(), (int)e->h_rowcells_on.size());
   return SCEMA_MD_OK;
 }
 
@@ -147,12 +188,31 @@ int RowPotStage::part_streams(std::vector<Part> &parts, std::vector<hipEvent_t> 
 int RowPotStage::read_back() { return run->read_scalars(); }
 
 int RowPotStage::after_read_back(int fault, double &need) {
-  for (int pos = 0; pos < run->ns; pos++)
+  for (int pos = 0; pos < run->ns; pos++) {
     need = std::max(need, (double)e->h_sc[run->order[pos]].maxneigh_seen / (double)std::max(e->h_rowviews[pos].cap, 1));
+    if (e->h_rowcells_on[pos]) e->prof.row_cell_builds += e->h_sc[run->order[pos]].nbuilds;
+  }
   return faults(fault);
 }
 
+// A replica marked RowView::cells leaves k_row_build at its top, so a launch group that holds one must have got the cell kernels, and
+// mdk_rows_build learns the paths from what upload() bound on this thread (md_rows.h): every launch is checked against the stage's own
+// flags, and a run in which one did not match ends in an error instead of forces from rows that were never built.
+void RowPotStage::forces(hipStream_t st, int pos0, int n, int, int) {
+  const long before = mdk_rows_cell_groups();
+  launch(st, pos0, n);
+  bool want = false;
+  for (int k = pos0; k < pos0 + n && k < (int)e->h_rowcells_on.size(); k++) want = want || e->h_rowcells_on[k] != 0;
+  if (want != (mdk_rows_cell_groups() != before)) cells_missed += 1;
+}
+
 int RowPotStage::faults(int fault) {
+  if (cells_missed)
+    return fail(e, SCEMA_MD_ERR_DEVICE, "%ld launch groups of this %s run were issued without the row build their replicas are laid out for (cell path)", cells_missed, what);
+  return crowded(fault);
+}
+
+int RowPotStage::crowded(int fault) {
   if (fault & 128) return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside the %s cutoff", ROW_MAXIN, what);
   return SCEMA_MD_OK;
 }
@@ -163,14 +223,14 @@ namespace {
 
 struct SwStage : RowPotStage {
   using RowPotStage::RowPotStage;
-  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+  void launch(hipStream_t st, int pos0, int n) override { mdk_sw_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
 // (Tersoff and its forms tersoff/mod(/c) and tersoff/zbl: one stage, the form's launch wrapper)
 template <void (*Launch)(hipStream_t, const SimDev *, RowView *, int, int)>
 struct TsStage : RowPotStage {
   using RowPotStage::RowPotStage;
-  void forces(hipStream_t st, int pos0, int n, int, int) override { Launch(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+  void launch(hipStream_t st, int pos0, int n) override { Launch(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
 };
 
 // What the two passes of the embedded-atom stage hand from one to the other, F'(rho) per atom, lives in the slot too and reaches the
@@ -192,8 +252,8 @@ struct EamStage : RowPotStage {
     AA = e->d_eamviews.as<EamView>();
     return SCEMA_MD_OK;
   }
-  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_eam_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
-  int faults(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
+  void launch(hipStream_t st, int pos0, int n) override { mdk_eam_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
+  int crowded(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
 };
 
 // The angular-dependent stage hands ten doubles per atom from its first pass to its second (md_adp.h AdpView): the slot's own array again
@@ -214,15 +274,15 @@ struct AdpStage : RowPotStage {
     AA = e->d_adpviews.as<AdpView>();
     return SCEMA_MD_OK;
   }
-  void forces(hipStream_t st, int pos0, int n, int, int) override { mdk_adp_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
-  int faults(int) override { return SCEMA_MD_OK; }   // (as for EAM: no list of 32)
+  void launch(hipStream_t st, int pos0, int n) override { mdk_adp_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
+  int crowded(int) override { return SCEMA_MD_OK; }   // (as for EAM: no list of 32)
 };
 
 // Vashishta: the list of ROW_MAXIN entries holds the neighbours inside r0, the three-body range, alone; the pair term takes any number
 // inside rc (158 in SiC), so the refusal names r0
 struct VsStage : TsStage<mdk_vs_forces> {
   using TsStage<mdk_vs_forces>::TsStage;
-  int faults(int fault) override {
+  int crowded(int fault) override {
     if (fault & 128)
       return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside r0, the three-body range of the %s potential (inside rc any number is taken)",
                   ROW_MAXIN, what);
@@ -250,7 +310,9 @@ const RowPot row_pots[ROW_NPOT] = {
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
   const std::unique_ptr<RowStage> stage(pot.stage(e, (int)sims.size(), pot));
-  return run_rows(e, sims, spec, *stage);
+  const int rc = run_rows(e, sims, spec, *stage);
+  if (rc == SCEMA_MD_OK) e->rows_run_ns = (int)sims.size();
+  return rc;
 }
 
 // The one line of in.strain.lammps that names a potential file of extension `ext` -- `pair_coeff * * ${locs}/<name><ext> <El> ...`, ${locs}
@@ -372,6 +434,26 @@ static int row_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, co
 }  // namespace scema_eng
 
 extern "C" {
+
+int scema_md_debug_rows(scema_md_engine *e, int32_t pos, int32_t *cnt, int32_t *rows, int64_t rows_cap, int32_t *info) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (e->rows_run_ns <= 0) return fail(e, SCEMA_MD_ERR_ARG, "debug_rows: no run or static evaluation of a row potential has ended on this engine yet");
+  if (pos < 0 || pos >= e->rows_run_ns || (size_t)pos >= e->h_rowviews.size())
+    return fail(e, SCEMA_MD_ERR_ARG, "debug_rows: position %d of a run of %d replicas", pos, e->rows_run_ns);
+  if (!info || (!cnt != !rows)) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  const RowView &V = e->h_rowviews[pos];
+  const RowCells &G = e->h_rowcells[pos];
+  info[0] = V.n; info[1] = V.cap; info[2] = V.cells;
+  for (int d = 0; d < 3; d++) info[3 + d] = G.nc[d];
+  if (!cnt) return SCEMA_MD_OK;
+  const int64_t want = (int64_t)V.n * V.cap;
+  if (rows_cap < want) return fail(e, SCEMA_MD_ERR_ARG, "debug_rows: rows_cap %lld < n * capacity = %d * %d", (long long)rows_cap, V.n, V.cap);
+  HIPCHK(hipSetDevice(e->p.device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(cnt, (const void *)V.cnt, (size_t)V.n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rows, (const void *)V.rows, (size_t)want * 4, hipMemcpyDeviceToHost));
+  return SCEMA_MD_OK;
+}
 
 int scema_md_sw_configure(scema_md_engine *e, const char *matid, const char *sw_path, const char *const *elements, int32_t n_elements,
                           int32_t energy_unit, double skin) {

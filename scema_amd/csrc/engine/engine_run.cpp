@@ -899,6 +899,7 @@ int OplsRun::finish() {
 // Advance sims[0..ns) (already assigned to slots 0..ns-1, scalars' box valid on the device).
 // On return the per-sim SimScalars are in e->h_sc.
 int run_phase(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec) {
+  e->rows_run_ns = 0;   // (scema_md_debug_rows describes the last run of a row potential that ended well)
   {   // simulations of a material with a Stillinger-Weber, Tersoff or EAM potential attached take that force stage, whichever entry point issued the run
     size_t n_pot[ROW_NPOT] = {};
     for (const ActiveSim &A : sims)

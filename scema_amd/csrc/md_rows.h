@@ -20,7 +20,7 @@ struct SimDev;
 typedef struct {
   int n, npad;               // atoms, n rounded up to 64
   int cap;                   // capacity (entries) of one neighbour row
-  int pad_;
+  int cells;                 // 1: the rows are built through cells (k_cell_bin, k_cell_rows: md_rowcells.hip; RowCells) and k_row_build returns at its top
   double rlist;              // radius the rows cover: the material's largest cutoff + list skin
   int mimg[3], pad2_;        // neighbour search: 0 0 0 = minimum image (box at least two list radii wide), else images up to mimg[d] boxes away
   double h[6], lo[3];        // box of the step: lx, ly, lz, yz, xz, xy and origin (k_row_prepare)
@@ -36,9 +36,26 @@ typedef struct {
 } RowView;
 static_assert(sizeof(double ROW_G *) == sizeof(double *), "the qualified pointers of RowView have the size of plain ones: host and device passes see one layout");
 
+// the cell arrays of a replica whose rows are built through cells (md_rowcells.h has the grid rule), parallel to the views; all zero for
+// a replica on the N^2 build
+typedef struct {
+  int nc[3], ncells;         // cells along each box vector (fractional coordinates of the step's box), their number
+  int ROW_G *cstart;         // [ncells + 1] first entry of a cell in clist
+  int ROW_G *ccur;           // [ncells] atoms of a cell while they are counted, then the fill cursor
+  int ROW_G *clist;          // [npad] atoms by cell; inside a cell in no fixed order
+  int ROW_G *cellof;         // [npad] cell of every atom
+} RowCells;
+
 // the row part of a step for the first ns replicas (k_row_prepare, k_row_wrap, k_row_build): neighbour rows where the rebuild flag of the
 // step is set; the rows cover RowView::rlist and read nothing of RowView::tab.  mdk_rows_finish is the last launch of a stage on them
-// (k_row_finish: eacc[0], eacc[1] and the fault bits into the engine's scalars)
+// (k_row_finish: eacc[0], eacc[1] and the fault bits into the engine's scalars).
+// mdk_rows_cells names, for the calling thread's launches from now on, the view array whose replicas `on` marks as built through cells and
+// the RowCells parallel to it (both on the device; `on` on the host, copied): mdk_rows_build puts the cell kernels (mdk_rowcells_build)
+// between k_row_wrap and k_row_build for a group v .. v + ns of that array that holds such a replica, and issues exactly the three launches
+// above for every other group
+void mdk_rows_cells(const RowView *views, const RowCells *cells, const unsigned char *on, int ns);
+long mdk_rows_cell_groups();   // launch groups of the calling thread that mdk_rows_build has given the cell kernels so far (the stage checks every launch against it)
+void mdk_rowcells_build(hipStream_t st, const SimDev *d, const RowView *v, const RowCells *c, int ns, int maxatoms);
 void mdk_rows_build(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms);
 void mdk_rows_finish(hipStream_t st, const SimDev *d, RowView *v, int ns);
 // a force stage on those rows: the row part, then `lacc` (replicas up to ROW_LDS_MAXPAD atoms, with the LDS force table) or `direct`, then

@@ -5,12 +5,16 @@
 //   k_row_prepare .. box -> view, rebuild bookkeeping, zero the step's sums
 //   k_row_wrap ..... zero the forces; at a rebuild wrap the atoms into the box (image counts keep the unwrapped information)
 //   k_row_build .... full neighbour rows inside cutoff + skin, rebuilt when the engine's displacement test says so (`neighbor 1.0 nsq`,
-//                    `neigh_modify every 1 delay 0 check yes`): an N^2 search, the replica's positions streamed through LDS
+//                    `neigh_modify every 1 delay 0 check yes`): an N^2 search, the replica's positions streamed through LDS.  Replicas
+//                    marked RowView::cells get the same rows from the cell kernels instead (md_rowcells.hip, launched from mdk_rows_build)
 //   k_row_finish ... energies and fault bits into the engine's scalars
 // and the launch sequence of a stage around its force kernels (mdk_row_forces).
 // Row entries carry an image code in the convention of the ReaxFF rows (md_row_entry.h): the shift of an entry is code . h with the box of
 // the STEP, so the rows hold while fix deform remaps the atoms with the box; a box flip forces a rebuild.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "md_kernels.h"
 #include "md_rowforce.h"
@@ -68,6 +72,7 @@ __global__ __launch_bounds__(ROW_BUILD_TPB) void k_row_build(const SimDev *sims,
   const SimDev &S = sims[blockIdx.y];
   if (!S.sc->rebuild) return;
   const RowView &V = views[blockIdx.y];
+  if (V.cells) return;   // (its rows come from k_cell_rows, md_rowcells.hip)
   const int n = V.n;
   if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup: no barrier is left waiting)
   __shared__ double s_x[3][ROW_JT];
@@ -166,12 +171,44 @@ __global__ void k_row_finish(const SimDev *sims, const RowView *views) {
 
 static inline int cdv(int a, int b) { return (a + b - 1) / b; }
 
+// the view array the calling thread's stage has bound last (mdk_rows_cells): its replicas on the cell path as a running count by position
+namespace {
+struct RowCellsBound {
+  const RowView *views = nullptr;
+  const RowCells *cells = nullptr;
+  std::vector<int> upto;   // [ns + 1]
+};
+thread_local RowCellsBound t_bound;
+thread_local long t_cell_groups = 0;
+}  // namespace
+
+void mdk_rows_cells(const RowView *views, const RowCells *cells, const unsigned char *on, int ns) {
+  t_bound.views = views;
+  t_bound.cells = cells;
+  t_bound.upto.assign((size_t)std::max(ns, 0) + 1, 0);
+  for (int k = 0; k < ns; k++) t_bound.upto[k + 1] = t_bound.upto[k] + (on[k] ? 1 : 0);
+}
+
+long mdk_rows_cell_groups() { return t_cell_groups; }
+
 void mdk_rows_build(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms) {
   if (ns <= 0 || maxatoms <= 0) return;
   const dim3 gt((unsigned)cdv(maxatoms, ROW_TILE), (unsigned)ns, 1);
   hipLaunchKernelGGL(k_row_prepare, dim3(ns), dim3(64), 0, st, d, v);
   hipLaunchKernelGGL(k_row_wrap, dim3((unsigned)cdv(maxatoms, TPB), (unsigned)ns, 1), dim3(TPB), 0, st, d, v);
-  hipLaunchKernelGGL(k_row_build, gt, dim3(ROW_BUILD_TPB), 0, st, d, v);
+  // replicas of this group whose rows are built through cells: none unless the group lies inside the array the stage has bound
+  int oncells = 0;
+  const RowCellsBound &B = t_bound;
+  const long nb = (long)B.upto.size() - 1;
+  if (B.views && nb > 0 && v >= B.views && v - B.views + ns <= nb) {
+    const long p0 = v - B.views;
+    oncells = B.upto[p0 + ns] - B.upto[p0];
+    if (oncells > 0) {
+      mdk_rowcells_build(st, d, v, B.cells + p0, ns, maxatoms);
+      t_cell_groups += 1;
+    }
+  }
+  if (oncells < ns) hipLaunchKernelGGL(k_row_build, gt, dim3(ROW_BUILD_TPB), 0, st, d, v);
 }
 
 void mdk_rows_finish(hipStream_t st, const SimDev *d, RowView *v, int ns) {

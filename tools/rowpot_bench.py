@@ -12,7 +12,7 @@ One warm-up update, then the timed ones, each continuing from the states of the 
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -48,38 +48,41 @@ def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1, basis_
     e.register_replica(matid, 1, capi.bare_system(types, x, box, v=v - v.mean(axis=0), masses=masses))
 
 
-def make_sw(e):
-    e.load_lammps_restart("sic", 1, os.path.join(GOLD, "lammps_17Nov16_init.sic_1.bin"), 192)
+def make_sw(e, cells=None):
+    if cells is None:
+        e.load_lammps_restart("sic", 1, os.path.join(GOLD, "lammps_17Nov16_init.sic_1.bin"), 192)
+    else:
+        register_lattice(e, "sic", DIAMOND, cells, 5.431, 28.0855)
     e.sw_configure("sic", os.path.join(GOLD, "Si.sw"))
 
 
-def make_tersoff(e):
-    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.432, 28.0855)
+def make_tersoff(e, cells=None):
+    register_lattice(e, "si", DIAMOND, cells or (3, 2, 4), 5.432, 28.0855)
     e.tersoff_configure("si", os.path.join(GOLD, "SiC.tersoff"), ("Si",))
 
 
-def make_tersoff_mod(e):
-    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.429, 28.0855)
+def make_tersoff_mod(e, cells=None):
+    register_lattice(e, "si", DIAMOND, cells or (3, 2, 4), 5.429, 28.0855)
     e.tersoff_mod_configure("si", os.path.join(GOLD, "Si.tersoff.mod"), ("Si",))
 
 
-def make_tersoff_zbl(e):
-    register_lattice(e, "si", DIAMOND, (3, 2, 4), 5.432, 28.0855)
+def make_tersoff_zbl(e, cells=None):
+    register_lattice(e, "si", DIAMOND, cells or (3, 2, 4), 5.432, 28.0855)
     e.tersoff_zbl_configure("si", os.path.join(GOLD, "SiC.tersoff.zbl"), ("Si",))
 
 
-def make_eam(e):
-    register_lattice(e, "cu", FCC, (4, 4, 4), 3.615, 63.546)
+def make_eam(e, cells=None):
+    register_lattice(e, "cu", FCC, cells or (4, 4, 4), 3.615, 63.546)
     e.eam_configure("cu", os.path.join(GOLD, "CuAg.eam.alloy"), ("Cu",))
 
 
-def make_adp(e):
-    register_lattice(e, "cu", FCC, (4, 4, 4), 3.615, 63.546)
+def make_adp(e, cells=None):
+    register_lattice(e, "cu", FCC, cells or (4, 4, 4), 3.615, 63.546)
     e.adp_configure("cu", os.path.join(GOLD, "CuAg.adp"), ("Cu",))
 
 
-def make_vashishta(e):
-    register_lattice(e, "sic", ZINCBLENDE, (4, 4, 4), 4.3581, (28.0855, 12.011), basis_types=[0, 0, 0, 0, 1, 1, 1, 1])
+def make_vashishta(e, cells=None):
+    register_lattice(e, "sic", ZINCBLENDE, cells or (4, 4, 4), 4.3581, (28.0855, 12.011), basis_types=[0, 0, 0, 0, 1, 1, 1, 1])
     e.vashishta_configure("sic", os.path.join(GOLD, "SiC.vashishta"), ("Si", "C"))
 
 
@@ -96,11 +99,13 @@ def main():
     ap.add_argument("--updates", type=int, default=5)
     ap.add_argument("--nss", type=int, default=100)
     ap.add_argument("--split", type=int, default=-1, help="scema_md_batch_split: 0 whole, 1 part batches, -1 the default")
+    ap.add_argument("--cells", type=int, default=None, metavar="K", help="K x K x K lattice cells per replica instead of the potential's shape above (sw: diamond silicon of 5.431 A "
+                    "instead of the example's file); the JSON line then names the atoms and the list builds through cells (SCEMA_MD_ROW_CELLS, DESIGN.md 7m)")
     ap.add_argument("--dump", default=None, metavar="FILE", help="write the stresses of the last update as FILE (.npy, float64, one row of six per quadrature point)")
     a = ap.parse_args()
     workload, mat, make = POTENTIALS[a.potential]
     e = capi.Engine(capi.default_params())
-    make(e)
+    make(e, None if a.cells is None else (a.cells,) * 3)
     e.batch_split(a.split)
     box, _, _ = e.get_state(capi.QP_NONE, mat, 1)
     L = box[3:6] - box[:3]
@@ -127,9 +132,14 @@ def main():
         np.save(a.dump, np.array([list(o.stress) for o in res], np.float64))
     prof = e.profile()
     best, med = min(times), sorted(times)[len(times) // 2]
+    extra = {}
+    if a.cells is not None:
+        natoms = e.natoms(mat, 1)
+        workload = "%s_%d" % (workload.rsplit("_", 1)[0], natoms)
+        extra = {"cells": a.cells, "atoms": natoms, "row_cell_builds": prof["row_cell_builds"], "row_cells_env": os.environ.get("SCEMA_MD_ROW_CELLS")}
     print(json.dumps({"workload": workload, "sims": a.sims, "steps_per_eval": 10 + a.nss, "updates": a.updates, "split": e.concurrency()["split"],
                       "evals_per_s_median": a.sims / med, "evals_per_s_best": a.sims / best, "update_s": times,
-                      "replica_steps_per_s_median": a.sims * (10 + a.nss) / med, "neigh_builds": prof["neigh_builds"], "md_steps": prof["md_steps"]}))
+                      "replica_steps_per_s_median": a.sims * (10 + a.nss) / med, "neigh_builds": prof["neigh_builds"], "md_steps": prof["md_steps"], **extra}))
     e.close()
 
 
