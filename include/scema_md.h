@@ -551,6 +551,41 @@ int scema_md_adp_debug_compute(scema_md_engine *e, int32_t qp_id, const char *ma
 int scema_md_adp_read_setfl(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                             int32_t *type_map, double *head, double *masses, double *tables, int64_t tables_cap, char *errbuf, int32_t errcap);
 
+/* ---- EDIP replicas (`pair_style edip`: silicon, Justo, Bazant, Kaxiras, Bulatov and Yip, Phys. Rev. B 58, 2539 (1998), Si.edip;
+ * `pair_style edip/multi`: SiC) ----
+ * configure = `pair_style edip` (or `edip/multi`) + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1,
+ * at most 4 distinct) for the replicas of ONE material id, registered before or after the call; list skin as for scema_md_sw_configure
+ * (skin < 0: 1.0).  energy_unit 0: A and lambda of the file are eV (units metal) and are converted to kcal/mol with 23.060549; 1: as
+ * written.  The form, evaluated in closed form in FP64 (LAMMPS interpolates grids; parity with it is unpinned):
+ *   f(r) = 1 (r <= c), exp(alpha/(1 - x^-3)) with x = (r - c)/(a - c) (c < r < a), 0 (r >= a);  Z_i = sum_m f(r_im);
+ *   V2(r,Z) = A [(B/r)^rho - exp(-beta Z^2)] exp(sigma/(r - a));  g(r) = exp(gamma/(r - a));  Q(Z) = Q0 exp(-mu Z);
+ *   tau(Z) = u1 + u2 (u3 exp(-u4 Z) - exp(-2 u4 Z));  h(l,Z) = lambda [(1 - exp(-Q (l + tau)^2)) + eta Q (l + tau)^2];
+ *   E = sum_i [ sum_{j != i} V2(r_ij, Z_i) + sum_{j<k} g(r_ij) g(r_ik) h(cos theta_jik, Z_i) ],  the pair sum over ordered pairs (no 1/2).
+ * Forces are the exact gradient, the part (dE_i/dZ_i) f'(r_im) on every neighbour m of i included.  Simulations of such a material take
+ * the EDIP force stage whatever MDSim.force_field says: no SHAKE, no k-space, no bonded terms.  At most 32 neighbours of an atom may lie
+ * inside a (cutoffA): more is an error of the run, never a truncation.  An update or run that mixes them with simulations of other
+ * materials is refused with SCEMA_MD_ERR_ARG.  A material holds ONE attachment: configuring replaces whatever it held, of any kind.  A
+ * bare replica whose material has nothing attached configures itself at a scema_md_strain_batch from the line
+ * `pair_coeff * * ${locs}/<name>.edip <El> ...` of <scripts_folder>/in.strain.lammps (energy unit eV), searched after every other
+ * extension; a malformed line of that kind is SCEMA_MD_ERR_ARG.  Not built: LAMMPS' interpolation grids. */
+int scema_md_edip_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                            int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], two-body and three-body energy (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz), info[4]: longest neighbour row
+ * the build asked for, row capacity, ordered pairs inside a (each pair counts at both ends), triplets */
+int scema_md_edip_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
+                                double *virial, double *info);
+/* The reader of LAMMPS *.edip files as a pure host function (no GPU, no engine).  `#` starts a comment; an entry is three element names and
+ * seventeen numbers (A B cutoffA cutoffC alpha beta eta gamma lambda mu rho sigma Q0 u1 u2 u3 u4) on one line or several; the entries
+ * whose three elements are all named are kept.  n_kept, type_map as for scema_md_sw_read_params; values[n_kept][n_kept][n_kept][17] (room
+ * for 4*4*4*17): the numbers of entry i j k, A and lambda in kcal/mol.  A B rho beta sigma a c alpha gamma of a pair (i, j) are those of
+ * entry i j j; lambda eta Q0 mu u1..u4 of a triplet those of entry i j k; the arm g of a triplet takes gamma and a of its own pair.  A
+ * missing triplet, a non-numeric field, a short or duplicate entry; in an entry i j j: cutoffA <= 0, cutoffC < 0, cutoffC >= cutoffA, a
+ * negative alpha, sigma, gamma or rho, B <= 0 with A != 0; entries i j k and i k j whose eight triplet numbers differ (the sum over
+ * j < k must not depend on the row's order); entries i j j and j i i whose cutoffA differ (a pair has one cutoff at both ends):
+ * SCEMA_MD_ERR_IO with the reason in errbuf. */
+int scema_md_edip_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                              int32_t *type_map, double *values, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

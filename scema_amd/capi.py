@@ -44,6 +44,7 @@ SYMBOLS = [
     "scema_md_tersoff_zbl_configure", "scema_md_tersoff_zbl_debug_compute", "scema_md_tersoff_zbl_read_params",
     "scema_md_vashishta_configure", "scema_md_vashishta_debug_compute", "scema_md_vashishta_read_params",
     "scema_md_adp_configure", "scema_md_adp_debug_compute", "scema_md_adp_read_setfl",
+    "scema_md_edip_configure", "scema_md_edip_debug_compute", "scema_md_edip_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -566,6 +567,17 @@ class Engine:
     def eam_compute(self, matid, replica, qp=QP_NONE):
         return self._row_compute("scema_md_eam_debug_compute", matid, replica, qp, "e_pair", "e_embed", "nabove")
 
+    def edip_configure(self, matid: str, path: str, elements=("Si",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style edip (edip/multi) + pair_coeff * * <path> <elements> for the replicas of one material id; energy_unit 0: A and lambda
+        are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_edip_configure", matid, path, elements, energy_unit, skin)
+
+    def edip_compute(self, matid, replica, qp=QP_NONE):
+        """npairs: ordered pairs inside a (cutoffA); ntriplets: pairs (a, b) of the lists inside a"""
+        return self._row_compute("scema_md_edip_debug_compute", matid, replica, qp, "e2", "e3", "ntriplets")
+
+    edip_debug_compute = edip_compute
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -646,6 +658,7 @@ SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", 
 TERSOFF_FIELDS = ["m", "gamma", "lambda3", "c", "d", "costheta0", "n", "beta", "lambda2", "B", "R", "D", "lambda1", "A"]
 TERSOFF_MOD_FIELDS = ["beta", "alpha", "h", "eta", "beta_ters", "lambda2", "B", "R", "D", "lambda1", "A", "n", "c1", "c2", "c3", "c4", "c5", "c0"]
 TERSOFF_ZBL_FIELDS = TERSOFF_FIELDS + ["Z_i", "Z_j", "ZBLcut", "ZBLexpscale"]
+EDIP_FIELDS = ["A", "B", "cutoffA", "cutoffC", "alpha", "beta", "eta", "gamma", "lambda", "mu", "rho", "sigma", "Q0", "u1", "u2", "u3", "u4"]
 VASHISHTA_FIELDS = ["H", "eta", "Zi", "Zj", "lambda1", "D", "lambda4", "W", "rc", "B", "gamma", "r0", "C", "costheta0"]
 
 
@@ -685,6 +698,12 @@ def tersoff_mod_read_params(path: str, elements, energy_unit: int = 0):
 def tersoff_zbl_read_params(path: str, elements, energy_unit: int = 0):
     """as tersoff_read_params for a *.tersoff.zbl file: values[n][n][n][18] in the order of TERSOFF_ZBL_FIELDS: scema_md_tersoff_zbl_read_params"""
     return _read_triplet_params("scema_md_tersoff_zbl_read_params", len(TERSOFF_ZBL_FIELDS), path, elements, energy_unit)
+
+
+def edip_read_params(path: str, elements, energy_unit: int = 0):
+    """(distinct elements kept, type_map, values[n][n][n][17] in the order of EDIP_FIELDS, A and lambda in kcal/mol) of a LAMMPS *.edip
+    file: scema_md_edip_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
+    return _read_triplet_params("scema_md_edip_read_params", len(EDIP_FIELDS), path, elements, energy_unit)
 
 
 def vashishta_read_params(path: str, elements, energy_unit: int = 0):

@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -290,6 +290,16 @@ struct VsStage : TsStage<mdk_vs_forces> {
   }
 };
 
+// EDIP: one range, a of a pair, for the pair term, the arms and the coordination alike, so the refusal names a
+struct EdipStage : TsStage<mdk_edip_forces> {
+  using TsStage<mdk_edip_forces>::TsStage;
+  int crowded(int fault) override {
+    if (fault & 128)
+      return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside a (cutoffA), the range of the %s potential", ROW_MAXIN, what);
+    return SCEMA_MD_OK;
+  }
+};
+
 template <class Stage>
 RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
 
@@ -306,6 +316,7 @@ const RowPot row_pots[ROW_NPOT] = {
      make_stage<TsStage<mdk_ts_zbl_forces>>},
     {RowKind::Vashishta, "Vashishta", "scema_md_vashishta_configure", {".vashishta", nullptr}, scema_md_vashishta_configure, make_stage<VsStage>},
     {RowKind::Adp, "ADP", "scema_md_adp_configure", {".adp", nullptr}, scema_md_adp_configure, make_stage<AdpStage>},
+    {RowKind::Edip, "EDIP", "scema_md_edip_configure", {".edip", nullptr}, scema_md_edip_configure, make_stage<EdipStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -565,6 +576,22 @@ int scema_md_adp_configure(scema_md_engine *e, const char *matid, const char *pa
 int scema_md_adp_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_manybody,
                                double *virial, double *info) {
   return row_debug_compute(e, RowKind::Adp, qp_id, matid, replica, f, e_pair, e_manybody, virial, info);
+}
+
+int scema_md_edip_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                            int32_t energy_unit, double skin) {
+  EdipTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_edip_params(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::Edip, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_edip_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
+                                double *virial, double *info) {
+  return row_debug_compute(e, RowKind::Edip, qp_id, matid, replica, f, e2, e3, virial, info);
 }
 
 }  // extern "C"

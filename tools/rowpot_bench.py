@@ -1,6 +1,7 @@
 """Throughput of a force stage on full neighbour rows: N quadrature points (default 576) x one replica, 10 straining + 100 sampling steps
 per evaluation at 1 fs.  The replica per potential:
   sw ....... the 192-atom silicon replica of the reference's example (tests/golden/lammps_17Nov16_init.sic_1.bin with tests/golden/Si.sw)
+  edip ..... the same 192-atom silicon replica as sw, under tests/golden/Si.edip (pair_style edip)
   tersoff .. 192 atoms of diamond silicon (3 x 2 x 4 cells of 5.432 A, thermal velocities at 300 K, tests/golden/SiC.tersoff)
   tersoff_mod, tersoff_zbl .. the same 192 silicon atoms under tests/golden/Si.tersoff.mod (a = 5.429 A) and tests/golden/SiC.tersoff.zbl
   eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
@@ -12,7 +13,7 @@ One warm-up update, then the timed ones, each continuing from the states of the 
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -56,6 +57,14 @@ def make_sw(e, cells=None):
     e.sw_configure("sic", os.path.join(GOLD, "Si.sw"))
 
 
+def make_edip(e, cells=None):
+    if cells is None:
+        e.load_lammps_restart("sic", 1, os.path.join(GOLD, "lammps_17Nov16_init.sic_1.bin"), 192)
+    else:
+        register_lattice(e, "sic", DIAMOND, cells, 5.430, 28.0855)
+    e.edip_configure("sic", os.path.join(GOLD, "Si.edip"))
+
+
 def make_tersoff(e, cells=None):
     register_lattice(e, "si", DIAMOND, cells or (3, 2, 4), 5.432, 28.0855)
     e.tersoff_configure("si", os.path.join(GOLD, "SiC.tersoff"), ("Si",))
@@ -89,7 +98,7 @@ def make_vashishta(e, cells=None):
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
-              "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp)}
+              "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip)}
 
 
 def main():
