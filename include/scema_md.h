@@ -362,6 +362,14 @@ int scema_md_get_concurrency(const scema_md_engine *e, int32_t *out);
  * aid that makes small meshes run as several tiles (16 .. 163 840; a mesh whose smallest brick is beyond it takes the kernels without
  * LDS, scema_md_pppm_paths says so).  Results do not depend on either beyond the order of summation. */
 int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes);
+/* Binned charge assignment (meshes whose padded copy is kept whole in LDS, every nx >= 5, interpolation not tiled): the charged atoms are
+ * grouped by nearest grid point once per step (k_pppm_bins) and a lane of the spreading kernel adds the sum of up to a few atoms with one set
+ * of 125 LDS atomics.  mode 0: off; 1: on for every launch that is eligible; 2 (default): by the launch policy -- replicas per launch and
+ * mean charged atoms per grid point; -1 keeps.  SCEMA_MD_PPPM_BINNED=0/1 in the environment forces 0 / 1 whatever is set here.  Results do
+ * not depend on it beyond the order of summation. */
+int scema_md_pppm_binning(scema_md_engine *e, int32_t mode);
+/* spreading launches of this engine that took the binned kernels so far (a test reads this), or a negative error code */
+long long scema_md_pppm_binned_launches(const scema_md_engine *e);
 /* out[8], for the last PPPM launch group: {charge assignment: 0 whole mesh in LDS, 1 tiled, 2 global atomics; interpolation: 0 staged, 1 tiled,
  * 2 unstaged; largest tile counts of the assignment in y and z; of the interpolation in y and z (1 1 where the kernel is not the tiled one);
  * the LDS budget in force in bytes; the mode} */

@@ -36,7 +36,7 @@ SYMBOLS = [
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
-    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
+    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_binning", "scema_md_pppm_binned_launches", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
     "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
     "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
@@ -482,6 +482,15 @@ class Engine:
         """tiled PPPM kernels for meshes beyond the LDS (1, default) or the kernels without LDS (0); lds_bytes: the LDS budget of the
         tile rule and the whole-mesh tests (0: device default); -1 keeps a setting"""
         self._chk(lib().scema_md_pppm_tiling(self.h, C.c_int32(mode), C.c_int32(lds_bytes)))
+
+    def pppm_binning(self, mode: int = -1):
+        """binned charge assignment: 0 off, 1 on for every eligible launch, 2 (default) by the launch policy; -1 keeps"""
+        self._chk(lib().scema_md_pppm_binning(self.h, C.c_int32(mode)))
+
+    def pppm_binned_launches(self) -> int:
+        """spreading launches that took the binned kernels so far"""
+        lib().scema_md_pppm_binned_launches.restype = C.c_longlong
+        return int(lib().scema_md_pppm_binned_launches(self.h))
 
     def pppm_paths(self) -> dict:
         """what the last PPPM launch group took: spread 0 whole / 1 tiled / 2 global atomics, force 0 staged / 1 tiled / 2 unstaged,

@@ -145,6 +145,7 @@ struct Topo {
   std::vector<double> q, mass_atom, lj;
   int nbonds = 0, nbonds_noshake = 0, nangles = 0, ndihedrals = 0, nimpropers = 0, nspecial = 0, nclus = 0, ncons = 0, nfree = 0;
   double qsqsum = 0, qsum = 0, excl_cut = 0;
+  int ncharged = 0;   // atoms with a charge
   double init_box[9];
   std::vector<double> init_x, init_v;
   // device copies
@@ -379,6 +380,8 @@ struct scema_md_engine {
   std::vector<std::unique_ptr<DevBuf>> bak_x, bak_v;
   int pppm_tile_mode = 1, pppm_lds_bytes = 0;   // scema_md_pppm_tiling: tiled kernels for meshes beyond the LDS; forced LDS budget (0: mdk_pppm_lds_limit())
   int pppm_paths[8] = {0, 0, 0, 0, 0, 0, 0, 1}; // scema_md_pppm_paths: what the last PPPM launch group took
+  int pppm_bin_mode = 2;                        // scema_md_pppm_binning: binned charge assignment 0 off, 1 wherever eligible, 2 by the launch policy (PppmBinPolicy)
+  long long pppm_binned_launches = 0;           // scema_md_pppm_binned_launches: spreading launches that took the binned kernels
   std::map<std::array<int, 6>, hipfftHandle> pppm_plans;   // (nx, ny, nz, batch, stream, distance between grids) -> batched 3-d Z2Z plan
   std::vector<int> h_kpack;   // host copy, alive until the stream has consumed the upload
   int local_stress_count = 0;

@@ -55,6 +55,7 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_PPPM_SOLVE_WIDE", "1 / 0: the in-LDS PPPM solve with 1 024 threads and three LDS grids / 512 threads and two (default: by batch size)"},
     {"SCEMA_MD_PPPM_SOLVE_TWO", "0 / 1: the in-LDS PPPM solve of the 1 024-thread shape as one / two workgroups per replica, one per transform back (default: two for batches under 8 replicas)"},
     {"SCEMA_MD_PPPM_PADX", "0: the LDS grid of the PPPM spreading kernel without the five pad points per x row (an address addition per stencil point instead of a constant offset)"},
+    {"SCEMA_MD_PPPM_BINNED", "0 / 1: the charge assignment of meshes kept whole in LDS never / wherever eligible as k_pppm_bins + k_pppm_spread_binned, atoms grouped by nearest grid point (default: by launch size and atoms per grid point)"},
     {"SCEMA_MD_PPPM_FFT", "hipFFT for every PPPM grid (default: grids of up to 2 900 points are solved in LDS)"},
     {"SCEMA_MD_FUSED_TAIL", "0 / 1: force assembly + SHAKE + second kick as three kernels / as k_finish (default: by batch size)"},
     {"SCEMA_MD_BONDED_SIDE", "0: the bonded kernel of a small batch always on the main stream behind the pair kernel (default: behind the PPPM chain on the side stream on steps without a new influence function)"},

@@ -433,6 +433,13 @@ int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes) {
   if (lds_bytes >= 0) e->pppm_lds_bytes = lds_bytes;
   return SCEMA_MD_OK;
 }
+int scema_md_pppm_binning(scema_md_engine *e, int32_t mode) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (mode < -1 || mode > 2) return fail(e, SCEMA_MD_ERR_ARG, "scema_md_pppm_binning: mode %d (0 off, 1 wherever eligible, 2 by the launch policy, -1 keeps)", mode);
+  if (mode >= 0) e->pppm_bin_mode = mode;
+  return SCEMA_MD_OK;
+}
+long long scema_md_pppm_binned_launches(const scema_md_engine *e) { return e ? e->pppm_binned_launches : -(long long)SCEMA_MD_ERR_ARG; }
 int scema_md_pppm_paths(const scema_md_engine *e, int32_t out[8]) {
   if (!e || !out) return SCEMA_MD_ERR_ARG;
   for (int k = 0; k < 8; k++) out[k] = e->pppm_paths[k];

@@ -136,6 +136,7 @@ struct Layout {
   int maxbt = 1, maxloc = 1, maxcoef = 0, maxrow = 64, maxcapj = 64, maxpoly = 1, maxatoms = 0, maxpad = 0, maxcells = 0, maxk = 0, mmax = 1,
       maxgrp = 0, maxclus = 0, maxunits = 0, maxsteps = 0;
   int maxgrid = 0, maxgridp = 0, maxdims = 0;   // PPPM: largest grid of the batch, ... with five more points per x row, largest nx + ny + nz
+  long long sum_charged = 0, sum_grid = 0;      // PPPM replicas: charged atoms and mesh points (binned charge assignment: atoms per point)
   bool padx_ok = true;                          // (the padded LDS copies of the spreading and interpolation kernels fold five distinct pad columns per row)
   PppmLaunch tl;                                // tiled PPPM kernels: budget, mode and the largest tile counts and LDS sizes of the batch (md_pppm_tile.h)
   bool tl_sp_fits = true, tl_fo_fits = true;    // no mesh of the batch whose smallest brick is beyond the budget
@@ -425,6 +426,7 @@ int OplsRun::lay_out_sim(int pos) {
     for (int d = 0; d < 3; d++) S.pg[d] = -ew.kmaxd[d];
     L.maxgrid = std::max(L.maxgrid, S.pg[0] * S.pg[1] * S.pg[2]);
     if (S.pg[0] < 5) L.padx_ok = false;
+    L.sum_charged += T.ncharged; L.sum_grid += (long long)S.pg[0] * S.pg[1] * S.pg[2];
     L.maxgridp = std::max(L.maxgridp, (S.pg[0] + 5) * S.pg[1] * S.pg[2]);
     for (int which = 0; which < 2; which++) {
       const PppmTile t = pppm_tile_shape(S.pg[0], S.pg[1], S.pg[2], L.tl.budget, which);
@@ -554,8 +556,9 @@ int OplsRun::lay_out_kspace() {
   if (L.maxgrid > 0) {
     const size_t mg = (size_t)L.maxgrid;
     // (behind the influence function of every simulation, pgstride doubles into its block: the home-tile keys of its atoms, one int each --
-    // k_pppm_keys; md_types.h, whose text the pair kernel's counters are pinned to, keeps its SimDev)
-    const size_t gfs = mg + ((size_t)L.maxatoms + 1) / 2;
+    // k_pppm_keys; md_types.h, whose text the pair kernel's counters are pinned to, keeps its SimDev -- or, in the same place, the lists of the
+    // binned charge assignment: item count, an item of two ints per atom at most, the charged atoms by bin: k_pppm_bins.  A launch takes either.)
+    const size_t gfs = mg + (3 * (size_t)L.maxatoms + 2 + 1) / 2;
     HIPCHK(e->d_pppm.ensure((size_t)ns * (mg * 4 * sizeof(double2) + gfs * sizeof(double))));
     double *gbase = e->d_pppm.as<double>(), *ebase = gbase + (size_t)ns * mg * 2, *fbase = gbase + (size_t)ns * mg * 8;
     for (int pos = 0; pos < ns; pos++) {
@@ -610,7 +613,17 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
     std::memcpy(e->pppm_paths, paths, sizeof paths);
   }
   if (sp_path == 1 || fo_path == 1) mdk_pppm_keys(st, Dp, na, L.maxatoms);   // home tiles from the positions of this step
-  mdk_pppm_spread(st, Dp, na, L.maxgrid, L.maxatoms, clean ? 1 : 0, maxgridp, &L.tl);   // (the tiled kernel stores every point: no zero launch)
+  // Binned charge assignment: one more launch on the chain, which a small launch waits for and a large one wins back several times over
+  // (PppmBinPolicy; SCEMA_MD_PPPM_BINNED and scema_md_pppm_binning force either)
+  static const int binned_env = scema_env("SCEMA_MD_PPPM_BINNED") ? (atoi(scema_env("SCEMA_MD_PPPM_BINNED")) != 0 ? 1 : 0) : -1;
+  const int bin_mode = binned_env >= 0 ? binned_env : e->pppm_bin_mode;
+  PppmLaunch tl = L.tl;
+  if (bin_mode != 0 && mdk_pppm_binned_ok(L.maxgrid, maxgridp, &L.tl)) {
+    const PppmBinPolicy bp;
+    tl.binned = bin_mode == 1 || (na >= bp.min_replicas && (double)L.sum_charged >= bp.min_per_point * (double)L.sum_grid) ? 1 : 0;
+  }
+  if (tl.binned) e->pppm_binned_launches += 1;
+  mdk_pppm_spread(st, Dp, na, L.maxgrid, L.maxatoms, clean ? 1 : 0, maxgridp, &tl);   // (the tiled kernel stores every point: no zero launch)
   clean = false;
   if (pol.pppm_in_lds) {   // small grids: the whole solve in one launch, in LDS (md_pppm.hip k_pppm_solve); it leaves the charge grids zeroed
     if (new_box) mdk_pppm_gf(st, Dp, na, L.maxgrid);

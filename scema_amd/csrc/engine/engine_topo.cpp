@@ -38,6 +38,7 @@ int build_topo(scema_md_engine *e, const scema_md_system *s, Topo &t) {
     t.type[i] = cls[s->type[i]];
     t.mass_atom[i] = s->mass[s->type[i]];
     t.qsqsum += t.q[i] * t.q[i];
+    t.ncharged += t.q[i] != 0.0 ? 1 : 0;
     t.qsum += t.q[i];
   }
   const int nt2 = ncls * ncls;

@@ -12,7 +12,16 @@ struct PppmLaunch {
   int budget = 0, mode = 1;
   int sp_ty = 0, sp_tz = 0, sp_tiles = 0, fo_ty = 0, fo_tz = 0, fo_tiles = 0;
   size_t sp_lds = 0, fo_lds = 0;
+  int binned = 0;   // this launch: the binned pair of spreading kernels where mdk_pppm_binned_ok (the engine decides: pppm_stage)
 };
+// Binned charge assignment (k_pppm_bins + k_pppm_spread_binned): from how many replicas per launch, and from how many charged atoms per
+// grid point in the mean, the pair of launches is taken when nothing forces it (scema_md_pppm_binning mode 2).  k_pppm_bins is one more
+// launch on the chain, one workgroup per replica: PE-10k, evaluations/s off / on by batch (replicas per launch): 1: 75.9 / 66.0, 4: 206.1 /
+// 193.5, 9 (3): 302.5 / 291.3, 36 (9): 436.5 / 430.8, 72 (36): 444.7 / 440.4, 144 (72): 455.7 / 462.8, 576 (288): 461.2 / 471.4
+// (profiles/pppm_binned_size_scan.log, pppm_binned_headline_ab.log).  Below two atoms per point there is nothing to merge.
+struct PppmBinPolicy { int min_replicas = 72; double min_per_point = 2.0; };
+// 1: the launch may take the binned kernels -- the whole padded mesh in LDS (spread path 0, every nx >= 5), no tiled interpolation
+int mdk_pppm_binned_ok(int maxgrid, int maxgridp, const PppmLaunch *tl);
 // 0: the whole mesh in LDS, 1: tiled, 2: no LDS (global atomics / unstaged reads) -- what mdk_pppm_spread / mdk_pppm_force take and return
 int mdk_pppm_spread_path(int maxgrid, int maxgridp, const PppmLaunch *tl);
 int mdk_pppm_force_path(int maxgrid, const PppmLaunch *tl);

@@ -7,6 +7,8 @@
 // launch group (they share the grid).  One launch per stage for the whole batch:
 //   k_pppm_spread   a few workgroups per replica, each with a private copy of the real grid in LDS while its atoms are spread
 //                   (ds_add_f64), added to the complex input of the transform at the end (grids beyond the LDS: global atomics)
+//   k_pppm_bins, k_pppm_spread_binned   large launches of meshes whose padded copy fits: the atoms grouped by nearest grid point first, a
+//                   lane adds the sum of a few atoms with one set of 125 atomics
 //   k_pppm_gf       influence function of the current box, 125 alias terms per mode; only when the box has changed
 //   k_pppm_poisson  energy, virial, field spectra -i k G rho(k)
 //   k_pppm_force    per atom: the 125 grid points of three field grids (staged in LDS when they fit), added to the forces the
@@ -70,10 +72,13 @@ __device__ __forceinline__ void pppm_wrap(int i, int n, int (&g)[PP_ORDER]) {
 #pragma unroll
     for (int k = 0; k < PP_ORDER; k++) g[k] = pmod(i + k - 2, n);
 }
-__device__ __forceinline__ void atom_lamda(const SimDev &S, const BoxD &b, int a, double &t0, double &t1, double &t2) {
-  const double d0 = S.x[3 * a] - b.lo[0], d1 = S.x[3 * a + 1] - b.lo[1], d2 = S.x[3 * a + 2] - b.lo[2];
+__device__ __forceinline__ void pos_lamda(const BoxD &b, double x0, double x1, double x2, double &t0, double &t1, double &t2) {
+  const double d0 = x0 - b.lo[0], d1 = x1 - b.lo[1], d2 = x2 - b.lo[2];
   const double l0 = b.hinv[0] * d0 + b.hinv[5] * d1 + b.hinv[4] * d2, l1 = b.hinv[1] * d1 + b.hinv[3] * d2, l2 = b.hinv[2] * d2;
   t0 = l0 - floor(l0); t1 = l1 - floor(l1); t2 = l2 - floor(l2);
+}
+__device__ __forceinline__ void atom_lamda(const SimDev &S, const BoxD &b, int a, double &t0, double &t1, double &t2) {
+  pos_lamda(b, S.x[3 * a], S.x[3 * a + 1], S.x[3 * a + 2], t0, t1, t2);
 }
 
 // grid 0 <- 0 for the spreading kernels that add to it from several workgroups
@@ -81,6 +86,40 @@ __global__ __launch_bounds__(256) void k_pppm_zero(const SimDev *sims) {
   const SimDev &S = sims[blockIdx.y];
   const int NG = S.pg[0] * S.pg[1] * S.pg[2], idx = blockIdx.x * 256 + threadIdx.x;
   if (idx < NG) ((double2 *)S.pgrid)[idx] = make_double2(0.0, 0.0);
+}
+
+extern __shared__ double s_grid[];
+// The workgroup's LDS copy of the charge grid leaves: added to grid 0 (a direct store when the replica has one workgroup).  PADX: after the
+// five pad columns of every row are folded back onto the points they alias.
+template <bool PADX>
+__device__ __forceinline__ void pppm_grid_out(const SimDev &S, int nx, int ny, int nz, int split) {
+  const int NG = nx * ny * nz, T = (int)blockDim.x, nxp = PADX ? nx + 5 : nx;
+  double2 *rho = (double2 *)S.pgrid;
+  __syncthreads();
+  if (PADX) {
+    // column c of a padded row holds grid point c - 2: columns 0, 1 belong to nx - 2, nx - 1 and columns nx + 2 .. nx + 4 to 0, 1, 2
+    // (five distinct targets per row as nx >= 5: plain additions, one thread each)
+    const int nrow = ny * nz;
+    for (int k = threadIdx.x; k < 5 * nrow; k += T) {
+      const int row = k / 5, pc = k - 5 * row;
+      const int src = pc < 2 ? pc : nx + pc, dst = (pc < 2 ? nx - 2 + pc : pc - 2) + 2;
+      s_grid[row * nxp + dst] += s_grid[row * nxp + src];
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < NG; k += T) {
+      const int row = k / nx, x = k - row * nx;
+      const double v = s_grid[row * nxp + x + 2];
+      if (split == 1) rho[k] = make_double2(v, 0.0);
+      else if (v != 0.0) atomicAdd(&rho[k].x, v);
+    }
+  } else if (split == 1) {
+    for (int k = threadIdx.x; k < NG; k += T) rho[k] = make_double2(s_grid[k], 0.0);
+  } else {
+    for (int k = threadIdx.x; k < NG; k += T) {
+      const double v = s_grid[k];
+      if (v != 0.0) atomicAdd(&rho[k].x, v);
+    }
+  }
 }
 
 // Charge assignment.  Workgroup (s, r) takes the s-th of `split` contiguous atom ranges of replica r.  Within a wave the lanes
@@ -91,7 +130,6 @@ __global__ __launch_bounds__(256) void k_pppm_zero(const SimDev *sims) {
 // PADX (LDS only, nx >= 5): the LDS copy has nx + 5 points per x row -- an atom's five x points are columns i .. i + 4 of the padded row, never
 // wrapped, so the address of a point is the row's plus a CONSTANT (the offset field of ds_add_f64) instead of an addition per point; the five
 // pad columns are folded back onto the points they alias before the copy leaves.
-extern __shared__ double s_grid[];
 template <bool LDS, int TPB_, bool PADX = false>
 __global__ __launch_bounds__(TPB_) void k_pppm_spread(const SimDev *sims, int split) {
   const SimDev &S = sims[blockIdx.y];
@@ -172,33 +210,208 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread(const SimDev *sims, int sp
       }
     }
   }
-  if (LDS) {
-    __syncthreads();
-    if (PADX) {
-      // column c of a padded row holds grid point c - 2: columns 0, 1 belong to nx - 2, nx - 1 and columns nx + 2 .. nx + 4 to 0, 1, 2
-      // (five distinct targets per row as nx >= 5: plain additions, one thread each)
-      const int nrow = ny * nz;
-      for (int k = threadIdx.x; k < 5 * nrow; k += T) {
-        const int row = k / 5, pc = k - 5 * row;
-        const int src = pc < 2 ? pc : nx + pc, dst = (pc < 2 ? nx - 2 + pc : pc - 2) + 2;
-        s_grid[row * nxp + dst] += s_grid[row * nxp + src];
+  if (LDS) pppm_grid_out<PADX>(S, nx, ny, nz, split);
+}
+
+// (the home-tile keys of a simulation (k_pppm_keys below), or its binned lists, lie behind its influence function, pgstride doubles into the block the engine lays out: engine_run.cpp lay_out_kspace)
+__device__ __forceinline__ int MD_G *pppm_keys_of(const SimDev &S) { return (int MD_G *)(S.pgf + S.pgstride); }
+
+// ---- binned charge assignment (whole padded mesh in LDS): the atoms of a replica grouped by nearest grid point, so that one set of 125 LDS
+// atomics carries up to PP_BIN_M atoms ----
+// k_pppm_spread waits for its ds_add_f64 at the rate the LDS executes them, and all atoms with the same nearest grid point add to the same 125
+// addresses (PE-10k on 12 x 12 x 12: six atoms per point).  k_pppm_bins, one workgroup per replica and step, sorts the charged atoms by
+// the BIN of their nearest point -- x as the unwrapped index 0 .. nx (in the padded rows the points nx and 0 are different columns), y and z
+// mod n -- and cuts every bin into ITEMS of up to M atoms; a lane of k_pppm_spread_binned takes one item, sums its atoms' products in
+// registers and issues the 125 atomics once.  The lists lie where the home-tile keys of the tiled kernels lie (pppm_keys_of; a launch
+// takes either), as ints: [0] the number of items, [1] unused, then natoms items (bin | count << 24, first index into perm), then perm,
+// the charged atoms by bin.  Order of the items: round r holds part r of every bin that has one, in bin order (consecutive bins along x are
+// consecutive LDS words), so that the lanes of a wave address distinct points; the parts from PP_BIN_ROUNDS - 1 on of a bin share the last round.
+#ifndef PP_BIN_M
+#define PP_BIN_M 4
+#endif
+#define PP_BIN_TPB 1024
+#define PP_BIN_ROUNDS 4
+#define PP_BIN_BATCH 4
+extern __shared__ int s_bins[];
+// exclusive prefix sums of NV values per thread over the PP_BIN_TPB threads; tot: the sums over the workgroup
+template <int NV>
+__device__ __forceinline__ void pppm_block_scan(int (&v)[NV], int (&tot)[NV], int *lds /* NV * waves */) {
+  constexpr int NW = PP_BIN_TPB / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    int x = v[i];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    inc[i] = x;
+    if (lane == 63) lds[i * NW + wave] = x;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    int before = 0, all = 0;
+    for (int w = 0; w < NW; w++) { const int t = lds[i * NW + w]; all += t; if (w < wave) before += t; }
+    v[i] = before + inc[i] - v[i];
+    tot[i] = all;
+  }
+  __syncthreads();
+}
+__global__ __launch_bounds__(PP_BIN_TPB) void k_pppm_bins(const SimDev *sims, int M) {
+  const SimDev &S = sims[blockIdx.x];
+  const int nx = S.pg[0], ny = S.pg[1], nz = S.pg[2];
+  if (nx == 0) return;
+  const int nbx = nx + 1, nbins = nbx * ny * nz, natoms = S.natoms;
+  int *s_cnt = s_bins, *s_start = s_bins + nbins;
+  __shared__ int s_scan[(PP_BIN_ROUNDS + 1) * (PP_BIN_TPB / 64)];
+  int MD_G *head = pppm_keys_of(S);
+  int2 MD_G *items = (int2 MD_G *)(head + 2);
+  int MD_G *perm = head + 2 + 2 * (size_t)natoms;
+  for (int k = threadIdx.x; k < nbins; k += PP_BIN_TPB) s_cnt[k] = 0;
+  __syncthreads();
+  BoxD b;
+  box_derive(S.sc->box, b);
+  box_uniform(b);
+  // bin and rank within the bin of every atom (kept in the room of the items until the bins have their places).  Four atoms per thread and
+  // turn, their charges and positions requested together: the kernel waits for memory, not for arithmetic.
+  for (int a0 = threadIdx.x; a0 < natoms; a0 += PP_BIN_BATCH * PP_BIN_TPB) {
+    double q[PP_BIN_BATCH], x0[PP_BIN_BATCH], x1[PP_BIN_BATCH], x2[PP_BIN_BATCH];
+#pragma unroll
+    for (int j = 0; j < PP_BIN_BATCH; j++) {
+      const int a = min(a0 + j * PP_BIN_TPB, natoms - 1);
+      q[j] = S.q[a]; x0[j] = S.x[3 * a]; x1[j] = S.x[3 * a + 1]; x2[j] = S.x[3 * a + 2];
+    }
+#pragma unroll
+    for (int j = 0; j < PP_BIN_BATCH; j++) {
+      const int a = a0 + j * PP_BIN_TPB;
+      if (a >= natoms) break;
+      int bin = -1, rank = 0;
+      if (q[j] != 0.0) {
+        double l0, l1, l2;
+        pos_lamda(b, x0[j], x1[j], x2[j], l0, l1, l2);
+        const int ix = min(max(pppm_nearest(l0 * nx), 0), nx), iy = pmod(pppm_nearest(l1 * ny), ny), iz = pmod(pppm_nearest(l2 * nz), nz);
+        bin = (iz * ny + iy) * nbx + ix;
+        rank = atomicAdd(&s_cnt[bin], 1);
       }
-      __syncthreads();
-      for (int k = threadIdx.x; k < NG; k += T) {
-        const int row = k / nx, x = k - row * nx;
-        const double v = s_grid[row * nxp + x + 2];
-        if (split == 1) rho[k] = make_double2(v, 0.0);
-        else if (v != 0.0) atomicAdd(&rho[k].x, v);
-      }
-    } else if (split == 1) {
-      for (int k = threadIdx.x; k < NG; k += T) rho[k] = make_double2(s_grid[k], 0.0);
-    } else {
-      for (int k = threadIdx.x; k < NG; k += T) {
-        const double v = s_grid[k];
-        if (v != 0.0) atomicAdd(&rho[k].x, v);
+      items[a] = make_int2(bin, rank);
+    }
+  }
+  __syncthreads();
+  // thread t owns the bins t per .. (t + 1) per - 1: atoms before them, and items before them in every round
+  const int per = (nbins + PP_BIN_TPB - 1) / PP_BIN_TPB, b0 = min(nbins, (int)threadIdx.x * per), b1 = min(nbins, b0 + per);
+  int v[PP_BIN_ROUNDS + 1], tot[PP_BIN_ROUNDS + 1];
+#pragma unroll
+  for (int r = 0; r <= PP_BIN_ROUNDS; r++) v[r] = 0;
+  for (int k = b0; k < b1; k++) {
+    const int n = s_cnt[k], parts = (n + M - 1) / M;
+    v[PP_BIN_ROUNDS] += n;
+#pragma unroll
+    for (int r = 0; r < PP_BIN_ROUNDS - 1; r++) v[r] += parts > r ? 1 : 0;
+    v[PP_BIN_ROUNDS - 1] += max(parts - (PP_BIN_ROUNDS - 1), 0);
+  }
+  pppm_block_scan<PP_BIN_ROUNDS + 1>(v, tot, s_scan);
+  {
+    int at = v[PP_BIN_ROUNDS];
+    for (int k = b0; k < b1; k++) { s_start[k] = at; at += s_cnt[k]; }
+  }
+  __syncthreads();
+  for (int a0 = threadIdx.x; a0 < natoms; a0 += PP_BIN_BATCH * PP_BIN_TPB) {
+    int2 br[PP_BIN_BATCH];
+#pragma unroll
+    for (int j = 0; j < PP_BIN_BATCH; j++) br[j] = items[min(a0 + j * PP_BIN_TPB, natoms - 1)];   // (this thread's own stores above)
+#pragma unroll
+    for (int j = 0; j < PP_BIN_BATCH; j++) {
+      const int a = a0 + j * PP_BIN_TPB;
+      if (a < natoms && br[j].x >= 0) perm[s_start[br[j].x] + br[j].y] = a;
+    }
+  }
+  __syncthreads();   // every (bin, rank) has been read: the items take their room
+  {
+    int at[PP_BIN_ROUNDS], base = 0;
+#pragma unroll
+    for (int r = 0; r < PP_BIN_ROUNDS; r++) { at[r] = base + v[r]; base += tot[r]; }
+    if (threadIdx.x == 0) head[0] = base;
+    for (int k = b0; k < b1; k++) {
+      const int n = s_cnt[k], first = s_start[k];
+      for (int p = 0, left = n; left > 0; p++, left -= M) {
+        int idx = 0;
+#pragma unroll
+        for (int r = 0; r < PP_BIN_ROUNDS; r++)
+          if (min(p, PP_BIN_ROUNDS - 1) == r) idx = at[r]++;
+        items[idx] = make_int2(k | (min(left, M) << 24), first + p * M);
       }
     }
   }
+}
+
+// Workgroup (s, r) takes the s-th of `split` ranges of replica r's items, a lane one item at a time.  The positions and charges of the
+// item's atoms are requested up front; every atom's weights are taken around the BIN's point (as the tiled kernels take theirs around the key:
+// an atom has one home, whatever its coordinate rounds to here), kept in registers, and the 25 rows of five points are summed over the atoms and
+// added one after the other.  The private padded LDS grid and its way out are those of k_pppm_spread<true, 256, true>.
+template <int M>
+__global__ __launch_bounds__(256) void k_pppm_spread_binned(const SimDev *sims, int split) {
+  const SimDev &S = sims[blockIdx.y];
+  const int nx = S.pg[0], ny = S.pg[1], nz = S.pg[2];
+  if (nx == 0) return;
+  const int NG = nx * ny * nz, nxp = nx + 5, NGP = nxp * ny * nz, nbx = nx + 1;
+  const int MD_G *head = pppm_keys_of(S);
+  const int2 MD_G *items = (const int2 MD_G *)(head + 2);
+  const int MD_G *perm = head + 2 + 2 * (size_t)S.natoms;
+  const int nitems = head[0];
+  const int chunk = (nitems + split - 1) / split, i0 = (int)blockIdx.x * chunk, i1 = min(nitems, i0 + chunk);
+  if (i0 >= i1 && split > 1) return;   // (a lone workgroup stores the grid, zeros included)
+  BoxD b;
+  box_derive(S.sc->box, b);
+  box_uniform(b);
+  for (int k = threadIdx.x; k < NGP; k += 256) s_grid[k] = 0.0;
+  __syncthreads();
+  const double delvolinv = (double)NG / b.vol;
+  for (int it = i0 + (int)threadIdx.x; it < i1; it += 256) {
+    const int2 item = items[it];
+    const int bin = item.x & 0xffffff, n = item.x >> 24, first = item.y;
+    const int rowb = bin / nbx, ix = bin - rowb * nbx, iz = rowb / ny, iy = rowb - iz * ny;
+    int at[M];
+    double px[M], py[M], pz[M], zq[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) at[j] = perm[first + min(j, n - 1)];   // (a short item repeats its last atom with charge 0)
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+      px[j] = S.x[3 * at[j]]; py[j] = S.x[3 * at[j] + 1]; pz[j] = S.x[3 * at[j] + 2];
+      zq[j] = j < n ? delvolinv * S.q[at[j]] : 0.0;
+    }
+    double wx[M][PP_ORDER], wy[M][PP_ORDER], wz[M][PP_ORDER];
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+      double l0, l1, l2;
+      pos_lamda(b, px[j], py[j], pz[j], l0, l1, l2);
+      pppm_blend(0.5 - ((double)ix - l0 * nx), wx[j]);
+      pppm_weights_at(l1 * ny, ny, iy, wy[j]); pppm_weights_at(l2 * nz, nz, iz, wz[j]);
+#pragma unroll
+      for (int k = 0; k < PP_ORDER; k++) wx[j][k] *= zq[j];
+    }
+    int gy[PP_ORDER], gz[PP_ORDER];
+    pppm_wrap(iy, ny, gy); pppm_wrap(iz, nz, gz);
+#pragma unroll
+    for (int c = 0; c < PP_ORDER; c++) {
+#pragma unroll
+      for (int bb = 0; bb < PP_ORDER; bb++) {
+        double acc[PP_ORDER] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+          const double zy = wz[j][c] * wy[j][bb];
+#pragma unroll
+          for (int k = 0; k < PP_ORDER; k++) acc[k] = fma(zy, wx[j][k], acc[k]);
+        }
+        double *prow = s_grid + (gz[c] * ny + gy[bb]) * nxp + ix;
+#pragma unroll
+        for (int k = 0; k < PP_ORDER; k++) (void)__hip_atomic_fetch_add(prow + k, acc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+  }
+  pppm_grid_out<true>(S, nx, ny, nz, split);
 }
 
 __device__ __forceinline__ double sinc_pow10(double x) {
@@ -525,8 +738,6 @@ __global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int spli
 // key = iy | iz << 16, bit 31: the atom is uncharged.
 #define PP_KEY_Y(key) ((key) & 0xffff)
 #define PP_KEY_Z(key) (((key) >> 16) & 0x7fff)
-// (the keys of a simulation lie behind its influence function, pgstride doubles into the block the engine lays out: engine_run.cpp lay_out_kspace)
-__device__ __forceinline__ int MD_G *pppm_keys_of(const SimDev &S) { return (int MD_G *)(S.pgf + S.pgstride); }
 __global__ __launch_bounds__(256) void k_pppm_keys(const SimDev *sims) {
   const SimDev &S = sims[blockIdx.y];
   if (S.pg[0] == 0) return;
@@ -759,6 +970,10 @@ int mdk_pppm_force_path(int maxgrid, const PppmLaunch *tl) {
   if (3 * (size_t)maxgrid * sizeof(double) <= pppm_budget(tl)) return 0;
   return tl && tl->mode != 0 && tl->fo_tiles > 0 ? 1 : 2;
 }
+int mdk_pppm_binned_ok(int maxgrid, int maxgridp, const PppmLaunch *tl) {
+  // (the lists lie where the keys of the tiled kernels lie: not beside a tiled interpolation, which reads its keys after the spreading)
+  return mdk_pppm_spread_path(maxgrid, maxgridp, tl) == 0 && pppm_padx(maxgridp, tl) && mdk_pppm_force_path(maxgrid, tl) != 1;
+}
 void mdk_pppm_keys(hipStream_t st, const SimDev *d, int ns, int maxatoms) { hipLaunchKernelGGL(k_pppm_keys, grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d); }
 int mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int zeroed, int maxgridp, const PppmLaunch *tl) {
   // maxgridp: the largest grid with five more points per x row (0: a grid of the batch has fewer than five points in x): the padded LDS copy
@@ -777,6 +992,11 @@ int mdk_pppm_spread(hipStream_t st, const SimDev *d, int ns, int maxgrid, int ma
   const bool use_lds = path == 0;
   const int split = pppm_split(ns, maxatoms);
   if ((!use_lds || split > 1) && !zeroed) hipLaunchKernelGGL(k_pppm_zero, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d);
+  if (tl && tl->binned && mdk_pppm_binned_ok(maxgrid, maxgridp, tl)) {   // the atoms by nearest grid point first, then an item of them per lane
+    hipLaunchKernelGGL(k_pppm_bins, dim3(ns), dim3(PP_BIN_TPB), 2 * (size_t)maxgridp * sizeof(int), st, d, PP_BIN_M);
+    hipLaunchKernelGGL((k_pppm_spread_binned<PP_BIN_M>), grid2(split, ns), dim3(256), lds, st, d, split);
+    return path;
+  }
   if (!use_lds) {
     hipLaunchKernelGGL((k_pppm_spread<false, 256>), grid2(split, ns), dim3(256), 0, st, d, split);
     return path;
