@@ -594,6 +594,50 @@ int scema_md_edip_debug_compute(scema_md_engine *e, int32_t qp_id, const char *m
 int scema_md_edip_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
                               int32_t *type_map, double *values, char *errbuf, int32_t errcap);
 
+/* ---- spline-MEAM replicas (`pair_style meam/spline`: Lenosky et al., Modelling Simul. Mater. Sci. Eng. 8, 825 (2000); Hennig et al.,
+ * Phys. Rev. B 78, 054121 (2008): Ti, Zr, Nb, Mo, Si, Ti-O) ----
+ * configure = `pair_style meam/spline` + `pair_coeff * * <path> <elements...>` (elements[k] = element of LAMMPS atom type k+1, at most 2
+ * distinct; the old one-element format names no element and takes any) for the replicas of ONE material id, registered before or after
+ * the call; list skin as for scema_md_sw_configure (skin < 0: 1.0).  energy_unit 0: phi and U of the file are eV (units metal) and are
+ * converted to kcal/mol with 23.060549; 1: as written.  The form:
+ *   E = sum_{i<j} phi_{ti tj}(r_ij) + sum_i [U_ti(rho_i) - U_ti(0)],
+ *   rho_i = sum_j rho_tj(r_ij) + sum_{j<k} f_tj(r_ij) f_tk(r_ik) g_{tj tk}(cos theta_jik),
+ * every function a clamped cubic spline through its knots (at most 32, equidistant or not) with the end slopes of the file and second
+ * derivatives from the tridiagonal solve (the file's third column is read and ignored), continued linearly beyond either end.  phi, rho
+ * and f are zero at and beyond their last knot, and a file in which one of them does not end with value 0 and slope 0 is refused; LAMMPS,
+ * as remembered, tests one global cutoff and lets rho and f continue linearly up to it -- the same thing for such a file (unpinned:
+ * DESIGN.md 7o).  Forces are the exact gradient.  Simulations of such a material take the spline-MEAM force stage whatever
+ * MDSim.force_field says: no SHAKE, no k-space, no bonded terms.  At most 32 neighbours of an atom may lie inside the last knot of f, the
+ * three-body range: more is an error of the run, never a truncation; inside the largest last knot (cutmax) any number is taken.  An update
+ * or run that mixes them with simulations of other materials is refused with SCEMA_MD_ERR_ARG.  A material holds ONE attachment:
+ * configuring replaces whatever it held, of any kind.  A bare replica whose material has nothing attached configures itself at a
+ * scema_md_strain_batch from the line `pair_coeff * * ${locs}/<name>.meam.spline <El> ...` of <scripts_folder>/in.strain.lammps (energy
+ * unit eV), searched after every other extension; a malformed line of that kind is SCEMA_MD_ERR_ARG.  Not built: `meam/sw/spline`. */
+int scema_md_meam_spline_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], pair energy sum phi and embedding energy sum U(rho) - U(0) (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz),
+ * info[4]: longest neighbour row the build asked for, row capacity, ordered pairs inside cutmax (each pair counts at both ends), triplets
+ * (pairs of the lists inside f's last knot) */
+int scema_md_meam_spline_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair,
+                                       double *e_embed, double *virial, double *info);
+/* The reader of meam/spline files as a pure host function (no GPU, no engine), both formats: old (a comment line, then phi rho U f g, each
+ * `N`, `d0 dN`, one skipped line, N lines `x y y2`) and new (a comment line, `meam/spline <n> <El1> .. <Eln>`, then the families phi rho U f
+ * g, pair families as the upper triangle row-major, each spline `spline3eq`, `N`, `d0 dN`, N lines `x y y2`).  n_kept, type_map as for
+ * scema_md_sw_read_params; the splines of the elements kept stand in the file's order (phi: n (n + 1) / 2, rho, U, f: n each, g), 12 at
+ * most: knots[12] their knot counts (0 beyond the last), head[8] = cutmax, number of splines, U(0) [2], cut_f [2][2] (the last knot of f of
+ * the second index' element), values[12][4 + 3 * 32] = d0, dN, 1 where the knots are equidistant, the inverse spacing there, x[32], y[32],
+ * y2[32], phi and U in kcal/mol.  Refused with SCEMA_MD_ERR_IO and the reason, which names the line, in errbuf: a truncated file, N < 2 or
+ * N > 32, knots not strictly ascending, a word that is no finite number, a missing `spline3eq`, an element count that disagrees with the
+ * header's list, more than 2 elements kept, an empty or NULL name, a name the file lacks, a phi, rho or f that does not end with value
+ * 0 and slope 0. */
+int scema_md_meam_spline_read_params(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t *n_kept,
+                                     int32_t *type_map, int32_t *knots, double *head, double *values, char *errbuf, int32_t errcap);
+/* spline `fn` of that list at the points x[n]: y and dy/dx, by the code the kernels run (meam_spline/ms_core.h ms_eval); mode 0: the
+ * interval from the inverse spacing where the knots are equidistant, by bisection elsewhere; mode 1: by bisection always (the two agree
+ * bit for bit).  fn or mode out of range: SCEMA_MD_ERR_ARG */
+int scema_md_meam_spline_eval(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t fn, int32_t mode,
+                              const double *x, int32_t n, double *y, double *dy, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

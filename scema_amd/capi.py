@@ -45,6 +45,7 @@ SYMBOLS = [
     "scema_md_vashishta_configure", "scema_md_vashishta_debug_compute", "scema_md_vashishta_read_params",
     "scema_md_adp_configure", "scema_md_adp_debug_compute", "scema_md_adp_read_setfl",
     "scema_md_edip_configure", "scema_md_edip_debug_compute", "scema_md_edip_read_params",
+    "scema_md_meam_spline_configure", "scema_md_meam_spline_debug_compute", "scema_md_meam_spline_read_params", "scema_md_meam_spline_eval",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -587,6 +588,17 @@ class Engine:
 
     edip_debug_compute = edip_compute
 
+    def meam_spline_configure(self, matid: str, path: str, elements=("Ti",), energy_unit: int = 0, skin: float = -1.0):
+        """pair_style meam/spline + pair_coeff * * <path> <elements> for the replicas of one material id (either file format); energy_unit 0:
+        phi and U are eV, 1: kcal/mol as written.  Replaces whatever potential the material held"""
+        self._row_configure("scema_md_meam_spline_configure", matid, path, elements, energy_unit, skin)
+
+    def meam_spline_compute(self, matid, replica, qp=QP_NONE):
+        """npairs: ordered pairs inside cutmax; ntriplets: pairs (a, b) of the lists inside f's last knot"""
+        return self._row_compute("scema_md_meam_spline_debug_compute", matid, replica, qp, "e_pair", "e_embed", "ntriplets")
+
+    meam_spline_debug_compute = meam_spline_compute
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -713,6 +725,57 @@ def edip_read_params(path: str, elements, energy_unit: int = 0):
     """(distinct elements kept, type_map, values[n][n][n][17] in the order of EDIP_FIELDS, A and lambda in kcal/mol) of a LAMMPS *.edip
     file: scema_md_edip_read_params, a pure host function (no GPU); raises IOError with the reader's message"""
     return _read_triplet_params("scema_md_edip_read_params", len(EDIP_FIELDS), path, elements, energy_unit)
+
+
+MS_MAXEL, MS_MAXKNOT = 2, 32
+MS_NFN = MS_MAXEL * (MS_MAXEL + 1) + 3 * MS_MAXEL
+
+
+def _ms_elements(elements):
+    return (C.c_char_p * len(elements))(*[None if e is None else e.encode() for e in elements])
+
+
+def meam_spline_read_params(path: str, elements, energy_unit: int = 0):
+    """dict of a LAMMPS meam/spline file of either format (scema_md_meam_spline_read_params, a pure host function, no GPU): n (distinct
+    elements kept), type_map, cutmax, u0[n], cut_f[n][n], and fn: the splines of the elements kept in the file's order (phi as the upper
+    triangle, rho, U, f, g as the upper triangle), each a dict n, d0, dn, uniform, ih, x, y, y2 with phi and U in kcal/mol; raises IOError
+    with the reader's message"""
+    read = lib().scema_md_meam_spline_read_params
+    read.restype = C.c_int
+    nk = C.c_int32(0)
+    tmap = np.zeros(len(elements), np.int32)
+    knots = np.zeros(MS_NFN, np.int32)
+    head = np.zeros(2 + MS_MAXEL + MS_MAXEL * MS_MAXEL)
+    stride = 4 + 3 * MS_MAXKNOT
+    vals = np.zeros(MS_NFN * stride)
+    err = C.create_string_buffer(512)
+    rc = read(path.encode(), _ms_elements(elements), C.c_int32(len(elements)), C.c_int32(energy_unit), C.byref(nk), _p(tmap), _p(knots), _p(head), _p(vals),
+              err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nk.value
+    fn = []
+    for k in range(int(head[1])):
+        v, m = vals[k * stride:(k + 1) * stride], int(knots[k])
+        fn.append(dict(n=m, d0=v[0], dn=v[1], uniform=int(v[2]), ih=v[3], x=v[4:4 + m].copy(), y=v[4 + MS_MAXKNOT:4 + MS_MAXKNOT + m].copy(),
+                       y2=v[4 + 2 * MS_MAXKNOT:4 + 2 * MS_MAXKNOT + m].copy()))
+    return dict(n=n, type_map=tmap, cutmax=head[0], u0=head[2:2 + n].copy(),
+                cut_f=head[2 + MS_MAXEL:].reshape(MS_MAXEL, MS_MAXEL)[:n, :n].copy(), fn=fn)
+
+
+def meam_spline_eval(path: str, elements, fn: int, x, energy_unit: int = 0, search: bool = False):
+    """(y, dy) of spline `fn` (the order of meam_spline_read_params) of the file at the points x, evaluated by the code the kernels run
+    (scema_md_meam_spline_eval, a pure host function); search: by bisection even where the knots are equidistant"""
+    ev = lib().scema_md_meam_spline_eval
+    ev.restype = C.c_int
+    x = np.ascontiguousarray(x, float).ravel()
+    y, dy = np.zeros(len(x)), np.zeros(len(x))
+    err = C.create_string_buffer(512)
+    rc = ev(path.encode(), _ms_elements(elements), C.c_int32(len(elements)), C.c_int32(energy_unit), C.c_int32(fn), C.c_int32(1 if search else 0), _p(x),
+            C.c_int32(len(x)), _p(y), _p(dy), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return y, dy
 
 
 def vashishta_read_params(path: str, elements, energy_unit: int = 0):

@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -300,6 +300,19 @@ struct EdipStage : TsStage<mdk_edip_forces> {
   }
 };
 
+// Spline MEAM: the two passes of the embedded-atom stage (it owns fp, here U'(rho)) around a list of ROW_MAXIN entries that holds the
+// neighbours inside f's last knot, the three-body range, alone; rho and phi take any number inside cutmax, so the refusal names f's range
+struct MsStage : EamStage {
+  using EamStage::EamStage;
+  void launch(hipStream_t st, int pos0, int n) override { mdk_ms_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
+  int crowded(int fault) override {
+    if (fault & 128)
+      return fail(e, SCEMA_MD_ERR_ARG, "an atom has more than %d neighbours inside the last knot of f, the three-body range of the %s potential (inside cutmax any number is taken)",
+                  ROW_MAXIN, what);
+    return SCEMA_MD_OK;
+  }
+};
+
 template <class Stage>
 RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
 
@@ -317,6 +330,7 @@ const RowPot row_pots[ROW_NPOT] = {
     {RowKind::Vashishta, "Vashishta", "scema_md_vashishta_configure", {".vashishta", nullptr}, scema_md_vashishta_configure, make_stage<VsStage>},
     {RowKind::Adp, "ADP", "scema_md_adp_configure", {".adp", nullptr}, scema_md_adp_configure, make_stage<AdpStage>},
     {RowKind::Edip, "EDIP", "scema_md_edip_configure", {".edip", nullptr}, scema_md_edip_configure, make_stage<EdipStage>},
+    {RowKind::MeamSpline, "MEAM/spline", "scema_md_meam_spline_configure", {".meam.spline", nullptr}, scema_md_meam_spline_configure, make_stage<MsStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -592,6 +606,22 @@ int scema_md_edip_configure(scema_md_engine *e, const char *matid, const char *p
 int scema_md_edip_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e2, double *e3,
                                 double *virial, double *info) {
   return row_debug_compute(e, RowKind::Edip, qp_id, matid, replica, f, e2, e3, virial, info);
+}
+
+int scema_md_meam_spline_configure(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements,
+                                   int32_t energy_unit, double skin) {
+  MsTable T;
+  auto read = [&](const std::vector<std::string> &el, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_meam_spline(path, el, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  return row_configure(e, RowKind::MeamSpline, matid, path, elements, n_elements, skin, read);
+}
+
+int scema_md_meam_spline_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_embed,
+                                       double *virial, double *info) {
+  return row_debug_compute(e, RowKind::MeamSpline, qp_id, matid, replica, f, e_pair, e_embed, virial, info);
 }
 
 }  // extern "C"

@@ -7,13 +7,15 @@ per evaluation at 1 fs.  The replica per potential:
   eam ...... 256 atoms of fcc copper, the fixture's first element (4 x 4 x 4 cells of 3.615 A, thermal velocities at 300 K,
              tests/golden/CuAg.eam.alloy)
   adp ...... the same 256 copper atoms under tests/golden/CuAg.adp (pair_style adp: the embedded-atom terms plus dipoles and quadrupoles)
+  meam_spline  the 256-atom fcc replica of the eam leg scaled to 3.9 A, next to the fixture's own fcc minimum (twelve neighbours at 2.76 A inside the three-body range of 3.4 A, 42
+             inside cutmax) with the mass of titanium, under the synthetic tests/golden/Ti.meam.spline (pair_style meam/spline)
   vashishta  512 atoms of zincblende SiC (4 x 4 x 4 cells of 4.3581 A: the box of 17.43 A is at least twice rc + skin = 8.35 A, so the rows
              are built by minimum image; masses 28.0855 and 12.011, thermal velocities at 300 K, tests/golden/SiC.vashishta)
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -90,6 +92,11 @@ def make_adp(e, cells=None):
     e.adp_configure("cu", os.path.join(GOLD, "CuAg.adp"), ("Cu",))
 
 
+def make_meam_spline(e, cells=None):
+    register_lattice(e, "ti", FCC, cells or (4, 4, 4), 3.9, 47.867)
+    e.meam_spline_configure("ti", os.path.join(GOLD, "Ti.meam.spline"), ("Ti",))
+
+
 def make_vashishta(e, cells=None):
     register_lattice(e, "sic", ZINCBLENDE, cells or (4, 4, 4), 4.3581, (28.0855, 12.011), basis_types=[0, 0, 0, 0, 1, 1, 1, 1])
     e.vashishta_configure("sic", os.path.join(GOLD, "SiC.vashishta"), ("Si", "C"))
@@ -98,7 +105,8 @@ def make_vashishta(e, cells=None):
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
-              "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip)}
+              "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip),
+              "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline)}
 
 
 def main():
