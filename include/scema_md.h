@@ -638,6 +638,48 @@ int scema_md_meam_spline_read_params(const char *path, const char *const *elemen
 int scema_md_meam_spline_eval(const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, int32_t fn, int32_t mode,
                               const double *x, int32_t n, double *y, double *dy, char *errbuf, int32_t errcap);
 
+/* ---- ionic replicas (`pair_style born/coul/dsf`; rock-salt halides, MgO, UO2, Buckingham and Born-Mayer-Huggins oxides and glasses) ----
+ * The first row stage that reads charges: the ones registered with the replica (scema_md_system.charge).  LAMMPS has no parameter file
+ * for this style: `path` is any text file that holds the script lines themselves (in.strain.lammps included); blank-separated words,
+ * `#` starts a comment, every other command is ignored:
+ *   pair_style born/coul/dsf <alpha> <cut_lj> [<cut_coul>]     (cut_coul defaults to cut_lj)
+ *   pair_coeff I J A rho sigma C D [cut_lj]                    (I <= J: numeric types from 1, or `*` alone for either)
+ *   units real|metal                                           (optional; must not contradict energy_unit)
+ * for the replicas of ONE material id, registered before or after the call; list skin as for scema_md_sw_configure (skin < 0: 1.0).
+ * energy_unit 0: A, C and D are eV-based (units metal), K = 14.399645 eV A, everything converted to kcal/mol with 23.060549; 1: the
+ * numbers as written and K = 332.06371 (units real).  The form, for a pair of types ti, tj, charges q_i, q_j at distance r:
+ *   E_born = A exp((sigma - r)/rho) - C/r^6 + D/r^8                              r < cut_lj[ti][tj], not shifted (no pair_modify shift)
+ *   E_coul = K q_i q_j [erfc(alpha r)/r - erfc(alpha rc)/rc + f_s (r - rc)]      r < rc = cut_coul
+ *   f_s    = erfc(alpha rc)/rc^2 + (2 alpha/sqrt(pi)) exp(-alpha^2 rc^2)/rc
+ *   E_self = -K q_i^2 [e_s/2 + alpha/sqrt(pi)] per atom, e_s = erfc(alpha rc)/rc + f_s rc
+ * with forces the exact gradients (the Coulomb force is K q_i q_j [erfc(alpha r)/r^2 + (2 alpha/sqrt(pi)) exp(-alpha^2 r^2)/r - f_s]);
+ * the self term has no force and no virial.  The fragment's types are 1 .. the largest type a pair_coeff line names (4 at most; where
+ * every line says `*`, all 4); an atom of a type beyond them is SCEMA_MD_ERR_ARG at the run.  Any number of neighbours is taken.
+ * Simulations of such a material take this force stage whatever MDSim.force_field says: no SHAKE, no k-space, no bonded terms.  An
+ * update or run that mixes them with simulations of other materials is refused with SCEMA_MD_ERR_ARG.  A material holds ONE attachment:
+ * configuring replaces whatever it held, of any kind.  A replica without topology, with zero Lennard-Jones coefficients, that holds
+ * charges and whose material has nothing attached configures itself at a scema_md_strain_batch if <scripts_folder>/in.strain.lammps
+ * holds a `pair_style born/coul/dsf` line, from that script's own lines (energy unit 1 iff it says `units real`); lines the reader
+ * refuses are SCEMA_MD_ERR_ARG; without such a line nothing changes for the replica.  Not built: born/coul/long (the PPPM chain on
+ * the row driver), born/coul/wolf, pair_modify shift. */
+int scema_md_born_dsf_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], e_born, e_coul with the self term (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz), info[4]: longest
+ * neighbour row the build asked for, row capacity, ordered pairs inside cutmax (the largest of all cutoffs; each pair counts at both
+ * ends), ordered pairs inside cut_coul */
+int scema_md_born_dsf_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
+                                    double *virial, double *info);
+/* The reader as a pure host function (no GPU, no engine).  n_types: the fragment's types; head[6]: alpha, cut_coul, e_s, f_s, K
+ * (kcal A/mol), cutmax; values[n_types][n_types][6] (room for 4*4*6): A rho sigma C D cut_lj of every ordered pair, A, C and D in
+ * kcal/mol.  Refused with SCEMA_MD_ERR_IO and "<path> line <n>: <reason>" in errbuf: no pair_style line (line 0) or two of them; another
+ * pair style; alpha <= 0, a cutoff <= 0, rho <= 0; a word that is not a finite number, a missing or surplus word; I > J, a range m*n, a
+ * type below 1 or above 4; a pair I <= J of the fragment's types that is never set (there is no mixing rule); a units line that is
+ * neither real nor metal or that contradicts energy_unit. */
+int scema_md_born_dsf_read_params(const char *path, int32_t energy_unit, int32_t *n_types, double *head, double *values, char *errbuf, int32_t errcap);
+/* bd_pair of the kernel (ionic/bd_core.h) on the host: out[n][4] = e_born, e_coul, and the force factors fb, fc (force on i =
+ * -(fb + fc)(x_j - x_i)) of a pair of types ti, tj (from 0) and charges qi, qj at the distances r[n]; e_self[2]: the self energies */
+int scema_md_born_dsf_eval(const char *path, int32_t energy_unit, int32_t ti, int32_t tj, double qi, double qj, const double *r, int32_t n, double *out,
+                           double *e_self, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

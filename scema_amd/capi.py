@@ -46,6 +46,7 @@ SYMBOLS = [
     "scema_md_adp_configure", "scema_md_adp_debug_compute", "scema_md_adp_read_setfl",
     "scema_md_edip_configure", "scema_md_edip_debug_compute", "scema_md_edip_read_params",
     "scema_md_meam_spline_configure", "scema_md_meam_spline_debug_compute", "scema_md_meam_spline_read_params", "scema_md_meam_spline_eval",
+    "scema_md_born_dsf_configure", "scema_md_born_dsf_debug_compute", "scema_md_born_dsf_read_params", "scema_md_born_dsf_eval",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -599,6 +600,19 @@ class Engine:
 
     meam_spline_debug_compute = meam_spline_compute
 
+    def born_dsf_configure(self, matid: str, path: str, energy_unit: int = 0, skin: float = -1.0):
+        """pair_style born/coul/dsf for the replicas of one material id: `path` is a text file with the script lines themselves (pair_style
+        born/coul/dsf alpha cut_lj [cut_coul]; pair_coeff I J A rho sigma C D [cut_lj]; optionally units real|metal); energy_unit 0: A, C
+        and D are eV-based with K = 14.399645 eV A, 1: kcal/mol as written with K = 332.06371.  The charges are those of the registered
+        replica (ionic_system).  Replaces whatever potential the material held"""
+        self._chk(lib().scema_md_born_dsf_configure(self.h, matid.encode(), path.encode(), C.c_int32(energy_unit), C.c_double(skin)))
+
+    def born_dsf_compute(self, matid, replica, qp=QP_NONE):
+        """e_coul holds the self term; npairs: ordered pairs inside cutmax; ncoul: ordered pairs inside cut_coul"""
+        return self._row_compute("scema_md_born_dsf_debug_compute", matid, replica, qp, "e_born", "e_coul", "ncoul")
+
+    born_dsf_debug_compute = born_dsf_compute
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -673,6 +687,53 @@ def sw_system(types, x, box, v=None, masses=(28.0855,)) -> dict:
 
 
 bare_system = sw_system   # (the same bare replica under a neutral name: what a Tersoff or an embedded-atom material registers too)
+
+
+def ionic_system(types, charges, x, box, masses, v=None) -> dict:
+    """System dict of an ionic replica (atom_style charge): LAMMPS types (0-based here), a charge per atom and masses -- no topology, zero
+    Lennard-Jones coefficients: what a born/coul/dsf material registers"""
+    s = sw_system(types, x, box, v=v, masses=tuple(masses))
+    q = np.asarray(charges, float)
+    if q.shape != (len(types),):
+        raise ValueError("ionic_system: one charge per atom")
+    s["charge"] = q.copy()
+    return s
+
+
+BORN_DSF_FIELDS = ["A", "rho", "sigma", "C", "D", "cut_lj"]
+BD_MAXEL = 4
+
+
+def born_dsf_read_params(path: str, energy_unit: int = 0):
+    """dict of the born/coul/dsf lines of a text file (scema_md_born_dsf_read_params, a pure host function, no GPU): n (the fragment's
+    types), alpha, cut_coul, e_s, f_s, K (kcal A/mol), cutmax, and values[n][n][6] in the order of BORN_DSF_FIELDS, A, C and D in kcal/mol;
+    raises IOError with the reader's message, which names the line"""
+    read = lib().scema_md_born_dsf_read_params
+    read.restype = C.c_int
+    nt = C.c_int32(0)
+    head, vals = np.zeros(6), np.zeros(BD_MAXEL * BD_MAXEL * len(BORN_DSF_FIELDS))
+    err = C.create_string_buffer(512)
+    rc = read(path.encode(), C.c_int32(energy_unit), C.byref(nt), _p(head), _p(vals), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nt.value
+    return dict(n=n, alpha=head[0], cut_coul=head[1], e_s=head[2], f_s=head[3], K=head[4], cutmax=head[5],
+                values=vals[:n * n * len(BORN_DSF_FIELDS)].reshape(n, n, len(BORN_DSF_FIELDS)).copy())
+
+
+def born_dsf_eval(path: str, ti: int, tj: int, qi: float, qj: float, r, energy_unit: int = 0):
+    """(e_born, e_coul, fb, fc) at the distances r and the two self energies, by the code the kernel runs (scema_md_born_dsf_eval, a pure
+    host function): the force on i is -(fb + fc) (x_j - x_i)"""
+    ev = lib().scema_md_born_dsf_eval
+    ev.restype = C.c_int
+    r = np.ascontiguousarray(r, float).ravel()
+    out, eself = np.zeros((len(r), 4)), np.zeros(2)
+    err = C.create_string_buffer(512)
+    rc = ev(path.encode(), C.c_int32(energy_unit), C.c_int32(ti), C.c_int32(tj), C.c_double(qi), C.c_double(qj), _p(r), C.c_int32(len(r)), _p(out),
+            _p(eself), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return out[:, 0], out[:, 1], out[:, 2], out[:, 3], eself
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]

@@ -46,6 +46,7 @@
 #include "host/vashishta_params.h"
 #include "host/edip_params.h"
 #include "host/meam_spline_params.h"
+#include "host/born_dsf_params.h"
 #include <hipfft/hipfft.h>
 
 #include "md_kernels.h"
@@ -60,6 +61,7 @@
 #include "md_vashishta.h"
 #include "md_edip.h"
 #include "md_meam_spline.h"
+#include "md_born_dsf.h"
 #include "md_rowcells.h"
 #include "md_types.h"
 
@@ -198,7 +200,7 @@ struct RowSlot {
   DevBuf cstart, ccur, clist, cellof;
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline, BornDsf };
 
 // a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure, ...: row_pots).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
@@ -208,7 +210,7 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable on the device
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -566,7 +568,7 @@ struct RowRun {
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM, Tersoff/mod,
-// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
+// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline, Born/DSF: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
 // folder is searched
 struct RowPot {
   RowKind kind;
@@ -576,7 +578,7 @@ struct RowPot {
   int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
   RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
-constexpr int ROW_NPOT = 9;
+constexpr int ROW_NPOT = 10;
 extern const RowPot row_pots[ROW_NPOT];
 // the entry of the potential attached to a material id, or null
 const RowPot *row_pot_of(scema_md_engine *e, const char *matid);
@@ -586,6 +588,11 @@ bool bare_replica(const Topo &t);
 // `pair_coeff * * ${locs}/<name><ext> <El> ...` in <folder>/in.strain.lammps, for the extensions of the table in its order: configures the
 // material from the first such line; no such file or line: nothing happens (0); a malformed line: an error
 int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
+// a replica without topology and Lennard-Jones coefficients that holds charges (what an atom_style charge restart registers)
+bool ionic_replica(const Topo &t);
+// <folder>/in.strain.lammps with a `pair_style born/coul/dsf` line configures the material from its own lines (host/born_dsf_params.h),
+// energy unit 1 iff it says `units real`; no such file or line: nothing happens (0); lines the reader refuses: an error
+int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

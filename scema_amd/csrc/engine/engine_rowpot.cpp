@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`; `pair_style born/coul/dsf`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -34,6 +34,14 @@ bool bare_replica(const Topo &t) {
   for (double q : t.original.q) if (q != 0.0) return false;
   for (double v : t.original.eps) if (v != 0.0) return false;
   return true;
+}
+
+bool ionic_replica(const Topo &t) {
+  const scema_md_system &s = t.original.sys;
+  if (s.nbonds || s.nangles || s.ndihedrals || s.nimpropers) return false;
+  for (double v : t.original.eps) if (v != 0.0) return false;
+  for (double q : t.original.q) if (q != 0.0) return true;
+  return false;
 }
 
 #define ROWSET(dst, src) dst = (decltype(dst))(src)
@@ -313,6 +321,19 @@ struct MsStage : EamStage {
   }
 };
 
+// Born/DSF: the first stage that reads the replica's charges (SimDev::q, bound for every run by sim_common).  The type map is the
+// identity: pair_coeff names types, not elements.  No list of ROW_MAXIN: any number of neighbours inside cutmax is taken
+struct BdStage : RowPotStage {
+  using RowPotStage::RowPotStage;
+  void launch(hipStream_t st, int pos0, int n) override { mdk_bd_forces(st, run->D + pos0, VV + pos0, n, run->maxatoms); }
+  int crowded(int) override { return SCEMA_MD_OK; }
+};
+
+// (the table's common signature: the style has no element list)
+int born_dsf_configure_entry(scema_md_engine *e, const char *matid, const char *path, const char *const *, int32_t, int32_t energy_unit, double skin) {
+  return scema_md_born_dsf_configure(e, matid, path, energy_unit, skin);
+}
+
 template <class Stage>
 RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
 
@@ -331,6 +352,7 @@ const RowPot row_pots[ROW_NPOT] = {
     {RowKind::Adp, "ADP", "scema_md_adp_configure", {".adp", nullptr}, scema_md_adp_configure, make_stage<AdpStage>},
     {RowKind::Edip, "EDIP", "scema_md_edip_configure", {".edip", nullptr}, scema_md_edip_configure, make_stage<EdipStage>},
     {RowKind::MeamSpline, "MEAM/spline", "scema_md_meam_spline_configure", {".meam.spline", nullptr}, scema_md_meam_spline_configure, make_stage<MsStage>},
+    {RowKind::BornDsf, "Born/DSF", "scema_md_born_dsf_configure", {nullptr, nullptr}, born_dsf_configure_entry, make_stage<BdStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -382,6 +404,19 @@ int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string
       if (rc || row_pot_of(e, matid)) return rc;
     }
   return SCEMA_MD_OK;
+}
+
+int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+  const std::string script = folder + "/in.strain.lammps";
+  if (!std::ifstream(script).good()) return SCEMA_MD_OK;
+  BdTable T;
+  std::vector<int> type_map;
+  std::string err;
+  bool has_style = false;
+  const bool ok = scema::read_born_dsf_params(script, -1, T, type_map, err, nullptr, &has_style);
+  if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
+  if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
+  return scema_md_born_dsf_configure(e, matid, script.c_str(), T.k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
 }
 
 // ---- what the entry points of the C ABI share.  row_configure: `read` fills type_map from the file and says where its host table
@@ -622,6 +657,23 @@ int scema_md_meam_spline_configure(scema_md_engine *e, const char *matid, const 
 int scema_md_meam_spline_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_pair, double *e_embed,
                                        double *virial, double *info) {
   return row_debug_compute(e, RowKind::MeamSpline, qp_id, matid, replica, f, e_pair, e_embed, virial, info);
+}
+
+int scema_md_born_dsf_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin) {
+  if (e && energy_unit != 0 && energy_unit != 1) return fail(e, SCEMA_MD_ERR_ARG, "energy unit %d (0: A, C and D eV-based, 1: in kcal/mol)", energy_unit);
+  BdTable T;
+  auto read = [&](const std::vector<std::string> &, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_born_dsf_params(path, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.cutmax};
+    return true;
+  };
+  static const char *const no_elements[1] = {"*"};   // (pair_coeff names types: the type map is the identity over the fragment's types)
+  return row_configure(e, RowKind::BornDsf, matid, path, no_elements, 1, skin, read);
+}
+
+int scema_md_born_dsf_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
+                                    double *virial, double *info) {
+  return row_debug_compute(e, RowKind::BornDsf, qp_id, matid, replica, f, e_born, e_coul, virial, info);
 }
 
 }  // extern "C"

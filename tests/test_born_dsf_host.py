@@ -1,0 +1,286 @@
+"""The born/coul/dsf arithmetic of the product (scema_amd/csrc/ionic/bd_core.h, the functions the HIP kernel of md_born_dsf.hip runs, with
+the table of host/born_dsf_params.cpp), compiled for the host as the stand-alone program tests/born_dsf_host_driver.cpp and held against
+the independent numpy restatement tests/born_dsf_numpy.py: energies, forces and virial to 1e-12 relative, the numpy forces against
+central differences of the numpy energy, the virial against the strain derivative, the Madelung constant of rock salt, the lattice
+minimum, both terms at their cutoffs.  No GPU needed: this is where every derivative is pinned; the `-m gpu` tests then compare the
+kernel's output with the same reference.  No LAMMPS exists here to compare with: parity with `pair_style born/coul/dsf` is unpinned.
+
+Madelung constant: with alpha = 0.25 /A and rc = 10 A the damped-shifted-force sum over rock salt at a = 5.64 A gives
+-E_coul (a/2)/K = 1.74710 per ion pair against the exact 1.747565; the budget is 1e-3.
+
+Wrong builds of the driver (-DBDH_WRONG=k, switches of the driver, not of the product), each with the check that fails:
+  1  the sign of f_s swapped ....... the +/- dimer (Coulomb energy and force), the Coulomb term no longer reaches 0 at rc, the Madelung
+                                     value; the ion next to an uncharged atom passes (no Coulomb term)
+  2  the self term missing ......... the single ion (its energy is the self term alone), the Madelung value; forces and virial of every
+                                     case pass (the self term has neither)
+  3  q_i^2 in place of q_i q_j ..... the +/- dimer (the sign of the Coulomb term); the +/+ dimer passes
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import born_dsf_numpy as bn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NACL = os.path.join(ROOT, "tests", "golden", "NaCl.born_dsf")
+KNACL = os.path.join(ROOT, "tests", "golden", "KNaCl.born_dsf")
+
+
+def _build_driver(wrong=0, flags=(), tag=""):
+    out = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, f"born_dsf_host_driver_{wrong}{tag}")
+    srcs = [os.path.join(ROOT, "tests", "born_dsf_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "born_dsf_params.cpp")]
+    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "ionic", "bd_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "born_dsf_params.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", f"-DBDH_WRONG={wrong}", "-I", os.path.join(ROOT, "include"), "-o", exe] + list(flags) + srcs)
+    return exe
+
+
+build_driver = _build_driver
+
+
+def _run(exe, path, x, box, types, q, energy_unit=0):
+    text = f"{len(x)}\n" + " ".join(repr(float(b)) for b in box) + "\n"
+    text += "".join(f"{int(t)} {float(c)!r} {float(p[0])!r} {float(p[1])!r} {float(p[2])!r}\n" for t, c, p in zip(types, q, x))
+    out = subprocess.run([exe, path, str(energy_unit)], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
+    head = out[0].split()
+    f = np.array([[float(v) for v in line.split()] for line in out[2:2 + len(x)]])
+    eb, ec = float(head[0]), float(head[1])
+    return dict(e_born=eb, e_coul=ec, e=eb + ec, npairs=int(head[2]), ncoul=int(head[3]), w=np.array([float(v) for v in out[1].split()]), f=f)
+
+
+def _inputs():
+    """name -> (file, case): every static input of the CPU tests"""
+    out = {"single": (NACL, bn.case_single())}
+    for name, (ti, tj, qi, qj) in {"pm": (0, 1, 1.0, -1.0), "pp": (0, 0, 1.0, 1.0), "neutral": (0, 1, 1.0, 0.0), "clcl": (1, 1, -1.0, -1.0)}.items():
+        for rn, r in (("near", 2.6), ("far", 8.5)):
+            out[f"dimer_{name}_{rn}"] = (NACL, bn.case_dimer(ti, tj, qi, qj, r))
+    out["cell8"] = (NACL, bn.case_cell8())
+    out["cell8j"] = (NACL, bn.case_cell8(jitter=0.05))
+    out["jitter64"] = (NACL, bn.case_jitter(2, 1))
+    out["jitter216"] = (NACL, bn.case_jitter(3, 2))
+    out["c63"] = (NACL, bn.case_63())
+    out["triclinic"] = (NACL, bn.case_triclinic())
+    out["gas"] = (NACL, bn.case_gas())
+    out["knacl"] = (KNACL, bn.case_knacl())
+    return out
+
+
+NAMES = sorted(_inputs())
+
+
+@pytest.fixture(scope="module")
+def refs():
+    """per input: (numpy object, file, case, numpy result, driver result), each computed once"""
+    exe = _build_driver()
+    out = {}
+    for name, (path, case) in _inputs().items():
+        ref = bn.BornDsf(bn.read_born_dsf(path))
+        out[name] = (ref, path, case, ref.compute(*case), _run(exe, path, *case))
+    return out
+
+
+def _mismatch(got, ref, tol=1e-12, scale=None):
+    """what differs beyond tol, relative to the largest force component, energy term and virial part of ref, or of `scale` (the
+    perfect cell, whose forces cancel, is measured on its jittered twin)"""
+    bad = []
+    scale = scale or ref
+    if (got["npairs"], got["ncoul"]) != (ref["npairs"], ref["ncoul"]):
+        bad.append("counts")
+    if not np.abs(got["f"] - ref["f"]).max() <= tol * max(np.abs(scale["f"]).max(), 1e-300):
+        bad.append("forces")
+    es = max(abs(ref["e_born"]), abs(ref["e_coul"]), 1e-300)
+    if not (abs(got["e_born"] - ref["e_born"]) <= tol * es and abs(got["e_coul"] - ref["e_coul"]) <= tol * es):
+        bad.append("energy")
+    # (the virial is a difference: Born and Coulomb parts of 2 000 kcal/mol cancel to 25, so 1e-12 is held on the scale of the parts)
+    ws = max(np.abs(scale["w_born"]).max(), np.abs(scale["w_coul"]).max()) if "w_born" in scale else np.abs(scale["w"]).max()
+    if not np.abs(got["w"] - ref["w"]).max() <= tol * max(ws, 1e-300):
+        bad.append("virial")
+    return bad
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_static_cases_match_numpy(refs, name):
+    _, _, case, ref, got = refs[name]
+    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and np.isfinite(got["e"])
+    scale = refs["cell8j"][3] if name == "cell8" else ref
+    assert _mismatch(got, ref, scale=scale) == [], _mismatch(got, ref, scale=scale)
+    # no net force
+    assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
+    assert abs(got["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
+    if name == "single":      # the self energy alone: no pair, no force, no virial
+        assert ref["npairs"] == 0 and ref["e_born"] == 0.0 and ref["e_coul"] == ref["e_self"] < 0.0
+        assert not got["f"].any() and not got["w"].any() and got["e_born"] == 0.0
+    if name.startswith("dimer"):
+        assert ref["npairs"] == 2 and ref["ncoul"] == 2
+    if name.startswith("dimer_neutral"):      # Coulomb exactly zero between an ion and an uncharged atom: the ion's self energy is all of e_coul
+        assert got["e_coul"] == ref["e_coul"] == ref["e_self"] and not ref["w_coul"].any()
+    if name == "dimer_pm_far":      # (8.5 A: inside both cutoffs of 10 A, both terms live)
+        assert ref["e_born"] != 0.0
+    if name == "cell8":
+        assert ref["maxrow"] > 150 and ref["npairs"] == 8 * ref["maxrow"]
+    if name == "knacl":
+        assert set(case[2]) == {0, 1, 2} and ref["ncoul"] > ref["npairs"] * 0.9 and ref["ncoul"] <= ref["npairs"]
+
+
+@pytest.mark.parametrize("name", ["jitter64", "c63", "gas", "knacl", "triclinic"])
+def test_numpy_forces_are_the_gradient_of_its_energy(refs, name):
+    """central differences of the numpy energy, h = 1e-5 A: truncation h^2 f'''/6 ~ 1e-10 f, rounding 1e-16 E / h ~ 1e-7 kcal/mol/A.  The
+    Coulomb term is continuous with its derivative at rc, so a pair may change sides there; the Born term jumps at cut_lj, so every input
+    keeps more than h from every cut_lj"""
+    ref_bd, _, (x, box, t, q), ref, _ = refs[name]
+    assert ref_bd.margin(x, box, t) >= 1e-4
+    eb, ec = ref_bd.energy(x, box, t, q)
+    assert abs(eb - ref["e_born"]) <= 1e-13 * abs(ref["e_born"]) and abs(ec - ref["e_coul"]) <= 1e-13 * abs(ref["e_coul"])
+    rng = np.random.default_rng(3)
+    h = 1e-5
+    for _ in range(3):
+        u = rng.normal(size=x.shape)
+        u /= np.linalg.norm(u)
+        num = -(sum(ref_bd.energy(x + h * u, box, t, q)) - sum(ref_bd.energy(x - h * u, box, t, q))) / (2 * h)
+        assert abs(num - np.sum(ref["f"] * u)) < 1e-6 * np.abs(ref["f"]).max(), name
+
+
+@pytest.mark.parametrize("name", ["jitter64", "knacl"])
+def test_numpy_virial_is_the_strain_derivative_of_its_energy(refs, name):
+    """W_ab = sum d_a f_b = -dE/d eps_ab, with E the total energy: the self term is in E, does not change with the strain, and so must
+    not enter the virial"""
+    ref_bd, _, (x, box, t, q), ref, _ = refs[name]
+    assert ref["e_self"] < -10.0
+    h = 1e-6
+    for k, (a, b) in enumerate([(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]):
+        e = np.zeros((3, 3))
+        e[a, b] = h
+        ep = sum(ref_bd.energy(*bn.strained(x, box, e), t, q))
+        em = sum(ref_bd.energy(*bn.strained(x, box, -e), t, q))
+        assert abs(-(ep - em) / (2 * h) - ref["w"][k]) < 1e-5 * np.abs(ref["w"]).max(), k
+    assert np.abs(ref["w"] - ref["w_born"] - ref["w_coul"]).max() <= 1e-15 * np.abs(ref["w_born"]).max()
+
+
+def test_invariance_under_translation(refs):
+    ref_bd, path, (x, box, t, q), ref, got = refs["jitter64"]
+    shift = np.array([3.21, -7.7, 0.113])
+    ref2, got2 = ref_bd.compute(x + shift, box, t, q), _run(_build_driver(), path, x + shift, box, t, q)
+    for a, b in ((ref2, ref), (got2, got)):
+        assert _mismatch(a, b, tol=1e-11) == []
+
+
+def test_madelung_constant_of_rock_salt(refs):
+    ref_bd, _, (x, box, t, q), ref, got = refs["cell8"]
+    only_coul = bn.BornDsf(dict(ref_bd.p, A=ref_bd.p["A"] * 0, C=ref_bd.p["C"] * 0, D=ref_bd.p["D"] * 0)).compute(x, box, t, q)
+    assert only_coul["e_born"] == 0.0 and only_coul["e_coul"] == ref["e_coul"]
+    for who, r in (("numpy", ref), ("driver", got)):
+        m = -r["e_coul"] / 4.0 * (bn.A_NACL / 2.0) / ref_bd.K
+        print(f"Madelung constant of rock salt at {bn.A_NACL} A by the damped shifted force sum ({who}): {m:.6f} (exact {bn.MADELUNG_NACL})")
+        assert abs(m - bn.MADELUNG_NACL) < 1e-3
+    assert np.abs(ref["f"]).max() < 1e-9      # (every ion sits on a centre of symmetry)
+
+
+def test_lattice_minimum_of_rock_salt(refs):
+    ref_bd = refs["cell8"][0]
+    grid = np.arange(5.30, 5.9001, 0.01)
+    e = np.array([ref_bd.compute(*bn.case_cell8(a))["e"] / 4.0 for a in grid])
+    k = int(np.argmin(e))
+    print(f"rock-salt minimum of the fixture: a = {grid[k]:.2f} A, {e[k]:.2f} kcal/mol per ion pair")
+    assert 5.5 <= grid[k] <= 5.75 and 0 < k < len(grid) - 1
+    assert abs(e[k] - (-185.7)) < 0.05
+
+
+@pytest.mark.parametrize("who", ["numpy", "driver"])
+def test_coulomb_term_vanishes_at_its_cutoff(refs, who):
+    """E_coul and its force go to 0 continuously at rc; at and beyond rc they are exactly 0 (the self terms remain)"""
+    ref_bd = refs["cell8"][0]
+    rc = ref_bd.rc
+    exe = _build_driver()
+    comp = (lambda c: ref_bd.compute(*c)) if who == "numpy" else (lambda c: _run(exe, NACL, *c))
+    zero = bn.BornDsf(dict(ref_bd.p, A=ref_bd.p["A"] * 0, C=ref_bd.p["C"] * 0, D=ref_bd.p["D"] * 0))      # (cut_lj = rc in this file: the Born part by numpy)
+    scale = abs(ref_bd.coul(-1.0, np.array([5.0]))[0][0])
+    eself = ref_bd.self_energy([1.0, -1.0])
+    for eps, bound in ((1e-3, 1e-5), (1e-6, 1e-11)):      # E ~ (r - rc)^2 E''/2, F ~ (r - rc) E'': both shrink with the distance to rc
+        c = bn.case_dimer(0, 1, 1.0, -1.0, rc - eps)
+        got, born = comp(c), zero.compute(*c)
+        assert got["ncoul"] == 2 and abs(got["e_coul"] - eself) <= bound * scale
+        fb = ref_bd.born(0, 1, np.array([rc - eps]))[1][0]
+        assert abs(got["f"][0, 0] - fb) <= 1e3 * eps * scale and born["e_born"] == 0.0
+    for r in (rc, rc + 1e-6, rc + 1.0):
+        got = comp(bn.case_dimer(0, 1, 1.0, -1.0, r))
+        assert got["ncoul"] == 0 and got["e_coul"] == eself and not got["f"].any() and not got["w"].any()
+
+
+@pytest.mark.parametrize("who", ["numpy", "driver"])
+def test_born_term_jumps_at_its_cutoff(who):
+    """the Born term is not shifted: just inside cut_lj of a pair (1-1 of KNaCl: 7 A, below cut_coul) the energy is E_born(cut_lj), at it
+    exactly 0, while the Coulomb term runs on"""
+    ref_bd = bn.BornDsf(bn.read_born_dsf(KNACL))
+    cut = ref_bd.p["cut_lj"][0, 0]
+    assert cut == 7.0 < ref_bd.rc
+    exe = _build_driver()
+    comp = (lambda c: ref_bd.compute(*c)) if who == "numpy" else (lambda c: _run(exe, KNACL, *c))
+    want = ref_bd.born(0, 0, np.array([cut * (1.0 - 1e-15)]))[0][0]
+    inside, at = comp(bn.case_dimer(0, 0, 1.0, 1.0, cut - 1e-9)), comp(bn.case_dimer(0, 0, 1.0, 1.0, cut))
+    assert want != 0.0 and abs(inside["e_born"] - want) <= 1e-8 * abs(want)
+    assert at["e_born"] == 0.0 and at["npairs"] == 2 and at["ncoul"] == 2 and abs(at["e_coul"] - inside["e_coul"]) < 1e-8 * abs(at["e_coul"])
+    assert abs(inside["e_born"] - at["e_born"] - want) <= 1e-8 * abs(want)
+
+
+def test_both_energy_units_describe_one_potential(refs, tmp_path):
+    """the fixture's numbers converted to kcal/mol by hand under `units real`, read with energy_unit 1, give the same energies and forces
+    as the fixture under `units metal` with energy_unit 0, up to the rounding of K: 14.399645 x 23.060549 = 332.06372 against 332.06371,
+    3e-8 relative, in the Coulomb term alone"""
+    _, _, case, ref, got = refs["jitter64"]
+    lines = []
+    for raw in open(NACL):
+        w = raw.split("#")[0].split()
+        if w and w[0] == "units":
+            lines.append("units real\n")
+        elif w and w[0] == "pair_coeff":
+            v = [float(s) for s in w[3:]]
+            for k in (0, 3, 4):
+                v[k] *= bn.EV_TO_KCALMOL
+            lines.append(" ".join(w[:3] + [repr(s) for s in v]) + "\n")
+        else:
+            lines.append(raw)
+    p = tmp_path / "NaCl_real.born_dsf"
+    p.write_text("".join(lines))
+    ref_real = bn.BornDsf(bn.read_born_dsf(str(p)))
+    assert ref_real.p["unit"] == 1 and ref_real.K == bn.K_KCALMOL
+    got_real = _run(_build_driver(), str(p), *case, energy_unit=1)
+    assert _mismatch(got_real, ref_real.compute(*case)) == []
+    assert abs(got_real["e_born"] - got["e_born"]) <= 1e-12 * abs(got["e_born"])
+    assert abs(got_real["e_coul"] - got["e_coul"]) <= 1e-7 * abs(got["e_coul"]) and _mismatch(got_real, got, tol=1e-7, scale=ref) == []
+    # the file's own units line against the other energy unit is refused
+    r = subprocess.run([_build_driver(), NACL, "1"], input="", capture_output=True, text=True)
+    assert r.returncode == 1 and "line 4: units metal contradicts energy unit 1" in r.stderr
+
+
+WRONG = {1: ("dimer_pm_near", ["forces", "energy", "virial"]), 2: ("single", ["energy"]), 3: ("dimer_pm_near", ["forces", "energy", "virial"])}
+PASSES = {1: "dimer_neutral_near", 3: "dimer_pp_near"}      # what a wrong build still passes: why the case named above is needed
+
+
+@pytest.mark.parametrize("wrong", sorted(WRONG))
+def test_wrong_builds_are_caught(refs, wrong):
+    exe = _build_driver(wrong)
+    name, what = WRONG[wrong]
+    _, path, case, ref, _ = refs[name]
+    bad = _mismatch(_run(exe, path, *case), ref)
+    print(f"wrong build {wrong} on {name}: {bad}")
+    assert bad == what
+    if wrong in PASSES:
+        _, path, case, ref, _ = refs[PASSES[wrong]]
+        assert _mismatch(_run(exe, path, *case), ref) == []
+    # the Madelung value catches all three (q_i^2 turns every attraction into a repulsion)
+    _, path, case, ref, _ = refs["cell8"]
+    m = -_run(exe, path, *case)["e_coul"] / 4.0 * (bn.A_NACL / 2.0) / refs["cell8"][0].K
+    print(f"wrong build {wrong}: Madelung value {m:.6f}")
+    assert abs(m - bn.MADELUNG_NACL) > 1e-3
+    if wrong == 2:      # forces and virial of every case pass: the self term has neither
+        for other in ("jitter64", "knacl"):
+            _, path, case, ref, _ = refs[other]
+            assert _mismatch(_run(exe, path, *case), ref) == ["energy"]
+    if wrong == 1:      # the Coulomb term no longer reaches zero at rc
+        rc = refs["cell8"][0].rc
+        got = _run(exe, NACL, *bn.case_dimer(0, 1, 1.0, -1.0, rc - 1e-6))
+        assert abs(got["e_coul"] - refs["cell8"][0].self_energy([1.0, -1.0])) > 1e-3

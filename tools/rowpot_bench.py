@@ -11,11 +11,14 @@ per evaluation at 1 fs.  The replica per potential:
              inside cutmax) with the mass of titanium, under the synthetic tests/golden/Ti.meam.spline (pair_style meam/spline)
   vashishta  512 atoms of zincblende SiC (4 x 4 x 4 cells of 4.3581 A: the box of 17.43 A is at least twice rc + skin = 8.35 A, so the rows
              are built by minimum image; masses 28.0855 and 12.011, thermal velocities at 300 K, tests/golden/SiC.vashishta)
+  born_dsf   512 ions of rock-salt NaCl (4 x 4 x 4 cells of 5.64 A: the box of 22.56 A is at least twice cut_coul + skin = 11 A, so the
+             rows are built by minimum image; charges +1 and -1, masses 22.98977 and 35.453, thermal velocities at 300 K,
+             tests/golden/NaCl.born_dsf: pair_style born/coul/dsf 0.25 10.0, about 190 neighbours per ion)
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -37,9 +40,9 @@ FCC = DIAMOND[:4]
 ZINCBLENDE = FCC + [[1, 1, 1], [1, 3, 3], [3, 1, 3], [3, 3, 1]]          # (the diamond sites: the fcc ones, then those a quarter diagonal further)
 
 
-def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1, basis_types=None):
+def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1, basis_types=None, type_charges=None):
     """a cubic lattice of that basis (in quarters of the cell) with thermal velocities, as a bare replica; mass: one number, or with
-    basis_types (the LAMMPS type, from 0, of every basis site) one per type"""
+    basis_types (the LAMMPS type, from 0, of every basis site) one per type; type_charges: a charge per type (an ionic replica)"""
     nx, ny, nz = cells
     grid = np.array(list(itertools.product(range(nx), range(ny), range(nz))), float)
     x = (grid[:, None, :] + np.array(basis, float)[None, :, :] * 0.25).reshape(-1, 3) * a
@@ -48,7 +51,10 @@ def register_lattice(e, matid, basis, cells, a, mass, temp=300.0, seed=1, basis_
     rng = np.random.default_rng(seed)
     v = rng.normal(size=x.shape) * np.sqrt(BOLTZ * temp / np.array(masses)[types] / MVV2E)[:, None]
     box = np.array([0.0, 0.0, 0.0, nx * a, ny * a, nz * a, 0.0, 0.0, 0.0])
-    e.register_replica(matid, 1, capi.bare_system(types, x, box, v=v - v.mean(axis=0), masses=masses))
+    if type_charges is None:
+        e.register_replica(matid, 1, capi.bare_system(types, x, box, v=v - v.mean(axis=0), masses=masses))
+    else:
+        e.register_replica(matid, 1, capi.ionic_system(types, np.array(type_charges, float)[types], x, box, masses, v=v - v.mean(axis=0)))
 
 
 def make_sw(e, cells=None):
@@ -102,11 +108,19 @@ def make_vashishta(e, cells=None):
     e.vashishta_configure("sic", os.path.join(GOLD, "SiC.vashishta"), ("Si", "C"))
 
 
+ROCKSALT = FCC + [[2, 0, 0], [2, 2, 2], [0, 0, 2], [0, 2, 0]]              # (the fcc sites, then those half a cell edge further along x)
+
+
+def make_born_dsf(e, cells=None):
+    register_lattice(e, "nacl", ROCKSALT, cells or (4, 4, 4), 5.64, (22.98977, 35.453), basis_types=[0, 0, 0, 0, 1, 1, 1, 1], type_charges=(1.0, -1.0))
+    e.born_dsf_configure("nacl", os.path.join(GOLD, "NaCl.born_dsf"))
+
+
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
               "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip),
-              "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline)}
+              "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline), "born_dsf": ("born_dsf_nacl_512", "nacl", make_born_dsf)}
 
 
 def main():
