@@ -660,8 +660,8 @@ int scema_md_meam_spline_eval(const char *path, const char *const *elements, int
  * configuring replaces whatever it held, of any kind.  A replica without topology, with zero Lennard-Jones coefficients, that holds
  * charges and whose material has nothing attached configures itself at a scema_md_strain_batch if <scripts_folder>/in.strain.lammps
  * holds a `pair_style born/coul/dsf` line, from that script's own lines (energy unit 1 iff it says `units real`); lines the reader
- * refuses are SCEMA_MD_ERR_ARG; without such a line nothing changes for the replica.  Not built: born/coul/long (the PPPM chain on
- * the row driver), born/coul/wolf, pair_modify shift. */
+ * refuses are SCEMA_MD_ERR_ARG; without such a line nothing changes for the replica.  The long-range form, born/coul/long and
+ * buck/coul/long with an Ewald sum, is scema_md_born_long_configure below.  Not built: born/coul/wolf, pair_modify shift. */
 int scema_md_born_dsf_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin);
 /* static evaluation: f [natoms*3], e_born, e_coul with the self term (kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz), info[4]: longest
  * neighbour row the build asked for, row capacity, ordered pairs inside cutmax (the largest of all cutoffs; each pair counts at both
@@ -679,6 +679,48 @@ int scema_md_born_dsf_read_params(const char *path, int32_t energy_unit, int32_t
  * -(fb + fc)(x_j - x_i)) of a pair of types ti, tj (from 0) and charges qi, qj at the distances r[n]; e_self[2]: the self energies */
 int scema_md_born_dsf_eval(const char *path, int32_t energy_unit, int32_t ti, int32_t tj, double qi, double qj, const double *r, int32_t n, double *out,
                            double *e_self, char *errbuf, int32_t errcap);
+
+/* ---- ionic replicas with an Ewald sum (`pair_style born/coul/long`, `pair_style buck/coul/long`, `kspace_style ewald <accuracy>`) ----
+ * The form ionic models are fitted with: the Born-Mayer-Huggins term of born/coul/dsf and the Coulomb sum split by Ewald's method, the
+ * reciprocal part summed plainly over a k list (row replicas are small: 512 ions of rock salt at 1e-5 need 709 k-vectors).  `path` is any
+ * text file that holds the script lines themselves (in.strain.lammps included):
+ *   pair_style born/coul/long <cut_lj> [<cut_coul>]   with   pair_coeff I J A rho sigma C D [cut_lj]
+ *   pair_style buck/coul/long <cut_lj> [<cut_coul>]   with   pair_coeff I J A rho C [cut_lj]          (sigma = 0, D = 0 of the same table)
+ *   kspace_style ewald|pppm <accuracy>                (required; `pppm` is honoured as the Ewald sum at that accuracy, the sum PPPM
+ *                                                      approximates; a kspace_modify line is refused: none of its options is honoured)
+ *   units real|metal                                  (optional; must not contradict energy_unit)
+ * Types, `*`, energy_unit, K, skin and the rules of attachment are those of scema_md_born_dsf_configure.  The form:
+ *   E_born  = A exp((sigma - r)/rho) - C/r^6 + D/r^8                         r < cut_lj[ti][tj], not shifted
+ *   E_real  = K q_i q_j erfc(g r)/r                                          r < cut_coul, not shifted
+ *   E_recip = (2 pi K/V) sum_{k != 0} exp(-k^2/4g^2)/k^2 |S(k)|^2            S(k) = sum_i q_i exp(i k.r_i)
+ *   E_self  = -K g/sqrt(pi) sum q_i^2 - K pi (sum q_i)^2/(2 g^2 V)           (the second term: the neutralising background)
+ * with forces the exact gradients and the virial the strain derivative of the whole energy at fixed g and fixed integer k triples (the
+ * background term included, which LAMMPS leaves out of its virial).  g_ewald and the triples are set up per run from the run's start box,
+ * the material's cut_coul and accuracy and the replica's charges, by the rule of `kspace_style ewald` (g from the accuracy, a kmax search
+ * per dimension, the Cartesian sphere); the triples stay over the run while fix deform moves the box, and a box flip re-expresses them.
+ * A replica whose list exceeds 4096 k-vectors, or an index of 20, is refused with SCEMA_MD_ERR_ARG (PPPM on the row driver is the
+ * follow-up).  Forces repeat bit for bit.  A charged topology-free replica with nothing attached configures itself from a
+ * `pair_style born/coul/long` or `buck/coul/long` line of <scripts_folder>/in.strain.lammps, after the born/coul/dsf search. */
+int scema_md_born_long_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], e_born, e_coul (real space, reciprocal space, self and background; kcal/mol), virial[6]
+ * (xx,yy,zz,xy,xz,yz), info[6]: the four numbers of scema_md_born_dsf_debug_compute, then the k-vectors of the half space and g_ewald */
+int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
+                                     double *virial, double *info);
+/* The reader as a pure host function (no GPU, no engine).  n_types: the fragment's types; head[6]: cut_coul, accuracy, solver (0 ewald,
+ * 1 pppm), K (kcal A/mol), cutmax, style (0 born/coul/long, 1 buck/coul/long); values[n_types][n_types][6] (room for 4*4*6): A rho sigma
+ * C D cut_lj of every ordered pair, A, C and D in kcal/mol.  Refused with SCEMA_MD_ERR_IO and "<path> line <n>: <reason>" in errbuf: what
+ * scema_md_born_dsf_read_params refuses (alpha apart), and no kspace_style line (line 0) or two of them, a solver that is neither ewald
+ * nor pppm, an accuracy <= 0 or >= 1, a kspace_modify line, a pair_coeff line with the word count of the other style. */
+int scema_md_born_long_read_params(const char *path, int32_t energy_unit, int32_t *n_types, double *head, double *values, char *errbuf, int32_t errcap);
+/* bl_pair of the kernel (ionic/bl_core.h) on the host at a given g_ewald: out[n][4] = e_born, e_real, and the force factors fb, fc (force
+ * on i = -(fb + fc)(x_j - x_i)) of a pair of types ti, tj (from 0) and charges qi, qj at the distances r[n] */
+int scema_md_born_long_eval(const char *path, int32_t energy_unit, double g_ewald, int32_t ti, int32_t tj, double qi, double qj, const double *r,
+                            int32_t n, double *out, char *errbuf, int32_t errcap);
+/* The k-space set-up a run would use for this box (xlo ylo zlo xhi yhi zhi xy xz yz), as a pure host function: g_ewald, kmax[3] (the
+ * largest |n_d| of the list), nk and the integer triples [nk][3] (triples may be null; triples_cap counts triples) for a replica of
+ * natoms atoms with sum q^2 = qsqsum under the cut_coul and accuracy of `path` */
+int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *kmax,
+                                int32_t *nk, int32_t *triples, int32_t triples_cap, char *errbuf, int32_t errcap);
 
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */

@@ -47,6 +47,8 @@ SYMBOLS = [
     "scema_md_edip_configure", "scema_md_edip_debug_compute", "scema_md_edip_read_params",
     "scema_md_meam_spline_configure", "scema_md_meam_spline_debug_compute", "scema_md_meam_spline_read_params", "scema_md_meam_spline_eval",
     "scema_md_born_dsf_configure", "scema_md_born_dsf_debug_compute", "scema_md_born_dsf_read_params", "scema_md_born_dsf_eval",
+    "scema_md_born_long_configure", "scema_md_born_long_debug_compute", "scema_md_born_long_read_params", "scema_md_born_long_eval",
+    "scema_md_born_long_kvectors",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -613,6 +615,25 @@ class Engine:
 
     born_dsf_debug_compute = born_dsf_compute
 
+    def born_long_configure(self, matid: str, path: str, energy_unit: int = 0, skin: float = -1.0):
+        """pair_style born/coul/long or buck/coul/long with an Ewald sum for the replicas of one material id: `path` is a text file with the
+        script lines themselves (pair_style born/coul/long cut_lj [cut_coul] with pair_coeff I J A rho sigma C D [cut_lj], or buck/coul/long
+        with pair_coeff I J A rho C [cut_lj]; kspace_style ewald|pppm accuracy; optionally units real|metal); energy_unit as for
+        born_dsf_configure.  The charges are those of the registered replica (ionic_system).  Replaces whatever potential the material held"""
+        self._chk(lib().scema_md_born_long_configure(self.h, matid.encode(), path.encode(), C.c_int32(energy_unit), C.c_double(skin)))
+
+    def born_long_compute(self, matid, replica, qp=QP_NONE):
+        """e_coul: real space, reciprocal space, self and background; npairs: ordered pairs inside cutmax; ncoul: ordered pairs inside
+        cut_coul; nk: k-vectors of the half space; g_ewald of the evaluation"""
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); ea = C.c_double(0.0); eb = C.c_double(0.0); w = np.zeros(6); info = np.zeros(6)
+        self._chk(lib().scema_md_born_long_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(ea), C.byref(eb), _p(w),
+                                                         _p(info)))
+        return {"f": f, "e_born": ea.value, "e_coul": eb.value, "w": w, "maxrow": int(info[0]), "rowcap": int(info[1]), "npairs": int(info[2]),
+                "ncoul": int(info[3]), "nk": int(info[4]), "g_ewald": float(info[5])}
+
+    born_long_debug_compute = born_long_compute
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -734,6 +755,57 @@ def born_dsf_eval(path: str, ti: int, tj: int, qi: float, qj: float, r, energy_u
     if rc != 0:
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     return out[:, 0], out[:, 1], out[:, 2], out[:, 3], eself
+
+
+def born_long_read_params(path: str, energy_unit: int = 0):
+    """dict of the born/coul/long or buck/coul/long lines of a text file (scema_md_born_long_read_params, a pure host function, no GPU): n,
+    cut_coul, accuracy, solver ("ewald" or "pppm"), K (kcal A/mol), cutmax, style ("born" or "buck") and values[n][n][6] in the order of
+    BORN_DSF_FIELDS, A, C and D in kcal/mol; raises IOError with the reader's message, which names the line"""
+    read = lib().scema_md_born_long_read_params
+    read.restype = C.c_int
+    nt = C.c_int32(0)
+    head, vals = np.zeros(6), np.zeros(BD_MAXEL * BD_MAXEL * len(BORN_DSF_FIELDS))
+    err = C.create_string_buffer(512)
+    rc = read(path.encode(), C.c_int32(energy_unit), C.byref(nt), _p(head), _p(vals), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    n = nt.value
+    return dict(n=n, cut_coul=head[0], accuracy=head[1], solver="pppm" if head[2] else "ewald", K=head[3], cutmax=head[4],
+                style="buck" if head[5] else "born", values=vals[:n * n * len(BORN_DSF_FIELDS)].reshape(n, n, len(BORN_DSF_FIELDS)).copy())
+
+
+def born_long_eval(path: str, g_ewald: float, ti: int, tj: int, qi: float, qj: float, r, energy_unit: int = 0):
+    """(e_born, e_real, fb, fc) at the distances r for that g_ewald, by the code the kernel runs (scema_md_born_long_eval, a pure host
+    function): the force on i is -(fb + fc) (x_j - x_i)"""
+    ev = lib().scema_md_born_long_eval
+    ev.restype = C.c_int
+    r = np.ascontiguousarray(r, float).ravel()
+    out = np.zeros((len(r), 4))
+    err = C.create_string_buffer(512)
+    rc = ev(path.encode(), C.c_int32(energy_unit), C.c_double(g_ewald), C.c_int32(ti), C.c_int32(tj), C.c_double(qi), C.c_double(qj), _p(r),
+            C.c_int32(len(r)), _p(out), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+
+
+def born_long_kvectors(path: str, box, natoms: int, qsqsum: float, energy_unit: int = 0):
+    """the k-space set-up a run would use for that box (scema_md_born_long_kvectors, a pure host function): dict g_ewald, kmax (3), nk,
+    triples [nk][3]"""
+    kv = lib().scema_md_born_long_kvectors
+    kv.restype = C.c_int
+    box = np.ascontiguousarray(box, float)
+    g, kmax, nk = C.c_double(0.0), np.zeros(3, np.int32), C.c_int32(0)
+    err = C.create_string_buffer(512)
+    args = (path.encode(), C.c_int32(energy_unit), _p(box), C.c_int32(natoms), C.c_double(qsqsum), C.byref(g), _p(kmax), C.byref(nk))
+    rc = kv(*args, None, C.c_int32(0), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    tr = np.zeros((max(nk.value, 1), 3), np.int32)
+    rc = kv(*args, _p(tr), C.c_int32(len(tr)), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return dict(g_ewald=g.value, kmax=kmax.copy(), nk=nk.value, triples=tr[:nk.value].copy())
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]

@@ -47,6 +47,7 @@
 #include "host/edip_params.h"
 #include "host/meam_spline_params.h"
 #include "host/born_dsf_params.h"
+#include "host/born_long_params.h"
 #include <hipfft/hipfft.h>
 
 #include "md_kernels.h"
@@ -62,6 +63,7 @@
 #include "md_edip.h"
 #include "md_meam_spline.h"
 #include "md_born_dsf.h"
+#include "md_born_long.h"
 #include "md_rowcells.h"
 #include "md_types.h"
 
@@ -195,12 +197,13 @@ struct RowSlot {
   DevBuf cnt, rows, misc;
   DevBuf fp;   // embedded-atom stage: F'(rho) per atom (md_eam.h EamView)
   DevBuf adp;  // angular-dependent stage: the record {F', mu, lam} per atom (md_adp.h AdpView)
+  DevBuf kn, sk, kshift;   // Ewald ionic stage: triples, the step's c_k S(k) and k, the flips of the run (md_born_long.h BlView); grown like the rows
   // rows built through cells (md_rows.h RowCells; md_rowcells.h has the rule): cell starts, counts / fill cursors, atoms by cell, cell of an atom
   int cap_cellpad = 0, cap_ncells = 0;
   DevBuf cstart, ccur, clist, cellof;
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline, BornDsf };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline, BornDsf, BornLong };
 
 // a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure, ...: row_pots).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
@@ -210,7 +213,8 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable on the device
+  double kspace_cut = 0.0, kspace_acc = 0.0;   // Born/long: cut_coul and the accuracy of the kspace_style line (the k-space set-up of a run: ewald_setup)
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable / BlTable on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -422,6 +426,8 @@ struct scema_md_engine {
   std::vector<RowView> h_rowviews;
   DevBuf d_eamviews;              // embedded-atom stage: parallel to the views
   std::vector<EamView> h_eamviews;
+  DevBuf d_blviews;               // Ewald ionic stage: parallel to the views
+  std::vector<BlView> h_blviews;
   DevBuf d_adpviews;              // angular-dependent stage: parallel to the views
   std::vector<AdpView> h_adpviews;
   DevBuf d_rowcells;              // rows built through cells: parallel to the views (all zero for a replica on the N^2 build)
@@ -540,6 +546,8 @@ struct RowStage {
   // after the synchronisation: statistics and profile, the stage's fault bits (faults), the largest demand / capacity of its rows
   virtual int after_read_back(int fault, double &need) = 0;
   virtual int faults(int fault) = 0;   // the stage's own fault bits of a run or a minimisation -> its error, or 0
+  // a box flip of position pos (fix deform, flip yes), called after mdk_flip on that part's stream st: what the stage keeps in the basis of the box
+  virtual void flipped(hipStream_t, int /*pos*/, const FlipEvent &) {}
 };
 struct RowRun {
   scema_md_engine *e;
@@ -568,7 +576,7 @@ struct RowRun {
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM, Tersoff/mod,
-// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline, Born/DSF: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
+// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline, Born/DSF, Born/long: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
 // folder is searched
 struct RowPot {
   RowKind kind;
@@ -578,7 +586,7 @@ struct RowPot {
   int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
   RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
-constexpr int ROW_NPOT = 10;
+constexpr int ROW_NPOT = 11;
 extern const RowPot row_pots[ROW_NPOT];
 // the entry of the potential attached to a material id, or null
 const RowPot *row_pot_of(scema_md_engine *e, const char *matid);
@@ -593,6 +601,8 @@ bool ionic_replica(const Topo &t);
 // <folder>/in.strain.lammps with a `pair_style born/coul/dsf` line configures the material from its own lines (host/born_dsf_params.h),
 // energy unit 1 iff it says `units real`; no such file or line: nothing happens (0); lines the reader refuses: an error
 int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
+// the same for a `pair_style born/coul/long` or `buck/coul/long` line (host/born_long_params.h), called after the DSF one
+int born_long_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

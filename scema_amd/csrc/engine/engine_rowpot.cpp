@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`; `pair_style born/coul/dsf`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`; `pair_style born/coul/dsf`; `pair_style born/coul/long`, `buck/coul/long`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -334,6 +334,70 @@ int born_dsf_configure_entry(scema_md_engine *e, const char *matid, const char *
   return scema_md_born_dsf_configure(e, matid, path, energy_unit, skin);
 }
 
+// Born/long: Born/DSF's real-space shape with the Ewald split, and a reciprocal sum of its own on the row layout (md_born_long.h).  The
+// k-space set-up is the run's: g_ewald and the integer triples from the run's start box by ewald_setup (engine_kspace.cpp) with the
+// material's cut_coul and accuracy and the replica's charges; the triples stay while fix deform moves the box, and a box flip re-expresses
+// them on the device (flipped).  Triples, the step's S(k) and the flip counts live in the slot and grow like the rows.
+void bl_setup(const scema_md_params &base, double cut_coul, double accuracy, const Topo &T, const double *box, EwaldSetup &ew) {
+  scema_md_params p = base;
+  p.cut_coul = cut_coul;
+  p.kspace_accuracy = accuracy;
+  ewald_setup(p, T, box, ew);
+}
+
+struct BlStage : RowPotStage {
+  BlView *BB = nullptr;   // on the device (upload)
+  BlStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowPotStage(e_, ns, pot) { e->h_blviews.assign(ns, BlView()); }
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
+    if (const int rc = RowPotStage::bind(pos, A, sl, S, need)) return rc;
+    const Topo &T = *A.st->topo;
+    const RowMaterial &M = *e->row_mats.find(T.matid)->second;
+    EwaldSetup ew;
+    bl_setup(e->p, M.kspace_cut, M.kspace_acc, T, e->h_sc[run->order[pos]].box, ew);
+    const int nk = (int)ew.kn.size() / 3;
+    if (nk > BL_MAXK || ew.kmaxd[0] > BL_MAXKD || ew.kmaxd[1] > BL_MAXKD || ew.kmaxd[2] > BL_MAXKD)
+      return fail(e, SCEMA_MD_ERR_ARG,
+                  "a %s replica of %d atoms needs %d k-vectors (indices up to %d %d %d) at accuracy %g: the Ewald sum of the row driver holds %d (indices up to %d); "
+                  "PPPM on the row driver is the follow-up for replicas of that size",
+                  what, T.natoms, nk, ew.kmaxd[0], ew.kmaxd[1], ew.kmaxd[2], M.kspace_acc, BL_MAXK, BL_MAXKD);
+    RowSlot &W = *sl.row;
+    const int nkcap = std::max(64, (nk + 63) / 64 * 64);
+    HIPCHK(W.kn.ensure((size_t)nkcap * 3 * sizeof(int)));
+    HIPCHK(W.sk.ensure((size_t)nkcap * 5 * sizeof(double)));
+    HIPCHK(W.kshift.ensure(2 * sizeof(int)));
+    if (nk) HIPCHK(hipMemcpy(W.kn.p, ew.kn.data(), (size_t)nk * 3 * sizeof(int), hipMemcpyHostToDevice));
+    e->h_zerotab.push_back(MdkZero{W.kshift.as<int>(), 2});   // (the triples are those of this run's start box)
+    BlView B;
+    std::memset(&B, 0, sizeof B);
+    B.nk = nk; B.nkcap = nkcap;
+    for (int d = 0; d < 3; d++) B.kmax[d] = ew.kmaxd[d];
+    B.g = ew.g;
+    for (double q : T.q) { B.qsqsum += q * q; B.qsum += q; }
+    ROWSET(B.kn, W.kn.as<int>()); ROWSET(B.sk, W.sk.as<double>()); ROWSET(B.shift, W.kshift.as<int>());
+    e->h_blviews[pos] = B;
+    return SCEMA_MD_OK;
+  }
+  int upload() override {
+    if (const int rc = RowPotStage::upload()) return rc;
+    const size_t bytes = e->h_blviews.size() * sizeof(BlView);
+    HIPCHK(e->d_blviews.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(e->d_blviews.p, e->h_blviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    BB = e->d_blviews.as<BlView>();
+    return SCEMA_MD_OK;
+  }
+  void launch(hipStream_t st, int pos0, int n) override {
+    int maxnk = 0;
+    for (int k = pos0; k < pos0 + n && k < (int)e->h_blviews.size(); k++) maxnk = std::max(maxnk, e->h_blviews[k].nk);
+    mdk_bl_forces(st, run->D + pos0, VV + pos0, BB + pos0, n, run->maxatoms, maxnk);
+  }
+  void flipped(hipStream_t st, int pos, const FlipEvent &fe) override { mdk_bl_flip(st, BB + pos, fe.nflip[0], fe.nflip[1]); }
+  int crowded(int) override { return SCEMA_MD_OK; }
+};
+
+int born_long_configure_entry(scema_md_engine *e, const char *matid, const char *path, const char *const *, int32_t, int32_t energy_unit, double skin) {
+  return scema_md_born_long_configure(e, matid, path, energy_unit, skin);
+}
+
 template <class Stage>
 RowStage *make_stage(scema_md_engine *e, int ns, const RowPot &pot) { return new Stage(e, ns, pot); }
 
@@ -353,6 +417,7 @@ const RowPot row_pots[ROW_NPOT] = {
     {RowKind::Edip, "EDIP", "scema_md_edip_configure", {".edip", nullptr}, scema_md_edip_configure, make_stage<EdipStage>},
     {RowKind::MeamSpline, "MEAM/spline", "scema_md_meam_spline_configure", {".meam.spline", nullptr}, scema_md_meam_spline_configure, make_stage<MsStage>},
     {RowKind::BornDsf, "Born/DSF", "scema_md_born_dsf_configure", {nullptr, nullptr}, born_dsf_configure_entry, make_stage<BdStage>},
+    {RowKind::BornLong, "Born/long", "scema_md_born_long_configure", {nullptr, nullptr}, born_long_configure_entry, make_stage<BlStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -417,6 +482,19 @@ int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::stri
   if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
   if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
   return scema_md_born_dsf_configure(e, matid, script.c_str(), T.k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
+}
+
+int born_long_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+  const std::string script = folder + "/in.strain.lammps";
+  if (!std::ifstream(script).good()) return SCEMA_MD_OK;
+  BlTable T;
+  std::vector<int> type_map;
+  std::string err;
+  bool has_style = false;
+  const bool ok = scema::read_born_long_params(script, -1, T, type_map, err, nullptr, &has_style);
+  if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
+  if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
+  return scema_md_born_long_configure(e, matid, script.c_str(), T.bd.k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
 }
 
 // ---- what the entry points of the C ABI share.  row_configure: `read` fills type_map from the file and says where its host table
@@ -674,6 +752,65 @@ int scema_md_born_dsf_configure(scema_md_engine *e, const char *matid, const cha
 int scema_md_born_dsf_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
                                     double *virial, double *info) {
   return row_debug_compute(e, RowKind::BornDsf, qp_id, matid, replica, f, e_born, e_coul, virial, info);
+}
+
+int scema_md_born_long_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin) {
+  if (e && energy_unit != 0 && energy_unit != 1) return fail(e, SCEMA_MD_ERR_ARG, "energy unit %d (0: A, C and D eV-based, 1: in kcal/mol)", energy_unit);
+  BlTable T;
+  auto read = [&](const std::vector<std::string> &, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::read_born_long_params(path, energy_unit, T, type_map, err)) return false;
+    blk = RowTableBlock{&T, sizeof T, T.bd.cutmax};
+    return true;
+  };
+  static const char *const no_elements[1] = {"*"};   // (pair_coeff names types: the type map is the identity over the fragment's types)
+  const int rc = row_configure(e, RowKind::BornLong, matid, path, no_elements, 1, skin, read);
+  if (rc) return rc;
+  RowMaterial &M = *e->row_mats[matid];
+  M.kspace_cut = T.bd.cut_coul;
+  M.kspace_acc = T.accuracy;
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
+                                     double *virial, double *info) {
+  double info4[4] = {0.0, 0.0, 0.0, 0.0};
+  const int rc = row_debug_compute(e, RowKind::BornLong, qp_id, matid, replica, f, e_born, e_coul, virial, info4);
+  if (rc) return rc;
+  if (info) {
+    for (int k = 0; k < 4; k++) info[k] = info4[k];
+    info[4] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].nk;
+    info[5] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].g;
+  }
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *kmax,
+                                int32_t *nk, int32_t *triples, int32_t triples_cap, char *errbuf, int32_t errcap) {
+  auto say = [&](const std::string &m) {
+    if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
+  };
+  say("");
+  if (!path || !box || natoms <= 0 || !(qsqsum >= 0.0) || (energy_unit != 0 && energy_unit != 1) || triples_cap < 0) { say("bad arguments"); return SCEMA_MD_ERR_ARG; }
+  BlTable T;
+  std::vector<int> map;
+  std::string err;
+  if (!scema::read_born_long_params(path, energy_unit, T, map, err)) { say(err); return SCEMA_MD_ERR_IO; }
+  scema_md_params p;
+  scema_md_default_params(&p);
+  Topo t;
+  t.natoms = natoms;
+  t.qsqsum = qsqsum;
+  EwaldSetup ew;
+  bl_setup(p, T.bd.cut_coul, T.accuracy, t, box, ew);
+  const int n = (int)ew.kn.size() / 3;
+  if (g_ewald) *g_ewald = ew.g;
+  if (kmax) for (int d = 0; d < 3; d++) kmax[d] = ew.kmaxd[d];
+  if (nk) *nk = n;
+  if (triples) {
+    if (triples_cap < n) { say("triples_cap " + std::to_string(triples_cap) + " < nk = " + std::to_string(n)); return SCEMA_MD_ERR_ARG; }
+    for (int k = 0; k < 3 * n; k++) triples[k] = ew.kn[k];
+  }
+  return SCEMA_MD_OK;
 }
 
 }  // extern "C"

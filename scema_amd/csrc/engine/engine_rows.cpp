@@ -399,7 +399,9 @@ void RowRun::run_steps() {
     if (fl != flip_at.end())
       for (const auto &pk : fl->second) {
         const FlipEvent &fe = flips[pk.first][pk.second];
-        mdk_flip(parts[part_of(parts, pk.first)].st, D + pk.first, fe.tilt[0], fe.tilt[1], fe.tilt[2]);
+        hipStream_t fs = parts[part_of(parts, pk.first)].st;
+        mdk_flip(fs, D + pk.first, fe.tilt[0], fe.tilt[1], fe.tilt[2]);
+        stage.flipped(fs, pk.first, fe);
         e->prof.box_flips += 1;
       }
   }

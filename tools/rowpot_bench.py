@@ -14,11 +14,13 @@ per evaluation at 1 fs.  The replica per potential:
   born_dsf   512 ions of rock-salt NaCl (4 x 4 x 4 cells of 5.64 A: the box of 22.56 A is at least twice cut_coul + skin = 11 A, so the
              rows are built by minimum image; charges +1 and -1, masses 22.98977 and 35.453, thermal velocities at 300 K,
              tests/golden/NaCl.born_dsf: pair_style born/coul/dsf 0.25 10.0, about 190 neighbours per ion)
+  born_long  the born_dsf replica under tests/golden/NaCl.born_long: pair_style born/coul/long 10.0 with kspace_style ewald 1.0e-5, the
+             same neighbours beside 709 k-vectors per replica
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf|born_long [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -116,11 +118,17 @@ def make_born_dsf(e, cells=None):
     e.born_dsf_configure("nacl", os.path.join(GOLD, "NaCl.born_dsf"))
 
 
+def make_born_long(e, cells=None):
+    register_lattice(e, "nacl", ROCKSALT, cells or (4, 4, 4), 5.64, (22.98977, 35.453), basis_types=[0, 0, 0, 0, 1, 1, 1, 1], type_charges=(1.0, -1.0))
+    e.born_long_configure("nacl", os.path.join(GOLD, "NaCl.born_long"))
+
+
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
               "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip),
-              "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline), "born_dsf": ("born_dsf_nacl_512", "nacl", make_born_dsf)}
+              "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline), "born_dsf": ("born_dsf_nacl_512", "nacl", make_born_dsf),
+              "born_long": ("born_long_nacl_512", "nacl", make_born_long)}
 
 
 def main():
