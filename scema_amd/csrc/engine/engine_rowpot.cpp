@@ -170,19 +170,23 @@ int RowPotStage::bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, co
   return SCEMA_MD_OK;
 }
 
+// a host vector of views (or of a stage's side array parallel to them) into its buffer on the device, on the engine's stream
+template <class T>
+static int upload_views(scema_md_engine *e, DevBuf &buf, const std::vector<T> &host, T *&dev) {
+  const size_t bytes = host.size() * sizeof(T);
+  HIPCHK(buf.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(buf.p, host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+  dev = buf.as<T>();
+  return SCEMA_MD_OK;
+}
+
 int RowPotStage::upload() {
-  const size_t bytes = e->h_rowviews.size() * sizeof(RowView);
-  HIPCHK(e->d_rowviews.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(e->d_rowviews.p, e->h_rowviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-  VV = e->d_rowviews.as<RowView>();
+  if (const int rc = upload_views(e, e->d_rowviews, e->h_rowviews, VV)) return rc;
   // the cell arrays travel only where a replica uses them; the launches of this thread learn either way which positions do (md_rows.h)
-  const bool any = std::any_of(e->h_rowcells_on.begin(), e->h_rowcells_on.end(), [](unsigned char c) { return c != 0; });
-  if (any) {
-    const size_t cb = e->h_rowcells.size() * sizeof(RowCells);
-    HIPCHK(e->d_rowcells.ensure(cb));
-    HIPCHK(hipMemcpyAsync(e->d_rowcells.p, e->h_rowcells.data(), cb, hipMemcpyHostToDevice, e->stream));
-  }
-  mdk_rows_cells(VV, any ? e->d_rowcells.as<RowCells>() : nullptr, e->h_rowcells_on.data(), (int)e->h_rowcells_on.size());
+  RowCells *cells = nullptr;
+  if (std::any_of(e->h_rowcells_on.begin(), e->h_rowcells_on.end(), [](unsigned char c) { return c != 0; }))
+    if (const int rc = upload_views(e, e->d_rowcells, e->h_rowcells, cells)) return rc;
+  mdk_rows_cells(VV, cells, e->h_rowcells_on.data(), (int)e->h_rowcells_on.size());
   return SCEMA_MD_OK;
 }
 
@@ -225,7 +229,8 @@ int RowPotStage::crowded(int fault) {
   return SCEMA_MD_OK;
 }
 
-// ---- the stages: each launches its kernels (md_sw.h, md_tersoff.h: both on mdk_row_forces; md_eam.h; md_adp.h) ----
+// ---- the stages: each launches its kernels (mdk_row_forces for the list kernels of md_sw.h, md_tersoff.h, md_vashishta.h, md_edip.h;
+// mdk_row_stage for the stages with launches of their own: md_eam.h, md_adp.h, md_meam_spline.h, md_born_dsf.h, md_born_long.h) ----
 
 namespace {
 
@@ -252,14 +257,7 @@ struct EamStage : RowPotStage {
     e->h_eamviews[pos].fp = (decltype(EamView::fp))sl.row->fp.as<double>();
     return SCEMA_MD_OK;
   }
-  int upload() override {
-    if (const int rc = RowPotStage::upload()) return rc;
-    const size_t bytes = e->h_eamviews.size() * sizeof(EamView);
-    HIPCHK(e->d_eamviews.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(e->d_eamviews.p, e->h_eamviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    AA = e->d_eamviews.as<EamView>();
-    return SCEMA_MD_OK;
-  }
+  int upload() override { const int rc = RowPotStage::upload(); return rc ? rc : upload_views(e, e->d_eamviews, e->h_eamviews, AA); }
   void launch(hipStream_t st, int pos0, int n) override { mdk_eam_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
   int crowded(int) override { return SCEMA_MD_OK; }   // (its kernels keep no list of 32: they never raise the "too many neighbours" bit)
 };
@@ -274,14 +272,7 @@ struct AdpStage : RowPotStage {
     e->h_adpviews[pos].rec = (decltype(AdpView::rec))sl.row->adp.as<double>();
     return SCEMA_MD_OK;
   }
-  int upload() override {
-    if (const int rc = RowPotStage::upload()) return rc;
-    const size_t bytes = e->h_adpviews.size() * sizeof(AdpView);
-    HIPCHK(e->d_adpviews.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(e->d_adpviews.p, e->h_adpviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    AA = e->d_adpviews.as<AdpView>();
-    return SCEMA_MD_OK;
-  }
+  int upload() override { const int rc = RowPotStage::upload(); return rc ? rc : upload_views(e, e->d_adpviews, e->h_adpviews, AA); }
   void launch(hipStream_t st, int pos0, int n) override { mdk_adp_forces(st, run->D + pos0, VV + pos0, AA + pos0, n, run->maxatoms); }
   int crowded(int) override { return SCEMA_MD_OK; }   // (as for EAM: no list of 32)
 };
@@ -377,14 +368,7 @@ struct BlStage : RowPotStage {
     e->h_blviews[pos] = B;
     return SCEMA_MD_OK;
   }
-  int upload() override {
-    if (const int rc = RowPotStage::upload()) return rc;
-    const size_t bytes = e->h_blviews.size() * sizeof(BlView);
-    HIPCHK(e->d_blviews.ensure(bytes));
-    HIPCHK(hipMemcpyAsync(e->d_blviews.p, e->h_blviews.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    BB = e->d_blviews.as<BlView>();
-    return SCEMA_MD_OK;
-  }
+  int upload() override { const int rc = RowPotStage::upload(); return rc ? rc : upload_views(e, e->d_blviews, e->h_blviews, BB); }
   void launch(hipStream_t st, int pos0, int n) override {
     int maxnk = 0;
     for (int k = pos0; k < pos0 + n && k < (int)e->h_blviews.size(); k++) maxnk = std::max(maxnk, e->h_blviews[k].nk);
@@ -471,30 +455,33 @@ int rowpot_from_scripts(scema_md_engine *e, const char *matid, const std::string
   return SCEMA_MD_OK;
 }
 
-int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+// Self-configuration of the ionic styles: a script with the pair_style line of `read`'s style attaches it to the material through
+// `configure`, in the units the script names
+static const BdTable &bd_of(const BdTable &T) { return T; }
+static const BdTable &bd_of(const BlTable &T) { return T.bd; }
+
+template <class Table>
+static int ionic_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder,
+                              bool (*read)(const std::string &, int, Table &, std::vector<int> &, std::string &, std::vector<double> *, bool *),
+                              int (*configure)(scema_md_engine *, const char *, const char *, int32_t, double)) {
   const std::string script = folder + "/in.strain.lammps";
   if (!std::ifstream(script).good()) return SCEMA_MD_OK;
-  BdTable T;
+  Table T;
   std::vector<int> type_map;
   std::string err;
   bool has_style = false;
-  const bool ok = scema::read_born_dsf_params(script, -1, T, type_map, err, nullptr, &has_style);
+  const bool ok = read(script, -1, T, type_map, err, nullptr, &has_style);
   if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
   if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
-  return scema_md_born_dsf_configure(e, matid, script.c_str(), T.k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
+  return configure(e, matid, script.c_str(), bd_of(T).k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
+}
+
+int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+  return ionic_from_scripts<BdTable>(e, matid, folder, scema::read_born_dsf_params, scema_md_born_dsf_configure);
 }
 
 int born_long_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
-  const std::string script = folder + "/in.strain.lammps";
-  if (!std::ifstream(script).good()) return SCEMA_MD_OK;
-  BlTable T;
-  std::vector<int> type_map;
-  std::string err;
-  bool has_style = false;
-  const bool ok = scema::read_born_long_params(script, -1, T, type_map, err, nullptr, &has_style);
-  if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
-  if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
-  return scema_md_born_long_configure(e, matid, script.c_str(), T.bd.k == BD_COULOMB_KCALMOL ? 1 : 0, -1.0);
+  return ionic_from_scripts<BlTable>(e, matid, folder, scema::read_born_long_params, scema_md_born_long_configure);
 }
 
 // ---- what the entry points of the C ABI share.  row_configure: `read` fills type_map from the file and says where its host table

@@ -16,32 +16,6 @@
 
 typedef const double ROW_G *AdpTab;
 
-// A group of 16 lanes walks the row of atom i, a lane per entry: entries with 0 < r^2 < cutoff^2 go to term(j, d, r2), d = x_j - x_i with
-// the entry's image shift.  Index and image code are clamped to what the builder can have written.  A group past the replica's last atom
-// (i >= n) walks nothing; no lane leaves, so the group sums that follow see whole waves.
-template <class Term>
-__device__ __forceinline__ void adp_walk(const RowView &V, const double *s_sh, double cut2, int i, int l16, Term term) {
-  const int n = V.n, cap = V.cap;
-  const bool valid = i < n;
-  const int ic = valid ? i : n - 1;
-  const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-  const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-  const size_t base = (size_t)ic * cap;
-  for (int c = l16; c < cnt; c += 16) {
-    const int ent = V.rows[base + c];
-    const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
-    const double *sh = s_sh + 3 * code;
-    const double d[3] = {V.x[3 * j] - xi0 + sh[0], V.x[3 * j + 1] - xi1 + sh[1], V.x[3 * j + 2] - xi2 + sh[2]};
-    const double r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    if (r2 < cut2 && r2 > 0.0) term(j, d, r2);
-  }
-}
-
-// the material's head into LDS (offsets are read per lane, by the partner's element)
-__device__ __forceinline__ void adp_head_to_lds(AdpTab blk, AdpHead *s_hd) {
-  for (int k = threadIdx.x; k < (int)(sizeof(AdpHead) / 4); k += ROW_FORCE_TPB) ((int *)s_hd)[k] = ((const int ROW_G *)blk)[k];
-}
-
 // Densities, dipoles and quadrupoles.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them
 // at a time; the group's first lane evaluates F, F' and the angular self-energy and writes the atom's record.  Value records only.
 __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_density(const SimDev *sims, const RowView *views, const AdpView *aux) {
@@ -54,7 +28,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_density(const SimDev *sim
   __shared__ AdpHead s_hd;
   __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
-  adp_head_to_lds(blk, &s_hd);
+  rowf_to_lds<int>(&s_hd, blk);   // (offsets are read per lane, by the partner's element)
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int nr = s_hd.eam.nr;
@@ -64,7 +38,9 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_density(const SimDev *sim
     const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const int ti = V.stype[min(i, n - 1)];
     double rho = 0.0, mu[3] = {0.0, 0.0, 0.0}, lam[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    adp_walk(V, s_sh, cut2, i, l16, [&](int j, const double (&d)[3], double r2) __attribute__((always_inline)) {
+    rowf_walk(V, s_sh, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
+      if (!(r2 < cut2 && r2 > 0.0)) return;
+      const double d[3] = {d0, d1, d2};
       const int tj = V.stype[j], pr = ti * EAM_MAXEL + tj;
       int k;
       double p;
@@ -108,7 +84,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_force(const SimDev *sims,
   __shared__ AdpHead s_hd;
   __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
-  adp_head_to_lds(blk, &s_hd);
+  rowf_to_lds<int>(&s_hd, blk);   // (offsets are read per lane, by the partner's element)
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int nr = s_hd.eam.nr;
@@ -124,7 +100,9 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_force(const SimDev *sims,
     const double fpi = ri[0];
     const double mu_i[3] = {ri[1], ri[2], ri[3]}, lam_i[6] = {ri[4], ri[5], ri[6], ri[7], ri[8], ri[9]};
     double fi[3] = {0.0, 0.0, 0.0};
-    adp_walk(V, s_sh, cut2, i, l16, [&](int j, const double (&d)[3], double r2) __attribute__((always_inline)) {
+    rowf_walk(V, s_sh, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
+      if (!(r2 < cut2 && r2 > 0.0)) return;
+      const double d[3] = {d0, d1, d2};
       const int tj = V.stype[j], pr = ti * EAM_MAXEL + tj;
       const double ROW_G *rj = rec + (size_t)ADP_REC * j;
       const double mu_j[3] = {rj[1], rj[2], rj[3]}, lam_j[6] = {rj[4], rj[5], rj[6], rj[7], rj[8], rj[9]};
@@ -142,9 +120,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_force(const SimDev *sims,
       const double fpair = fa + fb;
       fi[0] += g[0] - d[0] * fpair; fi[1] += g[1] - d[1] * fpair; fi[2] += g[2] - d[2] * fpair;   // (x_i - x_j = -d)
       esum[0] += 0.5 * phi;
-      const double ha = 0.5 * fa, hb = 0.5 * fb;
-      wa[0] += ha * d[0] * d[0]; wa[1] += ha * d[1] * d[1]; wa[2] += ha * d[2] * d[2]; wa[3] += ha * d[0] * d[1]; wa[4] += ha * d[0] * d[2]; wa[5] += ha * d[1] * d[2];
-      wb[0] += hb * d[0] * d[0]; wb[1] += hb * d[1] * d[1]; wb[2] += hb * d[2] * d[2]; wb[3] += hb * d[0] * d[1]; wb[4] += hb * d[0] * d[2]; wb[5] += hb * d[1] * d[2];
+      rowf_virial(wa, 0.5 * fa, d0, d1, d2);
+      rowf_virial(wb, 0.5 * fb, d0, d1, d2);
       adp_virial(d, g, wb);
     });
     fi[0] = row_sum(fi[0]); fi[1] = row_sum(fi[1]); fi[2] = row_sum(fi[2]);
@@ -156,10 +133,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_adp_force(const SimDev *sims,
 }
 
 void mdk_adp_forces(hipStream_t st, const SimDev *d, RowView *v, const AdpView *a, int ns, int maxatoms) {
-  if (ns <= 0 || maxatoms <= 0) return;
-  const dim3 gt((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1);
-  mdk_rows_build(st, d, v, ns, maxatoms);
-  hipLaunchKernelGGL(k_adp_density, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  hipLaunchKernelGGL(k_adp_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  mdk_rows_finish(st, d, v, ns);
+  mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
+    hipLaunchKernelGGL(k_adp_density, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+    hipLaunchKernelGGL(k_adp_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+  });
 }

@@ -3,7 +3,7 @@
 // plain Ewald sum is the right solver; the neighbour rows, the integrator, fix deform and the batch machinery are those of the other row
 // stages.  One launch covers every replica of the batch (blockIdx.y), padded to the largest atom count and the largest k list.
 //   k_bl_force ..... real space: the Born term and K q_i q_j erfc(g r)/r over every entry of an atom's row inside cutmax, in the shape of
-//                    k_bd_force (md_born_dsf.hip); stores f
+//                    k_bd_force (md_born_dsf.hip): the body both share (ionic_force, md_ionic_force.h); stores f
 //   k_bl_sfac ...... S(k) = sum_i q_i exp(i k.r_i): a workgroup owns BL_SF_TPB k-vectors of one replica, a thread one of them, and walks
 //                    every atom of the replica in atom order, BL_SF_ATOMS at a time staged in LDS as phase tables exp(2 pi i m u_d),
 //                    m = 0 .. kmax_d.  One writer and a fixed order per S(k), no atomic.  The same thread turns S(k) into c_k S(k) for the
@@ -22,8 +22,7 @@
 #include <algorithm>
 
 #include "md_born_long.h"
-#include "md_kernels.h"
-#include "md_rowforce.h"
+#include "md_ionic_force.h"
 
 #define BL_SF_TPB 128        /* k-vectors of one workgroup of k_bl_sfac */
 #define BL_SF_ATOMS 32       /* atoms staged per pass */
@@ -71,64 +70,17 @@ __device__ __forceinline__ double2 bl_phase(const double2 *p, int n1, int n2, in
   return make_double2(re * c.x - im * ci, re * ci + im * c.x);
 }
 
-// Real space.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time, a lane per
-// entry of its row with the entry's image shift.  Index and image code are clamped to what the builder can have written.  A group past
-// the replica's last atom (i >= n) walks nothing; no lane leaves, so the group sums see whole waves.  Half of a pair's energies and half
-// of its virial go to each end.  Plain FP64 erfc and exp.
-__global__ __launch_bounds__(ROW_FORCE_TPB) void k_bl_force(const SimDev *sims, const RowView *views, const BlView *bls) {
-  const RowView V = views[blockIdx.y];
-  const int n = V.n, cap = V.cap;
-  if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
-  const SimDev &S = sims[blockIdx.y];
-  SimScalars &sc = *S.sc;
-  const double MD_G *q = S.q;
-  const double g = bls[blockIdx.y].g;
-  __shared__ double s_sh[3 * ROW_NSHIFT];
-  __shared__ BlTable s_tab;
-  __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
-  static_assert(sizeof(BlTable) % 8 == 0, "BlTable is copied as doubles");
-  rowf_shifts(V, s_sh);
-  for (int k = threadIdx.x; k < (int)(sizeof(BlTable) / 8); k += ROW_FORCE_TPB) ((double *)&s_tab)[k] = ((const double ROW_G *)V.tab)[k];
-  __syncthreads();
-  const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
-  const double cutmax2 = s_tab.bd.cutmax * s_tab.bd.cutmax, cut_coul = s_tab.bd.cut_coul;
-  double esum[4] = {0.0, 0.0, 0.0, 0.0};   // Born energy, real-space Coulomb energy, ordered pairs inside cutmax, inside cut_coul
-  double wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup)
-    const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
-    const bool valid = i < n;
-    const int ic = valid ? i : n - 1;
-    const int ti = min(max(V.stype[ic], 0), BD_MAXEL - 1);
-    const double qi = q[ic];
-    const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-    const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-    const size_t base = (size_t)ic * cap;
-    double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
-    for (int c = l16; c < cnt; c += 16) {
-      const int ent = V.rows[base + c];
-      const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
-      const double *sh = s_sh + 3 * code;
-      const double d0 = V.x[3 * j] - xi0 + sh[0], d1 = V.x[3 * j + 1] - xi1 + sh[1], d2 = V.x[3 * j + 2] - xi2 + sh[2];
-      const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
-      if (r2 < cutmax2 && r2 > 0.0) {
-        const int tj = min(max(V.stype[j], 0), BD_MAXEL - 1);
-        double eb, ec, fb, fc;
-        bl_pair(s_tab, s_tab.bd.pair[ti * BD_MAXEL + tj], g, qi, q[j], r2, &eb, &ec, &fb, &fc);
-        const double fpair = fb + fc;
-        fi0 -= d0 * fpair; fi1 -= d1 * fpair; fi2 -= d2 * fpair;   // (x_i - x_j = -d)
-        esum[0] += 0.5 * eb; esum[1] += 0.5 * ec; esum[2] += 1.0;
-        if (sqrt(r2) < cut_coul) esum[3] += 1.0;
-        const double hb = 0.5 * fb, hc = 0.5 * fc;
-        wb[0] += hb * d0 * d0; wb[1] += hb * d1 * d1; wb[2] += hb * d2 * d2; wb[3] += hb * d0 * d1; wb[4] += hb * d0 * d2; wb[5] += hb * d1 * d2;
-        wc[0] += hc * d0 * d0; wc[1] += hc * d1 * d1; wc[2] += hc * d2 * d2; wc[3] += hc * d0 * d1; wc[4] += hc * d0 * d2; wc[5] += hc * d1 * d2;
-      }
-    }
-    fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
-    if (valid && l16 == 0) { V.f[3 * i] = fi0; V.f[3 * i + 1] = fi1; V.f[3 * i + 2] = fi2; }
+// Real space: the ionic body (md_ionic_force.h) with bl_pair at the replica's g; the self and background terms are k_bl_sfac's.
+struct BlTerms {
+  double g;
+  __device__ __forceinline__ const BdTable &bd(const BlTable &T) const { return T.bd; }
+  __device__ __forceinline__ void pair(const BlTable &T, const BdPairP &P, double qi, double qj, double r2, double *eb, double *ec, double *fb, double *fc) const {
+    bl_pair(T, P, g, qi, qj, r2, eb, ec, fb, fc);
   }
-  block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
-  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wb, &sc.vir[P_LJ * 6], s_red);
-  block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wc, &sc.vir[P_COUL * 6], s_red);
+  __device__ __forceinline__ void self(const BlTable &, double, double &) const {}
+};
+__global__ __launch_bounds__(ROW_FORCE_TPB) void k_bl_force(const SimDev *sims, const RowView *views, const BlView *bls) {
+  ionic_force<BlTable>(sims, views, BlTerms{bls[blockIdx.y].g});
 }
 
 // Structure factors.  No thread leaves before the last barrier: a thread past the replica's last k-vector sums a zero triple and stores
@@ -239,14 +191,12 @@ __global__ void k_bl_flip(const BlView *b, int fxy, int fxz) {
 }
 
 void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk) {
-  if (ns <= 0 || maxatoms <= 0) return;
-  const dim3 gt((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1);
-  const dim3 gk((unsigned)std::max(1, (maxnk + BL_SF_TPB - 1) / BL_SF_TPB), (unsigned)ns, 1);
-  mdk_rows_build(st, d, v, ns, maxatoms);
-  hipLaunchKernelGGL(k_bl_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
-  hipLaunchKernelGGL(k_bl_sfac, gk, dim3(BL_SF_TPB), 0, st, d, v, b);
-  hipLaunchKernelGGL(k_bl_recip, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
-  mdk_rows_finish(st, d, v, ns);
+  mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
+    const dim3 gk((unsigned)std::max(1, (maxnk + BL_SF_TPB - 1) / BL_SF_TPB), (unsigned)ns, 1);
+    hipLaunchKernelGGL(k_bl_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
+    hipLaunchKernelGGL(k_bl_sfac, gk, dim3(BL_SF_TPB), 0, st, d, v, b);
+    hipLaunchKernelGGL(k_bl_recip, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
+  });
 }
 
 void mdk_bl_flip(hipStream_t st, const BlView *b, int fxy, int fxz) { hipLaunchKernelGGL(k_bl_flip, dim3(1), dim3(64), 0, st, b, fxy, fxz); }

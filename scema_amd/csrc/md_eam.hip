@@ -3,7 +3,7 @@
 // ReaxFF rows); the integrator, thermostat, fix deform, pressure sampling and the batch machinery are the ones of the OPLS path.  One
 // launch covers every replica of the batch (blockIdx.y).
 //   k_eam_density .. rho_i over the entries of atom i's row inside the cutoff, F(rho_i) into the step's energy, F'(rho_i) into fp[i]
-//   k_eam_force .... the same walk with the full pair term (eam/eam_core.h): every F' exists before any force is formed
+//   k_eam_force .... the same walk (rowf_walk, md_rowforce.h) with the full pair term (eam/eam_core.h): every F' exists before any force is formed
 // between the row part and k_row_finish (md_rows.hip).  With full rows every atom sums its own force: neither kernel has an atomic on a
 // force or a density, rows are sorted and the sum over a group has a fixed order, so forces do not depend on the schedule.
 // Engine parts: phi and the virial of phi' go to P_LJ, the embedding energy and the virial of the F' terms to P_ANGLE.  Only their sum
@@ -15,32 +15,6 @@
 #include "md_rowforce.h"
 
 typedef const double ROW_G *EamTab;
-
-// A group of 16 lanes walks the row of atom i, a lane per entry: entries with 0 < r^2 < cutoff^2 go to term(j, d0, d1, d2, r2), d = x_j
-// - x_i with the entry's image shift.  Index and image code are clamped to what the builder can have written.  A group past the
-// replica's last atom (i >= n) walks nothing; no lane leaves, so the group sums that follow see whole waves.
-template <class Term>
-__device__ __forceinline__ void eam_walk(const RowView &V, const double *s_sh, double cut2, int i, int l16, Term term) {
-  const int n = V.n, cap = V.cap;
-  const bool valid = i < n;
-  const int ic = valid ? i : n - 1;
-  const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-  const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-  const size_t base = (size_t)ic * cap;
-  for (int c = l16; c < cnt; c += 16) {
-    const int ent = V.rows[base + c];
-    const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
-    const double *sh = s_sh + 3 * code;
-    const double d0 = V.x[3 * j] - xi0 + sh[0], d1 = V.x[3 * j + 1] - xi1 + sh[1], d2 = V.x[3 * j + 2] - xi2 + sh[2];
-    const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
-    if (r2 < cut2 && r2 > 0.0) term(j, d0, d1, d2, r2);
-  }
-}
-
-// the material's head into LDS (offsets are read per lane, by the partner's element)
-__device__ __forceinline__ void eam_head_to_lds(EamTab blk, EamHead *s_hd) {
-  for (int k = threadIdx.x; k < (int)(sizeof(EamHead) / 4); k += ROW_FORCE_TPB) ((int *)s_hd)[k] = ((const int ROW_G *)blk)[k];
-}
 
 // Densities.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time; the group's
 // first lane evaluates F and F'.  Value records only (eam_core.h).
@@ -54,7 +28,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_density(const SimDev *sim
   __shared__ EamHead s_hd;
   __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
-  eam_head_to_lds(blk, &s_hd);
+  rowf_to_lds<int>(&s_hd, blk);   // (offsets are read per lane, by the partner's element)
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int nr = s_hd.nr;
@@ -64,7 +38,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_density(const SimDev *sim
     const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const int ti = V.stype[min(i, n - 1)];
     double rho = 0.0;
-    eam_walk(V, s_sh, cut2, i, l16, [&](int j, double, double, double, double r2) __attribute__((always_inline)) {
+    rowf_walk(V, s_sh, i, l16, [&](int j, double, double, double, double r2) __attribute__((always_inline)) {
+      if (!(r2 < cut2 && r2 > 0.0)) return;
       int k;
       double p;
       eam_locate(sqrt(r2), rdr, nr, &k, &p);
@@ -97,7 +72,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
   __shared__ EamHead s_hd;
   __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
   rowf_shifts(V, s_sh);
-  eam_head_to_lds(blk, &s_hd);
+  rowf_to_lds<int>(&s_hd, blk);   // (offsets are read per lane, by the partner's element)
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int nr = s_hd.nr;
@@ -111,7 +86,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
     const int ti = V.stype[ic];
     const double fpi = fp[ic];
     double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
-    eam_walk(V, s_sh, cut2, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
+    rowf_walk(V, s_sh, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
+      if (!(r2 < cut2 && r2 > 0.0)) return;
       const int tj = V.stype[j];
       const double r = sqrt(r2);
       int k;
@@ -126,9 +102,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
       const double fpair = fa + fb;
       fi0 -= d0 * fpair; fi1 -= d1 * fpair; fi2 -= d2 * fpair;   // (x_i - x_j = -d)
       esum[0] += 0.5 * phi;
-      const double ha = 0.5 * fa, hb = 0.5 * fb;
-      wa[0] += ha * d0 * d0; wa[1] += ha * d1 * d1; wa[2] += ha * d2 * d2; wa[3] += ha * d0 * d1; wa[4] += ha * d0 * d2; wa[5] += ha * d1 * d2;
-      wb[0] += hb * d0 * d0; wb[1] += hb * d1 * d1; wb[2] += hb * d2 * d2; wb[3] += hb * d0 * d1; wb[4] += hb * d0 * d2; wb[5] += hb * d1 * d2;
+      rowf_virial(wa, 0.5 * fa, d0, d1, d2);
+      rowf_virial(wb, 0.5 * fb, d0, d1, d2);
     });
     fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
     if (i < n && l16 == 0) { V.f[3 * i] = fi0; V.f[3 * i + 1] = fi1; V.f[3 * i + 2] = fi2; }
@@ -139,10 +114,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
 }
 
 void mdk_eam_forces(hipStream_t st, const SimDev *d, RowView *v, const EamView *a, int ns, int maxatoms) {
-  if (ns <= 0 || maxatoms <= 0) return;
-  const dim3 gt((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1);
-  mdk_rows_build(st, d, v, ns, maxatoms);
-  hipLaunchKernelGGL(k_eam_density, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  hipLaunchKernelGGL(k_eam_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  mdk_rows_finish(st, d, v, ns);
+  mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
+    hipLaunchKernelGGL(k_eam_density, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+    hipLaunchKernelGGL(k_eam_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+  });
 }

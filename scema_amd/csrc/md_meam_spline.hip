@@ -4,8 +4,8 @@
 //   k_ms_density ... rho_i = sum_j rho(r_ij) over every entry inside rho's range + the triplets f f g(cos) over the few inside f's range
 //                    (meam_spline/ms_core.h); U(rho_i) - U(0) into the step's energy, U'(rho_i) into fp[i]; the three-body forces, which
 //                    need U' of the central atom alone, in the same launch (skeleton: md_rowforce.h)
-//   k_ms_force ..... the pair gather of k_eam_force: with every U' written, each end of a pair sums its own phi' + U'_i rho'_tj +
-//                    U'_j rho'_ti; no atomic
+//   k_ms_force ..... the pair gather of k_eam_force, on the gather skeleton of md_rowforce.h: with every U' written, each end of a pair
+//                    sums its own phi' + U'_i rho'_tj + U'_j rho'_ti; no atomic
 // The potential has two ranges, as Vashishta has: phi and rho reach their last knots (cutmax, the rows' range), f a clearly shorter one.
 // The list of ROW_MAXIN entries in LDS holds the entries inside f's range alone; the pair terms are taken in place, at any count.
 // Engine parts: phi and the virial of phi' go to P_LJ, the embedding energy, the virial of the U' rho' terms and of the triplets to
@@ -160,13 +160,13 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_ms_density(const SimDev *sims
   rowf_finish<LACC>(V, sc, np, crowded, esum, w0, w3, s_red);
 }
 
-// Pair forces: the walk of k_eam_force.  A lane's entry inside cutmax takes phi' and the two density slopes (each inside its own last
-// knot; phi and rho staged in LDS: three evaluations an entry, a bisection of dependent loads each where the knots are not equidistant)
+// Pair forces: the walk of k_eam_force (rowf_walk, md_rowforce.h).  A lane's entry inside cutmax takes phi' and the two density slopes
+// (each inside its own last knot; phi and rho staged in LDS: three evaluations an entry, a bisection of dependent loads each where the knots are not equidistant)
 // with U' of both ends; the group's sum joins what k_ms_density left in the atom's force -- this launch follows it on the stream
 // and one lane alone touches f[i], so the addition needs no atomic.  Half of a pair's phi and half of its virial go to each end.
 __global__ __launch_bounds__(ROW_FORCE_TPB) void k_ms_force(const SimDev *sims, const RowView *views, const EamView *aux) {
   const RowView V = views[blockIdx.y];
-  const int n = V.n, cap = V.cap;
+  const int n = V.n;
   if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
   const MsTable ROW_G *tab = (const MsTable ROW_G *)V.tab;
   const double ROW_G *fp = aux[blockIdx.y].fp;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_ms_force(const SimDev *sims, 
   const int ne = min(max(tab->nelem, 1), MS_MAXEL);
   const int off_rho = ne * (ne + 1) / 2;
   rowf_shifts(V, s_sh);
-  for (int k = threadIdx.x; k < (off_rho + ne) * (int)(sizeof(MsFn) / 8); k += ROW_FORCE_TPB) ((double *)fn)[k] = ((const double ROW_G *)&tab->fn[0])[k];
+  rowf_to_lds<double>(fn, &tab->fn[0], (off_rho + ne) * (int)(sizeof(MsFn) / 8));
   __syncthreads();
   const double cutmax = tab->cutmax;
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
@@ -185,29 +185,24 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_ms_force(const SimDev *sims, 
   double wa[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup)
     const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
-    const bool valid = i < n;
-    const int ic = valid ? i : n - 1;
+    const int ic = min(i, n - 1);
     const int ti = min(V.stype[ic], ne - 1);
-    const int cnt = valid ? min(V.cnt[ic], cap) : 0;
-    const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
-    const size_t base = (size_t)ic * cap;
     const double upi = fp[ic];
     double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
-    for (int c = l16; c < cnt; c += 16) {
-      const MsEntry E = ms_entry(V, s_sh, ne, base, c, xi0, xi1, xi2);
-      const double r = sqrt(E.r2);
-      if (!(E.r2 > 0.0 && r < cutmax)) continue;
+    rowf_walk(V, s_sh, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
+      const double r = sqrt(r2);
+      if (!(r2 > 0.0 && r < cutmax)) return;   // (r against cutmax, as k_ms_density decides it: not the squares)
+      const int tj = min(V.stype[j], ne - 1);
       double phi, fa, fb;
-      ms_pair(fn[ms_pair_index(ne, ti, E.tj)], fn[off_rho + E.tj], fn[off_rho + ti], r, upi, fp[E.j], &phi, &fa, &fb);
+      ms_pair(fn[ms_pair_index(ne, ti, tj)], fn[off_rho + tj], fn[off_rho + ti], r, upi, fp[j], &phi, &fa, &fb);
       const double fpair = fa + fb;
-      fi0 += E.d0 * fpair; fi1 += E.d1 * fpair; fi2 += E.d2 * fpair;   // (the force on i points along d where the slope is positive)
+      fi0 += d0 * fpair; fi1 += d1 * fpair; fi2 += d2 * fpair;   // (the force on i points along d where the slope is positive)
       esum[0] += 0.5 * phi;
-      const double ha = -0.5 * fa, hb = -0.5 * fb;   // d (x) (force on j), half at each end
-      wa[0] += ha * E.d0 * E.d0; wa[1] += ha * E.d1 * E.d1; wa[2] += ha * E.d2 * E.d2; wa[3] += ha * E.d0 * E.d1; wa[4] += ha * E.d0 * E.d2; wa[5] += ha * E.d1 * E.d2;
-      wb[0] += hb * E.d0 * E.d0; wb[1] += hb * E.d1 * E.d1; wb[2] += hb * E.d2 * E.d2; wb[3] += hb * E.d0 * E.d1; wb[4] += hb * E.d0 * E.d2; wb[5] += hb * E.d1 * E.d2;
-    }
+      rowf_virial(wa, -0.5 * fa, d0, d1, d2);   // d (x) (force on j), half at each end
+      rowf_virial(wb, -0.5 * fb, d0, d1, d2);
+    });
     fi0 = row_sum(fi0); fi1 = row_sum(fi1); fi2 = row_sum(fi2);
-    if (valid && l16 == 0) { V.f[3 * i] += fi0; V.f[3 * i + 1] += fi1; V.f[3 * i + 2] += fi2; }
+    if (i < n && l16 == 0) { V.f[3 * i] += fi0; V.f[3 * i + 1] += fi1; V.f[3 * i + 2] += fi2; }
   }
   block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
   block_atomic_add_n<6, ROW_FORCE_TPB / 64>(wa, &sc.vir[P_LJ * 6], s_red);
@@ -215,12 +210,10 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_ms_force(const SimDev *sims, 
 }
 
 void mdk_ms_forces(hipStream_t st, const SimDev *d, RowView *v, const EamView *a, int ns, int maxatoms) {
-  if (ns <= 0 || maxatoms <= 0) return;
-  const dim3 gt((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1);
-  mdk_rows_build(st, d, v, ns, maxatoms);
-  const int maxpad = (maxatoms + 63) / 64 * 64;
-  if (maxpad <= ROW_LDS_MAXPAD) hipLaunchKernelGGL(k_ms_density<true>, gt, dim3(ROW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v, a);
-  else hipLaunchKernelGGL(k_ms_density<false>, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  hipLaunchKernelGGL(k_ms_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
-  mdk_rows_finish(st, d, v, ns);
+  mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
+    const int maxpad = (maxatoms + 63) / 64 * 64;
+    if (maxpad <= ROW_LDS_MAXPAD) hipLaunchKernelGGL(k_ms_density<true>, gt, dim3(ROW_FORCE_TPB), 3 * (size_t)maxpad * sizeof(double), st, d, v, a);
+    else hipLaunchKernelGGL(k_ms_density<false>, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+    hipLaunchKernelGGL(k_ms_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, a);
+  });
 }

@@ -1,7 +1,9 @@
-// md_rowforce.h -- what the force kernels on the rows of mdk_rows_build share (k_sw_force, md_sw.hip; k_ts_force, md_tersoff.hip): the image
-// shifts, the table of the replica's forces in LDS, the filter of one atom's row and the end of a workgroup.  Device code, included by
-// those two files, for the image shifts and the launch shape alone by md_eam.hip, and for the launch shape by md_rows.hip.  No helper
-// holds a barrier: a kernel's three barriers per round stand in its own body.
+// md_rowforce.h -- what the force kernels on the rows of mdk_rows_build share.  Device code.
+//   the list kernels (k_sw_force, k_ts_force, k_vs_force, k_edip_force, k_ms_density): the image shifts, the table of the replica's
+//     forces in LDS, the filter of one atom's row (rowf_filter) and the end of a workgroup (rowf_finish)
+//   the gather kernels, which walk a whole row and take no atomic on a force (k_eam_*, k_adp_*, k_bd_force, k_bl_force, k_ms_force): the
+//     image shifts, the copy of a table into LDS (rowf_to_lds), the walk of one atom's row (rowf_walk) and the half-pair virial (rowf_virial)
+// md_rows.hip includes it for the launch shape.  No helper holds a barrier: a kernel's barriers stand in its own body.
 #pragma once
 #include "md_device.h"
 #include "md_rows.h"
@@ -21,6 +23,39 @@ __device__ __forceinline__ void rowf_shifts(const RowView &V, double *s_sh) {
     s_sh[3 * code + 1] = sy * V.h[1] + sz * V.h[3];
     s_sh[3 * code + 2] = sz * V.h[2];
   }
+}
+
+// a table (or its first `words` words) from global memory into LDS, by the whole workgroup, in words of the width the table is made of
+template <class Word, class T>
+__device__ __forceinline__ void rowf_to_lds(T *dst, const void ROW_G *src, int words = (int)(sizeof(T) / sizeof(Word))) {
+  static_assert(sizeof(T) % sizeof(Word) == 0, "a table is copied in whole words");
+  for (int k = threadIdx.x; k < words; k += ROW_FORCE_TPB) ((Word *)dst)[k] = ((const Word ROW_G *)src)[k];
+}
+
+// A group of 16 lanes walks the row of atom i, a lane per entry: every entry goes to term(j, d0, d1, d2, r2), d = x_j - x_i with the
+// entry's image shift.  Index and image code are clamped to what the builder can have written.  No cutoff is applied here: the kernel's
+// own acceptance test is the first statement of its term, and so is any clamp of an element.  A group past the replica's last atom
+// (i >= n) walks nothing; no lane leaves, so the group sums that follow see whole waves.
+template <class Term>
+__device__ __forceinline__ void rowf_walk(const RowView &V, const double *s_sh, int i, int l16, Term term) {
+  const int n = V.n, cap = V.cap;
+  const bool valid = i < n;
+  const int ic = valid ? i : n - 1;
+  const int cnt = valid ? min(V.cnt[ic], cap) : 0;
+  const double xi0 = V.x[3 * ic], xi1 = V.x[3 * ic + 1], xi2 = V.x[3 * ic + 2];
+  const size_t base = (size_t)ic * cap;
+  for (int c = l16; c < cnt; c += 16) {
+    const int ent = V.rows[base + c];
+    const int j = min(ent & ROW_JMASK, n - 1), code = min((ent >> 24) & 0x7F, ROW_NSHIFT - 1);
+    const double *sh = s_sh + 3 * code;
+    const double d0 = V.x[3 * j] - xi0 + sh[0], d1 = V.x[3 * j + 1] - xi1 + sh[1], d2 = V.x[3 * j + 2] - xi2 + sh[2];
+    term(j, d0, d1, d2, d0 * d0 + d1 * d1 + d2 * d2);
+  }
+}
+
+// w += h d (x) d (xx, yy, zz, xy, xz, yz): the share of one end of a pair in its virial, h = half the force factor
+__device__ __forceinline__ void rowf_virial(double (&w)[6], double h, double d0, double d1, double d2) {
+  w[0] += h * d0 * d0; w[1] += h * d1 * d1; w[2] += h * d2 * d2; w[3] += h * d0 * d1; w[4] += h * d0 * d2; w[5] += h * d1 * d2;
 }
 
 // LDS FP64 atomic add without return value (ds_add_f64)

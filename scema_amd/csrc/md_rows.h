@@ -62,3 +62,12 @@ void mdk_rows_finish(hipStream_t st, const SimDev *d, RowView *v, int ns);
 // k_row_finish.  mdk_sw_forces (md_sw.h) and mdk_ts_forces (md_tersoff.h) are this with their kernels
 typedef void (*RowForceKernel)(const SimDev *, const RowView *);
 void mdk_row_forces(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms, RowForceKernel lacc, RowForceKernel direct);
+// the same sequence for a stage with launches of its own (two passes, a side array, a k-space part): `launches(gt)` issues them on `st`,
+// gt being the grid of a tile of ROW_TILE central atoms per workgroup and a replica per blockIdx.y
+template <class Launches>
+inline void mdk_row_stage(hipStream_t st, const SimDev *d, RowView *v, int ns, int maxatoms, Launches launches) {
+  if (ns <= 0 || maxatoms <= 0) return;
+  mdk_rows_build(st, d, v, ns, maxatoms);
+  launches(dim3((unsigned)((maxatoms + ROW_TILE - 1) / ROW_TILE), (unsigned)ns, 1));
+  mdk_rows_finish(st, d, v, ns);
+}

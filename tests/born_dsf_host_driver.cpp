@@ -1,7 +1,7 @@
 // born_dsf_host_driver.cpp -- TEST HARNESS, not part of the product: a stand-alone program that runs the functions of
 // scema_amd/csrc/ionic/bd_core.h (the arithmetic the HIP kernel of md_born_dsf.hip executes) as plain loops on the host, with the table of
 // the product's reader (host/born_dsf_params.cpp), so that tests/test_born_dsf_host.py can hold energies, forces and virial against
-// tests/born_dsf_numpy.py without a GPU.  The loop structure follows k_bd_force: per central atom one walk over its neighbours inside
+// tests/born_dsf_numpy.py without a GPU.  The loop structure follows k_bd_force (ionic_force, md_ionic_force.h, with the terms of md_born_dsf.hip): per central atom one walk over its neighbours inside
 // cutmax, this end's half of the pair's energies and virial, then the atom's self energy.  Built by the test with g++; nothing in
 // scema_amd/ links it.
 //

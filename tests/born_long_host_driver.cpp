@@ -2,7 +2,7 @@
 // scema_amd/csrc/ionic/bl_core.h (the arithmetic the HIP kernels of md_born_long.hip execute) as plain loops on the host, with the table of
 // the product's reader (host/born_long_params.cpp), so that tests/test_born_long_host.py can hold energies, forces and virial against
 // tests/born_long_numpy.py without a GPU.  The loop structure follows the kernels: per central atom one walk over its neighbours inside
-// cutmax (k_bl_force); per k-vector S(k) over the atoms in atom order, c_k, the reciprocal energy and virial, then the self and background
+// cutmax (k_bl_force: ionic_force, md_ionic_force.h, with the terms of md_born_long.hip); per k-vector S(k) over the atoms in atom order, c_k, the reciprocal energy and virial, then the self and background
 // terms (k_bl_sfac); per atom the reciprocal force over the k list (k_bl_recip).  g_ewald and the triples come with the input (the test
 // takes them from scema_md_born_long_kvectors or from its own rule).  Built by the test with g++; nothing in scema_amd/ links it.
 //
