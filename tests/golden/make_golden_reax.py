@@ -7,7 +7,7 @@ rate 1e-3 /fs, 20 sampling steps (the replica-set workload of bench.py --force-f
 
   pe1620   the 1 620-atom polyethylene replica of that workload (scema_amd.systems.build_pe(3, 5, 9), velocities seed 3):
            tension, shear-dominated, compression with nts = 20, each followed by a continued second evaluation
-  mixture  864 atoms of water / ammonia / methane / formaldehyde (every element, hydrogen bonds; tests/test_reax_host._mixture,
+  mixture  864 atoms of water / ammonia / methane / formaldehyde (every element, hydrogen bonds; tests/test_reax_host.case_mixture,
            seed 10, velocities seed 2): two strains, each with a continuation
 
 PARITY UNPINNED (no LAMMPS / USER-REAXC here).  ~25 s per evaluation; the chains run in a process pool.  From the repo root:
@@ -42,8 +42,8 @@ def system(name):
         d = build_pe(3, 5, 9)
         sym = ["C" if d["mass"][k] > 5 else "H" for k in d["type"]]
         return sym, np.array(d["x"], float), np.array(d["box"], float), velocities(sym, 3)
-    from test_reax_host import _mixture
-    sym, x, box = _mixture(seed=10)
+    from test_reax_host import case_mixture
+    sym, x, box = case_mixture(seed=10)
     return sym, np.round(x, 10), box, velocities(sym, 2)   # rounded: the file stores exactly what was run
 
 

@@ -25,6 +25,7 @@ import pytest
 
 import adp_numpy as an
 import eam_numpy as en
+import hostdrv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUAG = os.path.join(ROOT, "tests", "golden", "CuAg.adp")
@@ -32,16 +33,7 @@ CUAG = os.path.join(ROOT, "tests", "golden", "CuAg.adp")
 
 @pytest.fixture(scope="module")
 def exe():
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    prog = os.path.join(out, "adp_host_driver")
-    csrc = os.path.join(ROOT, "scema_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "adp_host_driver.cpp"), os.path.join(csrc, "host", "eam_setfl.cpp")]
-    deps = srcs + [os.path.join(csrc, "eam", "eam_core.h"), os.path.join(csrc, "eam", "adp_core.h"), os.path.join(csrc, "host", "eam_setfl.h"),
-                   os.path.join(csrc, "host", "triplet_file.h")]
-    if not os.path.exists(prog) or any(os.path.getmtime(s) > os.path.getmtime(prog) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", prog] + srcs)
-    return prog
+    return hostdrv.build("adp_host_driver", ["tests/adp_host_driver.cpp", "scema_amd/csrc/host/eam_setfl.cpp"], shared=False)
 
 
 class Driver:

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from scema_amd import capi
-from test_born_dsf_host import build_driver
+from test_born_dsf_host import driver_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = {"NaCl": os.path.join(ROOT, "tests", "golden", "NaCl.born_dsf"), "KNaCl": os.path.join(ROOT, "tests", "golden", "KNaCl.born_dsf")}
@@ -60,7 +60,7 @@ def test_the_reader_never_crashes_and_every_refusal_names_a_line(tmp_path, which
 def test_the_corpus_through_the_sanitized_driver(tmp_path):
     """the stand-alone program with -fsanitize=address,undefined over both fixtures and the corpus: exit status 0 (taken) or 1 (refused
     with the reader's message), never a sanitizer report (which ends the program with another status and its own text on stderr)"""
-    exe = build_driver(0, ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"), "_asan")
+    exe = driver_exe(0, ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"), "_asan")
     n = 0
     for which, path in FILES.items():
         items = [("good", open(path, "rb").read())] + corpus(which)[::3]

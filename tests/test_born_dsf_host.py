@@ -15,6 +15,7 @@ Wrong builds of the driver (-DBDH_WRONG=k, switches of the driver, not of the pr
                                      case pass (the self term has neither)
   3  q_i^2 in place of q_i q_j ..... the +/- dimer (the sign of the Coulomb term); the +/+ dimer passes
 """
+import functools
 import os
 import subprocess
 
@@ -22,24 +23,16 @@ import numpy as np
 import pytest
 
 import born_dsf_numpy as bn
+import hostdrv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NACL = os.path.join(ROOT, "tests", "golden", "NaCl.born_dsf")
 KNACL = os.path.join(ROOT, "tests", "golden", "KNaCl.born_dsf")
 
 
-def _build_driver(wrong=0, flags=(), tag=""):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, f"born_dsf_host_driver_{wrong}{tag}")
-    srcs = [os.path.join(ROOT, "tests", "born_dsf_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "born_dsf_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "ionic", "bd_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "born_dsf_params.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", f"-DBDH_WRONG={wrong}", "-I", os.path.join(ROOT, "include"), "-o", exe] + list(flags) + srcs)
-    return exe
-
-
-build_driver = _build_driver
+def driver_exe(wrong=0, flags=(), tag=""):
+    return hostdrv.build(f"born_dsf_host_driver_{wrong}{tag}", ["tests/born_dsf_host_driver.cpp", "scema_amd/csrc/host/born_dsf_params.cpp"], shared=False,
+                         defines=(f"BDH_WRONG={wrong}",), flags=flags)
 
 
 def _run(exe, path, x, box, types, q, energy_unit=0):
@@ -75,7 +68,7 @@ NAMES = sorted(_inputs())
 @pytest.fixture(scope="module")
 def refs():
     """per input: (numpy object, file, case, numpy result, driver result), each computed once"""
-    exe = _build_driver()
+    exe = driver_exe()
     out = {}
     for name, (path, case) in _inputs().items():
         ref = bn.BornDsf(bn.read_born_dsf(path))
@@ -83,23 +76,10 @@ def refs():
     return out
 
 
-def _mismatch(got, ref, tol=1e-12, scale=None):
-    """what differs beyond tol, relative to the largest force component, energy term and virial part of ref, or of `scale` (the
-    perfect cell, whose forces cancel, is measured on its jittered twin)"""
-    bad = []
-    scale = scale or ref
-    if (got["npairs"], got["ncoul"]) != (ref["npairs"], ref["ncoul"]):
-        bad.append("counts")
-    if not np.abs(got["f"] - ref["f"]).max() <= tol * max(np.abs(scale["f"]).max(), 1e-300):
-        bad.append("forces")
-    es = max(abs(ref["e_born"]), abs(ref["e_coul"]), 1e-300)
-    if not (abs(got["e_born"] - ref["e_born"]) <= tol * es and abs(got["e_coul"] - ref["e_coul"]) <= tol * es):
-        bad.append("energy")
-    # (the virial is a difference: Born and Coulomb parts of 2 000 kcal/mol cancel to 25, so 1e-12 is held on the scale of the parts)
-    ws = max(np.abs(scale["w_born"]).max(), np.abs(scale["w_coul"]).max()) if "w_born" in scale else np.abs(scale["w"]).max()
-    if not np.abs(got["w"] - ref["w"]).max() <= tol * max(ws, 1e-300):
-        bad.append("virial")
-    return bad
+# what differs beyond 1e-12 of the largest force component, energy term and virial part of ref, or, forces and virial, of `scale` (the
+# perfect cell, whose forces cancel, is measured on its jittered twin).  The virial is a difference: Born and Coulomb parts of 2 000
+# kcal/mol cancel to 25, so 1e-12 is held on the scale of the parts
+mismatch = functools.partial(hostdrv.mismatch, counters=("npairs", "ncoul"), energies=("e_born", "e_coul"), tol=1e-12, virial_parts=("w_born", "w_coul"))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -107,7 +87,7 @@ def test_static_cases_match_numpy(refs, name):
     _, _, case, ref, got = refs[name]
     assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and np.isfinite(got["e"])
     scale = refs["cell8j"][3] if name == "cell8" else ref
-    assert _mismatch(got, ref, scale=scale) == [], _mismatch(got, ref, scale=scale)
+    assert mismatch(got, ref, scale=scale) == [], mismatch(got, ref, scale=scale)
     # no net force
     assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
     assert abs(got["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
@@ -163,9 +143,9 @@ def test_numpy_virial_is_the_strain_derivative_of_its_energy(refs, name):
 def test_invariance_under_translation(refs):
     ref_bd, path, (x, box, t, q), ref, got = refs["jitter64"]
     shift = np.array([3.21, -7.7, 0.113])
-    ref2, got2 = ref_bd.compute(x + shift, box, t, q), _run(_build_driver(), path, x + shift, box, t, q)
+    ref2, got2 = ref_bd.compute(x + shift, box, t, q), _run(driver_exe(), path, x + shift, box, t, q)
     for a, b in ((ref2, ref), (got2, got)):
-        assert _mismatch(a, b, tol=1e-11) == []
+        assert mismatch(a, b, tol=1e-11) == []
 
 
 def test_madelung_constant_of_rock_salt(refs):
@@ -194,7 +174,7 @@ def test_coulomb_term_vanishes_at_its_cutoff(refs, who):
     """E_coul and its force go to 0 continuously at rc; at and beyond rc they are exactly 0 (the self terms remain)"""
     ref_bd = refs["cell8"][0]
     rc = ref_bd.rc
-    exe = _build_driver()
+    exe = driver_exe()
     comp = (lambda c: ref_bd.compute(*c)) if who == "numpy" else (lambda c: _run(exe, NACL, *c))
     zero = bn.BornDsf(dict(ref_bd.p, A=ref_bd.p["A"] * 0, C=ref_bd.p["C"] * 0, D=ref_bd.p["D"] * 0))      # (cut_lj = rc in this file: the Born part by numpy)
     scale = abs(ref_bd.coul(-1.0, np.array([5.0]))[0][0])
@@ -217,7 +197,7 @@ def test_born_term_jumps_at_its_cutoff(who):
     ref_bd = bn.BornDsf(bn.read_born_dsf(KNACL))
     cut = ref_bd.p["cut_lj"][0, 0]
     assert cut == 7.0 < ref_bd.rc
-    exe = _build_driver()
+    exe = driver_exe()
     comp = (lambda c: ref_bd.compute(*c)) if who == "numpy" else (lambda c: _run(exe, KNACL, *c))
     want = ref_bd.born(0, 0, np.array([cut * (1.0 - 1e-15)]))[0][0]
     inside, at = comp(bn.case_dimer(0, 0, 1.0, 1.0, cut - 1e-9)), comp(bn.case_dimer(0, 0, 1.0, 1.0, cut))
@@ -247,12 +227,12 @@ def test_both_energy_units_describe_one_potential(refs, tmp_path):
     p.write_text("".join(lines))
     ref_real = bn.BornDsf(bn.read_born_dsf(str(p)))
     assert ref_real.p["unit"] == 1 and ref_real.K == bn.K_KCALMOL
-    got_real = _run(_build_driver(), str(p), *case, energy_unit=1)
-    assert _mismatch(got_real, ref_real.compute(*case)) == []
+    got_real = _run(driver_exe(), str(p), *case, energy_unit=1)
+    assert mismatch(got_real, ref_real.compute(*case)) == []
     assert abs(got_real["e_born"] - got["e_born"]) <= 1e-12 * abs(got["e_born"])
-    assert abs(got_real["e_coul"] - got["e_coul"]) <= 1e-7 * abs(got["e_coul"]) and _mismatch(got_real, got, tol=1e-7, scale=ref) == []
+    assert abs(got_real["e_coul"] - got["e_coul"]) <= 1e-7 * abs(got["e_coul"]) and mismatch(got_real, got, tol=1e-7, scale=ref) == []
     # the file's own units line against the other energy unit is refused
-    r = subprocess.run([_build_driver(), NACL, "1"], input="", capture_output=True, text=True)
+    r = subprocess.run([driver_exe(), NACL, "1"], input="", capture_output=True, text=True)
     assert r.returncode == 1 and "line 4: units metal contradicts energy unit 1" in r.stderr
 
 
@@ -262,15 +242,15 @@ PASSES = {1: "dimer_neutral_near", 3: "dimer_pp_near"}      # what a wrong build
 
 @pytest.mark.parametrize("wrong", sorted(WRONG))
 def test_wrong_builds_are_caught(refs, wrong):
-    exe = _build_driver(wrong)
+    exe = driver_exe(wrong)
     name, what = WRONG[wrong]
     _, path, case, ref, _ = refs[name]
-    bad = _mismatch(_run(exe, path, *case), ref)
+    bad = mismatch(_run(exe, path, *case), ref)
     print(f"wrong build {wrong} on {name}: {bad}")
     assert bad == what
     if wrong in PASSES:
         _, path, case, ref, _ = refs[PASSES[wrong]]
-        assert _mismatch(_run(exe, path, *case), ref) == []
+        assert mismatch(_run(exe, path, *case), ref) == []
     # the Madelung value catches all three (q_i^2 turns every attraction into a repulsion)
     _, path, case, ref, _ = refs["cell8"]
     m = -_run(exe, path, *case)["e_coul"] / 4.0 * (bn.A_NACL / 2.0) / refs["cell8"][0].K
@@ -279,7 +259,7 @@ def test_wrong_builds_are_caught(refs, wrong):
     if wrong == 2:      # forces and virial of every case pass: the self term has neither
         for other in ("jitter64", "knacl"):
             _, path, case, ref, _ = refs[other]
-            assert _mismatch(_run(exe, path, *case), ref) == ["energy"]
+            assert mismatch(_run(exe, path, *case), ref) == ["energy"]
     if wrong == 1:      # the Coulomb term no longer reaches zero at rc
         rc = refs["cell8"][0].rc
         got = _run(exe, NACL, *bn.case_dimer(0, 1, 1.0, -1.0, rc - 1e-6))

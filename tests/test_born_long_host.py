@@ -16,6 +16,7 @@ Wrong builds of the driver (-DBLH_WRONG=k, switches of the driver, not of the pr
   2  the half-space factor 1 for 2 ..... energy, forces and virial of every case with a reciprocal part, the Madelung value
   3  the sign of the reciprocal force .. the forces alone: energy and virial pass
 """
+import functools
 import os
 import subprocess
 
@@ -23,6 +24,7 @@ import numpy as np
 import pytest
 
 import born_long_numpy as bl
+import hostdrv
 from scema_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,19 +32,9 @@ NACL = os.path.join(ROOT, "tests", "golden", "NaCl.born_long")
 MGO = os.path.join(ROOT, "tests", "golden", "MgO.buck_long")
 
 
-def _build_driver(wrong=0, flags=(), tag=""):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, f"born_long_host_driver_{wrong}{tag}")
-    csrc = os.path.join(ROOT, "scema_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "born_long_host_driver.cpp"), os.path.join(csrc, "host", "born_long_params.cpp")]
-    deps = srcs + [os.path.join(csrc, "ionic", "bl_core.h"), os.path.join(csrc, "ionic", "bd_core.h"), os.path.join(csrc, "host", "born_long_params.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", f"-DBLH_WRONG={wrong}", "-I", os.path.join(ROOT, "include"), "-o", exe] + list(flags) + srcs)
-    return exe
-
-
-build_driver = _build_driver
+def driver_exe(wrong=0, flags=(), tag=""):
+    return hostdrv.build(f"born_long_host_driver_{wrong}{tag}", ["tests/born_long_host_driver.cpp", "scema_amd/csrc/host/born_long_params.cpp"], shared=False,
+                         defines=(f"BLH_WRONG={wrong}",), flags=flags)
 
 
 def _run(exe, path, x, box, types, q, g, triples, energy_unit=0):
@@ -85,7 +77,7 @@ NAMES = sorted(_inputs())
 @pytest.fixture(scope="module")
 def refs():
     """per input: (numpy object, file, case, numpy result, driver result, (g, triples) of the PRODUCT's set-up), each computed once"""
-    exe = _build_driver()
+    exe = driver_exe()
     out = {}
     for name, (path, case) in _inputs().items():
         ref = bl.BornLong(bl.read_born_long(path))
@@ -96,22 +88,10 @@ def refs():
     return out
 
 
-def _mismatch(got, ref, tol=1e-12, scale=None):
-    """what differs beyond tol, relative to the largest force component, energy term and virial part of ref, or of `scale` (the perfect
-    cell, whose forces cancel, is measured on its jittered twin)"""
-    bad = []
-    scale = scale or ref
-    if (got["npairs"], got["ncoul"]) != (ref["npairs"], ref["ncoul"]):
-        bad.append("counts")
-    if not np.abs(got["f"] - ref["f"]).max() <= tol * max(np.abs(scale["f"]).max(), 1e-300):
-        bad.append("forces")
-    es = max(abs(ref["e_born"]), abs(ref["e_coul"]), abs(ref.get("e_recip", 0.0)), abs(ref.get("e_self", 0.0)), 1e-300)
-    if not (abs(got["e_born"] - ref["e_born"]) <= tol * es and abs(got["e_coul"] - ref["e_coul"]) <= tol * es):
-        bad.append("energy")
-    ws = max(np.abs(scale[k]).max() for k in ("w_born", "w_real", "w_recip")) if "w_born" in scale else np.abs(scale["w"]).max()
-    if not np.abs(got["w"] - ref["w"]).max() <= tol * max(ws, 1e-300):
-        bad.append("virial")
-    return bad
+# what differs beyond 1e-12 of the largest force component, energy term (reciprocal and self terms among them) and virial part of ref, or,
+# forces and virial, of `scale` (the perfect cell, whose forces cancel, is measured on its jittered twin)
+mismatch = functools.partial(hostdrv.mismatch, counters=("npairs", "ncoul"), energies=("e_born", "e_coul"), tol=1e-12,
+                             energy_scale=("e_born", "e_coul", "e_recip", "e_self"), virial_parts=("w_born", "w_real", "w_recip"))
 
 
 def _scale(refs, name):
@@ -123,7 +103,7 @@ def test_static_cases_match_numpy(refs, name):
     ref_bl, _, case, ref, got, (g, tr) = refs[name]
     assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and np.isfinite(got["e"])
     scale = _scale(refs, name)
-    assert _mismatch(got, ref, scale=scale) == [], _mismatch(got, ref, scale=scale)
+    assert mismatch(got, ref, scale=scale) == [], mismatch(got, ref, scale=scale)
     fs = max(np.abs(scale["f"]).max(), ref_bl.K * 1e-12)
     assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * fs and abs(got["f"].sum(axis=0)).max() <= 1e-10 * fs      # no net force
     if name == "single":      # self, background and the ion's own images: no force
@@ -177,9 +157,9 @@ def test_numpy_virial_is_the_strain_derivative_of_its_energy(refs, name):
 def test_invariance_under_translation(refs):
     ref_bl, path, (x, box, t, q), ref, got, (g, tr) = refs["jitter64"]
     shift = np.array([3.21, -7.7, 0.113])
-    ref2, got2 = ref_bl.compute(x + shift, box, t, q, g, tr), _run(_build_driver(), path, x + shift, box, t, q, g, tr)
+    ref2, got2 = ref_bl.compute(x + shift, box, t, q, g, tr), _run(driver_exe(), path, x + shift, box, t, q, g, tr)
     for a, b in ((ref2, ref), (got2, got)):
-        assert _mismatch(a, b, tol=1e-11, scale=ref) == []
+        assert mismatch(a, b, tol=1e-11, scale=ref) == []
 
 
 @pytest.mark.parametrize("cells,accuracy", [(1, 1e-5), (2, 1e-5), (1, 1e-4), (2, 1e-4)])
@@ -273,11 +253,11 @@ def test_both_energy_units_describe_one_potential(refs, tmp_path):
     p.write_text("".join(lines))
     ref_real = bl.BornLong(bl.read_born_long(str(p)))
     assert ref_real.p["unit"] == 1 and ref_real.K == bl.K_KCALMOL
-    got_real = _run(_build_driver(), str(p), x, box, t, q, g, tr, energy_unit=1)
-    assert _mismatch(got_real, ref_real.compute(x, box, t, q, g, tr)) == []
+    got_real = _run(driver_exe(), str(p), x, box, t, q, g, tr, energy_unit=1)
+    assert mismatch(got_real, ref_real.compute(x, box, t, q, g, tr)) == []
     assert abs(got_real["e_born"] - got["e_born"]) <= 1e-12 * abs(got["e_born"])
-    assert abs(got_real["e_coul"] - got["e_coul"]) <= 1e-7 * abs(got["e_coul"]) and _mismatch(got_real, got, tol=1e-7, scale=ref) == []
-    r = subprocess.run([_build_driver(), NACL, "1"], input="", capture_output=True, text=True)
+    assert abs(got_real["e_coul"] - got["e_coul"]) <= 1e-7 * abs(got["e_coul"]) and mismatch(got_real, got, tol=1e-7, scale=ref) == []
+    r = subprocess.run([driver_exe(), NACL, "1"], input="", capture_output=True, text=True)
     assert r.returncode == 1 and "line 4: units metal contradicts energy unit 1" in r.stderr
 
 
@@ -298,10 +278,10 @@ WRONG = {1: ["energy"], 2: ["forces", "energy", "virial"], 3: ["forces"]}
 
 @pytest.mark.parametrize("wrong", sorted(WRONG))
 def test_wrong_builds_are_caught(refs, wrong):
-    exe = _build_driver(wrong)
+    exe = driver_exe(wrong)
     for name in ("jitter64", "c63", "mgo"):
         _, path, (x, box, t, q), ref, _, (g, tr) = refs[name]
-        bad = _mismatch(_run(exe, path, x, box, t, q, g, tr), ref)
+        bad = mismatch(_run(exe, path, x, box, t, q, g, tr), ref)
         print(f"wrong build {wrong} on {name}: {bad}")
         assert bad == WRONG[wrong]
     ref_bl, path, (x, box, t, q), ref, _, (g, tr) = refs["cell8"]

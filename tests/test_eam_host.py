@@ -13,27 +13,19 @@ test_wrong_builds_are_caught asserts all three.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import eam_numpy as en
+import hostdrv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUAG = os.path.join(ROOT, "tests", "golden", "CuAg.eam.alloy")
 
 
-def _build_driver():
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libeam_host.so")
-    csrc = os.path.join(ROOT, "scema_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "eam_host_driver.cpp"), os.path.join(csrc, "host", "eam_setfl.cpp")]
-    deps = srcs + [os.path.join(csrc, "eam", "eam_core.h"), os.path.join(csrc, "host", "eam_setfl.h"), os.path.join(csrc, "host", "triplet_file.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", so] + srcs)
-    L = C.CDLL(so)
+def driver_lib():
+    L = C.CDLL(hostdrv.build("libeam_host.so", ["tests/eam_host_driver.cpp", "scema_amd/csrc/host/eam_setfl.cpp"], shared=True))
     L.eamh_create.restype = C.c_void_p
     L.eamh_create.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]
     L.eamh_destroy.argtypes = [C.c_void_p]
@@ -64,7 +56,7 @@ class Driver:
 
 @pytest.fixture(scope="module")
 def lib():
-    return _build_driver()
+    return driver_lib()
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +103,7 @@ def refs(lib, files):
     return out
 
 
-def _same(got, ref, tol=1e-12):
+def same(got, ref, tol=1e-12):
     assert got["npairs"] == ref["npairs"] and got["nabove"] == ref["nabove"], (got["npairs"], ref["npairs"], got["nabove"], ref["nabove"])
     es = max(abs(ref["e_pair"]), abs(ref["e_embed"]))
     for k in ("e_pair", "e_embed"):
@@ -127,7 +119,7 @@ def _same(got, ref, tol=1e-12):
 @pytest.mark.parametrize("name", NAMES)
 def test_static_cases_match_numpy(refs, name):
     ref_e, drv, case, ref, got = refs[name]
-    _same(got, ref)
+    same(got, ref)
     assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(ref["f"]).max(), 1e-300)
     if name == "single":            # no neighbour: rho = 0, E = F[0] exactly
         assert got["e_embed"] == ref_e.t["F"][0][0] and got["e_pair"] == 0.0 and got["npairs"] == 0
@@ -138,9 +130,9 @@ def test_static_cases_match_numpy(refs, name):
     if name == "rhomax":
         assert ref["nabove"] == 32
     if name == "alloy_ac":          # the same crystal under the other element order: the same numbers
-        _same(got, refs["alloy"][3], tol=1e-13)
+        same(got, refs["alloy"][3], tol=1e-13)
     if name == "one_file":          # a file of copper alone holds the same copper
-        _same(got, refs["j32"][3], tol=1e-13)
+        same(got, refs["j32"][3], tol=1e-13)
 
 
 def test_dimer_at_the_cutoff_to_the_bit(lib):
@@ -156,7 +148,7 @@ def test_dimer_at_the_cutoff_to_the_bit(lib):
             assert o["npairs"] == 0 and o["e_pair"] == 0.0 and o["e_embed"] == 2.0 * f0 and not o["f"].any() and not o["w"].any()
         o = obj(*en.case_dimer(5.5 - 1e-6))
         assert o["npairs"] == 2 and np.isfinite(o["f"]).all() and np.abs(o["f"]).max() < 1e-2 and abs(o["e_pair"]) < 1e-5
-    _same(drv(*en.case_dimer(5.5 - 1e-6)), ref_e.compute(*en.case_dimer(5.5 - 1e-6)))
+    same(drv(*en.case_dimer(5.5 - 1e-6)), ref_e.compute(*en.case_dimer(5.5 - 1e-6)))
 
 
 def test_spline_reproduces_cubic_polynomials(files):
@@ -228,7 +220,7 @@ def test_wrong_builds_are_caught(lib, refs, files):
         path, el, case = inputs[name]
         got = Driver(lib, path, el, wrong=wrong)(*case)
         try:
-            _same(got, refs[name][3])
+            same(got, refs[name][3])
         except AssertionError:
             return True
         return False

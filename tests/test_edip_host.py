@@ -22,6 +22,7 @@ much that is), which is why that cell alone pins so little:
   4  the pair sum over the pairs an atom owns, twice .. coord27 (V2(r_ij, Z_i) != V2(r_ji, Z_j) as soon as Z_i != Z_j)
   5  the triplet numbers of i j j for those of i j k .. the synthetic file
 """
+import functools
 import os
 import subprocess
 
@@ -29,22 +30,16 @@ import numpy as np
 import pytest
 
 import edip_numpy as en
+import hostdrv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SI = os.path.join(ROOT, "tests", "golden", "Si.edip")
 SIC = os.path.join(ROOT, "tests", "golden", "SiC.edip")
 
 
-def _build_driver(wrong=0):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, f"edip_host_driver_{wrong}")
-    srcs = [os.path.join(ROOT, "tests", "edip_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "edip_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "edip", "edip_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "edip_params.h"),
-                   os.path.join(ROOT, "scema_amd", "csrc", "host", "triplet_file.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", f"-DEDH_WRONG={wrong}", "-I", os.path.join(ROOT, "include"), "-o", exe] + srcs)
-    return exe
+def driver_exe(wrong=0):
+    return hostdrv.build(f"edip_host_driver_{wrong}", ["tests/edip_host_driver.cpp", "scema_amd/csrc/host/edip_params.cpp"], shared=False,
+                         defines=(f"EDH_WRONG={wrong}",))
 
 
 def _run(exe, path, elements, x, box, types, energy_unit=0):
@@ -85,7 +80,7 @@ NAMES = sorted(_inputs())
 @pytest.fixture(scope="module")
 def refs():
     """per input: (numpy object, file, elements, case, numpy result, driver result), each computed once"""
-    exe = _build_driver()
+    exe = driver_exe()
     out = {}
     for name, (path, el, case) in _inputs().items():
         ref = en.Edip(en.read_edip(path, el)[0])
@@ -93,22 +88,9 @@ def refs():
     return out
 
 
-def _mismatch(got, ref, tol=1e-12, scale=None):
-    """what differs beyond tol, relative to the largest force component, energy term and virial component of ref, or of `scale` (the
-    perfect cell, whose forces and virial cancel, is measured on its jittered twin)"""
-    bad = []
-    scale = scale or ref
-    if (got["npairs"], got["ntriplets"], got["maxin"]) != (ref["npairs"], ref["ntriplets"], ref["maxin"]):
-        bad.append("counts")
-    fs = max(np.abs(scale["f"]).max(), 1e-300)
-    if not np.abs(got["f"] - ref["f"]).max() <= tol * fs:
-        bad.append("forces")
-    es = max(abs(scale["e2"]), abs(scale["e3"]), 1e-300)
-    if not (abs(got["e2"] - ref["e2"]) <= tol * es and abs(got["e3"] - ref["e3"]) <= tol * es):
-        bad.append("energy")
-    if not np.abs(got["w"] - ref["w"]).max() <= tol * max(np.abs(scale["w"]).max(), 1e-300):
-        bad.append("virial")
-    return bad
+# what differs beyond 1e-12 of the largest force component, energy term and virial component of ref, or of `scale` (the perfect cell,
+# whose forces and virial cancel, is measured on its jittered twin: its energy terms too)
+mismatch = functools.partial(hostdrv.mismatch, counters=("npairs", "ntriplets", "maxin"), energies=("e2", "e3"), tol=1e-12, energy_scale_of_scale=True)
 
 
 @pytest.mark.parametrize("name", COORDINATION)
@@ -124,7 +106,7 @@ def test_static_cases_match_numpy(refs, name):
     _, _, _, case, ref, got = refs[name]
     assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and np.isfinite(got["e"])
     scale = refs["cell8j"][4] if name == "cell8" else ref
-    assert _mismatch(got, ref, scale=scale) == [], _mismatch(got, ref, scale=scale)
+    assert mismatch(got, ref, scale=scale) == [], mismatch(got, ref, scale=scale)
     assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
     if name in ("cell8", "cell8j"):
         assert (ref["maxin"], ref["npairs"], ref["ntriplets"], ref["soft"]) == (4, 8 * 4, 8 * 6, 0)
@@ -146,7 +128,7 @@ def test_static_cases_match_numpy(refs, name):
 def test_a_dimer_at_or_beyond_a_is_exactly_zero(r):
     case = en.case_dimer(r)
     ref = en.Edip(en.read_edip(SI, ["Si"])[0])
-    for got in (ref.compute(*case), _run(_build_driver(), SI, ["Si"], *case)):
+    for got in (ref.compute(*case), _run(driver_exe(), SI, ["Si"], *case)):
         assert got["npairs"] == 0 and got["e2"] == 0.0 and got["e3"] == 0.0 and not got["f"].any() and not got["w"].any()
 
 
@@ -225,7 +207,7 @@ def test_element_orders_and_a_many_to_one_type_map(refs, order):
     else:
         types = np.where((t == 0) & (np.arange(len(t)) % 3 == 0), 2, t)
         assert set(types) == {0, 1, 2}
-    assert _mismatch(_run(_build_driver(), path, order.split(), x, box, types), ref) == []
+    assert mismatch(_run(driver_exe(), path, order.split(), x, box, types), ref) == []
 
 
 def test_both_energy_units(refs):
@@ -233,8 +215,8 @@ def test_both_energy_units(refs):
     _, _, _, case, ref, _ = refs["coord27"]
     p, _ = en.read_edip(SI, ["Si"], energy_unit=1)
     assert p[(0, 0, 0)]["A"] == 7.9821730 and p[(0, 0, 0)]["lambda"] == 1.4533108
-    got = _run(_build_driver(), SI, ["Si"], *case, energy_unit=1)
-    assert _mismatch(got, en.Edip(p).compute(*case)) == []
+    got = _run(driver_exe(), SI, ["Si"], *case, energy_unit=1)
+    assert mismatch(got, en.Edip(p).compute(*case)) == []
     assert abs(got["e"] * en.EV_TO_KCALMOL / ref["e"] - 1.0) < 1e-12
 
 
@@ -243,10 +225,10 @@ WRONG = {1: ("coord27", ["forces", "virial"]), 2: ("coord27", None), 3: ("coord2
 
 @pytest.mark.parametrize("wrong", sorted(WRONG))
 def test_wrong_builds_are_caught(refs, wrong):
-    exe = _build_driver(wrong)
+    exe = driver_exe(wrong)
     name, what = WRONG[wrong]
     _, path, el, case, ref, _ = refs[name]
-    bad = _mismatch(_run(exe, path, el, *case), ref)
+    bad = mismatch(_run(exe, path, el, *case), ref)
     print(f"wrong build {wrong} on {name}: {bad}")
     assert bad and (what is None or bad == what)
     # ... and the diamond cell sees none of them.  Build 3 at 1e-10: the published constants give tau(4) = 1/3 - 2.6e-7, not 1/3, so
@@ -254,4 +236,4 @@ def test_wrong_builds_are_caught(refs, wrong):
     # and its radial derivative, 1.4e-10 x 2 r gamma / (r - a)^2 ~ 1e-9 in the trace of the virial, is 1e-11 of the jittered twin's
     # virial: above the 1e-12 of rounding, below anything a test of the cell could tell from noise in FP64 sums at the GPU's budget
     _, path, el, case, ref, _ = refs["cell8"]
-    assert _mismatch(_run(exe, path, el, *case), ref, tol=1e-10 if wrong == 3 else 1e-12, scale=refs["cell8j"][4]) == []
+    assert mismatch(_run(exe, path, el, *case), ref, tol=1e-10 if wrong == 3 else 1e-12, scale=refs["cell8j"][4]) == []

@@ -10,7 +10,7 @@ pressure 1e-10 relative; whole evaluations 1e-10 / 1e-9 relative (the same arith
 sum in this stage: where two evaluations see the same state they are compared bit for bit.
 
 The trap: in a perfect cubic lattice mu = 0 and lam is a multiple of the unit tensor, the angular energy and forces vanish, and a
-perfect cell tests nothing of this stage.  Every parity case is a cluster, jittered, strained or an alloy; _check_static asserts that
+perfect cell tests nothing of this stage.  Every parity case is a cluster, jittered, strained or an alloy; _check asserts that
 the angular part of the reference force is at least a hundredth of the embedded-atom part wherever there is a pair.
 
 What the groups catch.  Static parity: mu_j with the wrong sign, the trace left in Lambda, the w' term, a pair index mixed up (both
@@ -28,6 +28,7 @@ import pytest
 
 import adp_numpy as an
 import eam_numpy as en
+import rowkit as rk
 from scema_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -60,38 +61,30 @@ def files(tmp_path_factory):
     return {"low": str(d / "CuLow.adp"), "zero": str(d / "zero.adp"), "twin": str(d / "twin.eam.alloy")}
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+ADP = rk.Pot("adp", "adp_configure", "adp_compute", "ADP", ("e_pair", "e_manybody"), ("npairs", "nabove"), counts="pairs {npairs}, above rhomax {nabove}",
+             energy_scale=("e_pair", "e_embed", "e_angular"))
 
 
-def _static(x, box, t, path=CUAG, elements=("Cu",), masses=MASS):
-    e = _engine()
-    try:
-        e.adp_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.adp_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(ADP, CUAG, ("Cu",), MASS)
 
 
-def _check_static(got, ref, what="adp static", angular=True):
-    assert got["npairs"] == ref["npairs"] and got["nabove"] == ref["nabove"], (got["npairs"], ref["npairs"], got["nabove"], ref["nabove"])
-    assert got["maxrow"] <= got["rowcap"]
-    es = max(abs(ref["e_pair"]), abs(ref["e_embed"]), abs(ref["e_angular"]))
-    de = max(abs(got["e_pair"] - ref["e_pair"]), abs(got["e_manybody"] - ref["e_manybody"]))
-    if ref["npairs"] == 0:      # no pair: the embedding energy of bare atoms, no force at all
-        assert not ref["f"].any() and (got["f"] == 0.0).all() and (got["w"] == 0.0).all() and got["e_pair"] == 0.0 and got["e_manybody"] == ref["e_embed"]
-        print(f"{what}: no pairs, forces exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs = np.abs(ref["f"]).max()
-    df = np.abs(got["f"] - ref["f"]).max()
-    dw = np.abs(got["w"] - ref["w"]).max()
-    share = np.abs(ref["f_angular"]).max() / np.abs(ref["f_eam"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / np.abs(ref['w']).max():.2e}, pairs {got['npairs']}, "
-          f"above rhomax {got['nabove']}, rows {got['maxrow']}/{got['rowcap']}, angular / embedded-atom force {share:.3f}")
-    if angular:
-        assert 0.01 <= share          # the case tests the angular terms
-    assert df <= 1e-10 * fs and de <= 1e-9 * es and dw <= 1e-9 * np.abs(ref["w"]).max()
+def no_pairs(got, ref, scale, what):
+    """no pair: the embedding energy of bare atoms, no force at all"""
+    if ref["npairs"] != 0:
+        return False
+    assert not ref["f"].any() and (got["f"] == 0.0).all() and (got["w"] == 0.0).all() and got["e_pair"] == 0.0 and got["e_manybody"] == ref["e_embed"]
+    print(f"{what}: no pairs, forces exactly zero, rows {got['maxrow']}/{got['rowcap']}")
+    return True
+
+
+def _check(got, ref, what="adp static", angular=True):
+    """angular: the case tests the angular terms -- their share of the reference force is asserted wherever there is a pair"""
+    share = np.abs(ref["f_angular"]).max() / np.abs(ref["f_eam"]).max() if ref["npairs"] else None
+    rk.check_static(got, ref, ADP, tol_f=1e-10, tol_e=1e-9, tol_w=1e-9, what=what, no_pairs=no_pairs,
+                    tail=f", angular / embedded-atom force {share:.3f}" if ref["npairs"] else "")
+    if angular and ref["npairs"]:
+        assert 0.01 <= share
 
 
 # the shapes at which a path changes: no pair; three atoms; the image search two boxes deep with an atom's own images; a triclinic box
@@ -110,7 +103,7 @@ def test_static_parity_copper(ref_cu, name):
         assert box[3] == an.A_CU < 6.5 and ref["maxin"] >= 50
     if name == "single":
         assert ref["npairs"] == 0 and ref["e_embed"] == ref_cu.t["F"][0][0]
-    _check_static(_static(x, box, t), ref, what=f"adp static {name}")
+    _check(_static(x, box, t), ref, what=f"adp static {name}")
 
 
 @pytest.mark.parametrize("pair", ["cucu", "cuag", "agag"])
@@ -120,7 +113,7 @@ def test_static_parity_dimers(ref_cuag, pair):
     x, box, t = an.case_dimer(r, types)
     ref = ref_cuag.compute(x, box, t)
     got = _static(x, box, t, elements=("Cu", "Ag"), masses=MASS2)
-    _check_static(got, ref, what=f"adp dimer {pair}")
+    _check(got, ref, what=f"adp dimer {pair}")
     assert np.abs(got["f"][0] + got["f"][1]).max() <= 1e-13 * np.abs(got["f"]).max()          # each end sums its own force: the exact negative to rounding
 
 
@@ -138,7 +131,7 @@ def test_dimer_around_the_cutoff(ref_cu):
         assert x[1, 0] - x[0, 0] == 5.5 + d
         got, ref = _static(x, box, t), ref_cu.compute(x, box, t)
         assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e_pair"]) and math.isfinite(got["e_manybody"])
-        _check_static(got, ref, what=f"adp dimer at the cutoff {d:+.0e}", angular=False)
+        _check(got, ref, what=f"adp dimer at the cutoff {d:+.0e}", angular=False)
         assert got["npairs"] == (2 if d < 0 else 0)
         if d >= 0:
             assert not got["f"].any() and not got["w"].any() and got["e_pair"] == 0.0 and got["e_manybody"] == 2.0 * f0
@@ -160,7 +153,7 @@ def test_static_parity_alloy(ref_cuag, order):
         types[np.nonzero(t == 0)[0][::2]] = 2
         masses = (an.CU_MASS, an.AG_MASS, an.CU_MASS)
         assert len(set(types)) == 3
-    _check_static(_static(x, box, types, elements=tuple(order.split()), masses=masses), ref, what=f"adp static alloy, elements {order}")
+    _check(_static(x, box, types, elements=tuple(order.split()), masses=masses), ref, what=f"adp static alloy, elements {order}")
 
 
 def test_static_parity_above_rhomax(files):
@@ -168,7 +161,7 @@ def test_static_parity_above_rhomax(files):
     x, box, t = an.case_jitter(2, a=0.95 * an.A_CU)
     ref = ref_e.compute(x, box, t)
     assert ref["nabove"] == 32
-    _check_static(_static(x, box, t, path=files["low"]), ref, what="adp static above rhomax")
+    _check(_static(x, box, t, path=files["low"]), ref, what="adp static above rhomax")
 
 
 @pytest.mark.parametrize("n", [63, 65, 1025])
@@ -178,7 +171,7 @@ def test_atom_count_edges(ref_cu, n):
     x, box, t = an.case_count(n)
     ref = ref_cu.compute(x, box, t)
     assert ref["maxin"] > 16
-    _check_static(_static(x, box, t), ref, what=f"adp static n = {n}")
+    _check(_static(x, box, t), ref, what=f"adp static n = {n}")
 
 
 def test_reproducible_bits_and_rows_regrown_after_an_overflow(ref_cu, monkeypatch):
@@ -198,7 +191,7 @@ def test_reproducible_bits_and_rows_regrown_after_an_overflow(ref_cu, monkeypatc
     assert np.abs(a["f"]).max() > 0.0 and np.array_equal(a["f"], b["f"]) and np.array_equal(b["f"], c["f"])
     monkeypatch.setenv("SCEMA_MD_NEIGH_GROW0", "0.05")
     got = _static(x, box, t)
-    _check_static(got, ref, what="adp static after a row overflow")
+    _check(got, ref, what="adp static after a row overflow")
     assert got["rowcap"] < a["rowcap"]          # it started at 8 entries and grew to what the rows asked for, not to the default
     assert np.array_equal(got["f"], a["f"])
 
@@ -274,98 +267,26 @@ def test_shear_constants_feel_the_angular_terms(ref_cu, files):
         e.close()
 
 
-def _velocities(n, temp, seed, mass=an.CU_MASS):
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(n, 3)) * math.sqrt(an.BOLTZ * temp / mass / an.MVV2E)
-    return v - v.mean(axis=0)
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_cu):
     x, box, t = an.case_jitter(2)
-    v = _velocities(len(x), 300.0, 1)
-    e = _engine()
-    try:
-        e.adp_configure("cu", CUAG)
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "cu", 1, box, x, v)
-        e.debug_run("cu", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "cu", 1)
-        xr, vr = ref_cu.nve(x, v, box, t, MASS, 1.0, 20)
-        dx = np.abs(an.minimage_diff(xg, xr, box)).max()
-        print(f"adp nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "cu", 1, box, x, v)
-        p = e.debug_run("cu", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_cu.nve(x, v, box, t, MASS, 1.0, 1)
-        want = ref_cu.pressure_atm(x1, v1, box, t, MASS)
-        print(f"adp sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
-    finally:
-        e.close()
-
-
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
+    s = rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 1))
+    rk.nve_and_sampled_pressure(ADP, ref_cu, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-10)
 
 
 def test_strain_batch_equals_the_two_runs():
     """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
     x, box, t = an.case_jitter(2)
-    v = _velocities(len(x), 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.adp_configure("cu", CUAG)
-            g.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        out = np.array(e.strain_batch([capi.make_sim(0, "cu", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
-        f.set_state(0, "cu", 1, box, x, v)
-        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
-        f.debug_run("cu", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
-        want = -f.debug_run("cu", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
-        print(f"adp strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
-        assert nts == 30 and np.abs(out - want).max() <= 1e-10 * np.abs(want).max()
-        assert e.has_state(0, "cu", 1)
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 2))
+    rk.strain_batch_vs_debug_runs(ADP, s, s1, expect_nts=30, tol=1e-10)
 
 
 @pytest.fixture(scope="module")
 def eleven():
     """11 simulations over two ADP materials (copper, and the alloy with two elements), each one's stress alone in a fresh engine"""
-    mats = {"cu": (an.case_jitter(2), ("Cu",), MASS), "cuag": (an.case_alloy(), ("Cu", "Ag"), MASS2)}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "cu" if q % 3 else "cuag"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), el, masses) in mats.items():
-            e.adp_configure(m, CUAG, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone), [m for _, m, _ in sims]
+    mats = {"cu": (an.case_jitter(2), CUAG, ("Cu",), MASS), "cuag": (an.case_alloy(), CUAG, ("Cu", "Ag"), MASS2)}
+    return rk.batch_vs_alone_fixture(ADP, mats, 11, 21, thermal_masses=MASS)
 
 
 @pytest.mark.parametrize("split", [0, 1])
@@ -373,22 +294,7 @@ def test_batch_of_eleven_equals_each_alone(eleven, split):
     """the stresses of the batch, whole and as part batches, against each simulation alone; and the forces on every end state, evaluated
     in the engine that ran the batch (its slots hold rows and records of other simulations) and in a fresh engine handed the same
     state: equal bit for bit"""
-    fresh, sims, alone, mat_of = eleven
-    e, g = fresh(), fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"adp batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-        for q, m in enumerate(mat_of):
-            box, x, v = e.get_state(q, m, 1)
-            g.set_state(q, m, 1, box, x, v)
-            a, b = e.adp_compute(m, 1, qp=q), g.adp_compute(m, 1, qp=q)
-            assert np.abs(a["f"]).max() > 0.0 and np.array_equal(a["f"], b["f"]), q
-    finally:
-        e.close()
-        g.close()
+    rk.assert_batch_vs_alone(ADP, eleven, split, what="adp batch of 11 over two materials", tol=1e-9, bitwise_forces=True)
 
 
 @pytest.fixture(scope="module")
@@ -399,44 +305,12 @@ def sheared():
     x = x + np.random.default_rng(17).uniform(-0.1, 0.1, x.shape)
     box[6] = 2.0 * an.A_CU
     t = an.zeros(len(x))
-    v = _velocities(len(x), 300.0, 31)
-    lx, ly, lz = box[3:6] - box[:3]
-    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
-
-    def fresh():
-        e = _engine()
-        e.adp_configure("cu", CUAG)
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        return e
-
-    mk = lambda q, s: capi.make_sim(q, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
-    alone, flips, boxes = [], 0, []
-    for q, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
-        flips += e.profile()["box_flips"]
-        boxes.append(e.get_state(q, "cu", 1)[0])
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+    return rk.sheared_fixture(ADP, rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 31)))
 
 
 def test_box_flips_inside_a_split_batch(sheared):
     """eight is the smallest batch that runs as two parts: same stresses as each simulation alone, as many flips, every box back inside"""
-    fresh, sims, alone, flips, boxes = sheared
-    assert flips >= 8
-    e = fresh()
-    try:
-        e.batch_split(1)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"adp sheared batch of 8 (split): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
-        assert err.max() <= 1e-9
-        assert e.profile()["box_flips"] == flips
-        for q in range(8):
-            b = e.get_state(q, "cu", 1)[0]
-            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
-    finally:
-        e.close()
+    rk.assert_flips_in_split_batch(sheared, "cu", 1, what="adp sheared batch of 8 (split)", tol=1e-9)
 
 
 def test_an_update_mixed_with_eam_is_refused():
@@ -481,37 +355,18 @@ def test_configuring_over_an_eam_attachment_and_back(ref_cu):
         with pytest.raises(capi.EngineError, match="no EAM potential"):
             e.eam_compute("m", 1)
         got = e.adp_compute("m", 1)
-        _check_static(got, ref_cu.compute(x, box, t), what="adp over an EAM attachment")
+        _check(got, ref_cu.compute(x, box, t), what="adp over an EAM attachment")
         assert np.array_equal(got["f"], fresh["f"])
         e.eam_configure("m", CUAG_EAM)
-        with pytest.raises(capi.EngineError, match="no ADP potential"):
-            e.adp_compute("m", 1)
+        rk.assert_not_attached(ADP, e, "m")
         eam1 = e.eam_compute("m", 1)
         assert np.array_equal(eam1["f"], eam0["f"]) and np.abs(eam1["f"] - ref_eam["f"]).max() <= 1e-10 * np.abs(ref_eam["f"]).max()
     finally:
         e.close()
 
 
-def _dimer_update(scripts, configure):
-    """one update of a two-atom replica (mu = +-u d, lam = w d (x) d: the angular terms act): every sum of the step has two terms, so its
-    bits do not depend on the order of the atomic sums, and two runs of the same configuration agree bit for bit"""
-    box = np.array([0.0, 0.0, 0.0, 14.0, 14.0, 14.0, 0.0, 0.0, 0.0])
-    x = np.array([[5.0, 6.0, 6.0], [7.4, 6.1, 5.9]])
-    t = an.zeros(2)
-    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
-    e = _engine()
-    try:
-        if configure:
-            e.adp_configure("cu", CUAG, ("Cu",))
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        s = np.array([1.4e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
-        sim = capi.make_sim(0, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
-                            scripts_folder=str(scripts))
-        out = np.array(e.strain_batch([sim])[0].stress[:])
-        box1, x1, v1 = e.get_state(0, "cu", 1)
-        return out, (box1, x1, v1), e.adp_compute("cu", 1, qp=0)["f"]
-    finally:
-        e.close()
+DIMER = rk.Setup("cu", CUAG, ("Cu",), MASS, (np.array([[5.0, 6.0, 6.0], [7.4, 6.1, 5.9]]), np.array([0.0, 0.0, 0.0, 14.0, 14.0, 14.0, 0.0, 0.0, 0.0]), an.zeros(2)),
+                 np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]]))
 
 
 def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
@@ -523,8 +378,11 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
     shutil.copy(CUAG, scripts / "CuAg.adp")
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style adp\n#pair_coeff * * ${locs}/other.adp Ag\n"
                                               "pair_coeff * * ${locs}/CuAg.adp Cu   # the potential\nfix 1 all nvt temp 300 300 100\n")
-    a, sa, fa = _dimer_update(scripts, configure=False)
-    b, sb, fb = _dimer_update(scripts, configure=True)
+    # (a two-atom replica -- mu = +-u d, lam = w d (x) d: the angular terms act -- whose every sum has two terms: two runs of the same
+    # configuration agree bit for bit; the third result is the force on the end state)
+    a, sa, fa = rk.dimer_update(ADP, DIMER, scripts, False, 1.4e-2, compute_qp=0)
+    b, sb, fb = rk.dimer_update(ADP, DIMER, scripts, True, 1.4e-2, compute_qp=0)
+    fa, fb = fa["f"], fb["f"]
     assert np.isfinite(a).all() and np.abs(a).max() > 0.0 and np.abs(fa).max() > 0.0
     assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb)) and np.array_equal(fa, fb)
     # the update configured the material: static forces of the 32-atom cell against the numpy helper
@@ -534,11 +392,10 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
                                       scripts_folder=str(folder))
     e = _engine()
     try:
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3), masses=MASS))
-        with pytest.raises(capi.EngineError, match="no ADP potential"):
-            e.adp_compute("cu", 1)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 3), masses=MASS))
+        rk.assert_not_attached(ADP, e, "cu")
         assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
-        _check_static(e.adp_compute("cu", 1), ref_cu.compute(x, box, t), what="adp self-configured")
+        _check(e.adp_compute("cu", 1), ref_cu.compute(x, box, t), what="adp self-configured")
     finally:
         e.close()
     # an EAM line keeps its precedence: the table is searched in its order
@@ -548,33 +405,11 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
     (both / "in.strain.lammps").write_text("pair_coeff * * ${locs}/CuAg.adp Cu\npair_coeff * * ${locs}/CuAg.eam.alloy Cu\n")
     e = _engine()
     try:
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3), masses=MASS))
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 3), masses=MASS))
         assert e.strain_batch([mk(both)])[0].stress_updated == 1
         assert e.eam_compute("cu", 1)["npairs"] > 0
-        with pytest.raises(capi.EngineError, match="no ADP potential"):
-            e.adp_compute("cu", 1)
+        rk.assert_not_attached(ADP, e, "cu")
     finally:
         e.close()
     # malformed lines, and a line that names a file the folder lacks: the reader's message
-    for k, line in enumerate(["pair_coeff 1 1 ${locs}/CuAg.adp Cu", "pair_coeff * * CuAg.adp Cu", "pair_coeff * * ${locs}/CuAg.adp", "pair_coeff * * ${locs}/sub/CuAg.adp Cu"]):
-        badf = tmp_path / f"bad{k}"
-        badf.mkdir()
-        shutil.copy(CUAG, badf / "CuAg.adp")
-        (badf / "in.strain.lammps").write_text(line + "\n")
-        e = _engine()
-        try:
-            e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
-            with pytest.raises(capi.EngineError, match=r"in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.adp"):
-                e.strain_batch([mk(badf)])
-        finally:
-            e.close()
-    miss = tmp_path / "miss"
-    miss.mkdir()
-    (miss / "in.strain.lammps").write_text("pair_coeff * * ${locs}/CuAg.adp Cu\n")
-    e = _engine()
-    try:
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
-        with pytest.raises(capi.EngineError, match="CuAg.adp: cannot open"):
-            e.strain_batch([mk(miss)])
-    finally:
-        e.close()
+    rk.assert_malformed_pair_coeff_lines(ADP, rk.Setup("cu", CUAG, None, MASS, (x, box, t)), tmp_path, ".adp", "Cu", missing_file=True)

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import born_dsf_numpy as bn
+import rowkit as rk
 from scema_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -46,38 +47,28 @@ def ref_knacl():
     return bn.BornDsf(bn.read_born_dsf(KNACL))
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+BORN_DSF = rk.Pot("born/dsf", "born_dsf_configure", "born_dsf_compute", "Born/DSF", ("e_born", "e_coul"), ("npairs", "ncoul"),
+                  counts="ordered pairs {npairs}, inside cut_coul {ncoul}", ionic=True)
 
 
-def _static(x, box, t, q, path=NACL, masses=MASS2):
-    e = _engine()
-    try:
-        e.born_dsf_configure("m", path)
-        e.register_replica("m", 1, capi.ionic_system(t, q, x, box, masses))
-        return e.born_dsf_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(BORN_DSF, NACL, None, MASS2)
 
 
-def _check_static(got, ref, what, scale=None):
-    scale = scale or ref
-    assert (got["npairs"], got["ncoul"]) == (ref["npairs"], ref["ncoul"]), (got["npairs"], ref["npairs"], got["ncoul"], ref["ncoul"])
-    assert got["maxrow"] <= got["rowcap"]
-    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e_born"]) and math.isfinite(got["e_coul"])
+def no_pairs(got, ref, scale, what):
+    """no pair: the self energy alone, every force and the virial exactly zero"""
+    if ref["npairs"] != 0:
+        return False
     es = max(abs(scale["e_born"]), abs(scale["e_coul"]))
     de = max(abs(got["e_born"] - ref["e_born"]), abs(got["e_coul"] - ref["e_coul"]))
-    if ref["npairs"] == 0:      # no pair: the self energy alone, every force and the virial exactly zero
-        assert not ref["f"].any() and not ref["w"].any() and ref["e_born"] == 0.0
-        assert got["e_born"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"{what}: no pairs, forces and virial exactly zero, self energy err {de / max(es, 1e-300):.2e}, rows {got['maxrow']}/{got['rowcap']}")
-        assert de <= 1e-10 * es
-        return
-    fs, ws = np.abs(scale["f"]).max(), np.abs(scale["w"]).max()
-    df, dw = np.abs(got["f"] - ref["f"]).max(), np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']}, "
-          f"inside cut_coul {got['ncoul']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= 1e-10 * fs and de <= 1e-10 * es and dw <= 1e-10 * ws
+    assert not ref["f"].any() and not ref["w"].any() and ref["e_born"] == 0.0
+    assert got["e_born"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
+    print(f"{what}: no pairs, forces and virial exactly zero, self energy err {de / max(es, 1e-300):.2e}, rows {got['maxrow']}/{got['rowcap']}")
+    assert de <= 1e-10 * es
+    return True
+
+
+_check_static = rk.checker(BORN_DSF, tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)
 
 
 # ---- one ion, dimers ----
@@ -246,16 +237,9 @@ def test_two_evaluations_of_one_state_agree_bit_for_bit():
 
 
 # ---- dynamics ----
-def _velocities(t, masses, temp, seed):
-    rng = np.random.default_rng(seed)
-    m = np.asarray(masses, float)[np.asarray(t)][:, None]
-    v = rng.normal(size=(len(t), 3)) * np.sqrt(bn.BOLTZ * temp / m / bn.MVV2E)
-    return v - (m * v).sum(axis=0) / m.sum()
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_nacl):
     x, box, t, q = bn.case_jitter(2, 6)
-    v = _velocities(t, MASS2, 300.0, 1)
+    v = rk.velocities(t, MASS2, 300.0, 1)
     e = _engine()
     try:
         e.born_dsf_configure("nacl", NACL)
@@ -283,7 +267,7 @@ def test_energy_drift_over_200_steps(ref_nacl):
     """total energy after 200 NVE steps of the jittered 8-ion cell: no further from its start than the numpy integrator's own drift plus
     the static energy budget"""
     x, box, t, q = bn.case_cell8(jitter=0.05)
-    v = _velocities(t, MASS2, 300.0, 5)
+    v = rk.velocities(t, MASS2, 300.0, 5)
     m = np.asarray(MASS2)[t]
     total = lambda c, vel: c["e_born"] + c["e_coul"] + 0.5 * bn.MVV2E * np.sum(m[:, None] * vel * vel)
     ref0 = ref_nacl.compute(x, box, t, q)
@@ -306,96 +290,29 @@ def test_energy_drift_over_200_steps(ref_nacl):
 
 
 # ---- whole evaluations ----
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
-def _by_debug_runs(f, qp, strain, box):
-    nts, rates = _nts_and_rates(strain, box, 1.0, 1e-4)
-    f.debug_run("nacl", 1, nts, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, rates=rates)
-    return -f.debug_run("nacl", 1, 10, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, sample=True) * 1.01325e5, nts
-
-
 def test_strain_batch_equals_the_two_runs_and_a_second_update_continues():
     """an update against the straining run and the sampling run issued through the parity hooks; then a second update from the stored
     states: qp 0 continues from its own, qp 1 branches from qp 0's"""
     x, box, t, q = bn.case_jitter(2, 8)
-    v = _velocities(t, MASS2, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
     s2 = np.array([1.0e-3 * L[0], 0.0, 1.0e-3 * L[2], 0.0, 0.0, 0.0])
-    kw = dict(nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.born_dsf_configure("nacl", NACL)
-            g.register_replica("nacl", 1, capi.ionic_system(t, q, x, box, MASS2, v=v))
-        out1 = np.array(e.strain_batch([capi.make_sim(0, "nacl", 1, s1, most_recent=capi.QP_NONE, **kw)])[0].stress[:])
-        f.set_state(0, "nacl", 1, box, x, v)
-        want1, nts = _by_debug_runs(f, 0, s1, box)
-        print(f"born/dsf strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out1 - want1).max() / np.abs(want1).max():.2e}")
-        assert np.abs(out1 - want1).max() <= 1e-10 * np.abs(want1).max()
-        assert e.has_state(0, "nacl", 1) and not e.has_state(1, "nacl", 1)
-        out2 = e.strain_batch([capi.make_sim(0, "nacl", 1, s2, most_recent=0, **kw), capi.make_sim(1, "nacl", 1, s2, most_recent=0, **kw)])
-        a, b = np.array(out2[0].stress[:]), np.array(out2[1].stress[:])
-        b1, _, _ = f.get_state(0, "nacl", 1)
-        want2, _ = _by_debug_runs(f, 0, s2, b1)
-        print(f"born/dsf second update: {np.abs(a - want2).max() / np.abs(want2).max():.2e}, branch {np.abs(b - want2).max() / np.abs(want2).max():.2e}")
-        assert np.abs(a - want2).max() <= 1e-10 * np.abs(want2).max() and np.abs(b - want2).max() <= 1e-10 * np.abs(want2).max()
-        assert e.has_state(1, "nacl", 1) and np.abs(a - out1).max() > 1e-3 * np.abs(out1).max()
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("nacl", NACL, None, MASS2, (x, box, t, q), rk.velocities(t, MASS2, 300.0, 2))
+    rk.strain_batch_and_a_second_update(BORN_DSF, s, s1, s2, tol=1e-10)
 
 
 @pytest.fixture(scope="module")
 def nine():
     """9 simulations (two part streams) over sodium chloride under NaCl.born_dsf and the three-type crystal under KNaCl.born_dsf, and
     each one's stress alone in a fresh engine"""
-    mats = {"nacl": (bn.case_jitter(2, 6), NACL, MASS2), "knacl": (bn.case_knacl(), KNACL, MASS3)}
-    vel = {m: _velocities(c[0][2], c[2], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for k in range(9):
-        m = "nacl" if k % 3 else "knacl"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((k, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t, q), path, masses) in mats.items():
-            e.born_dsf_configure(m, path)
-            e.register_replica(m, 1, capi.ionic_system(t, q, x, box, masses, v=vel[m]))
-        return e
-
-    mk = lambda k, m, s: capi.make_sim(k, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for k, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(k, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    mats = {"nacl": (bn.case_jitter(2, 6), NACL, None, MASS2), "knacl": (bn.case_knacl(), KNACL, None, MASS3)}
+    return rk.batch_vs_alone_fixture(BORN_DSF, mats, 9, 21)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_nine_over_two_materials_equals_each_alone(nine, split):
     """whole (split 0) and as part batches on two streams (split 1)"""
-    fresh, sims, alone = nine
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"born/dsf batch of 9 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert np.isfinite(out).all() and err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(BORN_DSF, nine, split, what="born/dsf batch of 9 over two materials", tol=1e-9)
 
 
 def test_a_replaced_attachment_rebuilds_the_rows(ref_nacl, ref_knacl):
@@ -410,8 +327,7 @@ def test_a_replaced_attachment_rebuilds_the_rows(ref_nacl, ref_knacl):
         e.born_dsf_configure("m", KNACL)
         _check_static(e.born_dsf_compute("m", 1), ref_knacl.compute(x, box, t, q), "born/dsf after the replacement")
         e.eam_configure("m", CUAG, ("Cu", "Ag"))
-        with pytest.raises(capi.EngineError, match="no Born/DSF potential"):
-            e.born_dsf_compute("m", 1)
+        rk.assert_not_attached(BORN_DSF, e, "m")
         assert e.eam_compute("m", 1)["npairs"] > 0
         e.born_dsf_configure("m", NACL)
         with pytest.raises(capi.EngineError, match="no EAM potential"):
@@ -450,7 +366,7 @@ def test_self_configuration_from_the_scripts_folder(units, tmp_path):
     ref = bn.BornDsf(bn.read_born_dsf(str(scripts / "in.strain.lammps")))
     assert ref.p["unit"] == (1 if units == "real" else 0)
     x, box, t, q = bn.case_jitter(2, 9)
-    v = _velocities(t, MASS2, 300.0, 3)
+    v = rk.velocities(t, MASS2, 300.0, 3)
     L = box[3:6] - box[:3]
     mk = lambda folder: capi.make_sim(0, "nacl", 1, np.array([1e-3 * L[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls",
                                       scripts_folder=str(folder))
@@ -462,8 +378,7 @@ def test_self_configuration_from_the_scripts_folder(units, tmp_path):
                 e.born_dsf_configure("nacl", str(scripts / "in.strain.lammps"), energy_unit=ref.p["unit"])
             e.register_replica("nacl", 1, capi.ionic_system(t, q, x, box, MASS2, v=v))
             if not configure:
-                with pytest.raises(capi.EngineError, match="no Born/DSF potential"):
-                    e.born_dsf_compute("nacl", 1)
+                rk.assert_not_attached(BORN_DSF, e, "nacl")
             o = e.strain_batch([mk(scripts)])[0]
             assert o.stress_updated == 1
             outs.append(np.array(o.stress[:]))

@@ -14,13 +14,13 @@ What the groups catch.  One ion: self, background and image energy with no pair.
 energy and virial).  48 ions in a 1 x 2 x 3 box: kmax differs per dimension.  512 ions: more than one k chunk (709 k-vectors).  The
 straining run: triples that stay while the box deforms, and their re-expression at a flip in xy and one in xz.
 """
-import math
 import os
 
 import numpy as np
 import pytest
 
 import born_long_numpy as bl
+import rowkit as rk
 from scema_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -42,8 +42,9 @@ def ref_mgo():
     return bl.BornLong(bl.read_born_long(MGO))
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+BORN_LONG = rk.Pot("born/long", "born_long_configure", "born_long_compute", "Born/long", ("e_born", "e_coul"), ("npairs", "ncoul"),
+                   counts="ordered pairs {npairs}, nk {got[nk]}, g {got[g_ewald]:.6f}", ionic=True,
+                   energy_scale=("e_born", "e_coul", "e_real", "e_recip", "e_self"))
 
 
 def _mgo_case(seed=17):
@@ -51,14 +52,8 @@ def _mgo_case(seed=17):
     return x, box, t, 1.2 * q
 
 
-def _static(x, box, t, q, path=NACL, masses=MASS_NACL):
-    e = _engine()
-    try:
-        e.born_long_configure("m", path)
-        e.register_replica("m", 1, capi.ionic_system(t, q, x, box, masses))
-        return e.born_long_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(BORN_LONG, NACL, None, MASS_NACL)
 
 
 def _reference(ref, got, x, box, t, q):
@@ -68,19 +63,11 @@ def _reference(ref, got, x, box, t, q):
     return ref.compute(x, box, t, q, g, tr)
 
 
-def _check_static(got, ref, what, scale=None, K=None):
-    scale = scale or ref
-    assert (got["npairs"], got["ncoul"]) == (ref["npairs"], ref["ncoul"]), (got["npairs"], ref["npairs"], got["ncoul"], ref["ncoul"])
-    assert got["maxrow"] <= got["rowcap"]
-    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e_born"]) and math.isfinite(got["e_coul"])
-    es = max(abs(scale[k]) for k in ("e_born", "e_coul", "e_real", "e_recip", "e_self"))
-    de = max(abs(got["e_born"] - ref["e_born"]), abs(got["e_coul"] - ref["e_coul"]))
-    fs = K * 1e-2 if K else np.abs(scale["f"]).max()      # (one ion: no force by symmetry, measured on K e^2/A^2 with the budget 1e-12)
-    ws = max(np.abs(scale[k]).max() for k in ("w_born", "w_real", "w_recip"))
-    df, dw = np.abs(got["f"] - ref["f"]).max(), np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']}, "
-          f"nk {got['nk']}, g {got['g_ewald']:.6f}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= 1e-10 * fs and de <= 1e-10 * es and dw <= 1e-10 * ws
+def _check(got, ref, what, scale=None, K=None):
+    """the virial on the largest of its three parts; one ion, which has no force by symmetry, on K e^2/A^2 with the budget 1e-12"""
+    sc = scale or ref
+    rk.check_static(got, ref, BORN_LONG, tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, what=what, scale=scale, fs=K * 1e-2 if K else None,
+                    ws=max(np.abs(sc[k]).max() for k in ("w_born", "w_real", "w_recip")))
 
 
 def _static_case(ref, case, what, path=NACL, masses=MASS_NACL, scale_case=None, K=None):
@@ -89,7 +76,7 @@ def _static_case(ref, case, what, path=NACL, masses=MASS_NACL, scale_case=None, 
     scale = None
     if scale_case is not None:
         scale = ref.compute(*scale_case)
-    _check_static(got, want, what, scale=scale, K=K)
+    _check(got, want, what, scale=scale, K=K)
     return got, want
 
 
@@ -166,16 +153,9 @@ def test_two_evaluations_of_one_state_agree_bit_for_bit():
 
 
 # ---- dynamics ----
-def _velocities(t, masses, temp, seed):
-    rng = np.random.default_rng(seed)
-    m = np.asarray(masses, float)[np.asarray(t)][:, None]
-    v = rng.normal(size=(len(t), 3)) * np.sqrt(bl.BOLTZ * temp / m / bl.MVV2E)
-    return v - (m * v).sum(axis=0) / m.sum()
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_nacl):
     x, box, t, q = bl.case_jitter(2, 6, sigma=0.08)
-    v = _velocities(t, MASS_NACL, 300.0, 1)
+    v = rk.velocities(t, MASS_NACL, 300.0, 1)
     e = _engine()
     try:
         e.born_long_configure("nacl", NACL)
@@ -204,7 +184,7 @@ def test_energy_drift_over_200_steps(ref_nacl):
     """total energy after 200 NVE steps of the jittered 8-ion cell: no further from its start than the numpy integrator's own drift plus
     the static energy budget"""
     x, box, t, q = bl.case_jitter(1, 4, sigma=0.05)
-    v = _velocities(t, MASS_NACL, 300.0, 5)
+    v = rk.velocities(t, MASS_NACL, 300.0, 5)
     m = np.asarray(MASS_NACL)[t]
     total = lambda c, vel: c["e_born"] + c["e_coul"] + 0.5 * bl.MVV2E * np.sum(m[:, None] * vel * vel)
     g, tr = ref_nacl.setup(box, q)
@@ -236,7 +216,7 @@ def test_a_straining_run_whose_box_flips_in_xy_and_in_xz(ref_nacl):
     ratio = lambda k, step: (box[6 + k] + rates[3 + k] * L * step) / L
     cross = [min(s for s in range(1, nsteps) if ratio(k, s) > 0.50001) for k in (0, 1)]
     assert cross == [6, 10] and ratio(0, 0) < 0.5 and ratio(1, 0) < 0.5
-    v = _velocities(t, MASS_NACL, 300.0, 9)
+    v = rk.velocities(t, MASS_NACL, 300.0, 9)
     xr, vr, box_r, p_r = ref_nacl.nve(x, v, box, t, q, MASS_NACL, 1.0, nsteps, rates=rates)
     e = _engine()
     try:
@@ -258,98 +238,30 @@ def test_a_straining_run_whose_box_flips_in_xy_and_in_xz(ref_nacl):
 
 
 # ---- whole evaluations ----
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
-def _by_debug_runs(f, qp, strain, box):
-    nts, rates = _nts_and_rates(strain, box, 1.0, 1e-4)
-    f.debug_run("nacl", 1, nts, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, rates=rates)
-    return -f.debug_run("nacl", 1, 10, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, sample=True) * 1.01325e5, nts
-
-
 def test_strain_batch_equals_the_two_runs_and_a_second_update_continues():
     """an update against the straining run and the sampling run issued through the parity hooks; then a second update from the stored
     states: qp 0 continues from its own, qp 1 branches from qp 0's"""
     x, box, t, q = bl.case_jitter(2, 8, sigma=0.08)
-    v = _velocities(t, MASS_NACL, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
     s2 = np.array([1.0e-3 * L[0], 0.0, 1.0e-3 * L[2], 0.0, 0.0, 0.0])
-    kw = dict(nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.born_long_configure("nacl", NACL)
-            g.register_replica("nacl", 1, capi.ionic_system(t, q, x, box, MASS_NACL, v=v))
-        out1 = np.array(e.strain_batch([capi.make_sim(0, "nacl", 1, s1, most_recent=capi.QP_NONE, **kw)])[0].stress[:])
-        f.set_state(0, "nacl", 1, box, x, v)
-        want1, nts = _by_debug_runs(f, 0, s1, box)
-        print(f"born/long strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out1 - want1).max() / np.abs(want1).max():.2e}")
-        assert np.abs(out1 - want1).max() <= 1e-10 * np.abs(want1).max()
-        assert e.has_state(0, "nacl", 1) and not e.has_state(1, "nacl", 1)
-        out2 = e.strain_batch([capi.make_sim(0, "nacl", 1, s2, most_recent=0, **kw), capi.make_sim(1, "nacl", 1, s2, most_recent=0, **kw)])
-        a, b = np.array(out2[0].stress[:]), np.array(out2[1].stress[:])
-        b1, _, _ = f.get_state(0, "nacl", 1)
-        want2, _ = _by_debug_runs(f, 0, s2, b1)
-        print(f"born/long second update: {np.abs(a - want2).max() / np.abs(want2).max():.2e}, branch {np.abs(b - want2).max() / np.abs(want2).max():.2e}")
-        assert np.abs(a - want2).max() <= 1e-10 * np.abs(want2).max() and np.abs(b - want2).max() <= 1e-10 * np.abs(want2).max()
-        assert e.has_state(1, "nacl", 1) and np.abs(a - out1).max() > 1e-3 * np.abs(out1).max()
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("nacl", NACL, None, MASS_NACL, (x, box, t, q), rk.velocities(t, MASS_NACL, 300.0, 2))
+    rk.strain_batch_and_a_second_update(BORN_LONG, s, s1, s2, tol=1e-10)
 
 
 @pytest.fixture(scope="module")
 def nine():
     """9 simulations (two part streams) over both fixtures and three sizes -- 64 ions of NaCl (nk 128), 48 ions of NaCl in the 1 x 2 x 3 box,
     64 ions under MgO.buck_long (nk of accuracy 1e-4) -- so one launch holds different nk; and each one's stress alone in a fresh engine"""
-    mats = {"nacl64": (bl.case_jitter(2, 6, sigma=0.08), NACL, MASS_NACL), "nacl48": (bl.case_jitter((1, 2, 3), 3, sigma=0.08), NACL, MASS_NACL),
-            "mgo64": (_mgo_case(), MGO, MASS_MGO)}
-    vel = {m: _velocities(c[0][2], c[2], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    names = sorted(mats)
-    rng = np.random.default_rng(21)
-    sims = []
-    for k in range(9):
-        m = names[k % 3]
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((k, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t, q), path, masses) in mats.items():
-            e.born_long_configure(m, path)
-            e.register_replica(m, 1, capi.ionic_system(t, q, x, box, masses, v=vel[m]))
-        return e
-
-    mk = lambda k, m, s: capi.make_sim(k, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for k, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(k, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    mats = {"nacl64": (bl.case_jitter(2, 6, sigma=0.08), NACL, None, MASS_NACL), "nacl48": (bl.case_jitter((1, 2, 3), 3, sigma=0.08), NACL, None, MASS_NACL),
+            "mgo64": (_mgo_case(), MGO, None, MASS_MGO)}
+    return rk.batch_vs_alone_fixture(BORN_LONG, mats, 9, 21, pick=lambda k: sorted(mats)[k % 3])
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_nine_over_both_fixtures_equals_each_alone(nine, split):
     """whole (split 0) and as part batches on two streams (split 1)"""
-    fresh, sims, alone = nine
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"born/long batch of 9 over both fixtures (split {split}): max rel err {err.max():.2e}")
-        assert np.isfinite(out).all() and err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(BORN_LONG, nine, split, what="born/long batch of 9 over both fixtures", tol=1e-9)
 
 
 def _real_units_copy(path, buck):
@@ -382,7 +294,7 @@ def test_self_configuration_from_the_scripts_folder(style, units, tmp_path):
     ref = bl.BornLong(bl.read_born_long(str(scripts / "in.strain.lammps")))
     assert ref.p["unit"] == (1 if units == "real" else 0) and ref.p["style"] == style
     x, box, t, q = bl.case_jitter(2, 9, sigma=0.08) if style == "born" else _mgo_case()
-    v = _velocities(t, masses, 300.0, 3)
+    v = rk.velocities(t, masses, 300.0, 3)
     L = box[3:6] - box[:3]
     mk = lambda folder: capi.make_sim(0, "ion", 1, np.array([1e-3 * L[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls",
                                       scripts_folder=str(folder))
@@ -394,13 +306,12 @@ def test_self_configuration_from_the_scripts_folder(style, units, tmp_path):
                 e.born_long_configure("ion", str(scripts / "in.strain.lammps"), energy_unit=ref.p["unit"])
             e.register_replica("ion", 1, capi.ionic_system(t, q, x, box, masses, v=v))
             if not configure:
-                with pytest.raises(capi.EngineError, match="no Born/long potential"):
-                    e.born_long_compute("ion", 1)
+                rk.assert_not_attached(BORN_LONG, e, "ion")
             o = e.strain_batch([mk(scripts)])[0]
             assert o.stress_updated == 1
             outs.append(np.array(o.stress[:]))
             got = e.born_long_compute("ion", 1)
-            _check_static(got, _reference(ref, got, x, box, t, q), f"{style}/long {'configured' if configure else 'self-configured'}, units {units}")
+            _check(got, _reference(ref, got, x, box, t, q), f"{style}/long {'configured' if configure else 'self-configured'}, units {units}")
         finally:
             e.close()
     assert np.isfinite(outs[0]).all() and np.abs(outs[0] - outs[1]).max() <= 1e-9 * np.abs(outs[1]).max()

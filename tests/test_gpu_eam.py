@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import eam_numpy as en
+import rowkit as rk
 import tersoff_numpy as tsn
 from scema_amd import capi
 
@@ -55,35 +56,23 @@ def low_file(tmp_path_factory):
     return p
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+EAM = rk.Pot("eam", "eam_configure", "eam_compute", "EAM", ("e_pair", "e_embed"), ("npairs", "nabove"), counts="pairs {npairs}, above rhomax {nabove}")
 
 
-def _static(x, box, t, path=CUAG, elements=("Cu",), masses=MASS):
-    e = _engine()
-    try:
-        e.eam_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.eam_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(EAM, CUAG, ("Cu",), MASS)
 
 
-def _check_static(got, ref, tol=1e-10, what="eam static"):
-    assert got["npairs"] == ref["npairs"] and got["nabove"] == ref["nabove"], (got["npairs"], ref["npairs"], got["nabove"], ref["nabove"])
-    assert got["maxrow"] <= got["rowcap"]
-    es = max(abs(ref["e_pair"]), abs(ref["e_embed"]))
-    de = max(abs(got["e_pair"] - ref["e_pair"]), abs(got["e_embed"] - ref["e_embed"]))
-    if ref["npairs"] == 0:      # no pair: the embedding energy of bare atoms, no force at all
-        assert not ref["f"].any() and (got["f"] == 0.0).all() and (got["w"] == 0.0).all() and got["e_pair"] == 0.0 and got["e_embed"] == ref["e_embed"]
-        print(f"{what}: no pairs, forces exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs = np.abs(ref["f"]).max()
-    df = np.abs(got["f"] - ref["f"]).max()
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / np.abs(ref['w']).max():.2e}, pairs {got['npairs']}, "
-          f"above rhomax {got['nabove']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= tol * fs and de <= tol * es and dw <= tol * np.abs(ref["w"]).max()
+def no_pairs(got, ref, scale, what):
+    """no pair: the embedding energy of bare atoms, no force at all"""
+    if ref["npairs"] != 0:
+        return False
+    assert not ref["f"].any() and (got["f"] == 0.0).all() and (got["w"] == 0.0).all() and got["e_pair"] == 0.0 and got["e_embed"] == ref["e_embed"]
+    print(f"{what}: no pairs, forces exactly zero, rows {got['maxrow']}/{got['rowcap']}")
+    return True
+
+
+_check_static = rk.checker(EAM, "eam static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)
 
 
 # the shapes at which a path changes: no pair; one pair; the image search two boxes deep with an atom's own images, at the example width
@@ -177,36 +166,10 @@ def test_forces_are_bit_reproducible(ref_cu):
     _check_static(a, ref_cu.compute(x, box, t), what="eam static 256 atoms")
 
 
-def _velocities(n, temp, seed, mass=en.CU_MASS):
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(n, 3)) * math.sqrt(en.BOLTZ * temp / mass / en.MVV2E)
-    return v - v.mean(axis=0)
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_cu):
     x, box, t = en.case_jitter(2)
-    v = _velocities(len(x), 300.0, 1)
-    e = _engine()
-    try:
-        e.eam_configure("cu", CUAG)
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "cu", 1, box, x, v)
-        e.debug_run("cu", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "cu", 1)
-        xr, vr = ref_cu.nve(x, v, box, t, MASS, 1.0, 20)
-        dx = np.abs(en.minimage_diff(xg, xr, box)).max()
-        print(f"eam nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "cu", 1, box, x, v)
-        p = e.debug_run("cu", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_cu.nve(x, v, box, t, MASS, 1.0, 1)
-        want = ref_cu.pressure_atm(x1, v1, box, t, MASS)
-        print(f"eam sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
-    finally:
-        e.close()
+    s = rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 1))
+    rk.nve_and_sampled_pressure(EAM, ref_cu, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-10)
 
 
 @pytest.fixture(scope="module")
@@ -259,89 +222,28 @@ def test_elastic_constants(static_constants):
         e.close()
 
 
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
 def test_strain_batch_equals_the_two_runs():
     """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
     x, box, t = en.case_jitter(2)
-    v = _velocities(len(x), 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.eam_configure("cu", CUAG)
-            g.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        out = np.array(e.strain_batch([capi.make_sim(0, "cu", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
-        f.set_state(0, "cu", 1, box, x, v)
-        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
-        f.debug_run("cu", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
-        want = -f.debug_run("cu", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
-        print(f"eam strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
-        assert nts == 30 and np.abs(out - want).max() <= 1e-10 * np.abs(want).max()
-        assert e.has_state(0, "cu", 1)
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 2))
+    rk.strain_batch_vs_debug_runs(EAM, s, s1, expect_nts=30, tol=1e-10)
 
 
 @pytest.fixture(scope="module")
 def eleven():
     """11 simulations over two EAM materials (copper, and the alloy with two elements), each one's stress and the forces on its end state
     alone in a fresh engine"""
-    mats = {"cu": (en.case_jitter(2), ("Cu",), MASS), "cuag": (en.case_alloy(), ("Cu", "Ag"), MASS2)}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "cu" if q % 3 else "cuag"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), el, masses) in mats.items():
-            e.eam_configure(m, CUAG, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone), [m for _, m, _ in sims]
+    mats = {"cu": (en.case_jitter(2), CUAG, ("Cu",), MASS), "cuag": (en.case_alloy(), CUAG, ("Cu", "Ag"), MASS2)}
+    return rk.batch_vs_alone_fixture(EAM, mats, 11, 21, thermal_masses=MASS)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_eleven_equals_each_alone(eleven, split):
     """the stresses of the batch against each simulation alone; and the forces on every end state, evaluated in the engine that ran the
     batch (its slots hold rows and F' of other simulations) and in a fresh engine handed the same state: equal bit for bit"""
-    fresh, sims, alone, mat_of = eleven
-    e, g = fresh(), fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"eam batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-        for q, m in enumerate(mat_of):
-            box, x, v = e.get_state(q, m, 1)
-            g.set_state(q, m, 1, box, x, v)
-            a, b = e.eam_compute(m, 1, qp=q), g.eam_compute(m, 1, qp=q)
-            assert np.abs(a["f"]).max() > 0.0 and np.array_equal(a["f"], b["f"]), q
-    finally:
-        e.close()
-        g.close()
+    rk.assert_batch_vs_alone(EAM, eleven, split, what="eam batch of 11 over two materials", tol=1e-9, bitwise_forces=True)
 
 
 @pytest.fixture(scope="module")
@@ -351,44 +253,12 @@ def sheared():
     x, box = en.fcc(5, 2, 2, en.A_CU)
     box[6] = 2.0 * en.A_CU
     t = en.zeros(len(x))
-    v = _velocities(len(x), 300.0, 31)
-    lx, ly, lz = box[3:6] - box[:3]
-    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
-
-    def fresh():
-        e = _engine()
-        e.eam_configure("cu", CUAG)
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=v, masses=MASS))
-        return e
-
-    mk = lambda q, s: capi.make_sim(q, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
-    alone, flips, boxes = [], 0, []
-    for q, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
-        flips += e.profile()["box_flips"]
-        boxes.append(e.get_state(q, "cu", 1)[0])
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+    return rk.sheared_fixture(EAM, rk.Setup("cu", CUAG, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 31)))
 
 
 def test_box_flips_inside_a_split_batch(sheared):
     """eight is the smallest batch that runs as two parts: same stresses as each simulation alone, as many flips, every box back inside"""
-    fresh, sims, alone, flips, boxes = sheared
-    assert flips >= 8
-    e = fresh()
-    try:
-        e.batch_split(1)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"eam sheared batch of 8 (split): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
-        assert err.max() <= 1e-9
-        assert e.profile()["box_flips"] == flips
-        for q in range(8):
-            b = e.get_state(q, "cu", 1)[0]
-            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
-    finally:
-        e.close()
+    rk.assert_flips_in_split_batch(sheared, "cu", 1, what="eam sheared batch of 8 (split)", tol=1e-9)
 
 
 def test_mixed_updates_are_refused(small_pe):
@@ -413,8 +283,7 @@ def test_mixed_updates_are_refused(small_pe):
             assert not e.has_state(0, "cu", 1) and not e.has_state(1, other, 1)
         assert e.strain_batch([mk(0, "cu")])[0].stress_updated == 1
         for other in ("pe", "sw", "ts"):
-            with pytest.raises(capi.EngineError, match="no EAM potential"):
-                e.eam_compute(other, 1)
+            rk.assert_not_attached(EAM, e, other)
     finally:
         e.close()
 
@@ -439,8 +308,7 @@ def test_configuring_replaces_the_other_attachment(ref_cu):
         _check_static(got, ref_cu.compute(x, box, t), what="eam over a Tersoff attachment")
         assert np.array_equal(got["f"], fresh["f"])
         e.tersoff_configure("m", SIC)
-        with pytest.raises(capi.EngineError, match="no EAM potential"):
-            e.eam_compute("m", 1)
+        rk.assert_not_attached(EAM, e, "m")
         ts1 = e.tersoff_compute("m", 2)
         assert ts1["npairs"] == ts0["npairs"] == ref_ts["npairs"]
         assert np.abs(ts1["f"] - ref_ts["f"]).max() <= 1e-10 * np.abs(ref_ts["f"]).max()
@@ -448,24 +316,8 @@ def test_configuring_replaces_the_other_attachment(ref_cu):
         e.close()
 
 
-def _dimer_update(scripts, configure):
-    """one update of a two-atom replica: every sum of the step has two terms, so its bits do not depend on the order of the atomic sums,
-    and two runs of the same configuration agree bit for bit"""
-    box = np.array([0.0, 0.0, 0.0, 14.0, 14.0, 14.0, 0.0, 0.0, 0.0])
-    x = np.array([[5.0, 6.0, 6.0], [7.4, 6.1, 5.9]])
-    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
-    e = _engine()
-    try:
-        if configure:
-            e.eam_configure("cu", CUAG, ("Cu",))
-        e.register_replica("cu", 1, capi.bare_system(en.zeros(2), x, box, v=v, masses=MASS))
-        s = np.array([1.4e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
-        sim = capi.make_sim(0, "cu", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
-                            scripts_folder=str(scripts))
-        out = np.array(e.strain_batch([sim])[0].stress[:])
-        return out, e.get_state(0, "cu", 1)
-    finally:
-        e.close()
+DIMER = rk.Setup("cu", CUAG, ("Cu",), MASS, (np.array([[5.0, 6.0, 6.0], [7.4, 6.1, 5.9]]), np.array([0.0, 0.0, 0.0, 14.0, 14.0, 14.0, 0.0, 0.0, 0.0]), en.zeros(2)),
+                 np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]]))
 
 
 def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
@@ -476,8 +328,9 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
     shutil.copy(CUAG, scripts / "CuAg.eam.alloy")
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style eam/alloy\n#pair_coeff * * ${locs}/other.eam.alloy Ag\n"
                                               "pair_coeff * * ${locs}/CuAg.eam.alloy Cu   # the potential\nfix 1 all nvt temp 300 300 100\n")
-    a, sa = _dimer_update(scripts, configure=False)
-    b, sb = _dimer_update(scripts, configure=True)
+    # (a two-atom replica: every sum of the step has two terms, so two runs of the same configuration agree bit for bit)
+    a, sa = rk.dimer_update(EAM, DIMER, scripts, False, 1.4e-2)
+    b, sb = rk.dimer_update(EAM, DIMER, scripts, True, 1.4e-2)
     assert np.isfinite(a).all() and np.abs(a).max() > 0.0
     assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
     # the update configured the material: static forces of the 32-atom cell against the numpy helper
@@ -487,9 +340,8 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
                                       scripts_folder=str(folder))
     e = _engine()
     try:
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3), masses=MASS))
-        with pytest.raises(capi.EngineError, match="no EAM potential"):
-            e.eam_compute("cu", 1)
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 3), masses=MASS))
+        rk.assert_not_attached(EAM, e, "cu")
         assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
         _check_static(e.eam_compute("cu", 1), ref_cu.compute(x, box, t), what="eam self-configured")
     finally:
@@ -505,40 +357,16 @@ def test_self_configuration_from_the_scripts_folder(ref_cu, tmp_path):
             shutil.copy(extra, d / "Si.sw")
         e = _engine()
         try:
-            e.register_replica("cu", 1, capi.bare_system(ts, xs, bs, v=_velocities(len(xs), 300.0, 3, tsn.SI_MASS)))
+            e.register_replica("cu", 1, capi.bare_system(ts, xs, bs, v=rk.velocities(ts, (tsn.SI_MASS,), 300.0, 3)))
             Ls = bs[3:6] - bs[:3]
             sim = capi.make_sim(0, "cu", 1, np.array([1e-3 * Ls[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls", scripts_folder=str(d))
             assert e.strain_batch([sim])[0].stress_updated == 1
             assert getattr(e, hook)("cu", 1)["npairs"] >= 2 * len(xs)
-            with pytest.raises(capi.EngineError, match="no EAM potential"):
-                e.eam_compute("cu", 1)
+            rk.assert_not_attached(EAM, e, "cu")
         finally:
             e.close()
-    # malformed lines
-    for k, line in enumerate(["pair_coeff 1 1 ${locs}/CuAg.eam.alloy Cu", "pair_coeff * * CuAg.eam.alloy Cu", "pair_coeff * * ${locs}/CuAg.eam.alloy",
-                              "pair_coeff * * ${locs}/sub/CuAg.eam.alloy Cu"]):
-        badf = tmp_path / f"bad{k}"
-        badf.mkdir()
-        shutil.copy(CUAG, badf / "CuAg.eam.alloy")
-        (badf / "in.strain.lammps").write_text(line + "\n")
-        e = _engine()
-        try:
-            e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
-            with pytest.raises(capi.EngineError, match=r"in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.eam\.alloy"):
-                e.strain_batch([mk(badf)])
-        finally:
-            e.close()
-    # a line that names a file the folder lacks: the reader's message
-    miss = tmp_path / "miss"
-    miss.mkdir()
-    (miss / "in.strain.lammps").write_text("pair_coeff * * ${locs}/CuAg.eam.alloy Cu\n")
-    e = _engine()
-    try:
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, masses=MASS))
-        with pytest.raises(capi.EngineError, match="CuAg.eam.alloy: cannot open"):
-            e.strain_batch([mk(miss)])
-    finally:
-        e.close()
+    # malformed lines, and a line that names a file the folder lacks: the reader's message
+    rk.assert_malformed_pair_coeff_lines(EAM, rk.Setup("cu", CUAG, None, MASS, (x, box, t)), tmp_path, ".eam.alloy", "Cu", missing_file=True)
 
 
 def test_init_material_runs_for_an_eam_material(static_constants):
@@ -550,7 +378,7 @@ def test_init_material_runs_for_an_eam_material(static_constants):
     e = _engine()
     try:
         e.eam_configure("cu", CUAG)
-        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 10.0, 9), masses=MASS))
+        e.register_replica("cu", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 10.0, 9), masses=MASS))
         length, stress, stiff = e.init_material("cu", 1, dt=1.0, temperature=10.0, nss=20, strain_ampl=0.005, strain_rate=1e-4)
         assert np.allclose(length, box[3:6] - box[:3]) and np.isfinite(stress).all() and np.isfinite(stiff).all()
         c11, c12 = stiff[0, 0] / 1e9, stiff[0, 3] / 1e9        # file order 00, 01, 02, 11, 12, 22

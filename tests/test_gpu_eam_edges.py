@@ -19,11 +19,19 @@ import numpy as np
 import pytest
 
 import eam_numpy as en
+import rowkit as rk
 from scema_amd import capi
-from test_gpu_eam import CUAG, MASS, _check_static, _engine, _nts_and_rates, _static, _velocities, low_file, ref_cu, sheared  # noqa: F401  (fixtures)
+from test_gpu_eam import CUAG, EAM, MASS, low_file, no_pairs, ref_cu, sheared  # noqa: F401  (fixtures)
 from test_row_edges_host import EAM_COUNTS, NVE_STEPS, four_variants, moved_and_outside, nve_case
 
 pytestmark = pytest.mark.gpu
+
+
+_engine, _nts_and_rates = rk.engine, rk.nts_and_rates
+_static = rk.static_of(EAM, CUAG, ("Cu",), MASS)
+
+
+_check_static = rk.checker(EAM, "eam static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)      # the static budget of tests/test_gpu_eam.py
 
 
 def _counts(ref):
@@ -139,7 +147,7 @@ def ragged(four_file):
     four-element file; each material under its own id; 10 straining steps, nss 10; and each one's stress alone in a fresh engine"""
     mats = {"c4": (en.case_cell4(), CUAG, ("Cu",), MASS), "big": (en.case_count(1200), CUAG, ("Cu",), MASS),
             "four": (en.case_four(4), four_file, tuple(en.FOUR), _masses(en.FOUR)), "j108": (en.case_jitter(3), CUAG, ("Cu",), MASS)}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 60 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
+    vel = {m: rk.velocities(np.zeros(len(c[0][0]), int), MASS, 300.0, 60 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
     sims = []
     for q, m in enumerate(["c4", "big", "four", "j108", "j108", "four", "big", "c4"]):      # (both parts hold every size)
         L = mats[m][0][1][3:6] - mats[m][0][1][:3]

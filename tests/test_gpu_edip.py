@@ -23,7 +23,6 @@ tile, the force table past the LDS limit.  Clusters: the ballot rank across a tr
 synthetic file: a swapped [i][j][k] index, pair numbers from the wrong end.  Dynamics and pressure: the sign of the coordination part in
 the virial.  Whole evaluations: rows kept or rebuilt under the wrong material, part streams.
 """
-import math
 import os
 import shutil
 
@@ -31,6 +30,7 @@ import numpy as np
 import pytest
 
 import edip_numpy as en
+import rowkit as rk
 import sw_numpy as swn
 from scema_amd import capi
 
@@ -55,18 +55,12 @@ def ref_sic():
     return en.Edip(en.read_edip(SIC, list(EL2))[0])
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+EDIP = rk.Pot("edip", "edip_configure", "edip_compute", "EDIP", ("e2", "e3"), ("npairs", "ntriplets"),
+              counts="ordered pairs {npairs} ({ref[soft]} in (c, a)), triplets {ntriplets}")
 
 
-def _static(x, box, t, path=SI, elements=EL1, masses=MASS1):
-    e = _engine()
-    try:
-        e.edip_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.edip_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(EDIP, SI, EL1, MASS1)
 
 
 def _soft(ref):
@@ -74,24 +68,15 @@ def _soft(ref):
     assert 2 * ref["soft"] >= ref["npairs"] > 0, (ref["soft"], ref["npairs"])
 
 
-def _check_static(got, ref, what, scale=None):
-    scale = scale or ref
-    assert (got["npairs"], got["ntriplets"]) == (ref["npairs"], ref["ntriplets"]), (got["npairs"], ref["npairs"], got["ntriplets"], ref["ntriplets"])
-    assert got["maxrow"] <= got["rowcap"]
-    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e2"]) and math.isfinite(got["e3"])
-    if ref["npairs"] == 0 or not np.abs(scale["f"]).max() > 0.0:      # no term at all (or all of them underflow to zero): exactly zero, and no scale to divide by
-        assert ref["e"] == 0.0 and not ref["f"].any() and not ref["w"].any()
-        assert got["e2"] == 0.0 and got["e3"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"{what}: {ref['npairs']} ordered pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs, ws = np.abs(scale["f"]).max(), np.abs(scale["w"]).max()
-    es = max(abs(scale["e2"]), abs(scale["e3"]))
-    df = np.abs(got["f"] - ref["f"]).max()
-    de = max(abs(got["e2"] - ref["e2"]), abs(got["e3"] - ref["e3"]))
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']} ({ref['soft']} in (c, a)), "
-          f"triplets {got['ntriplets']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= 1e-10 * fs and de <= 1e-9 * es and dw <= 1e-9 * ws
+def no_pairs(got, ref, scale, what):
+    """no term at all (or all of them underflow to zero): exactly zero, and no scale to divide by"""
+    if ref["npairs"] != 0 and np.abs(scale["f"]).max() > 0.0:
+        return False
+    rk.all_exactly_zero(got, ref, EDIP, what, head=f"{ref['npairs']} ordered pairs")
+    return True
+
+
+_check_static = rk.checker(EDIP, tol_f=1e-10, tol_e=1e-9, tol_w=1e-9, no_pairs=no_pairs)
 
 
 def test_dimers(ref_si):
@@ -202,13 +187,6 @@ def test_triclinic_box_with_atoms_outside(ref_si):
     _check_static(_static(x, box, t), ref, "edip triclinic")
 
 
-def _velocities(t, masses, temp, seed):
-    rng = np.random.default_rng(seed)
-    m = np.asarray(masses, float)[np.asarray(t)][:, None]
-    v = rng.normal(size=(len(t), 3)) * np.sqrt(en.BOLTZ * temp / m / en.MVV2E)
-    return v - (m * v).sum(axis=0) / m.sum()
-
-
 def test_static_parity_of_a_flipped_state(ref_si):
     """a 5 x 2 x 2 diamond cell written with xy = 2 a = 0.4 lx (a lattice translation: the same crystal), sheared by 0.12 lx so that it
     passes lx / 2 and flips; the forces on the state it leaves, in the box it leaves, against numpy"""
@@ -220,7 +198,7 @@ def test_static_parity_of_a_flipped_state(ref_si):
     e = _engine()
     try:
         e.edip_configure("si", SI, EL1)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS1, 300.0, 31), masses=MASS1))
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS1, 300.0, 31), masses=MASS1))
         s = np.array([0.0, 0.0, 0.0, 0.12 * lx * lz / ly, 0.0, 0.0])
         e.strain_batch([capi.make_sim(0, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)])
         flips = e.profile()["box_flips"]
@@ -299,105 +277,30 @@ def test_elastic_constants(static_constants):
 def test_nve_dynamics_and_sampled_pressure(ref_si):
     x, box, t = en.case_coordination(27)
     _soft(ref_si.compute(x, box, t))
-    v = _velocities(t, MASS1, 300.0, 1)
-    e = _engine()
-    try:
-        e.edip_configure("si", SI, EL1)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=v, masses=MASS1))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "si", 1, box, x, v)
-        e.debug_run("si", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "si", 1)
-        xr, vr = ref_si.nve(x, v, box, t, MASS1, 1.0, 20)
-        dx = np.abs(en.minimage_diff(xg, xr, box)).max()
-        print(f"edip nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "si", 1, box, x, v)
-        p = e.debug_run("si", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_si.nve(x, v, box, t, MASS1, 1.0, 1)
-        want = ref_si.pressure_atm(x1, v1, box, t, MASS1)
-        print(f"edip sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
-    finally:
-        e.close()
-
-
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
+    s = rk.Setup("si", SI, EL1, MASS1, (x, box, t), rk.velocities(t, MASS1, 300.0, 1))
+    rk.nve_and_sampled_pressure(EDIP, ref_si, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-10)
 
 
 def test_strain_batch_equals_the_two_runs():
     """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
     x, box, t = en.case_coordination(64)
-    v = _velocities(t, MASS1, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.edip_configure("si", SI, EL1)
-            g.register_replica("si", 1, capi.bare_system(t, x, box, v=v, masses=MASS1))
-        out = np.array(e.strain_batch([capi.make_sim(0, "si", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
-        f.set_state(0, "si", 1, box, x, v)
-        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
-        f.debug_run("si", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
-        want = -f.debug_run("si", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
-        print(f"edip strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
-        assert nts == 30 and np.abs(out - want).max() <= 1e-9 * np.abs(want).max()
-        assert e.has_state(0, "si", 1)
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("si", SI, EL1, MASS1, (x, box, t), rk.velocities(t, MASS1, 300.0, 2))
+    rk.strain_batch_vs_debug_runs(EDIP, s, s1, expect_nts=30, tol=1e-9)
 
 
 @pytest.fixture(scope="module")
 def eleven():
     """11 simulations over silicon and the synthetic two-element material, and each one's stress alone in a fresh engine"""
     mats = {"si": (en.case_coordination(27), SI, EL1, MASS1), "sic": (en.case_coordination(27, two_elements=True), SIC, EL2, MASS2)}
-    vel = {m: _velocities(c[0][2], c[3], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "si" if q % 3 else "sic"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), path, el, masses) in mats.items():
-            e.edip_configure(m, path, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    return rk.batch_vs_alone_fixture(EDIP, mats, 11, 21)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_eleven_equals_each_alone(eleven, split):
     """whole (split 0) and as part batches on two streams (split 1)"""
-    fresh, sims, alone = eleven
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"edip batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(EDIP, eleven, split, what="edip batch of 11 over two materials", tol=1e-9)
 
 
 def _cells_static(monkeypatch, cells, case):
@@ -437,24 +340,6 @@ def test_cell_binned_row_build(ref_si, monkeypatch):
             assert np.abs(on["f"] - off["f"]).max() <= 1e-10 * np.abs(ref["f"]).max()
 
 
-def _tetramer_update(scripts, configure):
-    """one update of the four-atom cluster: one wave does all the adding, so two runs of the same configuration agree bit for bit"""
-    x, box, t = en.case_tetramer(12.0)
-    v = _velocities(t, MASS1, 300.0, 4)
-    e = _engine()
-    try:
-        if configure:
-            e.edip_configure("si", SI, EL1)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=v, masses=MASS1))
-        s = np.array([1.2e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
-        sim = capi.make_sim(0, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
-                            scripts_folder=str(scripts))
-        out = np.array(e.strain_batch([sim])[0].stress[:])
-        return out, e.get_state(0, "si", 1)
-    finally:
-        e.close()
-
-
 def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
     """`pair_coeff * * ${locs}/Si.edip Si` in in.strain.lammps configures a bare replica whose material has nothing attached, bit for bit
     as the configured run; a malformed line of that kind is SCEMA_MD_ERR_ARG"""
@@ -463,8 +348,11 @@ def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
     shutil.copy(SI, scripts / "Si.edip")
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style edip\n#pair_coeff * * ${locs}/other.edip C\n"
                                               "pair_coeff * * ${locs}/Si.edip Si   # the potential\nfix 1 all nvt temp 300 300 100\n")
-    a, sa = _tetramer_update(scripts, configure=False)
-    b, sb = _tetramer_update(scripts, configure=True)
+    # (the four-atom cluster: one wave does all the adding, so two runs of the same configuration agree bit for bit)
+    case = en.case_tetramer(12.0)
+    tetramer = rk.Setup("si", SI, EL1, MASS1, case, rk.velocities(case[2], MASS1, 300.0, 4))
+    a, sa = rk.dimer_update(EDIP, tetramer, scripts, False, 1.2e-2)
+    b, sb = rk.dimer_update(EDIP, tetramer, scripts, True, 1.2e-2)
     assert np.isfinite(a).all() and np.abs(a).max() > 0.0
     assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
     # the update configured the material: static forces of the 64-atom coordination input against the numpy helper
@@ -474,25 +362,13 @@ def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
                                       scripts_folder=str(folder))
     e = _engine()
     try:
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS1, 300.0, 3), masses=MASS1))
-        with pytest.raises(capi.EngineError, match="no EDIP potential"):
-            e.edip_compute("si", 1)
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS1, 300.0, 3), masses=MASS1))
+        rk.assert_not_attached(EDIP, e, "si")
         assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
         _check_static(e.edip_compute("si", 1), ref_si.compute(x, box, t), "edip self-configured")
     finally:
         e.close()
-    for k, line in enumerate(["pair_coeff 1 1 ${locs}/Si.edip Si", "pair_coeff * * Si.edip Si", "pair_coeff * * ${locs}/Si.edip", "pair_coeff * * ${locs}/sub/Si.edip Si"]):
-        badf = tmp_path / f"bad{k}"
-        badf.mkdir()
-        shutil.copy(SI, badf / "Si.edip")
-        (badf / "in.strain.lammps").write_text(line + "\n")
-        e = _engine()
-        try:
-            e.register_replica("si", 1, capi.bare_system(t, x, box, masses=MASS1))
-            with pytest.raises(capi.EngineError, match=r"rc=1: .*in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.edip"):
-                e.strain_batch([mk(badf)])
-        finally:
-            e.close()
+    rk.assert_malformed_pair_coeff_lines(EDIP, rk.Setup("si", SI, EL1, MASS1, (x, box, t)), tmp_path, ".edip", "Si", match_head="rc=1: .*")
 
 
 def test_configuring_replaces_a_stillinger_weber_attachment_and_back(ref_si):
@@ -510,8 +386,7 @@ def test_configuring_replaces_a_stillinger_weber_attachment_and_back(ref_si):
             e.sw_compute("si", 1)
         _check_static(e.edip_compute("si", 1), ref, "edip over a Stillinger-Weber attachment")
         e.sw_configure("si", SI_SW)
-        with pytest.raises(capi.EngineError, match="no EDIP potential"):
-            e.edip_compute("si", 1)
+        rk.assert_not_attached(EDIP, e, "si")
         sw1 = e.sw_compute("si", 1)
         assert sw1["npairs"] == sw0["npairs"] > 0 and np.abs(sw1["f"] - sw0["f"]).max() <= 1e-10 * np.abs(sw0["f"]).max()
     finally:
@@ -536,7 +411,6 @@ def test_an_update_mixed_with_stillinger_weber_is_refused():
             assert not e.has_state(0, "ed", 1) and not e.has_state(1, "sw", 1)
         assert e.strain_batch([mk(0, "ed", box)])[0].stress_updated == 1
         assert e.strain_batch([mk(1, "sw", boxs)])[0].stress_updated == 1
-        with pytest.raises(capi.EngineError, match="no EDIP potential"):
-            e.edip_compute("sw", 1)
+        rk.assert_not_attached(EDIP, e, "sw")
     finally:
         e.close()

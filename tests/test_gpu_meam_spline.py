@@ -17,7 +17,6 @@ across a trip of 16, the limit of 32 on f's range alone.  Atom counts: a short l
 limit.  Two elements: a swapped pair index, rho or f of the wrong end.  Whole evaluations: rows kept or rebuilt under the wrong
 material, part streams.
 """
-import math
 import os
 import shutil
 
@@ -25,6 +24,7 @@ import numpy as np
 import pytest
 
 import meam_spline_numpy as mn
+import rowkit as rk
 from scema_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -48,38 +48,23 @@ def ref_tio():
     return mn.MeamSpline(mn.read_meam_spline(TIO, list(EL2))[0])
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+MEAM = rk.Pot("meam/spline", "meam_spline_configure", "meam_spline_compute", "MEAM/spline", ("e_pair", "e_embed"), ("npairs", "ntriplets"),
+              counts="ordered pairs {npairs}, triplets {ntriplets}")
 
 
-def _static(x, box, t, path=TI, elements=EL1, masses=MASS1):
-    e = _engine()
-    try:
-        e.meam_spline_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.meam_spline_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(MEAM, TI, EL1, MASS1)
 
 
-def _check_static(got, ref, what, scale=None):
-    scale = scale or ref
-    assert (got["npairs"], got["ntriplets"]) == (ref["npairs"], ref["ntriplets"]), (got["npairs"], ref["npairs"], got["ntriplets"], ref["ntriplets"])
-    assert got["maxrow"] <= got["rowcap"]
-    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e_pair"]) and math.isfinite(got["e_embed"])
-    if ref["npairs"] == 0 or not np.abs(scale["f"]).max() > 0.0:      # nothing inside cutmax, or inside it but beyond every function of the pair: exactly zero, U(0) - U(0) included
-        assert ref["e"] == 0.0 and not ref["f"].any() and not ref["w"].any()
-        assert got["e_pair"] == 0.0 and got["e_embed"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"{what}: {ref['npairs']} ordered pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs, ws = np.abs(scale["f"]).max(), np.abs(scale["w"]).max()
-    es = max(abs(scale["e_pair"]), abs(scale["e_embed"]))
-    df = np.abs(got["f"] - ref["f"]).max()
-    de = max(abs(got["e_pair"] - ref["e_pair"]), abs(got["e_embed"] - ref["e_embed"]))
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']}, "
-          f"triplets {got['ntriplets']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= 1e-10 * fs and de <= 1e-9 * es and dw <= 1e-9 * ws
+def no_pairs(got, ref, scale, what):
+    """nothing inside cutmax, or inside it but beyond every function of the pair: exactly zero, U(0) - U(0) included"""
+    if ref["npairs"] != 0 and np.abs(scale["f"]).max() > 0.0:
+        return False
+    rk.all_exactly_zero(got, ref, MEAM, what, head=f"{ref['npairs']} ordered pairs")
+    return True
+
+
+_check_static = rk.checker(MEAM, tol_f=1e-10, tol_e=1e-9, tol_w=1e-9, no_pairs=no_pairs)
 
 
 # ---- dimers ----
@@ -104,7 +89,7 @@ def test_dimers_of_each_pair_of_elements(ref_tio, pair):
         x, box, t = mn.case_dimer(r, *pair)
         ref = ref_tio.compute(x, box, t)
         assert ref["npairs"] == (2 if r < mn.TI_CUT else 0)
-        _check_static(_static(x, box, t, TIO, EL2, MASS2), ref, f"meam/spline dimer {pair} at {r!r}")
+        _check_static(_static(x, box, t, path=TIO, elements=EL2, masses=MASS2), ref, f"meam/spline dimer {pair} at {r!r}")
 
 
 # ---- trimers ----
@@ -128,7 +113,7 @@ def test_trimers_at_the_ends_of_g(ref_ti, ref_tio):
     assert ref["ntriplets"] >= 1
     _check_static(_static(x, box, t), ref, "meam/spline near-degenerate trimer, cos -> 1")
     x, box, t = mn.case_trimer(2.4, 2.7, 95.0, (1, 0, 1))
-    _check_static(_static(x, box, t, TIO, EL2, MASS2), ref_tio.compute(x, box, t), "meam/spline O-Ti-O trimer")
+    _check_static(_static(x, box, t, path=TIO, elements=EL2, masses=MASS2), ref_tio.compute(x, box, t), "meam/spline O-Ti-O trimer")
 
 
 # ---- densities outside U's knots ----
@@ -230,16 +215,9 @@ def test_two_elements(ref_tio, order, occupation):
 
 
 # ---- dynamics ----
-def _velocities(t, masses, temp, seed):
-    rng = np.random.default_rng(seed)
-    m = np.asarray(masses, float)[np.asarray(t)][:, None]
-    v = rng.normal(size=(len(t), 3)) * np.sqrt(mn.BOLTZ * temp / m / mn.MVV2E)
-    return v - (m * v).sum(axis=0) / m.sum()
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_ti):
     x, box, t = mn.case_bcc(2, 2, 2, 3.2, 0.05, 6)
-    v = _velocities(t, MASS1, 300.0, 1)
+    v = rk.velocities(t, MASS1, 300.0, 1)
     e = _engine()
     try:
         e.meam_spline_configure("ti", TI, EL1)
@@ -267,7 +245,7 @@ def test_energy_drift_over_200_steps(ref_ti):
     """total energy after 200 NVE steps of the jittered four-atom cell: no further from its start than the numpy integrator's own drift
     plus the static energy budget"""
     x, box, t = mn.case_bcc(1, 1, 2, 3.3, 0.05)
-    v = _velocities(t, MASS1, 300.0, 5)
+    v = rk.velocities(t, MASS1, 300.0, 5)
     m = np.asarray(MASS1)[t]
     total = lambda c, vel: c["e_pair"] + c["e_embed"] + 0.5 * mn.MVV2E * np.sum(m[:, None] * vel * vel)
     ref0 = ref_ti.compute(x, box, t)
@@ -290,50 +268,15 @@ def test_energy_drift_over_200_steps(ref_ti):
 
 
 # ---- whole evaluations ----
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
-def _by_debug_runs(f, qp, strain, box):
-    nts, rates = _nts_and_rates(strain, box, 1.0, 1e-4)
-    f.debug_run("ti", 1, nts, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, rates=rates)
-    return -f.debug_run("ti", 1, 10, 1.0, 300.0, qp=qp, nvt=True, use_shake=False, sample=True) * 1.01325e5, nts
-
-
 def test_strain_batch_equals_the_two_runs_and_a_second_update_continues(ref_ti):
     """an update against the straining run and the sampling run issued through the parity hooks; then a second update from the stored
     states: qp 0 continues from its own, qp 1 branches from qp 0's"""
     x, box, t = mn.case_count(64)
-    v = _velocities(t, MASS1, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
     s2 = np.array([1.0e-3 * L[0], 0.0, 1.0e-3 * L[2], 0.0, 0.0, 0.0])
-    kw = dict(nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.meam_spline_configure("ti", TI, EL1)
-            g.register_replica("ti", 1, capi.bare_system(t, x, box, v=v, masses=MASS1))
-        out1 = np.array(e.strain_batch([capi.make_sim(0, "ti", 1, s1, most_recent=capi.QP_NONE, **kw)])[0].stress[:])
-        f.set_state(0, "ti", 1, box, x, v)
-        want1, nts = _by_debug_runs(f, 0, s1, box)
-        print(f"meam/spline strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out1 - want1).max() / np.abs(want1).max():.2e}")
-        assert np.abs(out1 - want1).max() <= 1e-9 * np.abs(want1).max()
-        assert e.has_state(0, "ti", 1) and not e.has_state(1, "ti", 1)
-        out2 = e.strain_batch([capi.make_sim(0, "ti", 1, s2, most_recent=0, **kw), capi.make_sim(1, "ti", 1, s2, most_recent=0, **kw)])
-        a, b = np.array(out2[0].stress[:]), np.array(out2[1].stress[:])
-        b1, _, _ = f.get_state(0, "ti", 1)
-        want2, _ = _by_debug_runs(f, 0, s2, b1)
-        print(f"meam/spline second update: {np.abs(a - want2).max() / np.abs(want2).max():.2e}, branch {np.abs(b - want2).max() / np.abs(want2).max():.2e}")
-        assert np.abs(a - want2).max() <= 1e-9 * np.abs(want2).max() and np.abs(b - want2).max() <= 1e-9 * np.abs(want2).max()
-        assert e.has_state(1, "ti", 1) and np.abs(a - out1).max() > 1e-3 * np.abs(out1).max()
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("ti", TI, EL1, MASS1, (x, box, t), rk.velocities(t, MASS1, 300.0, 2))
+    rk.strain_batch_and_a_second_update(MEAM, s, s1, s2, tol=1e-9)
 
 
 @pytest.fixture(scope="module")
@@ -341,45 +284,13 @@ def nine():
     """9 simulations (two part streams) over titanium under Ti.meam.spline and the Ti-O compound under TiO.meam.spline, and each one's
     stress alone in a fresh engine"""
     mats = {"ti": (mn.case_bcc(2, 2, 2, 3.2, 0.05, 6), TI, EL1, MASS1), "tio": (mn.case_bcc(2, 2, 2, 3.3, 0.06, 3, "ordered"), TIO, EL2, MASS2)}
-    vel = {m: _velocities(c[0][2], c[3], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(9):
-        m = "ti" if q % 3 else "tio"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), path, el, masses) in mats.items():
-            e.meam_spline_configure(m, path, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    return rk.batch_vs_alone_fixture(MEAM, mats, 9, 21)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_nine_over_two_materials_equals_each_alone(nine, split):
     """whole (split 0) and as part batches on two streams (split 1)"""
-    fresh, sims, alone = nine
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"meam/spline batch of 9 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert np.isfinite(out).all() and err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(MEAM, nine, split, what="meam/spline batch of 9 over two materials", tol=1e-9)
 
 
 def test_a_replaced_potential_rebuilds_the_rows(ref_ti, ref_tio):
@@ -395,8 +306,7 @@ def test_a_replaced_potential_rebuilds_the_rows(ref_ti, ref_tio):
         e.meam_spline_configure("m", TIO, ("O",))
         _check_static(e.meam_spline_compute("m", 1), ref_o.compute(x, box, t), "meam/spline after the replacement")
         e.eam_configure("m", CUAG, ("Cu",))
-        with pytest.raises(capi.EngineError, match="no MEAM/spline potential"):
-            e.meam_spline_compute("m", 1)
+        rk.assert_not_attached(MEAM, e, "m")
         assert e.eam_compute("m", 1)["npairs"] > 0
         e.meam_spline_configure("m", TI, EL1)
         with pytest.raises(capi.EngineError, match="no EAM potential"):
@@ -415,7 +325,7 @@ def test_self_configuration_from_the_scripts_folder(ref_ti, tmp_path):
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style meam/spline\n#pair_coeff * * ${locs}/other.meam.spline Zr\n"
                                               "pair_coeff * * ${locs}/Ti.meam.spline Ti   # the potential\nfix 1 all nvt temp 300 300 100\n")
     x, box, t = mn.case_count(64)
-    v = _velocities(t, MASS1, 300.0, 3)
+    v = rk.velocities(t, MASS1, 300.0, 3)
     L = box[3:6] - box[:3]
     mk = lambda folder: capi.make_sim(0, "ti", 1, np.array([1e-3 * L[0], 0, 0, 0, 0, 0]), nss=10, dt=1.0, most_recent=capi.QP_NONE, force_field="opls",
                                       scripts_folder=str(folder))
@@ -427,8 +337,7 @@ def test_self_configuration_from_the_scripts_folder(ref_ti, tmp_path):
                 e.meam_spline_configure("ti", TI, EL1)
             e.register_replica("ti", 1, capi.bare_system(t, x, box, v=v, masses=MASS1))
             if not configure:
-                with pytest.raises(capi.EngineError, match="no MEAM/spline potential"):
-                    e.meam_spline_compute("ti", 1)
+                rk.assert_not_attached(MEAM, e, "ti")
             o = e.strain_batch([mk(scripts)])[0]
             assert o.stress_updated == 1
             outs.append(np.array(o.stress[:]))
@@ -436,17 +345,7 @@ def test_self_configuration_from_the_scripts_folder(ref_ti, tmp_path):
         finally:
             e.close()
     assert np.isfinite(outs[0]).all() and np.abs(outs[0] - outs[1]).max() <= 1e-9 * np.abs(outs[1]).max()
-    badf = tmp_path / "bad"
-    badf.mkdir()
-    shutil.copy(TI, badf / "Ti.meam.spline")
-    (badf / "in.strain.lammps").write_text("pair_coeff 1 1 ${locs}/Ti.meam.spline Ti\n")
-    e = _engine()
-    try:
-        e.register_replica("ti", 1, capi.bare_system(t, x, box, masses=MASS1))
-        with pytest.raises(capi.EngineError, match=r"rc=1: .*in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.meam\.spline"):
-            e.strain_batch([mk(badf)])
-    finally:
-        e.close()
+    rk.assert_malformed_pair_coeff_lines(MEAM, rk.Setup("ti", TI, EL1, MASS1, (x, box, t)), tmp_path, ".meam.spline", "Ti", match_head="rc=1: .*", lines=1)
 
 
 def _cells_static(monkeypatch, cells, case):

@@ -13,7 +13,7 @@ import pytest
 
 from test_gpu_pppm_meshes import (BATCH_ACC, BATCH_MATS, BATCH_T, COUNT_BOXES, assert_batch, assert_mesh, assert_static, batch_material, batch_strain, cut_to,
                                   engine, on_planes, reference, some_uncharged)
-from test_oracle_pppm_meshes import BY_NAME, ionic, oracle_compute, rel, row_fixture, _from_lamda, _lamda, _min_distance
+from test_oracle_pppm_meshes import BY_NAME, ionic, oracle_compute, rel, row_fixture, from_lamda, to_lamda, min_distance
 
 gpu = pytest.mark.gpu
 BIN_M = 4         # md_pppm.hip PP_BIN_M: atoms per item at most
@@ -24,7 +24,7 @@ BIN_ROUNDS = 4    # md_pppm.hip PP_BIN_ROUNDS
 def bins_of(d, grid):
     """bin of every atom as k_pppm_bins takes it: nearest grid point floor(u + 1/2), x unwrapped 0 .. nx, y and z mod n; -1: uncharged"""
     nx, ny, nz = grid
-    lam = _lamda(d)
+    lam = to_lamda(d)
     u = (lam - np.floor(lam)) * np.array(grid, float)
     i = np.floor(u + 0.5).astype(int)
     b = ((i[:, 2] % nz) * ny + i[:, 1] % ny) * (nx + 1) + np.clip(i[:, 0], 0, nx)
@@ -148,17 +148,17 @@ def test_a_small_launch_keeps_the_unbinned_kernel_by_default():
 def near_the_wrap(d, grid, dims):
     """the atoms of the last mesh cell of the dimensions `dims` moved to u in [n - 0.45, n - 0.05): their nearest grid point is n, not 0"""
     g = np.array(grid, float)
-    lam = _lamda(d)
+    lam = to_lamda(d)
     u = (lam - np.floor(lam)) * g
     for k in dims:
         top = u[:, k] >= g[k] - 1.0
         assert top.sum() >= 3, (k, top.sum())
         u[top, k] = g[k] - 0.45 + 0.4 * (u[top, k] - (g[k] - 1.0))
-    out = _from_lamda(d, u / g)
-    un = _lamda(out) * g
+    out = from_lamda(d, u / g)
+    un = to_lamda(out) * g
     for k in dims:
         assert np.count_nonzero(np.floor(un[:, k] + 0.5) == grid[k]) >= 3
-    assert _min_distance(out) > 0.3
+    assert min_distance(out) > 0.3
     return out
 
 
@@ -172,8 +172,8 @@ def test_half_planes_and_the_wrap(name, case):
     d = row_fixture(row, eps=1e-9)
     if case == "half_way":
         d = on_planes(d, row.grid, half=True)
-        u = _lamda(d) * np.array(row.grid, float)
-        assert np.abs(u - np.floor(u) - 0.5).max() < 1e-12 and _min_distance(d) > 0.3
+        u = to_lamda(d) * np.array(row.grid, float)
+        assert np.abs(u - np.floor(u) - 0.5).max() < 1e-12 and min_distance(d) > 0.3
     else:
         d = near_the_wrap(d, row.grid, (0,) if case == "wrap_x" else (1, 2))
     if case == "wrap_x":

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from test_oracle_pppm_meshes import (BY_NAME, KW, LDS_ROWS, PP_SOLVE_MAX, ROWS, STATIC_ROWS, ionic, oracle_compute, permuted_atoms, product_setup,
-                                     rel, relabel_sym6, row_fixture, shifted_by_lattice_vectors, _cell, _lamda, _from_lamda, _min_distance, on_faces)
+                                     rel, relabel_sym6, row_fixture, shifted_by_lattice_vectors, _cell, to_lamda, from_lamda, min_distance, on_faces)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -126,9 +126,9 @@ def test_the_other_in_lds_shapes_on_every_small_mesh(switch):
 # ---- 3. placement and count edges -------------------------------------------------------------------------------------------------
 def on_planes(d, grid, half):
     """every atom moved to the nearest grid plane in each lamda coordinate (half: half-way between two planes, the tie of floor(u + 1/2))"""
-    u = _lamda(d) * np.array(grid, float)
+    u = to_lamda(d) * np.array(grid, float)
     u = np.floor(u) + 0.5 if half else np.round(u)
-    return _from_lamda(d, u / np.array(grid, float))
+    return from_lamda(d, u / np.array(grid, float))
 
 
 def some_uncharged(d, every=4):
@@ -153,16 +153,16 @@ def merged_pairs(d, grid, seed=2):
     rng = np.random.default_rng(seed)
     n = d["natoms"] - d["natoms"] % 2
     g = np.array(grid, float)
-    centre = np.round(_lamda(d)[0:n:2] * g)
+    centre = np.round(to_lamda(d)[0:n:2] * g)
     delta = rng.uniform(0.15, 0.3, centre.shape) * rng.choice([-1.0, 1.0], centre.shape)
     lam = np.empty((n, 3))
     lam[0::2] = (centre + delta) / g
     lam[1::2] = (centre - delta) / g
-    out = _from_lamda(d, np.vstack([lam, _lamda(d)[n:]]))
+    out = from_lamda(d, np.vstack([lam, to_lamda(d)[n:]]))
     q = np.abs(np.asarray(d["charge"], float)).max()
     out["charge"] = np.concatenate([np.tile([q, -q], n // 2), np.zeros(d["natoms"] - n)])
     assert abs((out["charge"] ** 2).sum() - (np.asarray(d["charge"]) ** 2).sum()) < 1e-12
-    u = _lamda(out)[:n] * g
+    u = to_lamda(out)[:n] * g
     assert np.array_equal(np.floor(u[0::2] + 0.5), np.floor(u[1::2] + 0.5))
     return out
 
@@ -172,17 +172,17 @@ def placement_case(name, case):
     d = row_fixture(row, eps=1e-9)
     if case == "on_planes":
         out = on_planes(d, row.grid, half=False)
-        u = _lamda(out) * np.array(row.grid, float)
+        u = to_lamda(out) * np.array(row.grid, float)
         assert np.abs(u - np.round(u)).max() < 1e-12
     elif case == "half_way":
         out = on_planes(d, row.grid, half=True)
-        u = _lamda(out) * np.array(row.grid, float)
+        u = to_lamda(out) * np.array(row.grid, float)
         assert np.abs(u - np.floor(u) - 0.5).max() < 1e-12
     elif case == "faces":
         out = on_faces(d, row.cells)
     elif case == "lattice_shifts":
         out = shifted_by_lattice_vectors(d, seed=9, choices=(-1, 1, 2))
-        lam = _lamda(out)
+        lam = to_lamda(out)
         assert lam.min() < -0.5 and lam.max() > 2.0
     elif case == "some_uncharged":
         out = some_uncharged(d)
@@ -192,7 +192,7 @@ def placement_case(name, case):
         out, _ = permuted_atoms(merged_pairs(d, row.grid), seed=4)
     else:
         raise KeyError(case)
-    assert _min_distance(out) > 0.3, _min_distance(out)
+    assert min_distance(out) > 0.3, min_distance(out)
     return row, out
 
 
@@ -215,7 +215,7 @@ def test_atom_placement_edges(name, case):
         # and against itself 1e-9 of a box length inside the box, whatever the oracle says (the cell binning of the neighbour list gave an
         # atom at lamda = -1e-17 the cell of one periodic image and the position of another; the bound is that of the oracle's own
         # continuity test in test_oracle_pppm_meshes.py)
-        inside = _from_lamda(d, np.clip(_lamda(d), 1e-9, 1.0 - 1e-9))
+        inside = from_lamda(d, np.clip(to_lamda(d), 1e-9, 1.0 - 1e-9))
         eng.register_replica("inside", 1, inside)
         fi, ei, wi, _ = eng.debug_compute("inside", 1, use_shake=False)
         print(f"{name} faces against 1e-9 inside: f {rel(f, fi):.2e}  e1 {abs(e[1] - ei[1]) / abs(ei[1]):.2e}")

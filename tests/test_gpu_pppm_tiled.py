@@ -15,7 +15,7 @@ from copy import deepcopy
 import numpy as np
 import pytest
 
-from test_oracle_pppm_meshes import BY_NAME, oracle_compute, product_setup, rel, row_fixture, _from_lamda, _lamda, _min_distance
+from test_oracle_pppm_meshes import BY_NAME, oracle_compute, product_setup, rel, row_fixture, from_lamda, to_lamda, min_distance
 from test_gpu_pppm_meshes import (BATCH_ACC, BATCH_MATS, BATCH_T, assert_mesh, assert_static, batch_material, batch_reference, batch_strain, cut_to,
                                   engine, on_planes, reference, some_uncharged)
 from test_pppm_tiled_host import BIG, BIG_BY_NAME, DEFAULT_LDS, big_fixture
@@ -217,15 +217,15 @@ def test_atoms_on_the_planes_where_tiles_meet():
     row, d = batch600()
     out = on_planes(d, row.grid, half=False)
     # (the lattice has no site nearest to plane 0: every third atom of plane 1 in y, and of the others in z, moves onto the seam)
-    u = np.round(_lamda(out) * np.array(row.grid, float))
+    u = np.round(to_lamda(out) * np.array(row.grid, float))
     to_y = np.nonzero(u[:, 1] == 1)[0][::3]
     u[to_y, 1] = 0.0
     to_z = np.setdiff1d(np.nonzero(u[:, 2] == 1)[0], to_y)[::3]
     u[to_z, 2] = 0.0
     assert len(to_y) >= 10 and len(to_z) >= 10
-    out = _from_lamda(out, u / np.array(row.grid, float))
-    u = _lamda(out) * np.array(row.grid, float)
-    assert np.abs(u - np.round(u)).max() < 1e-12 and _min_distance(out) > 0.3
+    out = from_lamda(out, u / np.array(row.grid, float))
+    u = to_lamda(out) * np.array(row.grid, float)
+    assert np.abs(u - np.round(u)).max() < 1e-12 and min_distance(out) > 0.3
     iy, iz = np.round(u[:, 1]).astype(int) % 15, np.round(u[:, 2]).astype(int) % 15
     assert {0, 5, 10} <= set(iy) and {0, 8} <= set(iz)
     static_case(out, row, BOTH, "sf", "batch600 on planes")
@@ -270,7 +270,7 @@ def test_a_tile_without_atoms_leaves_zeros(lds, want):
     10, 11 is touched by no stencil; the interpolation tiles beyond plane 9 have no home atom.  Evaluated twice on one engine, first with
     every atom moved by L/2 in z: the second result must match a fresh engine's, because the slabs that are empty now were full before."""
     row, d = batch600()
-    lam = _lamda(d)
+    lam = to_lamda(d)
     q = np.asarray(d["charge"], float).copy()
     q2 = (q ** 2).sum()
     q[lam[:, 2] >= 0.5] = 0.0

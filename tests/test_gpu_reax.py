@@ -11,8 +11,8 @@ import pytest
 
 from oracle import pyreax as pr
 from scema_amd import capi
-from test_oracle_reax import FFIELD, _glycine_like
-from test_reax_host import BIGBOX, _check_dirs, _mixture, _pe_cell, _sym
+from test_oracle_reax import FFIELD, case_glycine_like
+from test_reax_host import BIGBOX, check_dirs, case_mixture, case_pe_cell, symbols
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +60,7 @@ def _compare_static(ff, eng, sym, x, box, name="m", full_fd=False, seed=1):
         fo = ff.forces(t, x, box=box, q=r["q"], h=1e-5)
         assert np.abs(f - fo).max() < 2e-6 * max(1.0, np.abs(fo).max())
     else:
-        good, worst = _check_dirs(ff, t, x, box, r["q"], f, seed=seed)
+        good, worst = check_dirs(ff, t, x, box, r["q"], f, seed=seed)
         assert good >= 5, worst
     w = _oracle_virial(ff, t, x, box, r["q"])
     assert np.abs(r["w"] - w).max() < 2e-6 * np.abs(w).max(), (r["w"], w)
@@ -68,8 +68,8 @@ def _compare_static(ff, eng, sym, x, box, name="m", full_fd=False, seed=1):
 
 
 def test_isolated_molecule_all_terms(ff, eng):
-    t, x = _glycine_like(ff)
-    r, po = _compare_static(ff, eng, _sym(ff, t), x + 0.0, BIGBOX, full_fd=True)
+    t, x = case_glycine_like(ff)
+    r, po = _compare_static(ff, eng, symbols(ff, t), x + 0.0, BIGBOX, full_fd=True)
     assert r["image_search"] == 0
     assert all(abs(po[k]) > 1e-6 for k in ("bond", "lp", "over", "under", "angle", "tors", "conj", "hb", "vdw", "coul", "pol"))
 
@@ -78,8 +78,8 @@ def test_atoms_without_any_neighbour_inside_the_taper_radius(ff, eng):
     """gas-phase case: a row of the charge matrix with no entry at all, walked in the same wave pass as a full one --
     the masked lanes must not read a column index out of the unwritten row.  Two lone hydrogens 40 A from a molecule, one of them
     between the molecule's atoms in the file so that its row is paired with a non-empty one."""
-    t, x = _glycine_like(ff)
-    sym = _sym(ff, t)
+    t, x = case_glycine_like(ff)
+    sym = symbols(ff, t)
     sym = sym[:1] + ["H"] + sym[1:] + ["H"]
     x = np.vstack([x[:1], [[24.0, 23.0, 25.0]], x[1:], [[-24.0, 22.0, -23.0]]])
     box = np.array([-30.0, -30.0, -30.0, 30.0, 30.0, 30.0, 0.0, 0.0, 0.0])
@@ -96,8 +96,8 @@ def test_atoms_without_any_neighbour_inside_the_taper_radius(ff, eng):
 
 def test_each_term_group_alone(ff, eng):
     """the parity switch `terms` isolates a launch: its forces are the central differences of just those energy parts"""
-    t, x = _glycine_like(ff)
-    sym = _sym(ff, t)
+    t, x = case_glycine_like(ff)
+    sym = symbols(ff, t)
     eng.register_replica("m", 1, capi.reax_system(sym, x, BIGBOX))
     q = eng.reax_compute("m", 1)["q"]
     groups = {1: ("bond", "lp", "over", "under"), 2: ("angle", "pen", "coa"), 4: ("tors", "conj"), 8: ("hb",), 16: ("vdw", "coul", "pol")}
@@ -130,20 +130,20 @@ def test_condensed_cell_minimum_image(ff, eng):
 
 
 def test_condensed_triclinic_cell_with_images(ff, eng):
-    sym, x, box = _pe_cell(ff, tilt=(3.0, -2.0, 1.5), amp=0.12)      # 20.27 A thick: several images inside the list radius
+    sym, x, box = case_pe_cell(ff, tilt=(3.0, -2.0, 1.5), amp=0.12)      # 20.27 A thick: several images inside the list radius
     r, _ = _compare_static(ff, eng, sym, x, box, seed=2)
     assert r["image_search"] > 0
 
 
 def test_mixture_with_hydrogen_bonds(ff, eng):
-    sym, x, box = _mixture()
+    sym, x, box = case_mixture()
     r, po = _compare_static(ff, eng, sym, x, box, seed=3)
     assert po["hb"] < -1.0
 
 
 def test_lammps_gradient_switch(ff, eng):
     """the switch that leaves out one d(SBO)/d(Delta) term of the valence-angle energy (off by default); energies are untouched"""
-    sym, x, box = _pe_cell(ff, amp=0.1)
+    sym, x, box = case_pe_cell(ff, amp=0.1)
     eng.register_replica("m", 1, capi.reax_system(sym, x, box))
     a = eng.reax_compute("m", 1)
     eng.reax_set(exact_gradient=0)
@@ -160,7 +160,7 @@ def _kinetic(mass_atom, v):
 def test_charges_do_not_depend_on_how_the_solver_is_launched(ff, monkeypatch):
     """the conjugate-gradient iterations run as launches over the batch, as many as the host issues; the rest, if any, in one
     workgroup per replica.  Same recurrences either way: no launches at all, too few, and plenty give the same charges."""
-    sym, x, box = _pe_cell(ff, amp=0.1)
+    sym, x, box = case_pe_cell(ff, amp=0.1)
     res = []
     for launches in ("0", "5", "200"):
         monkeypatch.setenv("SCEMA_REAX_QEQ_LAUNCH", launches)
@@ -210,7 +210,7 @@ def test_the_preconditioner_changes_the_iteration_count_not_the_charges(ff, monk
 
 
 def test_verlet_step_and_energy_conservation(ff, eng):
-    sym, x, box = _pe_cell(ff, amp=0.02)
+    sym, x, box = case_pe_cell(ff, amp=0.02)
     n = len(sym)
     rng = np.random.default_rng(0)
     masses = dict(H=1.008, C=12.011, N=14.007, O=15.999)
@@ -248,7 +248,7 @@ def test_verlet_step_and_energy_conservation(ff, eng):
     _, po = ff.energy(t, x2, box=box, q=r2["q"])
     for k in pr.PARTS:
         assert abs(r2["e"][k] - po[k]) < 1e-9 * max(1.0, abs(po[k])), k
-    good, worst = _check_dirs(ff, t, x2, box, r2["q"], r2["f"], seed=5)
+    good, worst = check_dirs(ff, t, x2, box, r2["q"], r2["f"], seed=5)
     assert good >= 5, worst
     # with the d(SBO)/d(Delta) term left out the same run gains about 100 kcal/mol: why that switch is off by default
     eng.set_state(1, "m", 1, box, x, v)
@@ -263,7 +263,7 @@ def test_verlet_step_and_energy_conservation(ff, eng):
 def test_sampled_pressure_against_the_oracle(ff, eng):
     """compute pressure + fix ave/time of the sampling run: with a time step so short that nothing moves, the average is the
     static pressure tensor, (sum m v v + W)/V with W the oracle's strain derivative"""
-    sym, x, box = _mixture(seed=9)
+    sym, x, box = case_mixture(seed=9)
     n = len(sym)
     rng = np.random.default_rng(1)
     masses = dict(H=1.008, C=12.011, N=14.007, O=15.999)
@@ -290,7 +290,7 @@ def test_strain_batch_with_reax_force_field(ff, tmp_path):
     scripts = tmp_path / "lammps_scripts_reax"
     scripts.mkdir()
     shutil.copy(FFIELD, scripts / "ffield.reax.2")
-    sym, x, box = _mixture(seed=10)
+    sym, x, box = case_mixture(seed=10)
     n = len(sym)
     masses = dict(H=1.008, C=12.011, N=14.007, O=15.999)
     m = np.array([masses[s] for s in sym])
@@ -320,7 +320,7 @@ def test_strain_batch_with_reax_force_field(ff, tmp_path):
         _, po = ff.energy(t, xs, box=b, q=r["q"])
         for name in pr.PARTS:
             assert abs(r["e"][name] - po[name]) < 1e-9 * max(1.0, abs(po[name])), name
-        good, worst = _check_dirs(ff, t, xs, b, r["q"], r["f"], seed=6 + k)
+        good, worst = check_dirs(ff, t, xs, b, r["q"], r["f"], seed=6 + k)
         assert good >= 5, worst
     # determinism of the whole update up to the order of atomic sums, and continuation from the stored states
     e2 = capi.Engine()
@@ -350,9 +350,9 @@ def test_fallback_kernels_of_large_replicas_equal_the_default_ones():
             "from oracle import pyreax as pr\n"
             "from scema_amd import capi\n"
             "from test_oracle_reax import FFIELD\n"
-            "from test_reax_host import _pe_cell\n"
+            "from test_reax_host import case_pe_cell\n"
             "ff = pr.ForceField(FFIELD)\n"
-            "sym, x, box = _pe_cell(ff, tilt=(3.0, -2.0, 1.5), amp=0.12)\n"
+            "sym, x, box = case_pe_cell(ff, tilt=(3.0, -2.0, 1.5), amp=0.12)\n"
             "e = capi.Engine()\n"
             "e.reax_configure(FFIELD, qeq_tol=1e-10)\n"
             "e.register_replica('m', 1, capi.reax_system(sym, x, box))\n"

@@ -11,7 +11,7 @@ import pytest
 from oracle import pyreax as pr
 from scema_amd import capi
 from test_oracle_reax import FFIELD
-from test_reax_host import _pe_cell
+from test_reax_host import case_pe_cell
 
 pytestmark = pytest.mark.gpu
 
@@ -74,10 +74,10 @@ def _sd_reference(fn, x, etol, ftol, maxiter, maxeval=50000):
 
 
 def test_minimiser_on_a_molecule_follows_the_oracle_driven_reference(ff):
-    from test_oracle_reax import _glycine_like
-    from test_reax_host import BIGBOX, _sym
-    t, x = _glycine_like(ff)
-    sym = _sym(ff, t)
+    from test_oracle_reax import case_glycine_like
+    from test_reax_host import BIGBOX, symbols
+    t, x = case_glycine_like(ff)
+    sym = symbols(ff, t)
     e = capi.Engine()
     e.reax_configure(FFIELD, qeq_tol=1e-10)
     e.register_replica("m", 1, capi.reax_system(sym, x, BIGBOX))
@@ -98,7 +98,7 @@ def test_minimiser_on_a_molecule_follows_the_oracle_driven_reference(ff):
 
 
 def test_minimiser_on_a_condensed_cell_goes_downhill_and_is_consistent(ff):
-    sym, x, box = _pe_cell(ff, amp=0.12)
+    sym, x, box = case_pe_cell(ff, amp=0.12)
     e = capi.Engine()
     e.reax_configure(FFIELD, qeq_tol=1e-8)
     e.register_replica("m", 1, capi.reax_system(sym, x, box))
@@ -119,7 +119,7 @@ def test_minimiser_on_a_condensed_cell_goes_downhill_and_is_consistent(ff):
 
 
 def test_npt_run_and_the_schedule_with_the_reax_force_stage(ff, tmp_path):
-    sym, x, box = _pe_cell(ff, amp=0.05)
+    sym, x, box = case_pe_cell(ff, amp=0.05)
     m = np.array([12.011 if s == "C" else 1.008 for s in sym])
     rng = np.random.default_rng(2)
     v = rng.standard_normal(x.shape) * np.sqrt(BOLTZ * 200.0 / (m[:, None] * MVV2E))

@@ -36,7 +36,7 @@ def scripts(tmp_path):
     return str(d)
 
 
-def _velocities(sym, seed):
+def _thermal_velocities(sym, seed):
     m = np.array([MASS[s] for s in sym])
     v = np.random.default_rng(seed).standard_normal((len(sym), 3)) * np.sqrt(0.0019872067 * 300.0 / (m[:, None] * 48.88821291 ** 2))
     return v - (m[:, None] * v).sum(0) / m.sum()
@@ -46,7 +46,7 @@ def _pe1620(gold):
     from scema_amd.systems import build_pe
     d = build_pe(3, 5, 9)
     sym = ["C" if d["mass"][k] > 5 else "H" for k in d["type"]]
-    x, box, v = np.array(d["x"], float), np.array(d["box"], float), _velocities(sym, 3)
+    x, box, v = np.array(d["x"], float), np.array(d["box"], float), _thermal_velocities(sym, 3)
     c = gold["pe1620"]
     # the fixture is rebuilt from seeded generators: refuse to compare if a library drifted
     assert abs(np.abs(x).sum() - c["x_checksum"]) < 1e-9 * c["x_checksum"] and abs(np.abs(v).sum() - c["v_checksum"]) < 1e-9 * c["v_checksum"]

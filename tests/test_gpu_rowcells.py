@@ -16,12 +16,13 @@ import numpy as np
 import pytest
 
 import eam_numpy as en
+import rowkit as rk
 import sw_numpy as swn
 import tersoff_numpy as tsn
-import test_gpu_eam as tge
-import test_gpu_sw as tgs
 import vashishta_numpy as vn
 from scema_amd import capi
+from test_gpu_eam import CUAG as CUAG_EAM, EAM
+from test_gpu_sw import SW
 
 pytestmark = pytest.mark.gpu
 
@@ -136,20 +137,20 @@ def test_si216_sw_three_cells_per_dimension(monkeypatch):
     on, off = on_and_off(monkeypatch, "sw", case, "sw 216", bits=False)
     assert on["rows"]["n"] == 216 and on["rows"]["ncell"] == [3, 3, 3]
     ref = swn.SW(swn.read_sw(os.path.join(G, "Si.sw"), ["Si"])[0]).compute(*case)
-    tgs._check_static(on, ref)
+    rk.check_static(on, ref, SW, tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, what="sw static")      # (the static budget of tests/test_gpu_sw.py)
 
 
 @pytest.fixture(scope="module")
 def cu864():
     case = cu(6, 6, 6)
-    return case, en.EAM(en.read_setfl(tge.CUAG, ["Cu"])[0]).compute(*case)
+    return case, en.EAM(en.read_setfl(CUAG_EAM, ["Cu"])[0]).compute(*case)
 
 
 def test_cu864_eam(monkeypatch, cu864):
     case, ref = cu864
     on, _ = on_and_off(monkeypatch, "eam", case, "eam 864", bits=True)
     assert on["rows"]["n"] == 864 and on["rows"]["ncell"] == [3, 3, 3]
-    tge._check_static(on, ref, what="eam 864 atoms through cells")
+    rk.check_static(on, ref, EAM, tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, what="eam 864 atoms through cells")      # (that of tests/test_gpu_eam.py)
 
 
 def test_cu1920_a_grid_of_3_4_5_cells(monkeypatch):

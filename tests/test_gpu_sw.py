@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import rowkit as rk
 import sw_numpy as swn
 from scema_amd import capi
 
@@ -28,36 +29,23 @@ def ref_sw():
     return swn.SW(swn.read_sw(SI_SW, ["Si"])[0])
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+SW = rk.Pot("sw", "sw_configure", "sw_compute", "Stillinger-Weber", ("e2", "e3"), ("npairs", "ntriplets"))
 
 
-def _static(x, box, t, sw_path=SI_SW, elements=("Si",), masses=MASS):
-    e = _engine()
-    try:
-        e.sw_configure("si", sw_path, elements)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, masses=masses))
-        return e.sw_compute("si", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(SW, SI_SW, ("Si",), MASS)
 
 
-def _check_static(got, ref, tol=1e-10, fterm=0.0):
-    """fterm: size of the largest single force term, for configurations near equilibrium, where the terms cancel in the sum"""
-    assert got["npairs"] == ref["npairs"] and got["ntriplets"] == ref["ntriplets"]
-    assert got["maxrow"] <= got["rowcap"]
-    if ref["npairs"] == 0:      # no pair, so no term at all: everything is exactly zero, and there is no scale to divide by
-        assert ref["e2"] == 0.0 and ref["e3"] == 0.0 and not ref["f"].any() and not ref["w"].any()
-        assert got["e2"] == 0.0 and got["e3"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"sw static: no pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs = max(np.abs(ref["f"]).max(), fterm)
-    df = np.abs(got["f"] - ref["f"]).max()
-    es = max(abs(ref["e2"]), abs(ref["e3"]))
-    de = max(abs(got["e2"] - ref["e2"]), abs(got["e3"] - ref["e3"]))
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"sw static: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / np.abs(ref['w']).max():.2e}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= tol * fs and de <= tol * es and dw <= tol * np.abs(ref["w"]).max()
+def no_pairs(got, ref, scale, what):
+    """no pair, so no term at all: everything is exactly zero, and there is no scale to divide by"""
+    if ref["npairs"] != 0:
+        return False
+    rk.all_exactly_zero(got, ref, SW, what, ref_keys=("e2", "e3"))
+    return True
+
+
+# (fterm=: size of the largest single force term, for configurations near equilibrium, where the terms cancel in the sum)
+_check_static = rk.checker(SW, "sw static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)
 
 
 # (a) 64 atoms; (b) 192 atoms, triclinic, atoms outside the box; (c) 16 neighbours in range; (f) eight tiles of the force kernel;
@@ -84,20 +72,20 @@ def test_row_overflow_regrows_and_retries(ref_sw, monkeypatch):
     mk = lambda: capi.make_sim(0, "si", 1, strain, nss=10, dt=1.0, most_recent=capi.QP_NONE)
     e = _engine()
     e.sw_configure("si", SI_SW)
-    e.register_replica("si", 1, capi.sw_system(t, x, box, v=_velocities(len(x), 300.0, 4)))
+    e.register_replica("si", 1, capi.sw_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 4)))
     want = np.array(e.strain_batch([mk()])[0].stress[:])
     e.close()
     monkeypatch.setenv("SCEMA_MD_NEIGH_GROW0", "0.05")
     e = _engine()
     try:
         e.sw_configure("si", SI_SW)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, v=_velocities(len(x), 300.0, 4)))
+        e.register_replica("si", 1, capi.sw_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 4)))
         got = e.sw_compute("si", 1)
         _check_static(got, ref)
         assert got["rowcap"] < normal["rowcap"]          # it started at 8 entries and grew to what the rows asked for, not to the default
         e2 = _engine()                                    # (a fresh engine starts small again: the update's own retry)
         e2.sw_configure("si", SI_SW)
-        e2.register_replica("si", 1, capi.sw_system(t, x, box, v=_velocities(len(x), 300.0, 4)))
+        e2.register_replica("si", 1, capi.sw_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 4)))
         out = np.array(e2.strain_batch([mk()])[0].stress[:])
         e2.close()
         assert np.abs(out - want).max() <= 1e-10 * np.abs(want).max()
@@ -127,7 +115,7 @@ def test_two_elements(tmp_path):
     p.write_text(swn.TWO_ELEMENT_SW)
     ref_two = swn.SW(swn.read_sw(str(p), ["Si", "X"])[0])
     x, box, t = swn.case_e()
-    _check_static(_static(x, box, t, sw_path=str(p), elements=("Si", "X"), masses=(swn.SI_MASS, 20.0)), ref_two.compute(x, box, t))
+    _check_static(_static(x, box, t, path=str(p), elements=("Si", "X"), masses=(swn.SI_MASS, 20.0)), ref_two.compute(x, box, t))
 
 
 def test_closed_forms(ref_sw):
@@ -157,59 +145,16 @@ def test_closed_forms(ref_sw):
         e.close()
 
 
-def _velocities(n, temp, seed):
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(n, 3)) * math.sqrt(swn.BOLTZ * temp / swn.SI_MASS / swn.MVV2E)
-    return v - v.mean(axis=0)
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_sw):
     x, box, t = swn.case_a()
-    v = _velocities(len(x), 300.0, 1)
-    e = _engine()
-    try:
-        e.sw_configure("si", SI_SW)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, v=v))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "si", 1, box, x, v)
-        e.debug_run("si", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "si", 1)
-        xr, vr = ref_sw.nve(x, v, box, t, MASS, 1.0, 20)
-        dx = np.abs(swn.minimage_diff(xg, xr, box)).max()
-        print(f"sw nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "si", 1, box, x, v)
-        p = e.debug_run("si", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_sw.nve(x, v, box, t, MASS, 1.0, 1)
-        want = ref_sw.pressure_atm(x1, v1, box, t, MASS)
-        print(f"sw sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
-    finally:
-        e.close()
-
-
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
-def _by_debug_runs(e, qp, strain, dt, temp, rate, nss):
-    """what strain_batch does for one simulation, issued through the parity hooks: the straining run, then the sampling run"""
-    box, _, _ = e.get_state(qp, "si", 1)
-    nts, rates = _nts_and_rates(strain, box, dt, rate)
-    e.debug_run("si", 1, nts, dt, temp, qp=qp, nvt=True, use_shake=False, rates=rates)
-    p = e.debug_run("si", 1, nss, dt, temp, qp=qp, nvt=True, use_shake=False, sample=True)
-    return -p * 1.01325e5, nts
+    s = rk.Setup("si", SI_SW, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 1))
+    rk.nve_and_sampled_pressure(SW, ref_sw, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-10)
 
 
 def test_strain_batch_equals_the_two_runs_and_continues(ref_sw):
     """tension plus a shear component, nss = 10; a second update that continues through most_recent_qp_id, and one that branches from it"""
     x, box, t = swn.case_a()
-    v = _velocities(len(x), 300.0, 2)
+    v = rk.velocities(t, MASS, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
     s2 = 1.5 * s1
@@ -222,7 +167,7 @@ def test_strain_batch_equals_the_two_runs_and_continues(ref_sw):
             g.register_replica("si", 1, capi.sw_system(t, x, box, v=v))
         out1 = np.array(e.strain_batch([capi.make_sim(0, "si", 1, s1, most_recent=capi.QP_NONE, **kw)])[0].stress[:])
         f.set_state(0, "si", 1, box, x, v)
-        want1, nts = _by_debug_runs(f, 0, s1, 1.0, 300.0, 1e-4, 10)
+        want1, nts = rk.by_debug_runs(f, "si", 0, s1, box)
         assert nts == 30
         print(f"sw strain_batch vs debug runs: {np.abs(out1 - want1).max() / np.abs(want1).max():.2e}")
         assert np.abs(out1 - want1).max() <= 1e-10 * np.abs(want1).max()
@@ -230,7 +175,7 @@ def test_strain_batch_equals_the_two_runs_and_continues(ref_sw):
         # second update: qp 0 continues from its own state, qp 1 branches from qp 0's; same strain -> same stress
         out2 = e.strain_batch([capi.make_sim(0, "si", 1, s2, most_recent=0, **kw), capi.make_sim(1, "si", 1, s2, most_recent=0, **kw)])
         a, b = np.array(out2[0].stress[:]), np.array(out2[1].stress[:])
-        want2, _ = _by_debug_runs(f, 0, s2, 1.0, 300.0, 1e-4, 10)
+        want2, _ = rk.by_debug_runs(f, "si", 0, s2, f.get_state(0, "si", 1)[0])
         assert np.abs(a - want2).max() <= 1e-10 * np.abs(want2).max()
         assert np.abs(b - want2).max() <= 1e-10 * np.abs(want2).max()
         assert e.has_state(1, "si", 1)
@@ -243,108 +188,46 @@ def test_strain_batch_equals_the_two_runs_and_continues(ref_sw):
 @pytest.fixture(scope="module")
 def eleven():
     """11 simulations over two SW materials with different boxes, and each one's stress when it runs alone in a fresh engine"""
-    mats = {"sia": swn.case_a(), "sib": swn.case_b()}
-    vel = {m: _velocities(len(c[0]), 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "sia" if q % 3 else "sib"
-        L = mats[m][1][3:6] - mats[m][1][:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, (x, box, t) in mats.items():
-            e.sw_configure(m, SI_SW)
-            e.register_replica(m, 1, capi.sw_system(t, x, box, v=vel[m]))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    mats = {"sia": (swn.case_a(), SI_SW, None, None), "sib": (swn.case_b(), SI_SW, None, None)}
+    return rk.batch_vs_alone_fixture(SW, mats, 11, 21, thermal_masses=MASS)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_eleven_equals_each_alone(eleven, split):
-    fresh, sims, alone = eleven
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"sw batch of 11 (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(SW, eleven, split, what="sw batch of 11", tol=1e-9)
 
 
-def sheared_set():
-    """Eight simulations of a 5 x 2 x 2 diamond cell (160 atoms) written with xy = 2 a = 0.4 lx -- the same unstrained crystal: a shift of a2
-    by two lattice constants along x is a lattice translation -- each sheared by 0.105 to 0.14 lx in xy within 110 to 150 straining steps, so
-    that every one crosses +lx / 2 and flips once: (engine with the replica registered, [(qp, strain)], strain -> simulation, unstrained box)"""
+def sheared_cell():
+    """a 5 x 2 x 2 diamond cell (160 atoms) written with xy = 2 a = 0.4 lx -- the same unstrained crystal: a shift of a2 by two lattice
+    constants along x is a lattice translation -- which the sheared set (rowkit.sheared_set) shears by 0.105 to 0.14 lx in xy within 110 to
+    150 straining steps, so that every simulation crosses +lx / 2 and flips once"""
     a = swn.si_lattice_constant()
     x, box = swn.diamond(5, 2, 2, a)
     box[6] = 2.0 * a
     t = np.zeros(len(x), int)
-    v = _velocities(len(x), 300.0, 31)
     lx, ly, lz = box[3:6] - box[:3]
-    # (the tilt xy moves by strain[3] * ly / lz: nts_rule and fix deform's xy rate)
-    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
     rlist = 1.8 * 2.0951 + 1.0      # a sigma + the skin of sw_configure
     w_x = lx * ly / math.hypot(ly, 0.5 * lx)     # the narrowest the box gets across its (a2, a3) faces, at xy = lx / 2
     print(f"sw sheared cell: widths {w_x:.2f} / {ly:.2f} / {lz:.2f} A against two list radii {2 * rlist:.2f} A: image search "
           f"{'on' if min(w_x, ly, lz) < 2 * rlist else 'off'}")
-
-    def fresh():
-        e = _engine()
-        e.sw_configure("si", SI_SW)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, v=v))
-        return e
-
-    mk = lambda q, s: capi.make_sim(q, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
-    return fresh, sims, mk, box
+    return rk.Setup("si", SI_SW, None, None, (x, box, t), rk.velocities(t, MASS, 300.0, 31))
 
 
 @pytest.fixture(scope="module")
 def sheared():
     """the sheared set, and each one's stress, flips and final box when it runs alone in a fresh engine"""
-    fresh, sims, mk, box = sheared_set()
-    alone, flips, boxes = [], 0, []
-    for q, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
-        flips += e.profile()["box_flips"]
-        boxes.append(e.get_state(q, "si", 1)[0])
-        e.close()
-    nts = [_nts_and_rates(s, box, 1.0, 3.4e-3)[0] for _, s in sims]
+    cell = sheared_cell()
+    out = rk.sheared_fixture(SW, cell)
+    nts = [rk.nts_and_rates(s, cell.case[1], 1.0, 3.4e-3)[0] for _, s in rk.sheared_set(SW, cell)[1]]
     assert len(set(nts)) >= 4 and max(nts) <= 150, nts       # a ragged batch
-    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+    return out
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_box_flips_inside_a_split_batch(sheared, split):
     """the flips of a batch are enqueued between two steps on the stream of the part that holds the simulation (eight: the smallest batch
     that runs as two parts): same stresses as each simulation alone, as many flips, every box back inside |xy| <= lx / 2"""
-    fresh, sims, alone, flips, boxes = sheared
-    assert flips >= 8
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"sw sheared batch of 8 (split {split}): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
-        assert err.max() <= 1e-9
-        assert e.profile()["box_flips"] == flips
-        for q in range(8):
-            b = e.get_state(q, "si", 1)[0]
-            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
-    finally:
-        e.close()
+    rk.assert_flips_in_split_batch(sheared, "si", split, what=f"sw sheared batch of 8 (split {split})", tol=1e-9)
 
 
 def test_kept_sw_neighbour_rows_equal_rebuilt_ones():
@@ -402,8 +285,7 @@ def test_mixed_update_is_refused(small_pe):
         assert not e.has_state(0, "si", 1) and not e.has_state(1, "pe", 1)
         # each alone runs
         assert e.strain_batch(sims[:1])[0].stress_updated == 1
-        with pytest.raises(capi.EngineError, match="no Stillinger-Weber potential"):
-            e.sw_compute("pe", 1)
+        rk.assert_not_attached(SW, e, "pe")
     finally:
         e.close()
 
@@ -430,8 +312,7 @@ def test_reference_example_files_drive_an_update(ref_sw, tmp_path):
         assert np.array_equal(rbox, box)
         assert np.abs(swn.minimage_diff(rx, at["x"][order], box)).max() < 1e-12       # unwrapped through the image flags
         assert info.units == b"metal" and np.array_equal(rv, 1.0e-3 * at["v"][order])   # A/ps -> A/fs
-        with pytest.raises(capi.EngineError, match="no Stillinger-Weber potential"):
-            e.sw_compute("sic", 1)
+        rk.assert_not_attached(SW, e, "sic")
         L = box[3:6] - box[:3]
         strains = [np.array([(1 + k) * 3e-4 * L[0], -1e-4 * L[1], -1e-4 * L[2], (k % 3) * 1e-4 * L[2], 0.0, 0.0]) for k in range(8)]
         sims = [capi.make_sim(q, "sic", 1, strains[q % 8], nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE,
@@ -459,7 +340,7 @@ def test_init_material_runs_for_an_sw_material():
     e = _engine()
     try:
         e.sw_configure("si", SI_SW)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, v=_velocities(len(x), 10.0, 9)))
+        e.register_replica("si", 1, capi.sw_system(t, x, box, v=rk.velocities(t, MASS, 10.0, 9)))
         length, stress, stiff = e.init_material("si", 1, dt=1.0, temperature=10.0, nss=20, strain_ampl=0.005, strain_rate=1e-4)
         assert np.allclose(length, box[3:6] - box[:3]) and np.isfinite(stress).all() and np.isfinite(stiff).all()
         assert np.array_equal(stiff, stiff.T)

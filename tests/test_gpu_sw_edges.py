@@ -18,14 +18,23 @@ longest row against the row capacity.
 import numpy as np
 import pytest
 
+import rowkit as rk
 import sw_numpy as swn
 from scema_amd import capi
-from test_gpu_sw import MASS, SI_SW, _check_static, _engine, _nts_and_rates, _static, _velocities, ref_sw, sheared_set  # noqa: F401  (ref_sw: a fixture)
-from test_sw_edges_host import COUNTS, _fterm
+from test_gpu_sw import MASS, SI_SW, SW, no_pairs, ref_sw, sheared_cell  # noqa: F401  (ref_sw: a fixture)
+from test_sw_edges_host import COUNTS, largest_force_term
 
 pytestmark = pytest.mark.gpu
 
 TWO = dict(elements=("Si", "X"), masses=(swn.SI_MASS, 20.0))
+
+
+_engine, _nts_and_rates = rk.engine, rk.nts_and_rates
+_static = rk.static_of(SW, SI_SW, ("Si",), MASS)
+
+
+# (fterm=: size of the largest single force term, for configurations near equilibrium, where the terms cancel in the sum)
+_check_static = rk.checker(SW, "sw static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)
 
 
 @pytest.fixture(scope="module")
@@ -42,13 +51,13 @@ def test_static_parity_narrow_and_tilted(ref_sw, two_sw, name):
     swn.check_box(box)
     if name == "N5":
         ref = two_sw[1].compute(x, box, t)
-        got = _static(x, box, t, sw_path=two_sw[0], **TWO)
+        got = _static(x, box, t, path=two_sw[0], **TWO)
     else:
         ref = ref_sw.compute(x, box, t)
         got = _static(x, box, t)
     assert (ref["npairs"], ref["ntriplets"], ref["maxin"]) == COUNTS[name][:3] and ref["maxin"] <= 32
     # (N4: one atom and its images; the net force is zero by symmetry, the pair terms set the rounding)
-    _check_static(got, ref, fterm=_fterm(ref_sw, x, box, t) if name == "N4" else 0.0)
+    _check_static(got, ref, fterm=largest_force_term(ref_sw, x, box, t) if name == "N4" else 0.0)
 
 
 def test_box_below_half_a_list_radius_is_refused(ref_sw):
@@ -73,7 +82,7 @@ def test_box_below_half_a_list_radius_is_refused(ref_sw):
 def test_static_parity_of_a_flipped_state(ref_sw):
     """the last simulation of the sheared set of tests/test_gpu_sw.py alone: its box passes xy = lx / 2 and flips; the forces on the state it
     leaves, in the box it leaves, against numpy"""
-    fresh, sims, mk, box0 = sheared_set()
+    fresh, sims, mk, box0 = rk.sheared_set(SW, sheared_cell())
     q, s = sims[-1]
     e = fresh()
     try:
@@ -144,7 +153,7 @@ def test_crowded_update_is_refused_and_leaves_no_state(ref_sw):
     e = _engine()
     try:
         e.sw_configure("si", SI_SW)
-        e.register_replica("si", 1, capi.sw_system(t, x, box, v=_velocities(len(x), 300.0, 4)))
+        e.register_replica("si", 1, capi.sw_system(t, x, box, v=rk.velocities(np.zeros(len(x), int), MASS, 300.0, 4)))
         sim = capi.make_sim(0, "si", 1, np.array([5e-4 * L[0], 0.0, 0.0, 0.0, 0.0, 0.0]), nss=10, dt=1.0, most_recent=capi.QP_NONE)
         with pytest.raises(capi.EngineError, match="more than 32 neighbours"):
             e.strain_batch([sim])
@@ -159,7 +168,7 @@ def test_nve_with_rebuilds_in_a_narrow_box(ref_sw):
     mid-run, two images deep -- and one ends outside the box.  The reference's own reordering noise on such a run is 9e-16 A and 8e-17 A/fs
     (atoms permuted), far below the budgets.  Then one sampled step FROM the reference's end state, an atom outside the box and all."""
     x, box, t = swn.narrow("N1")
-    v = _velocities(len(x), 300.0, 42)
+    v = rk.velocities(np.zeros(len(x), int), MASS, 300.0, 42)
     xr, vr = ref_sw.nve(x, v, box, t, MASS, 1.0, 20)
     s = (xr - box[:3]) @ np.linalg.inv(swn.h_matrix(box))
     moved = np.linalg.norm(xr - x, axis=1).max()
@@ -196,7 +205,7 @@ def mixed(two_sw):
     two-element file; each material under its own id; 10 straining steps, nss 10; and each one's stress alone in a fresh engine"""
     mats = {"n1": (swn.narrow("N1"), SI_SW, ("Si",), MASS), "sia": (swn.case_a(), SI_SW, ("Si",), MASS),
             "big": (swn.truncated(1025), SI_SW, ("Si",), MASS), "two": (swn.case_e(), two_sw[0], TWO["elements"], TWO["masses"])}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 50 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
+    vel = {m: rk.velocities(np.zeros(len(c[0][0]), int), MASS, 300.0, 50 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
     sims = []
     for q, m in enumerate(["n1", "sia", "big", "two", "two", "big", "sia", "n1"]):      # (both parts hold every kind but one)
         L = mats[m][0][1][3:6] - mats[m][0][1][:3]

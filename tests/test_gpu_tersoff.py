@@ -25,6 +25,7 @@ import shutil
 import numpy as np
 import pytest
 
+import rowkit as rk
 import sw_numpy as swn
 import tersoff_numpy as tsn
 from scema_amd import capi
@@ -56,36 +57,22 @@ def synth_files(tmp_path_factory):
     return {"synth": str(d / "synth.tersoff"), "clamp": str(d / "clamp.tersoff")}
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+TERSOFF = rk.Pot("tersoff", "tersoff_configure", "tersoff_compute", "Tersoff", ("e_rep", "e_att"), ("npairs", "nzeta"), counts="pairs {npairs}, (j, k) {nzeta}")
 
 
-def _static(x, box, t, path=SIC, elements=("Si",), masses=MASS):
-    e = _engine()
-    try:
-        e.tersoff_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.tersoff_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(TERSOFF, SIC, ("Si",), MASS)
 
 
-def _check_static(got, ref, tol=1e-10, what="tersoff static"):
-    assert got["npairs"] == ref["npairs"] and got["nzeta"] == ref["nzeta"], (got["npairs"], ref["npairs"], got["nzeta"], ref["nzeta"])
-    assert got["maxrow"] <= got["rowcap"]
-    if ref["npairs"] == 0:      # no pair, so no term at all: everything is exactly zero, and there is no scale to divide by
-        assert ref["e"] == 0.0 and not ref["f"].any() and not ref["w"].any()
-        assert got["e_rep"] == 0.0 and got["e_att"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"{what}: no pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs = np.abs(ref["f"]).max()
-    df = np.abs(got["f"] - ref["f"]).max()
-    es = max(abs(ref["e_rep"]), abs(ref["e_att"]))
-    de = max(abs(got["e_rep"] - ref["e_rep"]), abs(got["e_att"] - ref["e_att"]))
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / np.abs(ref['w']).max():.2e}, pairs {got['npairs']}, "
-          f"(j, k) {got['nzeta']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= tol * fs and de <= tol * es and dw <= tol * np.abs(ref["w"]).max()
+def no_pairs(got, ref, scale, what):
+    """no pair, so no term at all: everything is exactly zero, and there is no scale to divide by"""
+    if ref["npairs"] != 0:
+        return False
+    rk.all_exactly_zero(got, ref, TERSOFF, what)
+    return True
+
+
+_check_static = rk.checker(TERSOFF, "tersoff static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)
 
 
 # the smallest shapes at which a path changes: no pair; zeta = 0; one (j, k) per pair; the image search with an atom's own images' neighbours;
@@ -182,36 +169,10 @@ def test_more_than_32_neighbours_is_an_error():
     assert np.isfinite(_static(x, box, t)["f"]).all()
 
 
-def _velocities(n, temp, seed, mass=tsn.SI_MASS):
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(n, 3)) * math.sqrt(tsn.BOLTZ * temp / mass / tsn.MVV2E)
-    return v - v.mean(axis=0)
-
-
 def test_nve_dynamics_and_sampled_pressure(ref_si):
     x, box, t = tsn.case_a()
-    v = _velocities(len(x), 300.0, 1)
-    e = _engine()
-    try:
-        e.tersoff_configure("si", SIC)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=v))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "si", 1, box, x, v)
-        e.debug_run("si", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "si", 1)
-        xr, vr = ref_si.nve(x, v, box, t, MASS, 1.0, 20)
-        dx = np.abs(tsn.minimage_diff(xg, xr, box)).max()
-        print(f"tersoff nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "si", 1, box, x, v)
-        p = e.debug_run("si", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_si.nve(x, v, box, t, MASS, 1.0, 1)
-        want = ref_si.pressure_atm(x1, v1, box, t, MASS)
-        print(f"tersoff sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-10 * np.abs(want).max()
-    finally:
-        e.close()
+    s = rk.Setup("si", SIC, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 1))
+    rk.nve_and_sampled_pressure(TERSOFF, ref_si, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-10)
 
 
 @pytest.fixture(scope="module")
@@ -249,80 +210,25 @@ def test_elastic_constants(static_constants):
         e.close()
 
 
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
 def test_strain_batch_equals_the_two_runs():
     """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
     x, box, t = tsn.case_a()
-    v = _velocities(len(x), 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.tersoff_configure("si", SIC)
-            g.register_replica("si", 1, capi.bare_system(t, x, box, v=v))
-        out = np.array(e.strain_batch([capi.make_sim(0, "si", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
-        f.set_state(0, "si", 1, box, x, v)
-        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
-        f.debug_run("si", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
-        want = -f.debug_run("si", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
-        print(f"tersoff strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
-        assert nts == 30 and np.abs(out - want).max() <= 1e-10 * np.abs(want).max()
-        assert e.has_state(0, "si", 1)
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("si", SIC, None, MASS, (x, box, t), rk.velocities(t, MASS, 300.0, 2))
+    rk.strain_batch_vs_debug_runs(TERSOFF, s, s1, expect_nts=30, tol=1e-10)
 
 
 @pytest.fixture(scope="module")
 def eleven():
     """11 simulations over two Tersoff materials (silicon, and silicon carbide with two elements), and each one's stress alone in a fresh engine"""
-    mats = {"si": (tsn.case_a(), ("Si",), MASS), "sic": (tsn.case_sic(), ("Si", "C"), MASS2)}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "si" if q % 3 else "sic"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), el, masses) in mats.items():
-            e.tersoff_configure(m, SIC, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    mats = {"si": (tsn.case_a(), SIC, ("Si",), MASS), "sic": (tsn.case_sic(), SIC, ("Si", "C"), MASS2)}
+    return rk.batch_vs_alone_fixture(TERSOFF, mats, 11, 21, thermal_masses=MASS)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_eleven_equals_each_alone(eleven, split):
-    fresh, sims, alone = eleven
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"tersoff batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(TERSOFF, eleven, split, what="tersoff batch of 11 over two materials", tol=1e-9)
 
 
 @pytest.fixture(scope="module")
@@ -332,44 +238,12 @@ def sheared():
     x, box = tsn.diamond(5, 2, 2, tsn.A_SI)
     box[6] = 2.0 * tsn.A_SI
     t = tsn.zeros(len(x))
-    v = _velocities(len(x), 300.0, 31)
-    lx, ly, lz = box[3:6] - box[:3]
-    sims = [(q, np.array([0.0, 0.0, 0.0, d * lx * lz / ly, 0.0, 0.0])) for q, d in enumerate(np.linspace(0.105, 0.14, 8))]
-
-    def fresh():
-        e = _engine()
-        e.tersoff_configure("si", SIC)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=v))
-        return e
-
-    mk = lambda q, s: capi.make_sim(q, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)
-    alone, flips, boxes = [], 0, []
-    for q, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, s)])[0].stress[:]))
-        flips += e.profile()["box_flips"]
-        boxes.append(e.get_state(q, "si", 1)[0])
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone), flips, boxes
+    return rk.sheared_fixture(TERSOFF, rk.Setup("si", SIC, None, None, (x, box, t), rk.velocities(t, MASS, 300.0, 31)))
 
 
 def test_box_flips_inside_a_split_batch(sheared):
     """eight is the smallest batch that runs as two parts: same stresses as each simulation alone, as many flips, every box back inside"""
-    fresh, sims, alone, flips, boxes = sheared
-    assert flips >= 8
-    e = fresh()
-    try:
-        e.batch_split(1)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"tersoff sheared batch of 8 (split): max rel err {err.max():.2e}, box flips {e.profile()['box_flips']} (alone: {flips})")
-        assert err.max() <= 1e-9
-        assert e.profile()["box_flips"] == flips
-        for q in range(8):
-            b = e.get_state(q, "si", 1)[0]
-            assert abs(b[6]) <= 0.5 * (b[3] - b[0]) and abs(boxes[q][6]) <= 0.5 * (boxes[q][3] - boxes[q][0])
-    finally:
-        e.close()
+    rk.assert_flips_in_split_batch(sheared, "si", 1, what="tersoff sheared batch of 8 (split)", tol=1e-9)
 
 
 def test_mixed_updates_are_refused(small_pe):
@@ -390,10 +264,8 @@ def test_mixed_updates_are_refused(small_pe):
                 e.strain_batch([mk(0, "ts"), mk(1, other)])
             assert not e.has_state(0, "ts", 1) and not e.has_state(1, other, 1)
         assert e.strain_batch([mk(0, "ts")])[0].stress_updated == 1
-        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
-            e.tersoff_compute("pe", 1)
-        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
-            e.tersoff_compute("sw", 1)
+        rk.assert_not_attached(TERSOFF, e, "pe")
+        rk.assert_not_attached(TERSOFF, e, "sw")
     finally:
         e.close()
 
@@ -414,8 +286,7 @@ def test_configuring_replaces_the_other_attachment(ref_si):
             e.sw_compute("si", 1)
         _check_static(e.tersoff_compute("si", 1), ref, what="tersoff over an SW attachment")
         e.sw_configure("si", SI_SW)
-        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
-            e.tersoff_compute("si", 1)
+        rk.assert_not_attached(TERSOFF, e, "si")
         sw1 = e.sw_compute("si", 1)
         assert sw1["npairs"] == sw0["npairs"] == ref_sw["npairs"]
         assert np.abs(sw1["f"] - ref_sw["f"]).max() <= 1e-10 * np.abs(ref_sw["f"]).max()
@@ -423,24 +294,8 @@ def test_configuring_replaces_the_other_attachment(ref_si):
         e.close()
 
 
-def _dimer_update(scripts, configure):
-    """one update of a two-atom replica: every force component is the sum of two terms, so its bits do not depend on the order of the
-    atomic sums, and two runs of the same configuration agree bit for bit"""
-    box = np.array([0.0, 0.0, 0.0, 12.0, 12.0, 12.0, 0.0, 0.0, 0.0])
-    x = np.array([[5.0, 6.0, 6.0], [7.3, 6.1, 5.9]])
-    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
-    e = _engine()
-    try:
-        if configure:
-            e.tersoff_configure("si", SIC, ("Si",))
-        e.register_replica("si", 1, capi.bare_system(tsn.zeros(2), x, box, v=v))
-        s = np.array([1.2e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
-        sim = capi.make_sim(0, "si", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
-                            scripts_folder=str(scripts))
-        out = np.array(e.strain_batch([sim])[0].stress[:])
-        return out, e.get_state(0, "si", 1)
-    finally:
-        e.close()
+DIMER = rk.Setup("si", SIC, ("Si",), None, (np.array([[5.0, 6.0, 6.0], [7.3, 6.1, 5.9]]), np.array([0.0, 0.0, 0.0, 12.0, 12.0, 12.0, 0.0, 0.0, 0.0]), tsn.zeros(2)),
+                 np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]]))
 
 
 def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
@@ -451,8 +306,9 @@ def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
     shutil.copy(SIC, scripts / "SiC.tersoff")
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style tersoff\n#pair_coeff * * ${locs}/other.tersoff C\n"
                                               "pair_coeff * * ${locs}/SiC.tersoff Si   # the potential\nfix 1 all nvt temp 300 300 100\n")
-    a, sa = _dimer_update(scripts, configure=False)
-    b, sb = _dimer_update(scripts, configure=True)
+    # (a two-atom replica: every force component is the sum of two terms, so two runs of the same configuration agree bit for bit)
+    a, sa = rk.dimer_update(TERSOFF, DIMER, scripts, False, 1.2e-2)
+    b, sb = rk.dimer_update(TERSOFF, DIMER, scripts, True, 1.2e-2)
     assert np.isfinite(a).all() and np.abs(a).max() > 0.0
     assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
     # the update configured the material: static forces of the 64-atom cell against the numpy helper
@@ -462,9 +318,8 @@ def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
                                       scripts_folder=str(folder))
     e = _engine()
     try:
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3)))
-        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
-            e.tersoff_compute("si", 1)
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 3)))
+        rk.assert_not_attached(TERSOFF, e, "si")
         assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
         _check_static(e.tersoff_compute("si", 1), ref_si.compute(x, box, t), what="tersoff self-configured")
     finally:
@@ -475,38 +330,14 @@ def test_self_configuration_from_the_scripts_folder(ref_si, tmp_path):
     shutil.copy(SI_SW, both / "Si.sw")
     e = _engine()
     try:
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 3)))
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 300.0, 3)))
         assert e.strain_batch([mk(both)])[0].stress_updated == 1
         assert e.sw_compute("si", 1)["npairs"] >= 2 * len(x)      # (the Stillinger-Weber hook answers: that potential is attached)
-        with pytest.raises(capi.EngineError, match="no Tersoff potential"):
-            e.tersoff_compute("si", 1)
+        rk.assert_not_attached(TERSOFF, e, "si")
     finally:
         e.close()
-    # malformed lines
-    for k, line in enumerate(["pair_coeff 1 1 ${locs}/SiC.tersoff Si", "pair_coeff * * SiC.tersoff Si", "pair_coeff * * ${locs}/SiC.tersoff",
-                              "pair_coeff * * ${locs}/sub/SiC.tersoff Si"]):
-        badf = tmp_path / f"bad{k}"
-        badf.mkdir()
-        shutil.copy(SIC, badf / "SiC.tersoff")
-        (badf / "in.strain.lammps").write_text(line + "\n")
-        e = _engine()
-        try:
-            e.register_replica("si", 1, capi.bare_system(t, x, box))
-            with pytest.raises(capi.EngineError, match=r"in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.tersoff"):
-                e.strain_batch([mk(badf)])
-        finally:
-            e.close()
-    # a line that names a file the folder lacks: the reader's message
-    miss = tmp_path / "miss"
-    miss.mkdir()
-    (miss / "in.strain.lammps").write_text("pair_coeff * * ${locs}/SiC.tersoff Si\n")
-    e = _engine()
-    try:
-        e.register_replica("si", 1, capi.bare_system(t, x, box))
-        with pytest.raises(capi.EngineError, match="SiC.tersoff: cannot open"):
-            e.strain_batch([mk(miss)])
-    finally:
-        e.close()
+    # malformed lines, and a line that names a file the folder lacks: the reader's message
+    rk.assert_malformed_pair_coeff_lines(TERSOFF, rk.Setup("si", SIC, None, None, (x, box, t)), tmp_path, ".tersoff", "Si", missing_file=True)
 
 
 def test_init_material_runs_for_a_tersoff_material(static_constants):
@@ -516,7 +347,7 @@ def test_init_material_runs_for_a_tersoff_material(static_constants):
     e = _engine()
     try:
         e.tersoff_configure("si", SIC)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 10.0, 9)))
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS, 10.0, 9)))
         length, stress, stiff = e.init_material("si", 1, dt=1.0, temperature=10.0, nss=20, strain_ampl=0.005, strain_rate=1e-4)
         assert np.allclose(length, box[3:6] - box[:3]) and np.isfinite(stress).all() and np.isfinite(stiff).all()
         c11, c12 = stiff[0, 0] / 1e9, stiff[0, 3] / 1e9        # file order 00, 01, 02, 11, 12, 22

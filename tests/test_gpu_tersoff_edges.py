@@ -20,9 +20,10 @@ prints its errors and the longest row against the row capacity.
 import numpy as np
 import pytest
 
+import rowkit as rk
 import tersoff_numpy as tsn
 from scema_amd import capi
-from test_gpu_tersoff import MASS, SIC, _check_static, _engine, _nts_and_rates, _static, _velocities, ref_si, sheared, synth_files  # noqa: F401  (fixtures)
+from test_gpu_tersoff import MASS, SIC, TERSOFF, no_pairs, ref_si, sheared, synth_files  # noqa: F401  (fixtures)
 from test_row_edges_host import CROWDED_FAR, NVE_STEPS, THIRD_ONLY, TS_COUNTS, moved_and_outside, nve_case
 
 pytestmark = pytest.mark.gpu
@@ -30,12 +31,19 @@ pytestmark = pytest.mark.gpu
 TWO = dict(elements=("X", "Y"), masses=(28.0, 20.0))
 
 
+_engine, _nts_and_rates = rk.engine, rk.nts_and_rates
+_static = rk.static_of(TERSOFF, SIC, ("Si",), MASS)
+
+
+_check_static = rk.checker(TERSOFF, "tersoff static", tol_f=1e-10, tol_e=1e-10, tol_w=1e-10, no_pairs=no_pairs)      # the static budget of tests/test_gpu_tersoff.py
+
+
 def _counts(ref):
     return ref["maxin"], ref["npairs"], ref["nzeta"]
 
 
 def _check_terms(got, ref, fterm, what):
-    """_check_static where the net force is zero by symmetry: the force error on the scale of the largest single pair term"""
+    """the static check where the net force is zero by symmetry: the force error on the scale of the largest single pair term"""
     assert got["npairs"] == ref["npairs"] and got["nzeta"] == ref["nzeta"] and got["maxrow"] <= got["rowcap"]
     es = max(abs(ref["e_rep"]), abs(ref["e_att"]))
     de = max(abs(got["e_rep"] - ref["e_rep"]), abs(got["e_att"] - ref["e_att"]))
@@ -79,7 +87,7 @@ def test_crowded_update_is_refused_and_leaves_no_state():
     e = _engine()
     try:
         e.tersoff_configure("si", SIC)
-        e.register_replica("si", 1, capi.bare_system(t, x, box, v=_velocities(len(x), 300.0, 4)))
+        e.register_replica("si", 1, capi.bare_system(t, x, box, v=rk.velocities(np.zeros(len(x), int), MASS, 300.0, 4)))
         sim = capi.make_sim(0, "si", 1, np.array([5e-4 * L[0], 0.0, 0.0, 0.0, 0.0, 0.0]), nss=10, dt=1.0, most_recent=capi.QP_NONE)
         with pytest.raises(capi.EngineError, match="more than 32 neighbours"):
             e.strain_batch([sim])
@@ -205,7 +213,7 @@ def mixed(synth_files):
     two-element file; each material under its own id; 10 straining steps, nss 10; and each one's stress alone in a fresh engine"""
     mats = {"n3": (tsn.narrow("N3"), SIC, ("Si",), MASS), "sia": (tsn.case_a(), SIC, ("Si",), MASS),
             "big": (tsn.case_count(1025), SIC, ("Si",), MASS), "two": (tsn.case_shell(), synth_files["synth"], TWO["elements"], TWO["masses"])}
-    vel = {m: _velocities(len(c[0][0]), 300.0, 50 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
+    vel = {m: rk.velocities(np.zeros(len(c[0][0]), int), MASS, 300.0, 50 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
     sims = []
     for q, m in enumerate(["n3", "sia", "big", "two", "two", "big", "sia", "n3"]):      # (both parts hold every kind)
         L = mats[m][0][1][3:6] - mats[m][0][1][:3]

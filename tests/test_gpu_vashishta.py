@@ -14,13 +14,13 @@ Atom counts: a short last tile, the force table past the LDS limit.  Element ord
 arm numbers from the wrong entry, pow for a non-integer eta, lambda = 0, C = 0.  Dynamics and pressure: the sign and the 1/2 of the
 virial at each end.  Whole evaluations: rows kept or rebuilt under the wrong material, part streams.
 """
-import math
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+import rowkit as rk
 import sw_numpy as swn
 import vashishta_numpy as vn
 from scema_amd import capi
@@ -51,38 +51,23 @@ def synth(tmp_path_factory):
     return str(path), vn.Vashishta(p, K)
 
 
-def _engine(**kw):
-    return capi.Engine(capi.default_params(**kw))
+VASHISHTA = rk.Pot("vashishta", "vashishta_configure", "vashishta_compute", "Vashishta", ("e2", "e3"), ("npairs", "ntriplets"),
+                   counts="ordered pairs {npairs}, triplets {ntriplets}")
 
 
-def _static(x, box, t, path=SIC, elements=EL, masses=MASS2):
-    e = _engine()
-    try:
-        e.vashishta_configure("m", path, elements)
-        e.register_replica("m", 1, capi.bare_system(t, x, box, masses=masses))
-        return e.vashishta_compute("m", 1)
-    finally:
-        e.close()
+_engine = rk.engine
+_static = rk.static_of(VASHISHTA, SIC, EL, MASS2)
 
 
-def _check_static(got, ref, what, scale=None):
-    scale = scale or ref
-    assert (got["npairs"], got["ntriplets"]) == (ref["npairs"], ref["ntriplets"]), (got["npairs"], ref["npairs"], got["ntriplets"], ref["ntriplets"])
-    assert got["maxrow"] <= got["rowcap"]
-    assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and math.isfinite(got["e2"]) and math.isfinite(got["e3"])
-    if ref["npairs"] == 0:      # no pair, so no term at all: everything is exactly zero, and there is no scale to divide by
-        assert ref["e"] == 0.0 and not ref["f"].any() and not ref["w"].any()
-        assert got["e2"] == 0.0 and got["e3"] == 0.0 and (got["f"] == 0.0).all() and (got["w"] == 0.0).all()
-        print(f"{what}: no pairs, all exactly zero, rows {got['maxrow']}/{got['rowcap']}")
-        return
-    fs, ws = np.abs(scale["f"]).max(), np.abs(scale["w"]).max()
-    es = max(abs(scale["e2"]), abs(scale["e3"]))
-    df = np.abs(got["f"] - ref["f"]).max()
-    de = max(abs(got["e2"] - ref["e2"]), abs(got["e3"] - ref["e3"]))
-    dw = np.abs(got["w"] - ref["w"]).max()
-    print(f"{what}: force err {df / fs:.2e}, energy err {de / es:.2e}, virial err {dw / ws:.2e}, ordered pairs {got['npairs']}, "
-          f"triplets {got['ntriplets']}, rows {got['maxrow']}/{got['rowcap']}")
-    assert df <= 1e-10 * fs and de <= 1e-9 * es and dw <= 1e-9 * ws
+def no_pairs(got, ref, scale, what):
+    """no pair, so no term at all: everything is exactly zero, and there is no scale to divide by"""
+    if ref["npairs"] != 0:
+        return False
+    rk.all_exactly_zero(got, ref, VASHISHTA, what)
+    return True
+
+
+_check_static = rk.checker(VASHISHTA, tol_f=1e-10, tol_e=1e-9, tol_w=1e-9, no_pairs=no_pairs)
 
 
 PAIRS = {"SiSi": (0, 0), "CC": (1, 1), "SiC": (0, 1)}
@@ -178,13 +163,6 @@ def test_triclinic_box_with_atoms_outside(ref_sic):
     _check_static(_static(x, box, t), ref_sic.compute(x, box, t), "vashishta triclinic")
 
 
-def _velocities(t, masses, temp, seed):
-    rng = np.random.default_rng(seed)
-    m = np.asarray(masses, float)[np.asarray(t)][:, None]
-    v = rng.normal(size=(len(t), 3)) * np.sqrt(vn.BOLTZ * temp / m / vn.MVV2E)
-    return v - (m * v).sum(axis=0) / m.sum()
-
-
 def test_static_parity_of_a_flipped_state(ref_sic):
     """a 5 x 2 x 2 cell written with xy = 2 a = 0.4 lx (a lattice translation: the same crystal), sheared by 0.12 lx so that it passes
     lx / 2 and flips; the forces on the state it leaves, in the box it leaves, against numpy"""
@@ -194,7 +172,7 @@ def test_static_parity_of_a_flipped_state(ref_sic):
     e = _engine()
     try:
         e.vashishta_configure("sic", SIC, EL)
-        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS2, 300.0, 31), masses=MASS2))
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS2, 300.0, 31), masses=MASS2))
         s = np.array([0.0, 0.0, 0.0, 0.12 * lx * lz / ly, 0.0, 0.0])
         e.strain_batch([capi.make_sim(0, "sic", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=3.4e-3, most_recent=capi.QP_NONE)])
         flips = e.profile()["box_flips"]
@@ -233,28 +211,8 @@ def test_synthetic_file(synth):
 
 def test_nve_dynamics_and_sampled_pressure(ref_sic):
     x, box, t = vn.case_jitter(2, 1)
-    v = _velocities(t, MASS2, 300.0, 1)
-    e = _engine()
-    try:
-        e.vashishta_configure("sic", SIC, EL)
-        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=v, masses=MASS2))
-        # 20 steps NVE against the numpy velocity-Verlet stepper
-        e.set_state(0, "sic", 1, box, x, v)
-        e.debug_run("sic", 1, 20, 1.0, 300.0, qp=0, nvt=False, use_shake=False)
-        _, xg, vg = e.get_state(0, "sic", 1)
-        xr, vr = ref_sic.nve(x, v, box, t, MASS2, 1.0, 20)
-        dx = np.abs(vn.minimage_diff(xg, xr, box)).max()
-        print(f"vashishta nve 20 steps: max position difference {dx:.2e} A, velocity {np.abs(vg - vr).max():.2e} A/fs")
-        assert dx < 1e-9 and np.abs(vg - vr).max() < 1e-11
-        # one step with sampling: the sampled tensor is (sum m v v + W) / V of the state after the step, in atm
-        e.set_state(1, "sic", 1, box, x, v)
-        p = e.debug_run("sic", 1, 1, 1.0, 300.0, qp=1, nvt=False, use_shake=False, sample=True)
-        x1, v1 = ref_sic.nve(x, v, box, t, MASS2, 1.0, 1)
-        want = ref_sic.pressure_atm(x1, v1, box, t, MASS2)
-        print(f"vashishta sampled pressure (atm): {p}, max rel err {np.abs(p - want).max() / np.abs(want).max():.2e}")
-        assert np.abs(p - want).max() <= 1e-9 * np.abs(want).max()
-    finally:
-        e.close()
+    s = rk.Setup("sic", SIC, EL, MASS2, (x, box, t), rk.velocities(t, MASS2, 300.0, 1))
+    rk.nve_and_sampled_pressure(VASHISHTA, ref_sic, s, steps=20, tol_x=1e-9, tol_v=1e-11, tol_p=1e-9)
 
 
 def _shear(h):
@@ -302,100 +260,29 @@ def test_elastic_constants(static_constants):
         e.close()
 
 
-def _nts_and_rates(strain, box, dt, rate):
-    lb = box[3:6] - box[:3]
-    eps = np.array([strain[0] / lb[0], strain[1] / lb[1], strain[2] / lb[2], strain[3] / lb[2], strain[4] / lb[1], strain[5] / lb[0]])
-    nrm = math.sqrt(eps[0] ** 2 + eps[1] ** 2 + eps[2] ** 2 + 2.0 * (eps[3] ** 2 + eps[4] ** 2 + eps[5] ** 2))
-    nts = max(int(math.ceil(nrm / rate / dt / 10.0) * 10), 10)
-    return nts, np.array([float("%.6e" % (eps[k] / (nts * dt))) for k in range(6)])
-
-
 def test_strain_batch_equals_the_two_runs():
     """tension plus a shear component, nss = 10: the update against the straining run and the sampling run issued through the parity hooks"""
     x, box, t = vn.case_jitter(2, 1)
-    v = _velocities(t, MASS2, 300.0, 2)
     L = box[3:6] - box[:3]
     s1 = np.array([2.0e-3 * L[0], -5e-4 * L[1], -5e-4 * L[2], 8e-4 * L[2], 0.0, 0.0])
-    e, f = _engine(), _engine()
-    try:
-        for g in (e, f):
-            g.vashishta_configure("sic", SIC, EL)
-            g.register_replica("sic", 1, capi.bare_system(t, x, box, v=v, masses=MASS2))
-        out = np.array(e.strain_batch([capi.make_sim(0, "sic", 1, s1, most_recent=capi.QP_NONE, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4)])[0].stress[:])
-        f.set_state(0, "sic", 1, box, x, v)
-        nts, rates = _nts_and_rates(s1, box, 1.0, 1e-4)
-        f.debug_run("sic", 1, nts, 1.0, 300.0, qp=0, nvt=True, use_shake=False, rates=rates)
-        want = -f.debug_run("sic", 1, 10, 1.0, 300.0, qp=0, nvt=True, use_shake=False, sample=True) * 1.01325e5
-        print(f"vashishta strain_batch vs debug runs ({nts} + 10 steps): {np.abs(out - want).max() / np.abs(want).max():.2e}")
-        assert nts == 30 and np.abs(out - want).max() <= 1e-9 * np.abs(want).max()
-        assert e.has_state(0, "sic", 1)
-    finally:
-        e.close()
-        f.close()
+    s = rk.Setup("sic", SIC, EL, MASS2, (x, box, t), rk.velocities(t, MASS2, 300.0, 2))
+    rk.strain_batch_vs_debug_runs(VASHISHTA, s, s1, expect_nts=30, tol=1e-9)
 
 
 @pytest.fixture(scope="module")
 def eleven(synth):
     """11 simulations over the fixture material and the synthetic one, and each one's stress alone in a fresh engine"""
     mats = {"sic": (vn.case_jitter(2, 1), SIC, EL, MASS2), "xy": (vn.case_synth(), synth[0], SYNTH_EL, SYNTH_MASS)}
-    vel = {m: _velocities(c[0][2], c[3], 300.0, 7 + k) for k, (m, c) in enumerate(sorted(mats.items()))}
-    rng = np.random.default_rng(21)
-    sims = []
-    for q in range(11):
-        m = "sic" if q % 3 else "xy"
-        box = mats[m][0][1]
-        L = box[3:6] - box[:3]
-        ezz = rng.uniform(5e-4, 2.5e-3)          # 10 to 30 straining steps: a ragged batch
-        sims.append((q, m, np.array([-0.3 * ezz * L[0], -0.3 * ezz * L[1], ezz * L[2], 0.2 * ezz * L[2], 0.0, 0.0])))
-
-    def fresh():
-        e = _engine()
-        for m, ((x, box, t), path, el, masses) in mats.items():
-            e.vashishta_configure(m, path, el)
-            e.register_replica(m, 1, capi.bare_system(t, x, box, v=vel[m], masses=masses))
-        return e
-
-    mk = lambda q, m, s: capi.make_sim(q, m, 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE)
-    alone = []
-    for q, m, s in sims:
-        e = fresh()
-        alone.append(np.array(e.strain_batch([mk(q, m, s)])[0].stress[:]))
-        e.close()
-    return fresh, [mk(*s) for s in sims], np.array(alone)
+    return rk.batch_vs_alone_fixture(VASHISHTA, mats, 11, 21)
 
 
 @pytest.mark.parametrize("split", [0, 1])
 def test_batch_of_eleven_equals_each_alone(eleven, split):
-    fresh, sims, alone = eleven
-    e = fresh()
-    try:
-        e.batch_split(split)
-        out = np.array([list(o.stress) for o in e.strain_batch(sims)])
-        err = np.abs(out - alone).max(axis=1) / np.abs(alone).max(axis=1)
-        print(f"vashishta batch of 11 over two materials (split {split}): max rel err {err.max():.2e}")
-        assert err.max() <= 1e-9
-    finally:
-        e.close()
+    rk.assert_batch_vs_alone(VASHISHTA, eleven, split, what="vashishta batch of 11 over two materials", tol=1e-9)
 
 
-def _dimer_update(scripts, configure):
-    """one update of a two-atom replica (Si, C): no triplet, and each atom sums its own pair force, so two runs of the same configuration
-    agree bit for bit"""
-    box = np.array([0.0, 0.0, 0.0, 12.0, 12.0, 12.0, 0.0, 0.0, 0.0])
-    x = np.array([[5.0, 6.0, 6.0], [6.9, 6.1, 5.9]])
-    v = np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]])
-    e = _engine()
-    try:
-        if configure:
-            e.vashishta_configure("sic", SIC, EL)
-        e.register_replica("sic", 1, capi.bare_system(np.array([0, 1]), x, box, v=v, masses=MASS2))
-        s = np.array([1.2e-2, 0.0, 0.0, 0.0, 0.0, 0.0])
-        sim = capi.make_sim(0, "sic", 1, s, nss=10, dt=1.0, temperature=300.0, strain_rate=1e-4, most_recent=capi.QP_NONE, force_field="opls",
-                            scripts_folder=str(scripts))
-        out = np.array(e.strain_batch([sim])[0].stress[:])
-        return out, e.get_state(0, "sic", 1)
-    finally:
-        e.close()
+DIMER = rk.Setup("sic", SIC, EL, MASS2, (np.array([[5.0, 6.0, 6.0], [6.9, 6.1, 5.9]]), np.array([0.0, 0.0, 0.0, 12.0, 12.0, 12.0, 0.0, 0.0, 0.0]), np.array([0, 1])),
+                 np.array([[1e-3, 2e-3, -1e-3], [-1e-3, -2e-3, 1e-3]]))
 
 
 def test_self_configuration_from_the_scripts_folder(ref_sic, tmp_path):
@@ -406,8 +293,10 @@ def test_self_configuration_from_the_scripts_folder(ref_sic, tmp_path):
     shutil.copy(SIC, scripts / "SiC.vashishta")
     (scripts / "in.strain.lammps").write_text("# straining run\npair_style vashishta\n#pair_coeff * * ${locs}/other.vashishta C\n"
                                               "pair_coeff * * ${locs}/SiC.vashishta Si C   # the potential\nfix 1 all nvt temp 300 300 100\n")
-    a, sa = _dimer_update(scripts, configure=False)
-    b, sb = _dimer_update(scripts, configure=True)
+    # (a two-atom replica, Si and C: no triplet, and each atom sums its own pair force, so two runs of the same configuration agree bit
+    # for bit)
+    a, sa = rk.dimer_update(VASHISHTA, DIMER, scripts, False, 1.2e-2)
+    b, sb = rk.dimer_update(VASHISHTA, DIMER, scripts, True, 1.2e-2)
     assert np.isfinite(a).all() and np.abs(a).max() > 0.0
     assert np.array_equal(a, b) and all(np.array_equal(p, q) for p, q in zip(sa, sb))
     # the update configured the material: static forces of the 64-atom cell against the numpy helper
@@ -417,26 +306,13 @@ def test_self_configuration_from_the_scripts_folder(ref_sic, tmp_path):
                                       scripts_folder=str(folder))
     e = _engine()
     try:
-        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=_velocities(t, MASS2, 300.0, 3), masses=MASS2))
-        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
-            e.vashishta_compute("sic", 1)
+        e.register_replica("sic", 1, capi.bare_system(t, x, box, v=rk.velocities(t, MASS2, 300.0, 3), masses=MASS2))
+        rk.assert_not_attached(VASHISHTA, e, "sic")
         assert e.strain_batch([mk(scripts)])[0].stress_updated == 1
         _check_static(e.vashishta_compute("sic", 1), ref_sic.compute(x, box, t), "vashishta self-configured")
     finally:
         e.close()
-    for k, line in enumerate(["pair_coeff 1 1 ${locs}/SiC.vashishta Si C", "pair_coeff * * SiC.vashishta Si C", "pair_coeff * * ${locs}/SiC.vashishta",
-                              "pair_coeff * * ${locs}/sub/SiC.vashishta Si C"]):
-        badf = tmp_path / f"bad{k}"
-        badf.mkdir()
-        shutil.copy(SIC, badf / "SiC.vashishta")
-        (badf / "in.strain.lammps").write_text(line + "\n")
-        e = _engine()
-        try:
-            e.register_replica("sic", 1, capi.bare_system(t, x, box, masses=MASS2))
-            with pytest.raises(capi.EngineError, match=r"rc=1: .*in\.strain\.lammps line 1: expected `pair_coeff \* \* \$\{locs\}/<name>\.vashishta"):
-                e.strain_batch([mk(badf)])
-        finally:
-            e.close()
+    rk.assert_malformed_pair_coeff_lines(VASHISHTA, rk.Setup("sic", SIC, EL, MASS2, (x, box, t)), tmp_path, ".vashishta", "Si C", match_head="rc=1: .*")
 
 
 def test_configuring_replaces_a_tersoff_attachment_and_back(ref_sic):
@@ -454,8 +330,7 @@ def test_configuring_replaces_a_tersoff_attachment_and_back(ref_sic):
             e.tersoff_compute("sic", 1)
         _check_static(e.vashishta_compute("sic", 1), ref, "vashishta over a Tersoff attachment")
         e.tersoff_configure("sic", SIC_TERSOFF, EL)
-        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
-            e.vashishta_compute("sic", 1)
+        rk.assert_not_attached(VASHISHTA, e, "sic")
         ts1 = e.tersoff_compute("sic", 1)
         assert ts1["npairs"] == ts0["npairs"] > 0 and np.abs(ts1["f"] - ts0["f"]).max() <= 1e-10 * np.abs(ts0["f"]).max()
     finally:
@@ -480,7 +355,6 @@ def test_an_update_mixed_with_stillinger_weber_is_refused():
             assert not e.has_state(0, "vs", 1) and not e.has_state(1, "sw", 1)
         assert e.strain_batch([mk(0, "vs", box)])[0].stress_updated == 1
         assert e.strain_batch([mk(1, "sw", boxs)])[0].stress_updated == 1
-        with pytest.raises(capi.EngineError, match="no Vashishta potential"):
-            e.vashishta_compute("sw", 1)
+        rk.assert_not_attached(VASHISHTA, e, "sw")
     finally:
         e.close()

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from scema_amd import capi
-from test_meam_spline_host import build_driver
+from test_meam_spline_host import driver_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = {"Ti": (os.path.join(ROOT, "tests", "golden", "Ti.meam.spline"), ["Ti"]), "TiO": (os.path.join(ROOT, "tests", "golden", "TiO.meam.spline"), ["Ti", "O"])}
@@ -59,7 +59,7 @@ def test_the_reader_never_crashes_and_every_refusal_names_a_line(tmp_path, which
 def test_the_corpus_through_the_sanitized_driver(tmp_path):
     """the stand-alone program with -fsanitize=address,undefined over both fixtures and the corpus: exit status 0 (taken) or 1 (refused),
     never a sanitizer report (which ends the program with another status and text on stderr)"""
-    exe = build_driver(("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"), "_asan")
+    exe = driver_exe(("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"), "_asan")
     n = 0
     for which, (path, el) in FILES.items():
         items = [("good", open(path, "rb").read())] + corpus(which)[::3]

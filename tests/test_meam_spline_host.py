@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import hostdrv
 import meam_spline_numpy as mn
 from scema_amd import capi
 
@@ -20,16 +21,9 @@ TI = os.path.join(ROOT, "tests", "golden", "Ti.meam.spline")
 TIO = os.path.join(ROOT, "tests", "golden", "TiO.meam.spline")
 
 
-def build_driver(flags=(), tag=""):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "meam_spline_host_driver" + tag)
-    srcs = [os.path.join(ROOT, "tests", "meam_spline_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "meam_spline_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "meam_spline", "ms_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "meam_spline_params.h"),
-                   os.path.join(ROOT, "scema_amd", "csrc", "host", "triplet_file.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", *flags, "-I", os.path.join(ROOT, "include"), "-o", exe] + srcs)
-    return exe
+def driver_exe(flags=(), tag=""):
+    return hostdrv.build("meam_spline_host_driver" + tag, ["tests/meam_spline_host_driver.cpp", "scema_amd/csrc/host/meam_spline_params.cpp"], shared=False,
+                         flags=flags)
 
 
 def run_driver(exe, path, elements, x, box, types, energy_unit=0):
@@ -83,7 +77,7 @@ NAMES = sorted(shapes())
 @pytest.fixture(scope="module")
 def refs():
     """per shape: (numpy object, numpy result, driver result), each computed once"""
-    exe = build_driver()
+    exe = driver_exe()
     out = {}
     for name, (path, el, case) in shapes().items():
         splines, type_map = mn.read_meam_spline(path, el)
@@ -175,7 +169,7 @@ def test_the_triplet_sum_with_a_constant_g(tmp_path, elements):
     x, box, t = mn.case_bcc(2, 2, 2, 3.0, 0.1, 7, "random" if len(el) == 2 else None)
     ref = mn.MeamSpline(mn.read_meam_spline(path, el)[0])
     got = ref.compute(x, box, t)
-    drv = run_driver(build_driver(), path, el, x, box, t)
+    drv = run_driver(driver_exe(), path, el, x, box, t)
     I, J, D, R, n = ref.ordered_pairs(x, box, t)
     want = np.zeros(n)
     for i in range(n):
@@ -281,7 +275,7 @@ def test_energy_units():
     x, box, t = mn.case_count(63)
     a = mn.MeamSpline(mn.read_meam_spline(TI, ["Ti"], 0)[0]).compute(x, box, t)
     b = mn.MeamSpline(mn.read_meam_spline(TI, ["Ti"], 1)[0]).compute(x, box, t)
-    exe = build_driver()
+    exe = driver_exe()
     da, db = run_driver(exe, TI, ["Ti"], x, box, t, 0), run_driver(exe, TI, ["Ti"], x, box, t, 1)
     for p, q in ((a, b), (da, db)):
         assert abs(p["e"] / q["e"] / mn.EV_TO_KCALMOL - 1.0) < 1e-12 and np.abs(p["f"] / q["f"] / mn.EV_TO_KCALMOL - 1.0).max() < 1e-9

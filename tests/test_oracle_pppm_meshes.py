@@ -177,20 +177,20 @@ def _cell(d):
     return b[:3], np.array([[b[3] - b[0], 0, 0], [b[6], b[4] - b[1], 0], [b[7], b[8], b[5] - b[2]]])   # rows: the lattice vectors
 
 
-def _lamda(d):
+def to_lamda(d):
     lo, lat = _cell(d)
     return (np.asarray(d["x"]) - lo) @ np.linalg.inv(lat)
 
 
-def _from_lamda(d, lam):
+def from_lamda(d, lam):
     lo, lat = _cell(d)
     out = deepcopy(d)
     out["x"] = lo + np.asarray(lam) @ lat
     return out
 
 
-def _min_distance(d):
-    lam = _lamda(d)
+def min_distance(d):
+    lam = to_lamda(d)
     _, lat = _cell(d)
     dl = lam[:, None, :] - lam[None, :, :]
     dl -= np.round(dl)
@@ -201,7 +201,7 @@ def _min_distance(d):
 def on_faces(d, cells):
     """per coordinate c one atom at lamda_c = 0 exactly, one at -1e-17 and one at 1 - 1e-17 (in a box with lo = 0: lo - 1e-17 L and
     hi - 1e-17 L; the kernel's lamda - floor(lamda) rounds to 1.0 and the nearest plane is i == n), and one atom in the corner"""
-    lam = _lamda(d)
+    lam = to_lamda(d)
     site = lambda i, j, k: (i * cells[1] + j) * cells[2] + k
     moved = []
     for c in range(3):
@@ -216,7 +216,7 @@ def on_faces(d, cells):
     corner = site(1, 1, 1)
     assert corner not in moved
     lam[corner] = 0.0
-    out = _from_lamda(d, lam)
+    out = from_lamda(d, lam)
     lo, lat = _cell(d)
     if not np.any(d["box"][6:9]):   # orthogonal, lo = 0: the positions are the literal ones
         L = np.diag(lat)
@@ -315,9 +315,9 @@ def test_oracle_is_continuous_at_the_faces_of_the_box(name):
     changes forces of 0.1 kcal/mol/A with gradients of 1 per A by 1e-8 -- asked for: 1e-6 of the largest force; the defect was 0.7."""
     row = BY_NAME[name]
     d = on_faces(row_fixture(row), row.cells)
-    lam = _lamda(d)
+    lam = to_lamda(d)
     assert (lam < 0.0).any() and (lam == 0.0).any() and (lam == 1.0).any()
-    inside = _from_lamda(d, np.clip(lam, 1e-9, 1.0 - 1e-9))
+    inside = from_lamda(d, np.clip(lam, 1e-9, 1.0 - 1e-9))
     f, e, w, o = oracle_compute(d, row.acc)
     fi, ei, wi, oi = oracle_compute(inside, row.acc)
     assert o.npairs == oi.npairs and o.pppm_grid == row.grid

@@ -23,7 +23,7 @@ def ff():
     f.close()
 
 
-def _ethane(ff, phi):
+def case_ethane(ff, phi):
     cc, ch, th = 1.54, 1.10, np.deg2rad(111.0)
     x = [[0, 0, 0], [cc, 0, 0]]
     for k in range(3):
@@ -35,7 +35,7 @@ def _ethane(ff, phi):
     return ff.types(["C", "C"] + ["H"] * 6), np.array(x, float)
 
 
-def _ethylene(ff, phi):
+def case_ethylene(ff, phi):
     cc, ch, th = 1.33, 1.09, np.deg2rad(121.0)
     x = [[0, 0, 0], [cc, 0, 0]]
     for s in (1, -1):
@@ -45,7 +45,7 @@ def _ethylene(ff, phi):
     return ff.types(["C", "C"] + ["H"] * 4), np.array(x, float)
 
 
-def _water(o, rot=0.0):
+def case_water(o, rot=0.0):
     r, th = 0.96, np.deg2rad(104.5)
     h1 = np.array([r, 0, 0])
     h2 = np.array([r * np.cos(th), r * np.sin(th), 0])
@@ -54,7 +54,7 @@ def _water(o, rot=0.0):
     return np.array([o, o + R @ h1, o + R @ h2])
 
 
-def _glycine_like(ff, seed=3):
+def case_glycine_like(ff, seed=3):
     """a small C/H/O/N cluster with every term switched on (bonds, angles, torsions, a hydrogen bond, all four elements)"""
     rng = np.random.default_rng(seed)
     sym = ["N", "C", "C", "O", "O", "H", "H", "H", "H", "H"]
@@ -69,7 +69,7 @@ def test_force_field_file_is_read_completely(ff):
     assert ff.general(0) == 50.0 and ff.general(12) == 10.0 and ff.general(29) == 0.1 and ff.general(38) == 3.6942
     # the sections after the atoms are only visible through energies: a C-C-C-C torsion (specific entry) and an H-C-C-H one
     # (wildcard 0 1 1 0 overridden by the specific 2 1 1 2) must both act
-    t, x = _ethane(ff, 0.0)
+    t, x = case_ethane(ff, 0.0)
     assert ff.energy(t, x)[1]["tors"] > 1.0
 
 
@@ -109,13 +109,13 @@ def test_taper_is_smooth_at_both_ends(ff):
 
 
 def test_bond_orders_of_simple_molecules(ff):
-    t, x = _ethane(ff, np.pi / 3)
+    t, x = case_ethane(ff, np.pi / 3)
     ij, bo = ff.bond_orders(t, x)
     d = {tuple(p): b for p, b in zip(ij.tolist(), bo)}
     assert 0.9 < d[(0, 1)][0] < 1.2                                      # C-C single
     for h in (2, 3, 4):
         assert 0.9 < d[(0, h)][0] < 1.05                                  # C-H
-    t, x = _ethylene(ff, 0.0)
+    t, x = case_ethylene(ff, 0.0)
     ij, bo = ff.bond_orders(t, x)
     d = {tuple(p): b for p, b in zip(ij.tolist(), bo)}
     assert 1.5 < d[(0, 1)][0] < 2.1 and d[(0, 1)][1] > 0.5              # C=C carries a pi bond order
@@ -127,30 +127,30 @@ def test_rotation_barriers_pin_the_dihedral_convention(ff):
         q, _ = ff.qeq(t, x)
         return ff.energy(t, x, q=q)[0]
 
-    barrier = e(_ethane, 0.0) - e(_ethane, 60.0)                          # eclipsed above staggered, experiment 2.9 kcal/mol
+    barrier = e(case_ethane, 0.0) - e(case_ethane, 60.0)                          # eclipsed above staggered, experiment 2.9 kcal/mol
     assert 1.5 < barrier < 5.0
-    assert e(_ethane, 30.0) > e(_ethane, 60.0) and e(_ethane, 30.0) < e(_ethane, 0.0)
-    assert e(_ethylene, 90.0) - e(_ethylene, 0.0) > 40.0                   # twisting a double bond breaks the pi bond
-    assert e(_ethylene, 45.0) > e(_ethylene, 0.0)
+    assert e(case_ethane, 30.0) > e(case_ethane, 60.0) and e(case_ethane, 30.0) < e(case_ethane, 0.0)
+    assert e(case_ethylene, 90.0) - e(case_ethylene, 0.0) > 40.0                   # twisting a double bond breaks the pi bond
+    assert e(case_ethylene, 45.0) > e(case_ethylene, 0.0)
 
 
 def test_hydrogen_bond_of_the_water_dimer(ff):
     t = ff.types(["O", "H", "H"] * 2)
-    donor = _water(np.zeros(3))                                            # O-H along +x
-    acc = _water(np.array([2.85, 0.0, 0.0]), rot=np.deg2rad(-52.25))      # acceptor oxygen on the O-H axis, hydrogens pointing away
+    donor = case_water(np.zeros(3))                                            # O-H along +x
+    acc = case_water(np.array([2.85, 0.0, 0.0]), rot=np.deg2rad(-52.25))      # acceptor oxygen on the O-H axis, hydrogens pointing away
     x = np.vstack([donor, acc])
     e, p = ff.energy(t, x)
     assert -8.0 < p["hb"] < -2.0                                          # p_hb1(O-H..O) = -6.68 kcal/mol at full strength
     # the angular factor sin^4(theta/2) switches the term off when the acceptor sits behind the donor
-    x2 = np.vstack([donor, _water(np.array([-2.85, 0.0, 0.0]), rot=np.deg2rad(127.75))])
+    x2 = np.vstack([donor, case_water(np.array([-2.85, 0.0, 0.0]), rot=np.deg2rad(127.75))])
     assert abs(ff.energy(t, x2)[1]["hb"]) < 0.3 * abs(p["hb"])
     # and the radial cutoff of 7.5 A
-    x3 = np.vstack([donor, _water(np.array([0.96 + 7.6, 0.0, 0.0]), rot=np.deg2rad(-52.25))])
+    x3 = np.vstack([donor, case_water(np.array([0.96 + 7.6, 0.0, 0.0]), rot=np.deg2rad(-52.25))])
     assert ff.energy(t, x3)[1]["hb"] == 0.0
 
 
 def test_charge_equilibration_conditions(ff):
-    t, x = _glycine_like(ff)
+    t, x = case_glycine_like(ff)
     q, it = ff.qeq(t, x, tol=1e-10, maxiter=500)
     assert it > 0 and abs(q.sum()) < 1e-9
     sym = [ff.names[k] for k in t]
@@ -172,7 +172,7 @@ def test_charge_equilibration_conditions(ff):
 
 
 def test_invariances(ff):
-    t, x = _glycine_like(ff)
+    t, x = case_glycine_like(ff)
     q, _ = ff.qeq(t, x)
     e0, p0 = ff.energy(t, x, q=q)
     assert all(abs(p0[k]) > 1e-6 for k in ("bond", "lp", "over", "under", "angle", "tors", "conj", "hb", "vdw", "coul", "pol"))
@@ -196,7 +196,7 @@ def test_invariances(ff):
 
 
 def test_forces_and_virial_are_consistent(ff):
-    t, x = _glycine_like(ff)
+    t, x = case_glycine_like(ff)
     q, _ = ff.qeq(t, x)
     box = np.array([-15.0, -15.0, -15.0, 15.0, 15.0, 15.0, 4.0, -3.0, 2.0])
     f, w = ff.forces(t, x, box=box, q=q, virial=True)

@@ -14,8 +14,8 @@ import torch
 
 from oracle import pyreax as pr
 from oracle import reax_md, reax_torch as rt
-from test_oracle_reax import FFIELD, _ethane, _glycine_like
-from test_reax_host import _mixture, _pe_cell
+from test_oracle_reax import FFIELD, case_ethane, case_glycine_like
+from test_reax_host import case_mixture, case_pe_cell
 
 MVV2E = 48.88821291 ** 2
 BOLTZ = 0.0019872067
@@ -44,23 +44,23 @@ def _same_energy(ff, R, t, x, box, q):
 
 
 def test_energy_equals_the_c_oracle_part_by_part(ff, R):
-    t, x = _glycine_like(ff)
+    t, x = case_glycine_like(ff)
     q = np.linspace(-0.3, 0.3, len(t)); q -= q.mean()
     _same_energy(ff, R, t, x, None, q)
-    t, x = _ethane(ff, 0.3)
+    t, x = case_ethane(ff, 0.3)
     _same_energy(ff, R, t, x, None, None)
-    sym, x, box = _pe_cell(ff, tilt=(0.7, -0.4, 0.5))
+    sym, x, box = case_pe_cell(ff, tilt=(0.7, -0.4, 0.5))
     t = ff.types(sym)
     q, _ = ff.qeq(t, x, box)
     _same_energy(ff, R, t, x, box, q)
-    sym, x, box = _mixture()
+    sym, x, box = case_mixture()
     t = ff.types(sym)
     q, _ = ff.qeq(t, x, box)
     _same_energy(ff, R, t, x, box, q)
 
 
 def test_reverse_mode_forces_equal_central_differences(ff, R):
-    t, x = _glycine_like(ff)
+    t, x = case_glycine_like(ff)
     q = np.linspace(-0.3, 0.3, len(t)); q -= q.mean()
     f, _, _ = R.forces(t, x, None, q)
     fd = ff.forces(t, x, None, q, h=1e-5)
@@ -70,7 +70,7 @@ def test_reverse_mode_forces_equal_central_differences(ff, R):
 
 def test_forces_and_virial_in_a_condensed_triclinic_cell(ff, R):
     """all 4 320 force components along random directions, and the virial against the strain derivative of the C energy"""
-    sym, x, box = _pe_cell(ff, tilt=(0.7, -0.4, 0.5))
+    sym, x, box = case_pe_cell(ff, tilt=(0.7, -0.4, 0.5))
     t = ff.types(sym)
     q, _ = ff.qeq(t, x, box)
     f, w, e, _ = R.forces(t, x, box, q, virial=True)
@@ -87,7 +87,7 @@ def test_forces_and_virial_in_a_condensed_triclinic_cell(ff, R):
 
 
 def test_charge_equilibration_equals_the_c_solver(ff, R):
-    sym, x, box = _mixture()
+    sym, x, box = case_mixture()
     t = ff.types(sym)
     qc, _ = ff.qeq(t, x, box, tol=1e-10, maxiter=500)
     H, dia = R.h_matrix(t, x, box)
@@ -98,7 +98,7 @@ def test_charge_equilibration_equals_the_c_solver(ff, R):
     assert np.abs(q - qc).max() < 1e-9 and abs(q.sum()) < 1e-10
 
 
-def _velocities(sym, temperature, seed):
+def _thermal_velocities(sym, temperature, seed):
     m = np.array([MASS[s] for s in sym])
     v = np.random.default_rng(seed).standard_normal((len(sym), 3)) * np.sqrt(BOLTZ * temperature / (m[:, None] * MVV2E))
     return v - (m[:, None] * v).sum(0) / m.sum()
@@ -115,10 +115,10 @@ def test_nve_and_nose_hoover_conserved_quantities(ff):
     cannot be: the charges minimise the QEq functional with 14.4 eV A (fix_qeq_reax), the forces come from a Coulomb energy with
     332.06371 kcal A / mol (= 14.425 eV A; reaxc_nonbonded) at fixed charges, so (dE/dq - mu) dq/dt is not exactly zero -- USER-REAXC's
     own mismatch of constants, restated."""
-    t, x = _ethane(ff, 0.3)
+    t, x = case_ethane(ff, 0.3)
     sym = [ff.names[k] for k in t]
     box = np.array([-20.0, -20, -20, 20, 20, 20, 0, 0, 0])
-    v = _velocities(sym, 300.0, 5)
+    v = _thermal_velocities(sym, 300.0, 5)
     drift = []
     for dt, nsteps in ((0.4, 40), (0.2, 80)):
         M = _md(sym, x, box, v, qeq_tol=1e-10, qeq_maxiter=500)
@@ -138,8 +138,8 @@ def test_nve_and_nose_hoover_conserved_quantities(ff):
 def test_a_strained_evaluation_is_reproducible_and_continues(ff):
     """STMDProblem::strain with md_force_field reax on the condensed mixture: straining steps by the nts rule, the box ends
     where fix deform should leave it, the stress is reproducible, and a second evaluation continues from the stored state"""
-    sym, x, box = _mixture(seed=10)
-    v = _velocities(sym, 300.0, 2)
+    sym, x, box = case_mixture(seed=10)
+    v = _thermal_velocities(sym, 300.0, 2)
     lens = box[3:6] - box[:3]
     eps = np.array([0.004, -0.001, 0.0, 0.002, 0.0, -0.001])
     strain = eps * lens[[0, 1, 2, 2, 1, 0]]

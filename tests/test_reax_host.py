@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import pyreax as pr
-from test_oracle_reax import FFIELD, _ethane, _ethylene, _glycine_like, _water
+from test_oracle_reax import FFIELD, case_ethane, case_ethylene, case_glycine_like, case_water
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ELEMENTS = ["H", "C", "N", "O"]          # pair_coeff * * ffield.reax.2 H C N O  (lammps_scripts_reax/in.strain.lammps:11)
@@ -78,11 +78,11 @@ def drv(request):
 BIGBOX = np.array([-15.0, -15.0, -15.0, 15.0, 15.0, 15.0, 4.0, -3.0, 2.0])
 
 
-def _sym(ff, t):
+def symbols(ff, t):
     return [ff.names[k] for k in t]
 
 
-def _pe_cell(ff, tilt=(0.0, 0.0, 0.0), amp=0.1, seed=5):
+def case_pe_cell(ff, tilt=(0.0, 0.0, 0.0), amp=0.1, seed=5):
     from scema_amd.systems import build_pe
     d = build_pe(3, 5, 8)                        # 1440 atoms, 22.2 x 24.65 x 20.27 A: the smallest cell the oracle's minimum image takes
     box = d["box"].copy()
@@ -96,12 +96,12 @@ def _pe_cell(ff, tilt=(0.0, 0.0, 0.0), amp=0.1, seed=5):
     return sym, x, box
 
 
-def _mixture(seed=11, L=21.0):
+def case_mixture(seed=11, L=21.0):
     """water, ammonia, methane and formaldehyde on a jittered lattice: every element, hydrogen bonds, lone pairs"""
     rng = np.random.default_rng(seed)
     a = 1.09 / np.sqrt(3)
     mols = {
-        "water": (["O", "H", "H"], _water(np.zeros(3))),
+        "water": (["O", "H", "H"], case_water(np.zeros(3))),
         "ammonia": (["N", "H", "H", "H"], np.array([[0, 0, 0.1], [0.94, 0, -0.27], [-0.47, 0.81, -0.27], [-0.47, -0.81, -0.27]])),
         "methane": (["C", "H", "H", "H", "H"], np.array([[0, 0, 0], [a, a, a], [-a, -a, a], [-a, a, -a], [a, -a, -a]])),
         "formaldehyde": (["C", "O", "H", "H"], np.array([[0, 0, 0], [1.21, 0, 0], [-0.59, 0.94, 0], [-0.59, -0.94, 0]])),
@@ -119,7 +119,7 @@ def _mixture(seed=11, L=21.0):
     return sym, np.vstack(xs), np.array([0, 0, 0, L, L, L, 0.0, 0.0, 0.0])
 
 
-def _check_dirs(ff, t, x, box, q, f, ndir=6, h=1e-5, seed=1):
+def check_dirs(ff, t, x, box, q, f, ndir=6, h=1e-5, seed=1):
     rng = np.random.default_rng(seed)
     good = 0
     worst = 0.0
@@ -136,23 +136,23 @@ def _check_dirs(ff, t, x, box, q, f, ndir=6, h=1e-5, seed=1):
 
 def test_parser_and_energies_match_the_oracle(ff, drv):
     exact, lammps = drv
-    for t, x in (_glycine_like(ff), _ethane(ff, 0.4), _ethylene(ff, 0.5)):
+    for t, x in (case_glycine_like(ff), case_ethane(ff, 0.4), case_ethylene(ff, 0.5)):
         q, _ = ff.qeq(t, x, box=BIGBOX, tol=1e-10, maxiter=500)
-        r = exact(_sym(ff, t), x, BIGBOX)
+        r = exact(symbols(ff, t), x, BIGBOX)
         assert np.abs(r["q"] - q).max() < 1e-8
-        r = exact(_sym(ff, t), x, BIGBOX, q=q)
+        r = exact(symbols(ff, t), x, BIGBOX, q=q)
         _, po = ff.energy(t, x, box=BIGBOX, q=q)
         for k in pr.PARTS:
             assert abs(r["e"][k] - po[k]) < 1e-9 * max(1.0, abs(po[k])), k
-        assert lammps(_sym(ff, t), x, BIGBOX, q=q)["e"] == r["e"]      # the switch touches derivatives only
+        assert lammps(symbols(ff, t), x, BIGBOX, q=q)["e"] == r["e"]      # the switch touches derivatives only
 
 
 @pytest.mark.parametrize("terms,parts", [(1, ("bond", "lp", "over", "under")), (2, ("angle", "pen", "coa")), (4, ("tors", "conj")), (8, ("hb",)),
                                          (16, ("vdw", "coul", "pol")), (ALL, tuple(pr.PARTS))])
 def test_forces_of_each_pass_against_central_differences(ff, drv, terms, parts):
     exact, _ = drv
-    t, x = _glycine_like(ff)
-    sym = _sym(ff, t)
+    t, x = case_glycine_like(ff)
+    sym = symbols(ff, t)
     q, _ = ff.qeq(t, x, box=BIGBOX, tol=1e-10, maxiter=500)
     r = exact(sym, x, BIGBOX, q=q, terms=terms)
     h = 1e-5
@@ -175,7 +175,7 @@ def test_forces_of_each_pass_against_central_differences(ff, drv, terms, parts):
 @pytest.mark.parametrize("tilt", [(0.0, 0.0, 0.0), (3.0, -2.0, 1.5)])
 def test_condensed_polyethylene_cell(ff, drv, tilt):
     exact, lammps = drv
-    sym, x, box = _pe_cell(ff, tilt=tilt, amp=0.08 if tilt[0] == 0 else 0.15)
+    sym, x, box = case_pe_cell(ff, tilt=tilt, amp=0.08 if tilt[0] == 0 else 0.15)
     t = ff.types(sym)
     q, _ = ff.qeq(t, x, box=box, tol=1e-10, maxiter=500)
     r = exact(sym, x, box)
@@ -185,7 +185,7 @@ def test_condensed_polyethylene_cell(ff, drv, tilt):
     for k in pr.PARTS:
         assert abs(r["e"][k] - po[k]) < 1e-9 * max(1.0, abs(po[k])), k
     assert abs(po["tors"]) > 100 and abs(po["over"]) > 100 and abs(po["angle"]) > 100
-    good, worst = _check_dirs(ff, t, x, box, q, r["f"])
+    good, worst = check_dirs(ff, t, x, box, q, r["f"])
     assert good >= 5, worst
     assert np.abs(r["f"].sum(0)).max() < 1e-7 * np.abs(r["f"]).max()
     # virial against the strain derivative of the oracle's energy
@@ -204,7 +204,7 @@ def test_condensed_polyethylene_cell(ff, drv, tilt):
 
 def test_condensed_mixture_with_hydrogen_bonds(ff, drv):
     exact, _ = drv
-    sym, x, box = _mixture()
+    sym, x, box = case_mixture()
     t = ff.types(sym)
     q, _ = ff.qeq(t, x, box=box, tol=1e-10, maxiter=500)
     r = exact(sym, x, box)
@@ -214,13 +214,13 @@ def test_condensed_mixture_with_hydrogen_bonds(ff, drv):
     for k in pr.PARTS:
         assert abs(r["e"][k] - po[k]) < 1e-9 * max(1.0, abs(po[k])), k
     assert po["hb"] < -1.0 and abs(po["lp"]) > 0.01
-    good, worst = _check_dirs(ff, t, x, box, q, r["f"], seed=3)
+    good, worst = check_dirs(ff, t, x, box, q, r["f"], seed=3)
     assert good >= 5, worst
 
 
 def test_list_radius_beyond_the_cutoff_changes_nothing(ff, drv):
     exact, _ = drv
-    sym, x, box = _mixture(seed=4)
+    sym, x, box = case_mixture(seed=4)
     a = exact(sym, x, box, rlist=10.0)
     b = exact(sym, x, box, rlist=10.5)      # the skin of the neighbour rows
     assert np.abs(a["q"] - b["q"]).max() < 1e-9

@@ -144,7 +144,7 @@ def test_pinned_counts_eam(eam_refs):
     assert np.abs(rho - 1.0).min() > 1e-3          # no atom sits on rhomax: the count does not hang on rounding
     assert sorted(set(eam_refs["four"][1][2])) == [0, 1, 2, 3] and sorted(set(eam_refs["four_dup"][1][2])) == [0, 1]
     # the permuted list names the same crystal: the same numbers
-    eh._same(eam_refs["four_perm"][2], eam_refs["four"][2], tol=1e-13)
+    eh.same(eam_refs["four_perm"][2], eam_refs["four"][2], tol=1e-13)
 
 
 def test_conditions_on_the_boxes():
@@ -234,12 +234,12 @@ def test_forces_are_the_gradient_of_the_energy_eam(eam_refs, name):
 # ---------------------------------------------------------------- the host-compiled cores
 @pytest.fixture(scope="module")
 def ts_lib():
-    return th._build_driver()
+    return th.driver_lib()
 
 
 @pytest.fixture(scope="module")
 def eam_lib():
-    return eh._build_driver()
+    return eh.driver_lib()
 
 
 @pytest.mark.parametrize("name", TS_NAMES)
@@ -252,7 +252,7 @@ def test_host_compiled_tersoff_core(ts_lib, ts_refs, files, name):
     if name == "N1":      # zero net force: compare on the scale of the terms
         assert np.abs(got["f"]).max() <= 1e-12 * tsn.fterm(ref, *case)
         got["f"] = want["f"]
-    th._same(got, want)
+    th.same(got, want)
     if name == "shell_clamp":          # both clamps and the large-zeta end of b are reached here too
         assert got["t"].max() > 1e20
 
@@ -263,7 +263,7 @@ def test_host_compiled_eam_core(eam_lib, eam_refs, files, name):
     path, el, case = eam_inputs(files)[name]
     got = eh.Driver(eam_lib, path, el)(*case)
     assert got["maxin"] == eam_refs[name][2]["maxin"]
-    eh._same(got, eam_refs[name][2])
+    eh.same(got, eam_refs[name][2])
 
 
 def test_list_cut_at_the_pair_cutoff_is_caught(ts_lib, ts_refs, files):
@@ -273,11 +273,11 @@ def test_list_cut_at_the_pair_cutoff_is_caught(ts_lib, ts_refs, files):
     (tests/test_tersoff_host.py::test_wrong_builds_are_caught) and on the shell case as well, whose i j k entries carry their own R, D"""
     def fails(got, want):
         try:
-            th._same(got, want)
+            th.same(got, want)
         except AssertionError:
             return True
         return False
-    old = th._inputs((files["synth"], files["clamp"]))
+    old = th.inputs((files["synth"], files["clamp"]))
     for name in th.NAMES:
         path, el, case = old[name]
         want = tsn.Tersoff(tsn.read_tersoff(path, el)[0]).compute(*case)

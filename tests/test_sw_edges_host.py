@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import sw_numpy as swn
-from test_sw_host import SI_SW, Driver, _build_driver, _same
+from test_sw_host import SI_SW, Driver, driver_lib, same
 
 NARROW = ["N1", "N2", "N3", "N4", "N5"]
 # pairs, triplets, most neighbours inside the cutoff, row entries that name the row's own atom (summed over the atoms)
@@ -106,13 +106,13 @@ def test_supercell_identity(refs, name):
     de = max(abs(big["e2"] / 27 - one["e2"]), abs(big["e3"] / 27 - one["e3"])) / es
     dw = np.abs(big["w"] / 27 - one["w"]).max() / np.abs(one["w"]).max()
     # (N4: the net force on the one atom is zero by symmetry; the scale is the largest single pair term)
-    fs = max(np.abs(one["f"]).max(), _fterm(ref, x, box, t) if name == "N4" else 0.0)
+    fs = max(np.abs(one["f"]).max(), largest_force_term(ref, x, box, t) if name == "N4" else 0.0)
     df = np.abs(big["f"][:n] - one["f"]).max() / fs
     print(f"sw supercell {name}: energy {de:.1e}, forces {df:.1e}, virial {dw:.1e}")
     assert de <= 1e-12 and df <= 1e-12 and dw <= 1e-12
 
 
-def _fterm(ref, x, box, t):
+def largest_force_term(ref, x, box, t):
     """the largest two-body force among the pairs of a configuration (silicon): the size of the terms that cancel in a symmetric one"""
     P = ref.pair(0, 0)
     r = np.array([np.linalg.norm(d) for row in ref.neighbours(x, box, t) for _, _, d in row])
@@ -129,7 +129,7 @@ def test_forces_are_the_gradient_of_the_energy_in_narrow_boxes(refs, name):
     ref = refs[0]
     x, box, t = swn.narrow(name)
     f = ref.compute(x, box, t)["f"]
-    scale = max(np.abs(f).max(), _fterm(ref, x, box, t))
+    scale = max(np.abs(f).max(), largest_force_term(ref, x, box, t))
     rng = np.random.default_rng(3)
     h = 1e-5
     for _ in range(6):
@@ -171,7 +171,7 @@ def test_pinned_counts(refs):
 @pytest.mark.parametrize("name", NARROW)
 def test_host_compiled_core_in_narrow_boxes(refs, name):
     """sw_core.h as the kernels run it, with sw_owns deciding an atom's pair with its own image, against the reference at 1e-12"""
-    L = _build_driver()
+    L = driver_lib()
     if name == "N5":
         ref, drivers = refs[1], [Driver(L, refs[2], ["Si", "X"])]
     else:
@@ -181,6 +181,6 @@ def test_host_compiled_core_in_narrow_boxes(refs, name):
     for d in drivers:
         got = d(x, box, t)
         if name == "N4":      # zero net force: compare on the scale of the terms
-            assert np.abs(got["f"]).max() <= 1e-12 * _fterm(ref, x, box, t)
+            assert np.abs(got["f"]).max() <= 1e-12 * largest_force_term(ref, x, box, t)
             got["f"] = want["f"]
-        _same(got, want)
+        same(got, want)

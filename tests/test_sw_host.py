@@ -9,11 +9,11 @@ by symmetry, from second differences of the energy under +-1e-3 homogeneous stra
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostdrv
 import sw_numpy as swn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,15 +21,8 @@ SI_SW = os.path.join(ROOT, "tests", "golden", "Si.sw")
 EPS = 2.1683 * swn.EV_TO_KCALMOL
 
 
-def _build_driver():
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libsw_host.so")
-    srcs = [os.path.join(ROOT, "tests", "sw_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "sw_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "sw", "sw_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "sw_params.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", so] + srcs)
-    L = C.CDLL(so)
+def driver_lib():
+    L = C.CDLL(hostdrv.build("libsw_host.so", ["tests/sw_host_driver.cpp", "scema_amd/csrc/host/sw_params.cpp"], shared=True))
     L.swh_create.restype = C.c_void_p
     L.swh_create.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]
     L.swh_destroy.argtypes = [C.c_void_p]
@@ -61,7 +54,7 @@ class Driver:
 
 @pytest.fixture(scope="module")
 def lib():
-    return _build_driver()
+    return driver_lib()
 
 
 @pytest.fixture(scope="module")
@@ -89,7 +82,7 @@ def two(lib, two_sw):
     return swn.SW(prm), d
 
 
-def _same(got, ref, tol=1e-12):
+def same(got, ref, tol=1e-12):
     assert got["npairs"] == ref["npairs"] and got["ntriplets"] == ref["ntriplets"] and got["maxin"] == ref["maxin"]
     fs = max(np.abs(ref["f"]).max(), 1e-300)
     assert np.abs(got["f"] - ref["f"]).max() <= tol * fs
@@ -106,8 +99,8 @@ def test_static_cases_match_numpy(si, name):
     ref_sw, fast, general = si
     x, box, t = CASES[name]()
     ref = ref_sw.compute(x, box, t)
-    _same(fast(x, box, t), ref)
-    _same(general(x, box, t), ref)
+    same(fast(x, box, t), ref)
+    same(general(x, box, t), ref)
     if name == "c":
         assert ref["maxin"] == 16 and ref["ntriplets"] == 64 * 120
     assert abs(ref["f"].sum(axis=0)).max() < 1e-10 * np.abs(ref["f"]).max()
@@ -118,7 +111,7 @@ def test_two_elements_match_numpy(two):
     x, box, t = swn.case_e()
     ref = ref_sw.compute(x, box, t)
     assert ref["ntriplets"] > 0 and len(set(t)) == 2
-    _same(d(x, box, t), ref)
+    same(d(x, box, t), ref)
 
 
 @pytest.mark.parametrize("which", ["numpy", "fast", "general", "two"])

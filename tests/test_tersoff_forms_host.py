@@ -23,11 +23,11 @@ Wrong builds (tfh_create's `wrong`), tried on this driver; test_wrong_builds_are
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostdrv
 import tersoff_forms_numpy as tf
 import tersoff_numpy as tsn
 
@@ -36,16 +36,8 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MOD, MODC, ZBL, SIC = (os.path.join(GOLD, n) for n in ("Si.tersoff.mod", "Si.tersoff.modc", "SiC.tersoff.zbl", "SiC.tersoff"))
 
 
-def _build_driver():
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libtersoff_forms_host.so")
-    csrc = os.path.join(ROOT, "scema_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "tersoff_forms_host_driver.cpp"), os.path.join(csrc, "host", "tersoff_params.cpp")]
-    deps = srcs + [os.path.join(csrc, "tersoff", "ts_core.h"), os.path.join(csrc, "host", "tersoff_params.h"), os.path.join(csrc, "host", "triplet_file.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", so] + srcs)
-    L = C.CDLL(so)
+def driver_lib():
+    L = C.CDLL(hostdrv.build("libtersoff_forms_host.so", ["tests/tersoff_forms_host_driver.cpp", "scema_amd/csrc/host/tersoff_params.cpp"], shared=True))
     L.tfh_create.restype = C.c_void_p
     L.tfh_create.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]
     L.tfh_destroy.argtypes = [C.c_void_p]
@@ -85,7 +77,7 @@ class Driver:
 
 @pytest.fixture(scope="module")
 def lib():
-    return _build_driver()
+    return driver_lib()
 
 
 @pytest.fixture(scope="module")

@@ -22,26 +22,19 @@ input of this file; tests/test_row_edges_host.py has the case that catches it.
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostdrv
 import tersoff_numpy as tsn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIC = os.path.join(ROOT, "tests", "golden", "SiC.tersoff")
 
 
-def _build_driver():
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libtersoff_host.so")
-    srcs = [os.path.join(ROOT, "tests", "tersoff_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "tersoff_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "tersoff", "ts_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "tersoff_params.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", so] + srcs)
-    L = C.CDLL(so)
+def driver_lib():
+    L = C.CDLL(hostdrv.build("libtersoff_host.so", ["tests/tersoff_host_driver.cpp", "scema_amd/csrc/host/tersoff_params.cpp"], shared=True))
     L.tsh_create.restype = C.c_void_p
     L.tsh_create.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]
     L.tsh_destroy.argtypes = [C.c_void_p]
@@ -85,7 +78,7 @@ class Driver:
 
 @pytest.fixture(scope="module")
 def lib():
-    return _build_driver()
+    return driver_lib()
 
 
 @pytest.fixture(scope="module")
@@ -98,7 +91,7 @@ def synth_files(tmp_path_factory):
 
 # name -> (file, elements, case): every static input of the CPU tests.  "sic_cs" names the elements in the other order (types swapped
 # with them: the same crystal)
-def _inputs(synth_files):
+def inputs(synth_files):
     sic = tsn.case_sic()
     return {
         "dimer": (SIC, ["Si"], tsn.case_dimer()),
@@ -123,14 +116,14 @@ NAMES = ["dimer", "trimer", "cell8", "a", "scaled", "gas1", "triclinic", "carbon
 def refs(lib, synth_files):
     """per input: (numpy object, driver, case, numpy result, driver result), each computed once"""
     out = {}
-    for name, (path, el, case) in _inputs(synth_files).items():
+    for name, (path, el, case) in inputs(synth_files).items():
         ref = tsn.Tersoff(tsn.read_tersoff(path, el)[0])
         drv = Driver(lib, path, el)
         out[name] = (ref, drv, case, ref.compute(*case), drv(*case))
     return out
 
 
-def _same(got, ref, tol=1e-12):
+def same(got, ref, tol=1e-12):
     assert got["npairs"] == ref["npairs"] and got["nzeta"] == ref["nzeta"], (got["npairs"], ref["npairs"], got["nzeta"], ref["nzeta"])
     fs = max(np.abs(ref["f"]).max(), 1e-300)
     assert np.abs(got["f"] - ref["f"]).max() <= tol * fs, np.abs(got["f"] - ref["f"]).max() / fs
@@ -142,7 +135,7 @@ def _same(got, ref, tol=1e-12):
 @pytest.mark.parametrize("name", NAMES)
 def test_static_cases_match_numpy(refs, name):
     ref_ts, drv, case, ref, got = refs[name]
-    _same(got, ref)
+    same(got, ref)
     assert abs(ref["f"].sum(axis=0)).max() < 1e-10 * np.abs(ref["f"]).max()
     if name == "scaled":
         assert ref["maxin"] == 16 and ref["npairs"] == 64 * 16 and ref["nshell"] == 384
@@ -153,7 +146,7 @@ def test_static_cases_match_numpy(refs, name):
     if name == "clamp":          # both clamps and the large-zeta end of b are reached
         assert got["t"].max() > 1e20
     if name == "sic_cs":         # the same crystal under the other element order: the same numbers
-        _same(got, refs["sic"][3], tol=1e-13)
+        same(got, refs["sic"][3], tol=1e-13)
 
 
 def test_energy_loop_equals_compute(refs):
@@ -295,7 +288,7 @@ def test_wrong_builds_are_caught(lib, refs, synth_files):
     """the wrong builds of the module docstring fail where it says"""
     def fails(drv, name):
         try:
-            _same(drv(*refs[name][2]), refs[name][3])
+            same(drv(*refs[name][2]), refs[name][3])
         except AssertionError:
             return True
         return False

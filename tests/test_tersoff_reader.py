@@ -9,7 +9,7 @@ import pytest
 
 import tersoff_numpy as tsn
 from scema_amd import capi
-from test_tersoff_host import _build_driver
+from test_tersoff_host import driver_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIC = os.path.join(ROOT, "tests", "golden", "SiC.tersoff")
@@ -70,7 +70,7 @@ def test_comments_and_wrapped_entries(tmp_path):
 
 def test_which_entry_feeds_which_table_slot(tmp_path):
     """pair [i][j]: A B lambda1 lambda2 beta n R D of entry i j j; triplet [i][j][k]: gamma lambda3 c d costheta0 m AND R D of entry i j k"""
-    L = _build_driver()
+    L = driver_lib()
     L.tsh_create.restype = C.c_void_p
     # a file in which every number of every entry is distinct: entry number e (1-based) field f holds e + f / 100 (m stays 1 or 3)
     names = [(a, b, c) for a in "PQ" for b in "PQ" for c in "PQ"]

@@ -19,28 +19,23 @@ Wrong builds of the driver (-DVSH_WRONG=k, switches of the driver, not of the pr
   4  the pair energy in full at both ends .......... every case with a pair (energy only: forces and virial are not doubled)
   5  1 + C dc^2 missing from the derivative ........ the trimer (C = 5), jittered lattices; the perfect 8-atom cell passes (dc = 0)
 """
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import hostdrv
 import vashishta_numpy as vn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIC = os.path.join(ROOT, "tests", "golden", "SiC.vashishta")
 
 
-def _build_driver(wrong=0):
-    out = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, f"vashishta_host_driver_{wrong}")
-    srcs = [os.path.join(ROOT, "tests", "vashishta_host_driver.cpp"), os.path.join(ROOT, "scema_amd", "csrc", "host", "vashishta_params.cpp")]
-    deps = srcs + [os.path.join(ROOT, "scema_amd", "csrc", "vashishta", "vs_core.h"), os.path.join(ROOT, "scema_amd", "csrc", "host", "vashishta_params.h"),
-                   os.path.join(ROOT, "scema_amd", "csrc", "host", "triplet_file.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", f"-DVSH_WRONG={wrong}", "-I", os.path.join(ROOT, "include"), "-o", exe] + srcs)
-    return exe
+def driver_exe(wrong=0):
+    return hostdrv.build(f"vashishta_host_driver_{wrong}", ["tests/vashishta_host_driver.cpp", "scema_amd/csrc/host/vashishta_params.cpp"], shared=False,
+                         defines=(f"VSH_WRONG={wrong}",))
 
 
 def _run(exe, path, elements, x, box, types, energy_unit=0):
@@ -83,7 +78,7 @@ def _inputs(synth_file):
 @pytest.fixture(scope="module")
 def refs(synth_file):
     """per input: (numpy object, file, elements, case, numpy result, driver result), each computed once"""
-    exe = _build_driver()
+    exe = driver_exe()
     out = {}
     for name, (path, el, case) in _inputs(synth_file).items():
         p, _, K = vn.read_vashishta(path, el)
@@ -92,22 +87,9 @@ def refs(synth_file):
     return out
 
 
-def _mismatch(got, ref, tol=1e-12, scale=None):
-    """what differs beyond tol, relative to the largest force component, energy term and virial component of ref, or of `scale` (the
-    perfect cell, whose forces and virial cancel, is measured on its jittered twin)"""
-    bad = []
-    scale = scale or ref
-    if (got["npairs"], got["ntriplets"], got["maxin"]) != (ref["npairs"], ref["ntriplets"], ref["maxin"]):
-        bad.append("counts")
-    fs = max(np.abs(scale["f"]).max(), 1e-300)
-    if not np.abs(got["f"] - ref["f"]).max() <= tol * fs:
-        bad.append("forces")
-    es = max(abs(ref["e2"]), abs(ref["e3"]), 1e-300)
-    if not (abs(got["e2"] - ref["e2"]) <= tol * es and abs(got["e3"] - ref["e3"]) <= tol * es):
-        bad.append("energy")
-    if not np.abs(got["w"] - ref["w"]).max() <= tol * max(np.abs(scale["w"]).max(), 1e-300):
-        bad.append("virial")
-    return bad
+# what differs beyond 1e-12 of the largest force component, energy term and virial component of ref, or, forces and virial, of `scale` (the
+# perfect cell, whose forces and virial cancel, is measured on its jittered twin)
+mismatch = functools.partial(hostdrv.mismatch, counters=("npairs", "ntriplets", "maxin"), energies=("e2", "e3"), tol=1e-12)
 
 
 NAMES = [f"dimer_{p}_{r}" for p in PAIRS for r in ("inside_r0", "between", "next_to_rc")] + ["trimer_r0", "trimer", "cell8", "cell8j", "jitter64", "jitter216", "synth"]
@@ -118,7 +100,7 @@ def test_static_cases_match_numpy(refs, name):
     _, _, _, case, ref, got = refs[name]
     assert np.isfinite(got["f"]).all() and np.isfinite(got["w"]).all() and np.isfinite(got["e"])
     scale = refs["cell8j"][4] if name == "cell8" else ref
-    assert _mismatch(got, ref, scale=scale) == [], _mismatch(got, ref, scale=scale)
+    assert mismatch(got, ref, scale=scale) == [], mismatch(got, ref, scale=scale)
     assert abs(ref["f"].sum(axis=0)).max() <= 1e-10 * max(np.abs(scale["f"]).max(), 1e-300)
     if name in ("cell8", "cell8j"):
         assert (ref["maxin"], ref["npairs"], ref["ntriplets"], ref["maxrc"]) == (4, 8 * 158, 8 * 6, 158)
@@ -172,7 +154,7 @@ def test_pair_term_vanishes_at_its_cutoff(refs, pair):
     """E2 and its force go to 0 at rc (1 - 1e-12); at and beyond rc they are exactly 0 and the pair is not counted (numpy and driver)"""
     ref_vs = refs["cell8"][0]
     a, b = PAIRS[pair]
-    exe = _build_driver()
+    exe = driver_exe()
     e, de = ref_vs.e2(a, b, np.array([vn.RC_SIC * (1.0 - 1e-12)]))
     scale = abs(ref_vs.e2(a, b, np.array([4.0]))[0][0])
     assert abs(e[0]) <= 1e-12 * scale and abs(de[0]) <= 1e-9 * scale
@@ -191,8 +173,8 @@ def test_both_energy_units(refs, tmp_path):
     _, _, _, case, ref, _ = refs["jitter64"]
     p, _, K = vn.read_vashishta(SIC, ["Si", "C"], energy_unit=1)
     assert K == vn.K_KCALMOL and p[(0, 1, 1)]["H"] == 447.09026
-    got = _run(_build_driver(), SIC, ["Si", "C"], *case, energy_unit=1)
-    assert _mismatch(got, vn.Vashishta(p, K).compute(*case)) == []
+    got = _run(driver_exe(), SIC, ["Si", "C"], *case, energy_unit=1)
+    assert mismatch(got, vn.Vashishta(p, K).compute(*case)) == []
     assert abs(got["e"] - ref["e"]) > 1e-2 * abs(ref["e"])
 
 
@@ -203,12 +185,12 @@ PASSES = {2: "jitter64", 5: "cell8"}      # what a wrong build still passes: why
 
 @pytest.mark.parametrize("wrong", sorted(WRONG))
 def test_wrong_builds_are_caught(refs, wrong):
-    exe = _build_driver(wrong)
+    exe = driver_exe(wrong)
     name, what = WRONG[wrong]
     _, path, el, case, ref, _ = refs[name]
-    bad = _mismatch(_run(exe, path, el, *case), ref)
+    bad = mismatch(_run(exe, path, el, *case), ref)
     print(f"wrong build {wrong} on {name}: {bad}")
     assert bad and (what is None or bad == what)
     if wrong in PASSES:
         _, path, el, case, ref, _ = refs[PASSES[wrong]]
-        assert _mismatch(_run(exe, path, el, *case), ref, scale=refs["cell8j"][4] if PASSES[wrong] == "cell8" else None) == []
+        assert mismatch(_run(exe, path, el, *case), ref, scale=refs["cell8j"][4] if PASSES[wrong] == "cell8" else None) == []

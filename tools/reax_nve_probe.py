@@ -4,15 +4,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from scema_amd import capi
-from test_reax_host import _mixture, _pe_cell
+from test_reax_host import case_mixture, case_pe_cell
 from test_oracle_reax import FFIELD
 MVV2E = 48.88821291 ** 2
 masses = dict(H=1.008, C=12.011, N=14.007, O=15.999)
 which = sys.argv[1] if len(sys.argv) > 1 else "mix"
 if which == "mix":
-    sym, x, box = _mixture(seed=8)
+    sym, x, box = case_mixture(seed=8)
 else:
-    sym, x, box = _pe_cell(None, amp=0.02)
+    sym, x, box = case_pe_cell(None, amp=0.02)
 n = len(sym)
 m = np.array([masses[s] for s in sym])
 v = np.random.default_rng(0).standard_normal((n, 3)) * np.sqrt(0.0019872067 * 300.0 / (m[:, None] * MVV2E))
