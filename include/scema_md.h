@@ -368,6 +368,15 @@ int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes);
  * mean charged atoms per grid point; -1 keeps.  SCEMA_MD_PPPM_BINNED=0/1 in the environment forces 0 / 1 whatever is set here.  Results do
  * not depend on it beyond the order of summation. */
 int scema_md_pppm_binning(scema_md_engine *e, int32_t mode);
+/* LDS layout of the staged interpolation kernel (k_pppm_force with the three field grids of a replica in LDS).  mode 0: the dense layout,
+ * plane stride nx ny; 1: the plane stride of the rule in csrc/md_pppm_fstride.h, which keeps the stencil points of neighbouring atoms off
+ * each other's LDS banks (dense where the padded copy does not fit the LDS budget, would cost a resident workgroup, or the mesh has a
+ * dimension of five points or fewer) and 512 instead of 256 threads per workgroup; -1: the default, which is 1.  SCEMA_MD_PPPM_FLAYOUT=0/1 in the environment forces 0 / 1 whatever is
+ * set here.  Only where a field point lies in LDS changes; the arithmetic of an atom, and with it every result, is the same in both. */
+int scema_md_pppm_force_layout(scema_md_engine *e, int32_t mode);
+/* the rule's answer for a mesh and an LDS budget in bytes (0: the device limit): out[3] = {row stride, plane stride (doubles), LDS bytes of
+ * the three staged fields}.  A pure host function (no GPU). */
+int scema_md_pppm_force_strides(const int32_t grid[3], int32_t lds_bytes, int32_t out[3]);
 /* spreading launches of this engine that took the binned kernels so far (a test reads this), or a negative error code */
 long long scema_md_pppm_binned_launches(const scema_md_engine *e);
 /* out[8], for the last PPPM launch group: {charge assignment: 0 whole mesh in LDS, 1 tiled, 2 global atomics; interpolation: 0 staged, 1 tiled,

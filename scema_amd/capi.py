@@ -36,7 +36,7 @@ SYMBOLS = [
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
-    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_binning", "scema_md_pppm_binned_launches", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
+    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_binning", "scema_md_pppm_force_layout", "scema_md_pppm_force_strides", "scema_md_pppm_binned_launches", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
     "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
     "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
@@ -490,6 +490,10 @@ class Engine:
     def pppm_binning(self, mode: int = -1):
         """binned charge assignment: 0 off, 1 on for every eligible launch, 2 (default) by the launch policy; -1 keeps"""
         self._chk(lib().scema_md_pppm_binning(self.h, C.c_int32(mode)))
+
+    def pppm_force_layout(self, mode: int = -1):
+        """LDS layout of the staged interpolation kernel: 0 dense, 1 the stride rule of md_pppm_fstride.h, -1 the default (the rule)"""
+        self._chk(lib().scema_md_pppm_force_layout(self.h, C.c_int32(mode)))
 
     def pppm_binned_launches(self) -> int:
         """spreading launches that took the binned kernels so far"""
@@ -993,6 +997,19 @@ def pppm_tile_shape(grid, lds_bytes: int = 0, which: int = 0):
     rc = L.scema_md_pppm_tile_shape(g, C.c_int32(lds_bytes), C.c_int32(which), out)
     if rc != 0:
         raise EngineError(f"scema_md_pppm_tile_shape rc={rc}")
+    return tuple(int(v) for v in out)
+
+
+def pppm_force_strides(grid, lds_bytes: int = 0):
+    """(row stride, plane stride, LDS bytes) of the staged interpolation kernel's field copy for this mesh and LDS budget (0: device
+    default) by the rule of md_pppm_fstride.h.  scema_md_pppm_force_strides, a pure host function (no GPU)"""
+    L = lib()
+    L.scema_md_pppm_force_strides.restype = C.c_int
+    g = (C.c_int32 * 3)(*[int(n) for n in grid])
+    out = (C.c_int32 * 3)()
+    rc = L.scema_md_pppm_force_strides(g, C.c_int32(lds_bytes), out)
+    if rc != 0:
+        raise EngineError(f"scema_md_pppm_force_strides rc={rc}")
     return tuple(int(v) for v in out)
 
 

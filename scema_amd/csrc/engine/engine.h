@@ -54,6 +54,7 @@
 #include "md_equil.h"
 #include "md_pppm.h"
 #include "md_pppm_tile.h"
+#include "md_pppm_fstride.h"
 #include "md_reax.h"
 #include "md_sw.h"
 #include "md_eam.h"
@@ -389,6 +390,7 @@ struct scema_md_engine {
   int pppm_tile_mode = 1, pppm_lds_bytes = 0;   // scema_md_pppm_tiling: tiled kernels for meshes beyond the LDS; forced LDS budget (0: mdk_pppm_lds_limit())
   int pppm_paths[8] = {0, 0, 0, 0, 0, 0, 0, 1}; // scema_md_pppm_paths: what the last PPPM launch group took
   int pppm_bin_mode = 2;                        // scema_md_pppm_binning: binned charge assignment 0 off, 1 wherever eligible, 2 by the launch policy (PppmBinPolicy)
+  int pppm_flayout_mode = 1;                    // scema_md_pppm_force_layout: staged interpolation 0 the dense LDS layout, 1 the strides of md_pppm_fstride.h
   long long pppm_binned_launches = 0;           // scema_md_pppm_binned_launches: spreading launches that took the binned kernels
   std::map<std::array<int, 6>, hipfftHandle> pppm_plans;   // (nx, ny, nz, batch, stream, distance between grids) -> batched 3-d Z2Z plan
   std::vector<int> h_kpack;   // host copy, alive until the stream has consumed the upload

@@ -55,6 +55,8 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_PPPM_SOLVE_WIDE", "1 / 0: the in-LDS PPPM solve with 1 024 threads and three LDS grids / 512 threads and two (default: by batch size)"},
     {"SCEMA_MD_PPPM_SOLVE_TWO", "0 / 1: the in-LDS PPPM solve of the 1 024-thread shape as one / two workgroups per replica, one per transform back (default: two for batches under 8 replicas)"},
     {"SCEMA_MD_PPPM_PADX", "0: the LDS grid of the PPPM spreading kernel without the five pad points per x row (an address addition per stencil point instead of a constant offset)"},
+    {"SCEMA_MD_PPPM_FLAYOUT", "0 / 1: the staged interpolation kernel keeps its field grids in LDS densely / at the plane stride of md_pppm_fstride.h (default: the stride rule)"},
+    {"SCEMA_MD_PPPM_FTPB", "256 / 512: threads per workgroup of the staged interpolation kernel (default: 512 with the strided layout, 256 with the dense one)"},
     {"SCEMA_MD_PPPM_BINNED", "0 / 1: the charge assignment of meshes kept whole in LDS never / wherever eligible as k_pppm_bins + k_pppm_spread_binned, atoms grouped by nearest grid point (default: by launch size and atoms per grid point)"},
     {"SCEMA_MD_PPPM_FFT", "hipFFT for every PPPM grid (default: grids of up to 2 900 points are solved in LDS)"},
     {"SCEMA_MD_FUSED_TAIL", "0 / 1: force assembly + SHAKE + second kick as three kernels / as k_finish (default: by batch size)"},

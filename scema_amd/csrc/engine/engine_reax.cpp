@@ -439,6 +439,19 @@ int scema_md_pppm_binning(scema_md_engine *e, int32_t mode) {
   if (mode >= 0) e->pppm_bin_mode = mode;
   return SCEMA_MD_OK;
 }
+int scema_md_pppm_force_layout(scema_md_engine *e, int32_t mode) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (mode < -1 || mode > 1) return fail(e, SCEMA_MD_ERR_ARG, "scema_md_pppm_force_layout: mode %d (0 the dense layout, 1 the stride rule, -1 the default)", mode);
+  e->pppm_flayout_mode = mode < 0 ? 1 : mode;
+  return SCEMA_MD_OK;
+}
+int scema_md_pppm_force_strides(const int32_t grid[3], int32_t lds_bytes, int32_t out[3]) {
+  if (!grid || !out || grid[0] < 1 || grid[1] < 1 || grid[2] < 1 || lds_bytes < 0) return SCEMA_MD_ERR_ARG;
+  const PppmFStride fs = pppm_fstride(grid[0], grid[1], grid[2], lds_bytes > 0 ? lds_bytes : (long long)mdk_pppm_lds_limit());
+  if (fs.bytes > INT32_MAX) return SCEMA_MD_ERR_ARG;
+  out[0] = fs.rs; out[1] = fs.ps; out[2] = (int32_t)fs.bytes;
+  return SCEMA_MD_OK;
+}
 long long scema_md_pppm_binned_launches(const scema_md_engine *e) { return e ? e->pppm_binned_launches : -(long long)SCEMA_MD_ERR_ARG; }
 int scema_md_pppm_paths(const scema_md_engine *e, int32_t out[8]) {
   if (!e || !out) return SCEMA_MD_ERR_ARG;

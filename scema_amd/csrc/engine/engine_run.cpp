@@ -428,6 +428,7 @@ int OplsRun::lay_out_sim(int pos) {
     if (S.pg[0] < 5) L.padx_ok = false;
     L.sum_charged += T.ncharged; L.sum_grid += (long long)S.pg[0] * S.pg[1] * S.pg[2];
     L.maxgridp = std::max(L.maxgridp, (S.pg[0] + 5) * S.pg[1] * S.pg[2]);
+    L.tl.fs_lds = std::max(L.tl.fs_lds, (size_t)pppm_fstride(S.pg[0], S.pg[1], S.pg[2], L.tl.budget).bytes);   // (the staged interpolation's padded copy)
     for (int which = 0; which < 2; which++) {
       const PppmTile t = pppm_tile_shape(S.pg[0], S.pg[1], S.pg[2], L.tl.budget, which);
       bool &fits = which ? L.tl_fo_fits : L.tl_sp_fits;
@@ -623,13 +624,18 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
     tl.binned = bin_mode == 1 || (na >= bp.min_replicas && (double)L.sum_charged >= bp.min_per_point * (double)L.sum_grid) ? 1 : 0;
   }
   if (tl.binned) e->pppm_binned_launches += 1;
+  // Staged interpolation: the field grids at the plane stride of md_pppm_fstride.h (SCEMA_MD_PPPM_FLAYOUT and scema_md_pppm_force_layout
+  // force the dense layout or the rule; the default is the rule at every launch size: profiles/pppm_fstride_size_scan.log)
+  static const int flayout_env = scema_env("SCEMA_MD_PPPM_FLAYOUT") ? (atoi(scema_env("SCEMA_MD_PPPM_FLAYOUT")) != 0 ? 1 : 0) : -1;
+  PppmLaunch tlf = L.tl;
+  if ((flayout_env >= 0 ? flayout_env : e->pppm_flayout_mode) == 0) tlf.fs_lds = 0;
   mdk_pppm_spread(st, Dp, na, L.maxgrid, L.maxatoms, clean ? 1 : 0, maxgridp, &tl);   // (the tiled kernel stores every point: no zero launch)
   clean = false;
   if (pol.pppm_in_lds) {   // small grids: the whole solve in one launch, in LDS (md_pppm.hip k_pppm_solve); it leaves the charge grids zeroed
     if (new_box) mdk_pppm_gf(st, Dp, na, L.maxgrid);
     mdk_pppm_solve(st, Dp, na, L.maxgrid, L.maxdims);
     clean = true;
-    mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 1, &L.tl);
+    mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 1, &tlf);
     return SCEMA_MD_OK;
   }
   auto transform = [&](bool fields, int dir) -> int {   // the charge grids forward, or the three field grids of every simulation back
@@ -651,7 +657,7 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
   if (new_box) mdk_pppm_gf(st, Dp, na, L.maxgrid);
   mdk_pppm_poisson(st, Dp, na, L.maxgrid);
   if ((rc = transform(true, HIPFFT_BACKWARD))) return rc;
-  mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 0, &L.tl);
+  mdk_pppm_force(st, Dp, na, L.maxgrid, L.maxatoms, add, 0, &tlf);
   return SCEMA_MD_OK;
 }
 

@@ -13,6 +13,9 @@ struct PppmLaunch {
   int sp_ty = 0, sp_tz = 0, sp_tiles = 0, fo_ty = 0, fo_tz = 0, fo_tiles = 0;
   size_t sp_lds = 0, fo_lds = 0;
   int binned = 0;   // this launch: the binned pair of spreading kernels where mdk_pppm_binned_ok (the engine decides: pppm_stage)
+  // staged interpolation (force path 0): the largest LDS size of the batch's meshes in the layout of md_pppm_fstride.h, by pppm_fstride at
+  // this budget -- the largest PADDED size, not the size of the largest mesh; 0: every replica keeps the dense layout (scema_md_pppm_force_layout)
+  size_t fs_lds = 0;
 };
 // Binned charge assignment (k_pppm_bins + k_pppm_spread_binned): from how many replicas per launch, and from how many charged atoms per
 // grid point in the mean, the pair of launches is taken when nothing forces it (scema_md_pppm_binning mode 2).  k_pppm_bins is one more

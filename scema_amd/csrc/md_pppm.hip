@@ -19,6 +19,7 @@
 #include "md_device.h"
 #include "md_env.h"
 #include "md_pppm.h"
+#include "md_pppm_fstride.h"
 #include "md_pppm_tile.h"
 #include "md_types.h"
 
@@ -668,8 +669,10 @@ __global__ __launch_bounds__(PP_SOLVE_TPB) void k_pppm_solve(const SimDev *sims)
 // (consecutive atoms in consecutive lanes: neighbours read the same grid points, which the LDS broadcasts); LDS = false reads
 // the grids through the caches.
 // REALF: the fields are three real arrays at a spacing of gs doubles (written by k_pppm_solve) instead of the real parts of three complex grids
-template <bool LDS, bool REALF = false>
-__global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int split, int add) {
+// LDS layout (md_pppm_fstride.h): point (gx, gy, gz) of field f at f * ps * nz + gz * ps + gy * rs + gx; fs_budget > 0: the strides of
+// pppm_fstride for the mesh of the replica where they fit the fs_lds bytes of the launch, else (and with fs_budget == 0) the dense ones
+template <bool LDS, bool REALF = false, int TPB_ = 256>
+__global__ __launch_bounds__(TPB_) void k_pppm_force(const SimDev *sims, int split, int add, int fs_budget, int fs_lds) {
   const SimDev &S = sims[blockIdx.y];
   const int nx = S.pg[0], ny = S.pg[1], nz = S.pg[2];
   if (nx == 0) return;
@@ -680,19 +683,40 @@ __global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int spli
   if (a0 >= a1) return;
   const size_t gs = (size_t)S.pgstride;
   const double2 *ex = (const double2 *)S.pfield, *ey = ex + gs, *ez = ey + gs;
+  int rs = nx, ps = nx * ny;
+  if (LDS && fs_budget > 0) {
+    const PppmFStride fs = pppm_fstride(nx, ny, nz, fs_budget);
+    if (fs.bytes <= (long long)fs_lds) { rs = fs.rs; ps = fs.ps; }
+  }
+  const int FS = ps * nz;   // doubles of one staged field
   if (LDS) {
-    if (REALF) {
-      const double *fr = (const double *)S.pfield;
-      for (int k = threadIdx.x; k < NG; k += 256) { s_grid[k] = fr[k]; s_grid[NG + k] = fr[gs + k]; s_grid[2 * NG + k] = fr[2 * gs + k]; }
+    // point k of the mesh goes to k + (its plane) * (pad of a plane): the plane is followed from turn to turn instead of divided out
+    // (rows stay dense in every layout of the rule; a padded row takes the general form)
+    const int plane = nx * ny, padz = ps - plane;
+    if (rs == nx) {
+      const int qz = TPB_ / plane, rz = TPB_ - qz * plane;
+      int z = (int)threadIdx.x / plane, r = (int)threadIdx.x - z * plane;
+      for (int k = threadIdx.x; k < NG; k += TPB_) {
+        const int g = k + z * padz;
+        if (REALF) { const double *fr = (const double *)S.pfield; s_grid[g] = fr[k]; s_grid[FS + g] = fr[gs + k]; s_grid[2 * FS + g] = fr[2 * gs + k]; }
+        else { s_grid[g] = ex[k].x; s_grid[FS + g] = ey[k].x; s_grid[2 * FS + g] = ez[k].x; }
+        z += qz; r += rz;
+        if (r >= plane) { r -= plane; z += 1; }
+      }
     } else {
-      for (int k = threadIdx.x; k < NG; k += 256) { s_grid[k] = ex[k].x; s_grid[NG + k] = ey[k].x; s_grid[2 * NG + k] = ez[k].x; }
+      for (int k = threadIdx.x; k < NG; k += TPB_) {
+        const int z = k / plane, yx = k - z * plane, y = yx / nx;
+        const int g = z * ps + y * rs + (yx - y * nx);
+        if (REALF) { const double *fr = (const double *)S.pfield; s_grid[g] = fr[k]; s_grid[FS + g] = fr[gs + k]; s_grid[2 * FS + g] = fr[2 * gs + k]; }
+        else { s_grid[g] = ex[k].x; s_grid[FS + g] = ey[k].x; s_grid[2 * FS + g] = ez[k].x; }
+      }
     }
     __syncthreads();
   }
   BoxD b;
   box_derive(S.sc->box, b);
   box_uniform(b);
-  for (int a = a0 + (int)threadIdx.x; a < a1; a += 256) {
+  for (int a = a0 + (int)threadIdx.x; a < a1; a += TPB_) {
     const double qa = S.q[a];
     if (qa == 0.0) {
       if (!add) { S.f[3 * a] = 0.0; S.f[3 * a + 1] = 0.0; S.f[3 * a + 2] = 0.0; }
@@ -711,12 +735,12 @@ __global__ __launch_bounds__(256) void k_pppm_force(const SimDev *sims, int spli
 #pragma unroll
       for (int bb = 0; bb < PP_ORDER; bb++) {
         const double zy = wz[c] * wy[bb];
-        const int row = (gz[c] * ny + gy[bb]) * nx;
+        const int row = LDS ? gz[c] * ps + gy[bb] * rs : (gz[c] * ny + gy[bb]) * nx;
         double rx = 0.0, ry = 0.0, rz = 0.0;
 #pragma unroll
         for (int k = 0; k < PP_ORDER; k++) {
           const int g = row + gx[k];
-          if (LDS) { rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[NG + g], ry); rz = fma(wx[k], s_grid[2 * NG + g], rz); }
+          if (LDS) { rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[FS + g], ry); rz = fma(wx[k], s_grid[2 * FS + g], rz); }
           else if (REALF) { const double *fr = (const double *)S.pfield; rx = fma(wx[k], fr[g], rx); ry = fma(wx[k], fr[gs + g], ry); rz = fma(wx[k], fr[2 * gs + g], rz); }
           else { rx = fma(wx[k], ex[g].x, rx); ry = fma(wx[k], ey[g].x, ry); rz = fma(wx[k], ez[g].x, rz); }
         }
@@ -1031,7 +1055,7 @@ void mdk_pppm_solve(hipStream_t st, const SimDev *d, int ns, int maxgrid, int ma
 void mdk_pppm_gf(hipStream_t st, const SimDev *d, int ns, int maxgrid) { hipLaunchKernelGGL(k_pppm_gf, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d); }
 void mdk_pppm_poisson(hipStream_t st, const SimDev *d, int ns, int maxgrid) { hipLaunchKernelGGL(k_pppm_poisson, grid2(cdiv(maxgrid, 256), ns), dim3(256), 0, st, d); }
 int mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int maxatoms, int add, int real_fields, const PppmLaunch *tl) {
-  const size_t lds = 3 * (size_t)maxgrid * sizeof(double);
+  size_t lds = 3 * (size_t)maxgrid * sizeof(double);
   const int path = mdk_pppm_force_path(maxgrid, tl);
   if (path == 1) {   // the field grids over a brick and its halo in LDS, every atom served by its home tile (keys: mdk_pppm_keys)
     const size_t tlds = tl->fo_lds;
@@ -1055,19 +1079,33 @@ int mdk_pppm_force(hipStream_t st, const SimDev *d, int ns, int maxgrid, int max
   }
   if (path == 2) {
     // (real field arrays without LDS: only under a forced budget -- a mesh of the in-LDS solve always fits the device's)
-    if (real_fields) hipLaunchKernelGGL((k_pppm_force<false, true>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add);
-    else hipLaunchKernelGGL((k_pppm_force<false, false>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add);
+    if (real_fields) hipLaunchKernelGGL((k_pppm_force<false, true>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add, 0, 0);
+    else hipLaunchKernelGGL((k_pppm_force<false, false>), grid2(cdiv(maxatoms, 256), ns), dim3(256), 0, st, d, cdiv(maxatoms, 256), add, 0, 0);
     return path;
   }
+  // the staged copy in the layout of md_pppm_fstride.h: the launch takes the largest padded size of its meshes (PppmLaunch::fs_lds, by
+  // the same rule and budget the kernel evaluates per replica); without it every replica keeps the dense layout
+  const int fs_budget = tl && tl->fs_lds >= lds && tl->fs_lds <= pppm_budget(tl) ? (int)pppm_budget(tl) : 0;
+  if (fs_budget > 0) lds = tl->fs_lds;
   static size_t optin_tab[16] = {0};
   size_t &optin = lds_optin_slot(optin_tab);
   if (lds > 64 * 1024 && lds > optin) {
     (void)hipFuncSetAttribute((const void *)k_pppm_force<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void *)k_pppm_force<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void *)k_pppm_force<true, false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void *)k_pppm_force<true, true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     optin = lds;
   }
   const int split = pppm_split(ns, maxatoms);
-  if (real_fields) hipLaunchKernelGGL((k_pppm_force<true, true>), grid2(split, ns), dim3(256), lds, st, d, split, add);
-  else hipLaunchKernelGGL((k_pppm_force<true, false>), grid2(split, ns), dim3(256), lds, st, d, split, add);
+  // Block size: 512 threads with the strided layout, the parent's 256 with the dense one (SCEMA_MD_PPPM_FTPB forces either).  At 95
+  // registers 256 threads are 3 x 4 waves per CU beside three 41 KB copies, 512 threads 2 x 8; the kernel gains from the fourth wave per
+  // SIMD only once its reads no longer queue on the banks (576 x PE-10k: dense 432 / 426 us per step at 256 / 512 threads, strided 352 / 325)
+  static const int ftpb_env = scema_env("SCEMA_MD_PPPM_FTPB") ? atoi(scema_env("SCEMA_MD_PPPM_FTPB")) : 0;
+  const int tpb = ftpb_env == 256 || ftpb_env == 512 ? ftpb_env : (fs_budget > 0 ? 512 : 256);
+  const dim3 g = grid2(split, ns);
+#define PP_FORCE_LAUNCH(R, T) hipLaunchKernelGGL((k_pppm_force<true, R, T>), g, dim3(T), lds, st, d, split, add, fs_budget, (int)lds)
+  if (tpb == 512) { if (real_fields) PP_FORCE_LAUNCH(true, 512); else PP_FORCE_LAUNCH(false, 512); }
+  else { if (real_fields) PP_FORCE_LAUNCH(true, 256); else PP_FORCE_LAUNCH(false, 256); }
+#undef PP_FORCE_LAUNCH
   return path;
 }
