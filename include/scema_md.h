@@ -689,14 +689,17 @@ int scema_md_born_dsf_read_params(const char *path, int32_t energy_unit, int32_t
 int scema_md_born_dsf_eval(const char *path, int32_t energy_unit, int32_t ti, int32_t tj, double qi, double qj, const double *r, int32_t n, double *out,
                            double *e_self, char *errbuf, int32_t errcap);
 
-/* ---- ionic replicas with an Ewald sum (`pair_style born/coul/long`, `pair_style buck/coul/long`, `kspace_style ewald <accuracy>`) ----
+/* ---- ionic replicas with an Ewald sum or a PPPM mesh (`pair_style born/coul/long`, `pair_style buck/coul/long`, `kspace_style
+ * ewald|pppm <accuracy>`) ----
  * The form ionic models are fitted with: the Born-Mayer-Huggins term of born/coul/dsf and the Coulomb sum split by Ewald's method, the
- * reciprocal part summed plainly over a k list (row replicas are small: 512 ions of rock salt at 1e-5 need 709 k-vectors).  `path` is any
+ * reciprocal part summed plainly over a k list where the list fits (512 ions of rock salt at 1e-5 need 709 k-vectors) and on a PPPM
+ * mesh beyond it (scema_md_born_long_kspace below).  `path` is any
  * text file that holds the script lines themselves (in.strain.lammps included):
  *   pair_style born/coul/long <cut_lj> [<cut_coul>]   with   pair_coeff I J A rho sigma C D [cut_lj]
  *   pair_style buck/coul/long <cut_lj> [<cut_coul>]   with   pair_coeff I J A rho C [cut_lj]          (sigma = 0, D = 0 of the same table)
  *   kspace_style ewald|pppm <accuracy>                (required; `pppm` is honoured as the Ewald sum at that accuracy, the sum PPPM
- *                                                      approximates; a kspace_modify line is refused: none of its options is honoured)
+ *                                                      approximates, where the k list fits, and runs on the mesh beyond it; a
+ *                                                      kspace_modify line is refused: none of its options is honoured)
  *   units real|metal                                  (optional; must not contradict energy_unit)
  * Types, `*`, energy_unit, K, skin and the rules of attachment are those of scema_md_born_dsf_configure.  The form:
  *   E_born  = A exp((sigma - r)/rho) - C/r^6 + D/r^8                         r < cut_lj[ti][tj], not shifted
@@ -707,14 +710,25 @@ int scema_md_born_dsf_eval(const char *path, int32_t energy_unit, int32_t ti, in
  * background term included, which LAMMPS leaves out of its virial).  g_ewald and the triples are set up per run from the run's start box,
  * the material's cut_coul and accuracy and the replica's charges, by the rule of `kspace_style ewald` (g from the accuracy, a kmax search
  * per dimension, the Cartesian sphere); the triples stay over the run while fix deform moves the box, and a box flip re-expresses them.
- * A replica whose list exceeds 4096 k-vectors, or an index of 20, is refused with SCEMA_MD_ERR_ARG (PPPM on the row driver is the
- * follow-up).  Forces repeat bit for bit.  A charged topology-free replica with nothing attached configures itself from a
+ * A replica whose list exceeds 4096 k-vectors, or an index of 20, is refused with SCEMA_MD_ERR_ARG under `kspace_style ewald` and runs
+ * on the mesh under `kspace_style pppm` (scema_md_born_long_kspace).  Forces repeat bit for bit on either solver.  A charged topology-free replica with nothing attached configures itself from a
  * `pair_style born/coul/long` or `buck/coul/long` line of <scripts_folder>/in.strain.lammps, after the born/coul/dsf search. */
 int scema_md_born_long_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin);
 /* static evaluation: f [natoms*3], e_born, e_coul (real space, reciprocal space, self and background; kcal/mol), virial[6]
  * (xx,yy,zz,xy,xz,yz), info[6]: the four numbers of scema_md_born_dsf_debug_compute, then the k-vectors of the half space and g_ewald */
 int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
                                      double *virial, double *info);
+/* Which reciprocal solver the replicas of a Born/long material get, decided per replica and run.  mode 0 (the default): the Ewald sum
+ * wherever its k list fits, whatever the script's solver word; beyond the limits a `kspace_style ewald` script is refused and a
+ * `kspace_style pppm` script runs on the mesh.  mode 1: the mesh for every replica.  mode 2: the Ewald sum, refused beyond its limits.
+ * The mesh is PPPM as LAMMPS' `kspace_style pppm` does it: order-5 assignment, ik differentiation, the optimal influence function of the
+ * step's box, grid and g_ewald per run from the run's start box (set_grid_global, adjust_gewald), fixed over the run; the charge grid is
+ * summed in 64-bit fixed point, so forces repeat bit for bit.  On the mesh info[4] of the static evaluation (the k-vectors) is 0 and
+ * info[5] the adjusted g_ewald.  Refused with SCEMA_MD_ERR_ARG when a run starts: a mesh of more than 4 194 304 points, a mesh dimension
+ * that reaches the search cap of 4096.  SCEMA_MD_ERR_ARG here: an unknown material, one without a Born/long potential, an unknown mode. */
+int scema_md_born_long_kspace(scema_md_engine *e, const char *matid, int32_t mode);
+/* grid[3]: the mesh of the last scema_md_born_long_debug_compute, zeros if it ran the Ewald sum */
+int scema_md_born_long_last_mesh(scema_md_engine *e, int32_t *grid);
 /* The reader as a pure host function (no GPU, no engine).  n_types: the fragment's types; head[6]: cut_coul, accuracy, solver (0 ewald,
  * 1 pppm), K (kcal A/mol), cutmax, style (0 born/coul/long, 1 buck/coul/long); values[n_types][n_types][6] (room for 4*4*6): A rho sigma
  * C D cut_lj of every ordered pair, A, C and D in kcal/mol.  Refused with SCEMA_MD_ERR_IO and "<path> line <n>: <reason>" in errbuf: what
@@ -730,6 +744,10 @@ int scema_md_born_long_eval(const char *path, int32_t energy_unit, double g_ewal
  * natoms atoms with sum q^2 = qsqsum under the cut_coul and accuracy of `path` */
 int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *kmax,
                                 int32_t *nk, int32_t *triples, int32_t triples_cap, char *errbuf, int32_t errcap);
+/* The mesh counterpart: the adjusted g_ewald and the mesh grid[3] a run on the mesh solver would use for this box.  A mesh the solver
+ * refuses is SCEMA_MD_ERR_ARG with the refusal in errbuf; g_ewald and grid are filled in all the same. */
+int scema_md_born_long_mesh(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *grid,
+                            char *errbuf, int32_t errcap);
 
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */

@@ -48,7 +48,7 @@ SYMBOLS = [
     "scema_md_meam_spline_configure", "scema_md_meam_spline_debug_compute", "scema_md_meam_spline_read_params", "scema_md_meam_spline_eval",
     "scema_md_born_dsf_configure", "scema_md_born_dsf_debug_compute", "scema_md_born_dsf_read_params", "scema_md_born_dsf_eval",
     "scema_md_born_long_configure", "scema_md_born_long_debug_compute", "scema_md_born_long_read_params", "scema_md_born_long_eval",
-    "scema_md_born_long_kvectors",
+    "scema_md_born_long_kvectors", "scema_md_born_long_kspace", "scema_md_born_long_last_mesh", "scema_md_born_long_mesh",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -638,6 +638,23 @@ class Engine:
 
     born_long_debug_compute = born_long_compute
 
+    def born_long_kspace(self, matid: str, mode: int = 0):
+        """the reciprocal solver of a Born/long material's replicas: 0 by the script and the Ewald limits (the Ewald sum where its k list
+        fits; beyond it a `pppm` script runs on the mesh and an `ewald` script is refused), 1 the PPPM mesh for every replica, 2 the Ewald
+        sum always.  On the mesh born_long_compute reports nk 0 and the adjusted g_ewald"""
+        self._chk(lib().scema_md_born_long_kspace(self.h, matid.encode(), C.c_int32(mode)))
+
+    def born_long_mesh_configure(self, matid: str, path: str, energy_unit: int = 0, skin: float = -1.0):
+        """born_long_configure, then the mesh solver for every replica of the material (born_long_kspace mode 1)"""
+        self.born_long_configure(matid, path, energy_unit, skin)
+        self.born_long_kspace(matid, 1)
+
+    def born_long_last_mesh(self):
+        """the mesh (nx, ny, nz) of the last born_long_compute, zeros if it ran the Ewald sum"""
+        grid = np.zeros(3, np.int32)
+        self._chk(lib().scema_md_born_long_last_mesh(self.h, _p(grid)))
+        return tuple(int(v) for v in grid)
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -810,6 +827,20 @@ def born_long_kvectors(path: str, box, natoms: int, qsqsum: float, energy_unit: 
     if rc != 0:
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     return dict(g_ewald=g.value, kmax=kmax.copy(), nk=nk.value, triples=tr[:nk.value].copy())
+
+
+def born_long_mesh(path: str, box, natoms: int, qsqsum: float, energy_unit: int = 0):
+    """the mesh set-up a run on the mesh solver would use for that box (scema_md_born_long_mesh, a pure host function): dict g_ewald,
+    grid (3); a mesh the solver refuses raises IOError with the refusal"""
+    fn = lib().scema_md_born_long_mesh
+    fn.restype = C.c_int
+    box = np.ascontiguousarray(box, float)
+    g, grid = C.c_double(0.0), np.zeros(3, np.int32)
+    err = C.create_string_buffer(512)
+    rc = fn(path.encode(), C.c_int32(energy_unit), _p(box), C.c_int32(natoms), C.c_double(qsqsum), C.byref(g), _p(grid), err, C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return dict(g_ewald=g.value, grid=tuple(int(v) for v in grid))
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]

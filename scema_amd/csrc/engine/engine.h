@@ -65,6 +65,7 @@
 #include "md_meam_spline.h"
 #include "md_born_dsf.h"
 #include "md_born_long.h"
+#include "md_born_long_mesh.h"
 #include "md_rowcells.h"
 #include "md_types.h"
 
@@ -215,6 +216,7 @@ struct RowMaterial {
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
   double kspace_cut = 0.0, kspace_acc = 0.0;   // Born/long: cut_coul and the accuracy of the kspace_style line (the k-space set-up of a run: ewald_setup)
+  int kspace_pppm = 0, kspace_mode = 0;        // Born/long: 1: the script said `kspace_style pppm`; scema_md_born_long_kspace (0 by the script and the Ewald limits, 1 the mesh, 2 the Ewald sum)
   DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable / BlTable on the device
 };
 
@@ -430,6 +432,12 @@ struct scema_md_engine {
   std::vector<EamView> h_eamviews;
   DevBuf d_blviews;               // Ewald ionic stage: parallel to the views
   std::vector<BlView> h_blviews;
+  // its mesh solver (md_born_long_mesh.h): the views, and the grids of a run laid out position-major at the stride of the run's largest
+  // mesh (hipFFT wants the grids of a batch at one stride): fixed-point and complex charge grids, three complex field grids per
+  // replica, influence functions.  Grown by BlStage::upload, never in the step loop
+  DevBuf d_blmviews, blm_igrid, blm_cgrid, blm_field, blm_gf;
+  std::vector<BlmView> h_blmviews;
+  int blm_last_mesh[3] = {0, 0, 0};   // scema_md_born_long_last_mesh: the mesh of the last static evaluation (zeros: it ran the Ewald sum)
   DevBuf d_adpviews;              // angular-dependent stage: parallel to the views
   std::vector<AdpView> h_adpviews;
   DevBuf d_rowcells;              // rows built through cells: parallel to the views (all zero for a replica on the N^2 build)

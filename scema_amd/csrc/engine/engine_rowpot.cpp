@@ -336,21 +336,93 @@ void bl_setup(const scema_md_params &base, double cut_coul, double accuracy, con
   ewald_setup(p, T, box, ew);
 }
 
+// The mesh set-up of a run: LAMMPS' initial g_ewald estimate (ewald_setup, g only), then the grid and the adjusted g of pppm_setup_host,
+// with the material's cut_coul and accuracy as bl_setup takes them.  The accuracy is relative, so K cancels.
+void bl_mesh_setup(const scema_md_params &base, double cut_coul, double accuracy, const Topo &T, const double *box, double &g, int pg[3]) {
+  scema_md_params p = base;
+  p.cut_coul = cut_coul;
+  p.kspace_accuracy = accuracy;
+  EwaldSetup ew;
+  ewald_setup(p, T, box, ew, true);
+  g = ew.g;
+  pg[0] = pg[1] = pg[2] = 0;
+  if (T.qsqsum > 0.0) pppm_setup_host(p, T, box, g, pg);
+}
+
+// what the mesh solver refuses, or an empty string
+std::string bl_mesh_refusal(const char *what, int natoms, double accuracy, const int pg[3]) {
+  char buf[512];
+  buf[0] = 0;
+  const long long ng = (long long)pg[0] * pg[1] * pg[2];
+  if (pg[0] >= BLM_MAXDIM || pg[1] >= BLM_MAXDIM || pg[2] >= BLM_MAXDIM)
+    snprintf(buf, sizeof buf, "a %s replica of %d atoms at accuracy %g: the mesh search reached its cap of %d points in a dimension (mesh %d x %d x %d)", what,
+             natoms, accuracy, BLM_MAXDIM, pg[0], pg[1], pg[2]);
+  else if (ng > BLM_MAXGRID)
+    snprintf(buf, sizeof buf, "a %s replica of %d atoms needs a mesh of %d x %d x %d = %lld points at accuracy %g: the mesh solver of the row driver holds %d",
+             what, natoms, pg[0], pg[1], pg[2], ng, accuracy, BLM_MAXGRID);
+  return buf;
+}
+
+// A batched 3-d Z2Z plan over grids `stride` complex elements apart, on the map of the molecular path's plans (OplsRun::pppm_plan,
+// engine_run.cpp, whose key this is): a plan owns a work area, so each stream that may run it has its own
+static int row_pppm_plan(scema_md_engine *e, const int pg[3], int batch, hipStream_t st, int stride, hipfftHandle &plan) {
+  const int sk = st == e->stream ? 0 : st == e->stream2 ? 1 : st == e->stream3 ? 2 : st == e->rx_side1 ? 3 : -1;
+  if (sk < 0) return fail(e, SCEMA_MD_ERR_ARG, "mesh transform on a stream the engine does not know");
+  const std::array<int, 6> key = {pg[0], pg[1], pg[2], batch, sk, stride};
+  auto it = e->pppm_plans.find(key);
+  if (it == e->pppm_plans.end()) {
+    hipfftHandle h;
+    int n[3] = {pg[2], pg[1], pg[0]};   // slowest dimension first
+    if (hipfftPlanMany(&h, 3, n, n, 1, stride, n, 1, stride, HIPFFT_Z2Z, batch) != HIPFFT_SUCCESS)
+      return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftPlanMany failed for a %d x %d x %d grid, batch %d", pg[0], pg[1], pg[2], batch);
+    it = e->pppm_plans.emplace(key, h).first;
+  }
+  plan = it->second;
+  return SCEMA_MD_OK;
+}
+
+// Which reciprocal solver a replica gets is decided here, per replica and run (RowMaterial::kspace_mode, scema_md_born_long_kspace): mode 0
+// is the Ewald sum wherever its k list fits, whatever the script's solver word, and the mesh for a `pppm` script beyond the limits; mode 1
+// the mesh (md_born_long_mesh.h) for every replica; mode 2 the Ewald sum or its refusal.  A launch group may hold replicas of both.
 struct BlStage : RowPotStage {
-  BlView *BB = nullptr;   // on the device (upload)
-  BlStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowPotStage(e_, ns, pot) { e->h_blviews.assign(ns, BlView()); }
+  BlView *BB = nullptr;    // on the device (upload)
+  BlmView *MM = nullptr;   // the mesh views, parallel
+  int cur_step = 0;        // the step of the force call being issued (forces)
+  int fft_rc = 0;          // a hipFFT call of this run failed: nothing more of the run is enqueued (launch), and faults() reports it
+  std::string fft_msg;
+  BlStage(scema_md_engine *e_, int ns, const RowPot &pot) : RowPotStage(e_, ns, pot) {
+    e->h_blviews.assign(ns, BlView());
+    e->h_blmviews.assign(ns, BlmView());
+  }
   int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
     if (const int rc = RowPotStage::bind(pos, A, sl, S, need)) return rc;
     const Topo &T = *A.st->topo;
     const RowMaterial &M = *e->row_mats.find(T.matid)->second;
+    const double *box = e->h_sc[run->order[pos]].box;
     EwaldSetup ew;
-    bl_setup(e->p, M.kspace_cut, M.kspace_acc, T, e->h_sc[run->order[pos]].box, ew);
+    bool mesh = M.kspace_mode == 1 && T.qsqsum > 0.0;
+    if (!mesh) {
+      bl_setup(e->p, M.kspace_cut, M.kspace_acc, T, box, ew);
+      const int nk = (int)ew.kn.size() / 3;
+      if (nk > BL_MAXK || ew.kmaxd[0] > BL_MAXKD || ew.kmaxd[1] > BL_MAXKD || ew.kmaxd[2] > BL_MAXKD) {
+        if (M.kspace_mode == 0 && M.kspace_pppm) mesh = true;
+        else
+          return fail(e, SCEMA_MD_ERR_ARG,
+                      "a %s replica of %d atoms needs %d k-vectors (indices up to %d %d %d) at accuracy %g: the Ewald sum of the row driver holds %d (indices up to %d); "
+                      "PPPM on the row driver is the follow-up for replicas of that size",
+                      what, T.natoms, nk, ew.kmaxd[0], ew.kmaxd[1], ew.kmaxd[2], M.kspace_acc, BL_MAXK, BL_MAXKD);
+      }
+    }
+    BlmView G;
+    std::memset(&G, 0, sizeof G);
+    if (mesh) {
+      ew = EwaldSetup();
+      bl_mesh_setup(e->p, M.kspace_cut, M.kspace_acc, T, box, ew.g, G.n);
+      const std::string no = bl_mesh_refusal(what, T.natoms, M.kspace_acc, G.n);
+      if (!no.empty()) return fail(e, SCEMA_MD_ERR_ARG, "%s", no.c_str());
+      G.g = ew.g;
+    }
     const int nk = (int)ew.kn.size() / 3;
-    if (nk > BL_MAXK || ew.kmaxd[0] > BL_MAXKD || ew.kmaxd[1] > BL_MAXKD || ew.kmaxd[2] > BL_MAXKD)
-      return fail(e, SCEMA_MD_ERR_ARG,
-                  "a %s replica of %d atoms needs %d k-vectors (indices up to %d %d %d) at accuracy %g: the Ewald sum of the row driver holds %d (indices up to %d); "
-                  "PPPM on the row driver is the follow-up for replicas of that size",
-                  what, T.natoms, nk, ew.kmaxd[0], ew.kmaxd[1], ew.kmaxd[2], M.kspace_acc, BL_MAXK, BL_MAXKD);
     RowSlot &W = *sl.row;
     const int nkcap = std::max(64, (nk + 63) / 64 * 64);
     HIPCHK(W.kn.ensure((size_t)nkcap * 3 * sizeof(int)));
@@ -362,19 +434,97 @@ struct BlStage : RowPotStage {
     std::memset(&B, 0, sizeof B);
     B.nk = nk; B.nkcap = nkcap;
     for (int d = 0; d < 3; d++) B.kmax[d] = ew.kmaxd[d];
+    B.mesh = mesh ? 1 : 0;
     B.g = ew.g;
-    for (double q : T.q) { B.qsqsum += q * q; B.qsum += q; }
+    for (double q : T.q) { B.qsqsum += q * q; B.qsum += q; G.qabs += std::fabs(q); }
+    G.qsqsum = B.qsqsum; G.qsum = B.qsum;
     ROWSET(B.kn, W.kn.as<int>()); ROWSET(B.sk, W.sk.as<double>()); ROWSET(B.shift, W.kshift.as<int>());
     e->h_blviews[pos] = B;
+    e->h_blmviews[pos] = G;
     return SCEMA_MD_OK;
   }
-  int upload() override { const int rc = RowPotStage::upload(); return rc ? rc : upload_views(e, e->d_blviews, e->h_blviews, BB); }
-  void launch(hipStream_t st, int pos0, int n) override {
-    int maxnk = 0;
-    for (int k = pos0; k < pos0 + n && k < (int)e->h_blviews.size(); k++) maxnk = std::max(maxnk, e->h_blviews[k].nk);
-    mdk_bl_forces(st, run->D + pos0, VV + pos0, BB + pos0, n, run->maxatoms, maxnk);
+  // the grids of the run's mesh replicas, position-major at the stride of the largest mesh, then the views
+  int upload() override {
+    if (const int rc = RowPotStage::upload()) return rc;
+    const size_t ns = e->h_blmviews.size();
+    size_t stride = 0;
+    for (const BlmView &G : e->h_blmviews) stride = std::max(stride, (size_t)G.n[0] * G.n[1] * G.n[2]);
+    if (stride) {
+      HIPCHK(e->blm_igrid.ensure(ns * stride * sizeof(long long)));
+      HIPCHK(e->blm_cgrid.ensure(ns * stride * 2 * sizeof(double)));
+      HIPCHK(e->blm_field.ensure(ns * stride * 6 * sizeof(double)));
+      HIPCHK(e->blm_gf.ensure(ns * stride * sizeof(double)));
+      HIPCHK(hipMemsetAsync(e->blm_igrid.p, 0, ns * stride * sizeof(long long), e->stream));   // (k_blm_convert leaves it zeroed; a run that failed midway may not have)
+      for (size_t pos = 0; pos < ns; pos++) {
+        BlmView &G = e->h_blmviews[pos];
+        G.gcap = (int)stride;
+        ROWSET(G.igrid, e->blm_igrid.as<long long>() + pos * stride);
+        ROWSET(G.cgrid, e->blm_cgrid.as<double>() + pos * stride * 2);
+        ROWSET(G.field, e->blm_field.as<double>() + pos * stride * 6);
+        ROWSET(G.gf, e->blm_gf.as<double>() + pos * stride);
+      }
+    }
+    if (const int rc = upload_views(e, e->d_blviews, e->h_blviews, BB)) return rc;
+    return upload_views(e, e->d_blmviews, e->h_blmviews, MM);
   }
-  void flipped(hipStream_t st, int pos, const FlipEvent &fe) override { mdk_bl_flip(st, BB + pos, fe.nflip[0], fe.nflip[1]); }
+  void forces(hipStream_t st, int pos0, int n, int step, int part) override {
+    cur_step = step;
+    RowPotStage::forces(st, pos0, n, step, part);
+  }
+  // the transforms of a launch group: one exec per run of consecutive positions with equal mesh, forward on the charge grids, backward
+  // on 3 x run field grids
+  struct FftCall { BlStage *stage; hipStream_t st; int pos0, n; };
+  int transform(hipStream_t st, int pos0, int n, bool backward) {
+    const int end = std::min(pos0 + n, (int)e->h_blmviews.size());
+    for (int k = pos0; k < end;) {
+      const BlmView &G = e->h_blmviews[k];
+      int len = 1;
+      while (k + len < end && std::memcmp(e->h_blmviews[k + len].n, G.n, sizeof G.n) == 0) len++;
+      if (G.n[0] > 0) {
+        hipfftHandle plan;
+        if (const int rc = row_pppm_plan(e, G.n, (backward ? 3 : 1) * len, st, G.gcap, plan)) return rc;
+        double *grid = backward ? (double *)G.field : (double *)G.cgrid;
+        if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS ||
+            hipfftExecZ2Z(plan, (hipfftDoubleComplex *)grid, (hipfftDoubleComplex *)grid, backward ? HIPFFT_BACKWARD : HIPFFT_FORWARD) != HIPFFT_SUCCESS)
+          return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftExecZ2Z failed on a %d x %d x %d mesh, batch %d", G.n[0], G.n[1], G.n[2], (backward ? 3 : 1) * len);
+      }
+      k += len;
+    }
+    return SCEMA_MD_OK;
+  }
+  static int transform_entry(void *ctx, int backward) {
+    const FftCall &c = *(const FftCall *)ctx;
+    return c.stage->transform(c.st, c.pos0, c.n, backward != 0);
+  }
+  void launch(hipStream_t st, int pos0, int n) override {
+    if (fft_rc) return;
+    int maxnk = 0, maxgrid = 0;
+    bool ewald = false;
+    for (int k = pos0; k < pos0 + n && k < (int)e->h_blviews.size(); k++) {
+      const BlmView &G = e->h_blmviews[k];
+      maxnk = std::max(maxnk, e->h_blviews[k].nk);
+      maxgrid = std::max(maxgrid, G.n[0] * G.n[1] * G.n[2]);
+      ewald = ewald || !e->h_blviews[k].mesh;
+    }
+    if (maxgrid == 0) {
+      mdk_bl_forces(st, run->D + pos0, VV + pos0, BB + pos0, n, run->maxatoms, maxnk);
+      return;
+    }
+    // the influence function follows the box: every step of a run whose box moves (fix deform, the barostat), else the run's first call
+    const RunSpec &sp = run->spec;
+    const bool new_box = cur_step == 0 || sp.deform || (sp.nh && sp.npt);
+    FftCall call{this, st, pos0, n};
+    fft_rc = mdk_bl_mesh_forces(st, run->D + pos0, VV + pos0, BB + pos0, MM + pos0, n, run->maxatoms, maxnk, ewald, maxgrid, new_box, transform_entry, &call);
+    if (fft_rc) fft_msg = e->err;
+  }
+  // (the mesh lives in the fractional coordinates of the step's box, and the box of the step after a flip is the flipped one)
+  void flipped(hipStream_t st, int pos, const FlipEvent &fe) override {
+    if (!e->h_blviews[pos].mesh) mdk_bl_flip(st, BB + pos, fe.nflip[0], fe.nflip[1]);
+  }
+  int faults(int fault) override {
+    if (fft_rc) return fail(e, SCEMA_MD_ERR_DEVICE, "a mesh transform of this %s run failed: %s", what, fft_msg.c_str());
+    return RowPotStage::faults(fault);
+  }
   int crowded(int) override { return SCEMA_MD_OK; }
 };
 
@@ -755,14 +905,35 @@ int scema_md_born_long_configure(scema_md_engine *e, const char *matid, const ch
   RowMaterial &M = *e->row_mats[matid];
   M.kspace_cut = T.bd.cut_coul;
   M.kspace_acc = T.accuracy;
+  M.kspace_pppm = T.pppm;
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_kspace(scema_md_engine *e, const char *matid, int32_t mode) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (!matid) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  auto it = e->row_mats.find(matid);
+  if (it == e->row_mats.end() || it->second->kind != RowKind::BornLong)
+    return fail(e, SCEMA_MD_ERR_ARG, "no Born/long potential attached to material %s (scema_md_born_long_configure)", matid);
+  if (mode < 0 || mode > 2) return fail(e, SCEMA_MD_ERR_ARG, "reciprocal solver mode %d (0: by the script and the Ewald limits, 1: the mesh, 2: the Ewald sum)", mode);
+  it->second->kspace_mode = mode;
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_last_mesh(scema_md_engine *e, int32_t *grid) {
+  if (!e || !grid) return SCEMA_MD_ERR_ARG;
+  for (int d = 0; d < 3; d++) grid[d] = e->blm_last_mesh[d];
   return SCEMA_MD_OK;
 }
 
 int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
                                      double *virial, double *info) {
   double info4[4] = {0.0, 0.0, 0.0, 0.0};
+  if (e) e->blm_last_mesh[0] = e->blm_last_mesh[1] = e->blm_last_mesh[2] = 0;
   const int rc = row_debug_compute(e, RowKind::BornLong, qp_id, matid, replica, f, e_born, e_coul, virial, info4);
   if (rc) return rc;
+  if (!e->h_blmviews.empty())
+    for (int d = 0; d < 3; d++) e->blm_last_mesh[d] = e->h_blmviews[0].n[d];
   if (info) {
     for (int k = 0; k < 4; k++) info[k] = info4[k];
     info[4] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].nk;
@@ -797,6 +968,32 @@ int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const dou
     if (triples_cap < n) { say("triples_cap " + std::to_string(triples_cap) + " < nk = " + std::to_string(n)); return SCEMA_MD_ERR_ARG; }
     for (int k = 0; k < 3 * n; k++) triples[k] = ew.kn[k];
   }
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_mesh(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *grid,
+                            char *errbuf, int32_t errcap) {
+  auto say = [&](const std::string &m) {
+    if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
+  };
+  say("");
+  if (!path || !box || natoms <= 0 || !(qsqsum > 0.0) || (energy_unit != 0 && energy_unit != 1)) { say("bad arguments"); return SCEMA_MD_ERR_ARG; }
+  BlTable T;
+  std::vector<int> map;
+  std::string err;
+  if (!scema::read_born_long_params(path, energy_unit, T, map, err)) { say(err); return SCEMA_MD_ERR_IO; }
+  scema_md_params p;
+  scema_md_default_params(&p);
+  Topo t;
+  t.natoms = natoms;
+  t.qsqsum = qsqsum;
+  double g = 0.0;
+  int pg[3] = {0, 0, 0};
+  bl_mesh_setup(p, T.bd.cut_coul, T.accuracy, t, box, g, pg);
+  if (g_ewald) *g_ewald = g;
+  if (grid) for (int d = 0; d < 3; d++) grid[d] = pg[d];
+  const std::string no = bl_mesh_refusal("Born/long", natoms, T.accuracy, pg);
+  if (!no.empty()) { say(no); return SCEMA_MD_ERR_ARG; }
   return SCEMA_MD_OK;
 }
 

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
+
 #include "ionic/bl_core.h"
 #include "md_rows.h"
 
@@ -12,7 +14,8 @@
 // the run's start box (scema_eng::ewald_setup), fixed over the run.  The charges are those of the replica (SimDev::q).
 typedef struct {
   int nk, nkcap;             // k-vectors of the half space (at most BL_MAXK); stride of `sk`
-  int kmax[3], pad_;         // largest |n_d| of the triples (at most BL_MAXKD each)
+  int kmax[3], mesh;         // largest |n_d| of the triples (at most BL_MAXKD each); 1: the replica's reciprocal part runs on the mesh
+                             // (md_born_long_mesh.h: nk is 0, the Ewald pair leaves the replica alone, its self energy included)
   double g;                  // g_ewald of the run
   double qsqsum, qsum;       // sum q_i^2, sum q_i of the replica
   const int ROW_G *kn;       // [nk][3] the triples in the reciprocal basis of the run's start box
@@ -23,7 +26,9 @@ typedef struct {
 // the force stage of one step for the first ns replicas: neighbour rows where the rebuild flag of the step is set (mdk_rows_build),
 // k_bl_force (real space, stores SimDev::f), k_bl_sfac (S(k), reciprocal energy and virial, self energy), k_bl_recip (adds the reciprocal
 // force), k_row_finish.  maxnk: the largest BlView::nk of the ns replicas.  Virial parts: P_LJ for the Born term, P_COUL for everything
-// Coulomb.
-void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk);
+// Coulomb.  ewald false: no replica of the group runs the Ewald sum and the pair of reciprocal kernels is not launched; mesh: what the
+// mesh solver enqueues for its replicas between the Ewald pair and k_row_finish (md_born_long_mesh.h), given the grid of k_bl_force.
+void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk, bool ewald = true,
+                   const std::function<void(dim3)> *mesh = nullptr);
 // a box flip of one replica by fxy, fxz lattice steps, after mdk_flip on the same stream: the triples keep their Cartesian vectors
 void mdk_bl_flip(hipStream_t st, const BlView *b, int fxy, int fxz);

@@ -88,6 +88,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_bl_force(const SimDev *sims, 
 __global__ __launch_bounds__(BL_SF_TPB) void k_bl_sfac(const SimDev *sims, const RowView *views, const BlView *bls) {
   const RowView V = views[blockIdx.y];
   const BlView B = bls[blockIdx.y];
+  if (B.mesh) return;   // (the whole workgroup: a mesh replica's reciprocal part, self and background terms are k_blm_poisson's)
   const BlShape sh = bl_shape(B);
   if (blockIdx.x > 0 && (int)(blockIdx.x * BL_SF_TPB) >= sh.nk) return;   // (the whole workgroup)
   const SimDev &S = sims[blockIdx.y];
@@ -190,12 +191,16 @@ __global__ void k_bl_flip(const BlView *b, int fxy, int fxz) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { b->shift[0] += fxy; b->shift[1] += fxz; }
 }
 
-void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk) {
+void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk, bool ewald,
+                   const std::function<void(dim3)> *mesh) {
   mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
     const dim3 gk((unsigned)std::max(1, (maxnk + BL_SF_TPB - 1) / BL_SF_TPB), (unsigned)ns, 1);
     hipLaunchKernelGGL(k_bl_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
-    hipLaunchKernelGGL(k_bl_sfac, gk, dim3(BL_SF_TPB), 0, st, d, v, b);
-    hipLaunchKernelGGL(k_bl_recip, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
+    if (ewald) {
+      hipLaunchKernelGGL(k_bl_sfac, gk, dim3(BL_SF_TPB), 0, st, d, v, b);
+      hipLaunchKernelGGL(k_bl_recip, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
+    }
+    if (mesh) (*mesh)(gt);
   });
 }
 

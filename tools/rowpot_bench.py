@@ -15,12 +15,12 @@ per evaluation at 1 fs.  The replica per potential:
              rows are built by minimum image; charges +1 and -1, masses 22.98977 and 35.453, thermal velocities at 300 K,
              tests/golden/NaCl.born_dsf: pair_style born/coul/dsf 0.25 10.0, about 190 neighbours per ion)
   born_long  the born_dsf replica under tests/golden/NaCl.born_long: pair_style born/coul/long 10.0 with kspace_style ewald 1.0e-5, the
-             same neighbours beside 709 k-vectors per replica
+             same neighbours beside 709 k-vectors per replica; --kspace mesh puts the reciprocal part on the PPPM mesh (24^3) instead
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf|born_long [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf|born_long [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--kspace ewald|mesh] [--dump stress.npy]
 """
 import argparse
 import itertools
@@ -140,11 +140,17 @@ def main():
     ap.add_argument("--split", type=int, default=-1, help="scema_md_batch_split: 0 whole, 1 part batches, -1 the default")
     ap.add_argument("--cells", type=int, default=None, metavar="K", help="K x K x K lattice cells per replica instead of the potential's shape above (sw: diamond silicon of 5.431 A "
                     "instead of the example's file); the JSON line then names the atoms and the list builds through cells (SCEMA_MD_ROW_CELLS, DESIGN.md 7m)")
+    ap.add_argument("--kspace", default=None, choices=("ewald", "mesh"), help="born_long only: the reciprocal solver of every replica, the Ewald sum (born_long_kspace "
+                    "mode 2) or the PPPM mesh (mode 1); default: by the script and the Ewald limits (mode 0)")
     ap.add_argument("--dump", default=None, metavar="FILE", help="write the stresses of the last update as FILE (.npy, float64, one row of six per quadrature point)")
     a = ap.parse_args()
     workload, mat, make = POTENTIALS[a.potential]
     e = capi.Engine(capi.default_params())
     make(e, None if a.cells is None else (a.cells,) * 3)
+    if a.kspace is not None:
+        if a.potential != "born_long":
+            ap.error("--kspace needs --potential born_long")
+        e.born_long_kspace(mat, {"ewald": 2, "mesh": 1}[a.kspace])
     e.batch_split(a.split)
     box, _, _ = e.get_state(capi.QP_NONE, mat, 1)
     L = box[3:6] - box[:3]
@@ -172,10 +178,12 @@ def main():
     prof = e.profile()
     best, med = min(times), sorted(times)[len(times) // 2]
     extra = {}
+    if a.kspace is not None:
+        extra["kspace"] = a.kspace
     if a.cells is not None:
         natoms = e.natoms(mat, 1)
         workload = "%s_%d" % (workload.rsplit("_", 1)[0], natoms)
-        extra = {"cells": a.cells, "atoms": natoms, "row_cell_builds": prof["row_cell_builds"], "row_cells_env": os.environ.get("SCEMA_MD_ROW_CELLS")}
+        extra = {**extra, "cells": a.cells, "atoms": natoms, "row_cell_builds": prof["row_cell_builds"], "row_cells_env": os.environ.get("SCEMA_MD_ROW_CELLS")}
     print(json.dumps({"workload": workload, "sims": a.sims, "steps_per_eval": 10 + a.nss, "updates": a.updates, "split": e.concurrency()["split"],
                       "evals_per_s_median": a.sims / med, "evals_per_s_best": a.sims / best, "update_s": times,
                       "replica_steps_per_s_median": a.sims * (10 + a.nss) / med, "neigh_builds": prof["neigh_builds"], "md_steps": prof["md_steps"], **extra}))
