@@ -483,6 +483,7 @@ int build_topo(scema_md_engine *e, const scema_md_system *s, Topo &t);
 void ewald_setup(const scema_md_params &p, const Topo &t, const double *box, EwaldSetup &out, bool g_only = false);
 void ewald_tables(EwaldSetup &out);
 void pppm_setup_host(const scema_md_params &p, const Topo &t, const double *box, double &g, int pg[3]);
+int pppm_exec(scema_md_engine *e, const int pg[3], int batch, hipStream_t st, long long stride, double *grid, int dir);
 double cached_coul_poly(scema_md_engine *, double g, double rc, double *poly, int *npoly, double *uscale);
 void tilt_closest(double tilt[3], double xprd_new, double yprd_new, double xy, double xz, double yz, double xprd, double yprd);
 int tilt_flip(const double tilt[3], double xprd, double yprd, double flipped[3], int nflip[3]);

@@ -273,6 +273,38 @@ void pppm_setup_host(const scema_md_params &p, const Topo &t, const double *box,
   }
 }
 
+// ---- the transforms of the two mesh solvers (OplsRun::pppm_stage, BlStage::transform) ----
+// The batched 3-d Z2Z plan over `batch` grids of the mesh pg that lie `stride` complex elements apart (the charge grids of neighbouring
+// simulations, and all their field grids: three per simulation, simulation-major).  A plan owns a work area and is bound to a stream
+// when it runs: ONE PER STREAM that may run it.  (Until round 6 the key knew the main stream, the side stream and "the other one": with
+// three or four part batches two parts shared the plans of their common mesh sizes -- two replicas with the same mesh beyond the in-LDS
+// solve, one in each, transformed through one work area at the same time.)
+static int pppm_plan(scema_md_engine *e, const int pg[3], int batch, hipStream_t st, long long stride, hipfftHandle &plan) {
+  if (stride > 0x7fffffffLL) return fail(e, SCEMA_MD_ERR_ARG, "PPPM grid of %lld points is too large", stride);
+  const int sk = st == e->stream ? 0 : st == e->stream2 ? 1 : st == e->stream3 ? 2 : st == e->rx_side1 ? 3 : -1;
+  if (sk < 0) return fail(e, SCEMA_MD_ERR_ARG, "PPPM transform on a stream the engine does not know");
+  const std::array<int, 6> key = {pg[0], pg[1], pg[2], batch, sk, (int)stride};
+  auto it = e->pppm_plans.find(key);
+  if (it == e->pppm_plans.end()) {
+    hipfftHandle h;
+    int n[3] = {pg[2], pg[1], pg[0]};   // slowest dimension first
+    // embed = the grid itself; the distance between consecutive grids is the batch's stride, not the grid's size
+    if (hipfftPlanMany(&h, 3, n, n, 1, (int)stride, n, 1, (int)stride, HIPFFT_Z2Z, batch) != HIPFFT_SUCCESS)
+      return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftPlanMany failed for a %d x %d x %d grid, batch %d", pg[0], pg[1], pg[2], batch);
+    it = e->pppm_plans.emplace(key, h).first;
+  }
+  plan = it->second;
+  return SCEMA_MD_OK;
+}
+// the transform of those grids, the first at `grid`, in place on st by their plan; dir is HIPFFT_FORWARD or HIPFFT_BACKWARD
+int pppm_exec(scema_md_engine *e, const int pg[3], int batch, hipStream_t st, long long stride, double *grid, int dir) {
+  hipfftHandle plan;
+  if (const int rc = pppm_plan(e, pg, batch, st, stride, plan)) return rc;
+  if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS || hipfftExecZ2Z(plan, (hipfftDoubleComplex *)grid, (hipfftDoubleComplex *)grid, dir) != HIPFFT_SUCCESS)
+    return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftExecZ2Z failed on a %d x %d x %d mesh, batch %d", pg[0], pg[1], pg[2], batch);
+  return SCEMA_MD_OK;
+}
+
 struct PolyFit { int n; double uscale, err; double c[MD_MAXPOLY]; };
 static std::map<long, PolyFit> &poly_cache() { static std::map<long, PolyFit> m; return m; }
 double cached_coul_poly(scema_md_engine *, double g, double rc, double *poly, int *npoly, double *uscale) {

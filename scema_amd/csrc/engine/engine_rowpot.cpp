@@ -363,24 +363,6 @@ std::string bl_mesh_refusal(const char *what, int natoms, double accuracy, const
   return buf;
 }
 
-// A batched 3-d Z2Z plan over grids `stride` complex elements apart, on the map of the molecular path's plans (OplsRun::pppm_plan,
-// engine_run.cpp, whose key this is): a plan owns a work area, so each stream that may run it has its own
-static int row_pppm_plan(scema_md_engine *e, const int pg[3], int batch, hipStream_t st, int stride, hipfftHandle &plan) {
-  const int sk = st == e->stream ? 0 : st == e->stream2 ? 1 : st == e->stream3 ? 2 : st == e->rx_side1 ? 3 : -1;
-  if (sk < 0) return fail(e, SCEMA_MD_ERR_ARG, "mesh transform on a stream the engine does not know");
-  const std::array<int, 6> key = {pg[0], pg[1], pg[2], batch, sk, stride};
-  auto it = e->pppm_plans.find(key);
-  if (it == e->pppm_plans.end()) {
-    hipfftHandle h;
-    int n[3] = {pg[2], pg[1], pg[0]};   // slowest dimension first
-    if (hipfftPlanMany(&h, 3, n, n, 1, stride, n, 1, stride, HIPFFT_Z2Z, batch) != HIPFFT_SUCCESS)
-      return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftPlanMany failed for a %d x %d x %d grid, batch %d", pg[0], pg[1], pg[2], batch);
-    it = e->pppm_plans.emplace(key, h).first;
-  }
-  plan = it->second;
-  return SCEMA_MD_OK;
-}
-
 // Which reciprocal solver a replica gets is decided here, per replica and run (RowMaterial::kspace_mode, scema_md_born_long_kspace): mode 0
 // is the Ewald sum wherever its k list fits, whatever the script's solver word, and the mesh for a `pppm` script beyond the limits; mode 1
 // the mesh (md_born_long_mesh.h) for every replica; mode 2 the Ewald sum or its refusal.  A launch group may hold replicas of both.
@@ -480,14 +462,10 @@ struct BlStage : RowPotStage {
       const BlmView &G = e->h_blmviews[k];
       int len = 1;
       while (k + len < end && std::memcmp(e->h_blmviews[k + len].n, G.n, sizeof G.n) == 0) len++;
-      if (G.n[0] > 0) {
-        hipfftHandle plan;
-        if (const int rc = row_pppm_plan(e, G.n, (backward ? 3 : 1) * len, st, G.gcap, plan)) return rc;
-        double *grid = backward ? (double *)G.field : (double *)G.cgrid;
-        if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS ||
-            hipfftExecZ2Z(plan, (hipfftDoubleComplex *)grid, (hipfftDoubleComplex *)grid, backward ? HIPFFT_BACKWARD : HIPFFT_FORWARD) != HIPFFT_SUCCESS)
-          return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftExecZ2Z failed on a %d x %d x %d mesh, batch %d", G.n[0], G.n[1], G.n[2], (backward ? 3 : 1) * len);
-      }
+      if (G.n[0] > 0)
+        if (const int rc = pppm_exec(e, G.n, (backward ? 3 : 1) * len, st, G.gcap, backward ? (double *)G.field : (double *)G.cgrid,
+                                     backward ? HIPFFT_BACKWARD : HIPFFT_FORWARD))
+          return rc;
       k += len;
     }
     return SCEMA_MD_OK;
@@ -942,30 +920,37 @@ int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const ch
   return SCEMA_MD_OK;
 }
 
-int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *kmax,
-                                int32_t *nk, int32_t *triples, int32_t triples_cap, char *errbuf, int32_t errcap) {
-  auto say = [&](const std::string &m) {
-    if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
-  };
-  say("");
-  if (!path || !box || natoms <= 0 || !(qsqsum >= 0.0) || (energy_unit != 0 && energy_unit != 1) || triples_cap < 0) { say("bad arguments"); return SCEMA_MD_ERR_ARG; }
-  BlTable T;
+// what the two pure host entries below open with: the message buffer emptied, the common argument rules beside the entry's own
+// (args_ok), the table of the file, a run's default parameters and a Topo of the two numbers the k-space set-up reads
+struct BlHostCase { BlTable T; scema_md_params p; Topo t; };
+static void bl_host_say(char *errbuf, int32_t errcap, const std::string &m) {
+  if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
+}
+static int bl_host_case(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, bool args_ok, char *errbuf, int32_t errcap,
+                        BlHostCase &C) {
+  bl_host_say(errbuf, errcap, "");
+  if (!path || !box || natoms <= 0 || !args_ok || (energy_unit != 0 && energy_unit != 1)) { bl_host_say(errbuf, errcap, "bad arguments"); return SCEMA_MD_ERR_ARG; }
   std::vector<int> map;
   std::string err;
-  if (!scema::read_born_long_params(path, energy_unit, T, map, err)) { say(err); return SCEMA_MD_ERR_IO; }
-  scema_md_params p;
-  scema_md_default_params(&p);
-  Topo t;
-  t.natoms = natoms;
-  t.qsqsum = qsqsum;
+  if (!scema::read_born_long_params(path, energy_unit, C.T, map, err)) { bl_host_say(errbuf, errcap, err); return SCEMA_MD_ERR_IO; }
+  scema_md_default_params(&C.p);
+  C.t.natoms = natoms;
+  C.t.qsqsum = qsqsum;
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *kmax,
+                                int32_t *nk, int32_t *triples, int32_t triples_cap, char *errbuf, int32_t errcap) {
+  BlHostCase C;
+  if (const int rc = bl_host_case(path, energy_unit, box, natoms, qsqsum, qsqsum >= 0.0 && triples_cap >= 0, errbuf, errcap, C)) return rc;
   EwaldSetup ew;
-  bl_setup(p, T.bd.cut_coul, T.accuracy, t, box, ew);
+  bl_setup(C.p, C.T.bd.cut_coul, C.T.accuracy, C.t, box, ew);
   const int n = (int)ew.kn.size() / 3;
   if (g_ewald) *g_ewald = ew.g;
   if (kmax) for (int d = 0; d < 3; d++) kmax[d] = ew.kmaxd[d];
   if (nk) *nk = n;
   if (triples) {
-    if (triples_cap < n) { say("triples_cap " + std::to_string(triples_cap) + " < nk = " + std::to_string(n)); return SCEMA_MD_ERR_ARG; }
+    if (triples_cap < n) { bl_host_say(errbuf, errcap, "triples_cap " + std::to_string(triples_cap) + " < nk = " + std::to_string(n)); return SCEMA_MD_ERR_ARG; }
     for (int k = 0; k < 3 * n; k++) triples[k] = ew.kn[k];
   }
   return SCEMA_MD_OK;
@@ -973,27 +958,15 @@ int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const dou
 
 int scema_md_born_long_mesh(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *grid,
                             char *errbuf, int32_t errcap) {
-  auto say = [&](const std::string &m) {
-    if (errbuf && errcap > 0) { std::strncpy(errbuf, m.c_str(), (size_t)errcap - 1); errbuf[errcap - 1] = 0; }
-  };
-  say("");
-  if (!path || !box || natoms <= 0 || !(qsqsum > 0.0) || (energy_unit != 0 && energy_unit != 1)) { say("bad arguments"); return SCEMA_MD_ERR_ARG; }
-  BlTable T;
-  std::vector<int> map;
-  std::string err;
-  if (!scema::read_born_long_params(path, energy_unit, T, map, err)) { say(err); return SCEMA_MD_ERR_IO; }
-  scema_md_params p;
-  scema_md_default_params(&p);
-  Topo t;
-  t.natoms = natoms;
-  t.qsqsum = qsqsum;
+  BlHostCase C;
+  if (const int rc = bl_host_case(path, energy_unit, box, natoms, qsqsum, qsqsum > 0.0, errbuf, errcap, C)) return rc;
   double g = 0.0;
   int pg[3] = {0, 0, 0};
-  bl_mesh_setup(p, T.bd.cut_coul, T.accuracy, t, box, g, pg);
+  bl_mesh_setup(C.p, C.T.bd.cut_coul, C.T.accuracy, C.t, box, g, pg);
   if (g_ewald) *g_ewald = g;
   if (grid) for (int d = 0; d < 3; d++) grid[d] = pg[d];
-  const std::string no = bl_mesh_refusal("Born/long", natoms, T.accuracy, pg);
-  if (!no.empty()) { say(no); return SCEMA_MD_ERR_ARG; }
+  const std::string no = bl_mesh_refusal("Born/long", natoms, C.T.accuracy, pg);
+  if (!no.empty()) { bl_host_say(errbuf, errcap, no); return SCEMA_MD_ERR_ARG; }
   return SCEMA_MD_OK;
 }
 

@@ -99,7 +99,7 @@ Policy plan_launch(const scema_md_engine *e, int ns) {
   // +6..12 % at 10-30 replicas, +4..6 % at 36-60; three parts 1-2 % behind, two 4-7 %); from 64 on two halves (three or
   // four parts: -0.5..+0.7 %, the chip is full either way).  Four is the most: a process has four hardware queues and further streams share them.  Five to eight
   // parts were measured -- six parts of a 36-replica batch: -12 %; with GPU_MAX_HW_QUEUES=8 -29 % -- and removed.  (They
-  // also showed a bug: the hipFFT plans of the PPPM path were shared by all part streams beyond the second, pppm_plan below.)
+  // also showed a bug: the hipFFT plans of the PPPM path were shared by all part streams beyond the second, pppm_plan of engine_kspace.cpp.)
   // SCEMA_MD_PARTS (2-4) forces a count for batches of 2 replicas per part and more, SCEMA_MD_SPLIT=0 runs every batch whole.
   if (e->split_streams && e->stream3 != nullptr && ns >= 9) {
     pol.nparts = parts_env > 0 ? (ns >= 2 * parts_env ? parts_env : 2) : ns < 10 ? 3 : ns < 64 ? 4 : 2;
@@ -227,7 +227,6 @@ struct OplsRun {
   int make_parts();
   int lay_out_sim(int pos);
   int lay_out_kspace();
-  int pppm_plan(const int pg[3], int batch, hipStream_t st, hipfftHandle &plan);
   int pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add = 1);
   int pppm_fork(hipStream_t st, int pos0, int na, bool new_box, bool with_bonded = false);
   hipError_t force_stage(hipStream_t st, const SimDev *Dh, int na, bool side, int bparts, int pairvir, bool pppm_ahead);
@@ -578,29 +577,6 @@ int OplsRun::lay_out_kspace() {
 }
 
 // ---- the PPPM chain ----
-// Batched 3-d Z2Z plans over grids that lie maxgrid complex elements apart (the charge grids of neighbouring simulations, and
-// all their field grids: three per simulation, simulation-major).  A plan owns work space, so each stream has its own.
-int OplsRun::pppm_plan(const int pg[3], int batch, hipStream_t st, hipfftHandle &plan) {
-  if ((long long)L.maxgrid > 0x7fffffffLL) return fail(e, SCEMA_MD_ERR_ARG, "PPPM grid of %d points is too large", L.maxgrid);
-  // A plan owns a work area and is bound to a stream when it runs: ONE PER STREAM that may run it.  (Until round 6 the key knew the main
-  // stream, the side stream and "the other one": with three or four part batches two parts shared the plans of their common mesh sizes --
-  // two replicas with the same mesh beyond the in-LDS solve, one in each, transformed through one work area at the same time.)
-  const int sk = st == e->stream ? 0 : st == e->stream2 ? 1 : st == e->stream3 ? 2 : st == e->rx_side1 ? 3 : -1;
-  if (sk < 0) return fail(e, SCEMA_MD_ERR_ARG, "PPPM transform on a stream the engine does not know");
-  const std::array<int, 6> key = {pg[0], pg[1], pg[2], batch, sk, L.maxgrid};
-  auto it = e->pppm_plans.find(key);
-  if (it == e->pppm_plans.end()) {
-    hipfftHandle h;
-    int n[3] = {pg[2], pg[1], pg[0]};   // slowest dimension first
-    // embed = the grid itself; the distance between consecutive grids is the batch's stride, not the grid's size
-    if (hipfftPlanMany(&h, 3, n, n, 1, L.maxgrid, n, 1, L.maxgrid, HIPFFT_Z2Z, batch) != HIPFFT_SUCCESS)
-      return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftPlanMany failed for a %d x %d x %d grid, batch %d", pg[0], pg[1], pg[2], batch);
-    it = e->pppm_plans.emplace(key, h).first;
-  }
-  plan = it->second;
-  return SCEMA_MD_OK;
-}
-
 // reciprocal part by PPPM for the simulations [pos0, pos0 + na) of a launch group (md_pppm.hip); after force_stage
 int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add) {
   if (L.maxgrid <= 0 || na <= 0) return SCEMA_MD_OK;
@@ -643,12 +619,7 @@ int OplsRun::pppm_stage(hipStream_t st, int pos0, int na, bool new_box, int add)
       if (run.first + run.second <= pos0 || run.first >= pos0 + na) continue;   // outside this launch group, or none of it is active any more
       const SimDev &S0 = e->h_sims[run.first];
       if (S0.pg[0] == 0) continue;
-      hipfftHandle plan;
-      const int rc = pppm_plan(S0.pg, (fields ? 3 : 1) * run.second, st, plan);
-      if (rc) return rc;
-      double *g = fields ? S0.pfield : S0.pgrid;
-      if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS || hipfftExecZ2Z(plan, (hipfftDoubleComplex *)g, (hipfftDoubleComplex *)g, dir) != HIPFFT_SUCCESS)
-        return fail(e, SCEMA_MD_ERR_DEVICE, "hipfftExecZ2Z failed");
+      if (const int rc = pppm_exec(e, S0.pg, (fields ? 3 : 1) * run.second, st, L.maxgrid, fields ? S0.pfield : S0.pgrid, dir)) return rc;
     }
     return SCEMA_MD_OK;
   };

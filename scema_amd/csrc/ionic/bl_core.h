@@ -49,13 +49,19 @@ BD_HD double bl_self(double k, double g, double vol, double qsqsum, double qsum,
   return -k * g * BD_ONE_OVER_SQRTPI * qsqsum + *e_background;
 }
 
-// Cartesian k of an integer triple in the box h = lx, ly, lz, yz, xz, xy (k = 2 pi n . h^-1), the layout of scema_eng::ewald_setup
+// the six inverse entries of the box h = lx, ly, lz, yz, xz, xy in the layout of BoxD::hinv (1/lx, 1/ly, 1/lz, the yz-, xz- and xy-term), with
+// the expressions of box_derive (md_device.h)
+BD_HD void bl_hinv(const double *h, double *i) {
+  i[0] = 1.0 / h[0]; i[1] = 1.0 / h[1]; i[2] = 1.0 / h[2];
+  i[3] = -h[3] / (h[1] * h[2]); i[4] = (h[3] * h[5] - h[1] * h[4]) / (h[0] * h[1] * h[2]); i[5] = -h[5] / (h[0] * h[1]);
+}
+// Cartesian k of an integer triple in that box (k = 2 pi n . h^-1), the layout of scema_eng::ewald_setup
 BD_HD void bl_kvec(const double *h, int n1, int n2, int n3, double *k) {
-  const double i0 = 1.0 / h[0], i1 = 1.0 / h[1], i2 = 1.0 / h[2];
-  const double i3 = -h[3] / (h[1] * h[2]), i4 = (h[3] * h[5] - h[1] * h[4]) / (h[0] * h[1] * h[2]), i5 = -h[5] / (h[0] * h[1]);
-  k[0] = BL_TWO_PI * (i0 * n1);
-  k[1] = BL_TWO_PI * (i5 * n1 + i1 * n2);
-  k[2] = BL_TWO_PI * (i4 * n1 + i3 * n2 + i2 * n3);
+  double i[6];
+  bl_hinv(h, i);
+  k[0] = BL_TWO_PI * (i[0] * n1);
+  k[1] = BL_TWO_PI * (i[5] * n1 + i[1] * n2);
+  k[2] = BL_TWO_PI * (i[4] * n1 + i[3] * n2 + i[2] * n3);
 }
 
 // c_k of a k-vector: (4 pi K/V) exp(-k^2/4g^2)/k^2 (the half-space factor 2 is inside)

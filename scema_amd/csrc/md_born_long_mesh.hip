@@ -1,6 +1,6 @@
 // md_born_long_mesh.hip -- gfx950 kernels of the mesh reciprocal solver of the Ewald ionic force stage: PPPM (order 5, ik
 // differentiation, the optimal influence function of the step's box) on the row layout, for the replicas beyond the k list of
-// md_born_long.hip.  The arithmetic is ionic/blm_core.h; the transforms between the kernels are the engine's batched hipFFT plans.  One
+// md_born_long.hip.  The arithmetic is pppm/pppm_core.h and ionic/blm_core.h; the transforms between the kernels are the engine's batched hipFFT plans.  One
 // launch covers every replica of the group (blockIdx.y); a replica on the Ewald sum (BlmView::n = 0) is left alone by every kernel.
 //   k_blm_assign ... every atom adds its 125 weighted charges q w_x w_y w_z NG/V to the replica's 64-bit FIXED-POINT grid with integer
 //                    atomics: integer addition commutes, so the grid does not depend on arrival order, launch shape or batch composition.
@@ -23,8 +23,8 @@
 #include "md_rowforce.h"
 
 #define BLM_TPB 256
-#define BLM_NPT (BLM_ORDER * BLM_ORDER * BLM_ORDER)
-static_assert(BLM_ORDER == 5 && BLM_NPT <= 128, "two passes of a wave cover an atom's stencil");
+#define BLM_NPT (PPPM_ORDER * PPPM_ORDER * PPPM_ORDER)
+static_assert(PPPM_ORDER == 5 && BLM_NPT <= 128, "two passes of a wave cover an atom's stencil");
 
 // what the kernels take from a BlmView: a mesh whose dimensions or product the buffers do not hold counts as none
 struct BlmShape { int n[3], ng; };
@@ -42,25 +42,25 @@ __device__ __forceinline__ void blm_box(const RowView &V, double *h, double *lo)
   for (int k = 0; k < 3; k++) lo[k] = V.lo[k];
 }
 // w[k] of a runtime k in 0 .. 4 without an indexed register array
-__device__ __forceinline__ double blm_pick(const double (&w)[BLM_ORDER], int k) {
+__device__ __forceinline__ double blm_pick(const double (&w)[PPPM_ORDER], int k) {
   return k == 0 ? w[0] : (k == 1 ? w[1] : (k == 2 ? w[2] : (k == 3 ? w[3] : w[4])));
 }
 // the stencil of atom i: weights per dimension and the nearest grid point per dimension
-__device__ __forceinline__ void blm_stencil(const RowView &V, const BlmShape &sh, const double *h, const double *lo, int i, double (&wx)[BLM_ORDER],
-                                            double (&wy)[BLM_ORDER], double (&wz)[BLM_ORDER], int &ix, int &iy, int &iz) {
+__device__ __forceinline__ void blm_stencil(const RowView &V, const BlmShape &sh, const double *h, const double *lo, int i, double (&wx)[PPPM_ORDER],
+                                            double (&wy)[PPPM_ORDER], double (&wz)[PPPM_ORDER], int &ix, int &iy, int &iz) {
   const double x[3] = {V.x[3 * i], V.x[3 * i + 1], V.x[3 * i + 2]};
   double t[3];
   blm_frac(h, lo, x, t);
-  ix = min(max(blm_weights(t[0] * sh.n[0], wx), 0), sh.n[0]);
-  iy = min(max(blm_weights(t[1] * sh.n[1], wy), 0), sh.n[1]);
-  iz = min(max(blm_weights(t[2] * sh.n[2], wz), 0), sh.n[2]);
+  ix = min(max(pppm_weights(t[0] * sh.n[0], wx), 0), sh.n[0]);
+  iy = min(max(pppm_weights(t[1] * sh.n[1], wy), 0), sh.n[1]);
+  iz = min(max(pppm_weights(t[2] * sh.n[2], wz), 0), sh.n[2]);
 }
 // point p of 125 (x fastest) of that stencil: its grid index and the product of its weights
-__device__ __forceinline__ int blm_point(const BlmShape &sh, int p, const double (&wx)[BLM_ORDER], const double (&wy)[BLM_ORDER], const double (&wz)[BLM_ORDER],
+__device__ __forceinline__ int blm_point(const BlmShape &sh, int p, const double (&wx)[PPPM_ORDER], const double (&wy)[PPPM_ORDER], const double (&wz)[PPPM_ORDER],
                                          int ix, int iy, int iz, double &w) {
   const int c = p / 25, r = p - 25 * c, b = r / 5, k = r - 5 * b;
   w = blm_pick(wz, c) * blm_pick(wy, b) * blm_pick(wx, k);
-  const int gx = blm_wrap(ix + k - 2, sh.n[0]), gy = blm_wrap(iy + b - 2, sh.n[1]), gz = blm_wrap(iz + c - 2, sh.n[2]);
+  const int gx = pppm_wrap1(ix + k - 2, sh.n[0]), gy = pppm_wrap1(iy + b - 2, sh.n[1]), gz = pppm_wrap1(iz + c - 2, sh.n[2]);
   return min((gz * sh.n[1] + gy) * sh.n[0] + gx, sh.ng - 1);
 }
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(BLM_TPB) void k_blm_assign(const SimDev *sims, cons
     if (i >= n) break;   // (uniform over the wave)
     const double z = q[i] * delvolinv;
     if (z == 0.0) continue;
-    double wx[BLM_ORDER], wy[BLM_ORDER], wz[BLM_ORDER];
+    double wx[PPPM_ORDER], wy[PPPM_ORDER], wz[PPPM_ORDER];
     int ix, iy, iz;
     blm_stencil(V, sh, h, lo, i, wx, wy, wz, ix, iy, iz);
 #pragma unroll
@@ -118,10 +118,10 @@ __global__ __launch_bounds__(BLM_TPB) void k_blm_gf(const RowView *views, const 
   const BlmShape sh = blm_shape(M);
   const int idx = blockIdx.x * BLM_TPB + threadIdx.x;
   if (idx >= sh.ng) return;
-  double h[6], lo[3];
-  blm_box(views[blockIdx.y], h, lo);
+  double hinv[6];
+  bl_hinv(views[blockIdx.y].h, hinv);
   const int m1 = idx % sh.n[0], m2 = (idx / sh.n[0]) % sh.n[1], m3 = idx / (sh.n[0] * sh.n[1]);
-  M.gf[idx] = M.g > 0.0 ? blm_gf(h, M.g, sh.n, m1, m2, m3) : 0.0;
+  M.gf[idx] = M.g > 0.0 ? pppm_gf(hinv, M.g, sh.n[0], sh.n[1], sh.n[2], m1, m2, m3) : 0.0;
 }
 
 // (no thread leaves before the sums: a thread past the mesh adds zeros)
@@ -139,8 +139,12 @@ __global__ __launch_bounds__(BLM_TPB) void k_blm_poisson(const SimDev *sims, con
   double esum[1] = {0.0}, w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (idx < sh.ng) {
     const int m1 = idx % sh.n[0], m2 = (idx / sh.n[0]) % sh.n[1], m3 = idx / (sh.n[0] * sh.n[1]);
-    double kv[3], pr, pi;
-    blm_mode(h, M.g, kc, sh.n, m1, m2, m3, M.cgrid[2 * (size_t)idx], M.cgrid[2 * (size_t)idx + 1], M.gf[idx], kv, w, &esum[0], &pr, &pi);
+    double hinv[6], kv[3], pr, pi;
+    bl_hinv(h, hinv);
+    pppm_kvec(hinv, pppm_signed(m1, sh.n[0]), pppm_signed(m2, sh.n[1]), pppm_signed(m3, sh.n[2]), kv[0], kv[1], kv[2]);
+    const double scaleinv = 1.0 / (double)sh.ng;
+    pppm_mode_term(h[0] * h[1] * h[2], kc, M.g, kv[0], kv[1], kv[2], M.cgrid[2 * (size_t)idx] * scaleinv, M.cgrid[2 * (size_t)idx + 1] * scaleinv, M.gf[idx], w,
+                   esum[0], pr, pi);
     const size_t gs = (size_t)M.gcap;
 #pragma unroll
     for (int c = 0; c < 3; c++) {   // (a + i b)(-i k) = b k - i a k
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_blm_interp(const SimDev *sims
     const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
     const bool valid = i < n;
     const int ic = valid ? i : n - 1;
-    double wx[BLM_ORDER], wy[BLM_ORDER], wz[BLM_ORDER];
+    double wx[PPPM_ORDER], wy[PPPM_ORDER], wz[PPPM_ORDER];
     int ix, iy, iz;
     blm_stencil(V, sh, h, lo, ic, wx, wy, wz, ix, iy, iz);
     double f0 = 0.0, f1 = 0.0, f2 = 0.0;

@@ -22,6 +22,7 @@
 #include "md_pppm_fstride.h"
 #include "md_pppm_tile.h"
 #include "md_types.h"
+#include "pppm/pppm_core.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -29,50 +30,9 @@
 static inline dim3 grid2(int nx, int ns) { return dim3((unsigned)nx, (unsigned)ns, 1); }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-#define PP_ORDER 5
 #define PP_TPB 1024
 #define PP_SOLVE_MAX 2900   // grid points up to which k_pppm_solve keeps three complex grids and the twiddles in 144 KB of LDS
 
-// weights of the order-5 cardinal B-spline at the 5 grid points i-2 .. i+2 around u, i = floor(u + 1/2).  With dx = i - u in (-1/2, 1/2] the
-// argument of weight k, t_k = 9/2 - k - dx, lies in the spline's piece 4 - k for every k, at the SAME local coordinate s = 1/2 - dx in [0, 1):
-// the five weights are the five quartic blending polynomials of the uniform B-spline in s (they sum to 1) -- 18 multiply-adds instead of the
-// recursion over indicator functions that the oracle walks (oracle: pppm_weights; 330 instructions per dimension, half of the spreading and of
-// the interpolation kernel until round 5).  Same numbers to the last places (the two forms round differently: 1e-16).
-static_assert(PP_ORDER == 5, "the blending polynomials below are those of order 5");
-// the nearest grid point of u (0 <= u <= n gives 0 .. n): the centre of the stencil, and -- taken mod n -- what decides an atom's home tile
-__device__ __forceinline__ int pppm_nearest(double u) { return (int)floor(u + 0.5); }
-__device__ __forceinline__ void pppm_blend(double s, double (&w)[PP_ORDER]) {
-  const double r = 1.0 - s;
-  const double s2 = s * s, r2 = r * r;
-  constexpr double q = 1.0 / 24.0;
-  w[4] = q * (s2 * s2);
-  w[0] = q * (r2 * r2);
-  w[3] = fma(fma(fma(fma(-4.0 * q, s, 4.0 * q), s, 6.0 * q), s, 4.0 * q), s, q);
-  w[2] = fma(fma(fma(fma(6.0 * q, s, -12.0 * q), s, -6.0 * q), s, 12.0 * q), s, 11.0 * q);
-  w[1] = fma(fma(fma(fma(-4.0 * q, s, 12.0 * q), s, -6.0 * q), s, -12.0 * q), s, 11.0 * q);
-}
-__device__ __forceinline__ int pppm_weights(double u, double (&w)[PP_ORDER]) {
-  const int i = pppm_nearest(u);
-  pppm_blend(0.5 - ((double)i - u), w);
-  return i;
-}
-// the same weights around a nearest point that was decided before (k_pppm_keys) and is known mod n: km == 0 stands for 0 or for n
-__device__ __forceinline__ void pppm_weights_at(double u, int n, int km, double (&w)[PP_ORDER]) {
-  const int i = (km == 0 && u >= 1.0) ? n : km;
-  pppm_blend(0.5 - ((double)i - u), w);
-}
-__device__ __forceinline__ int pmod(int a, int n) { const int r = a % n; return r < 0 ? r + n : r; }
-// the five periodic grid indices i-2 .. i+2 of one dimension (0 <= i <= n); grids of fewer than 4 points wrap more than once
-__device__ __forceinline__ void pppm_wrap(int i, int n, int (&g)[PP_ORDER]) {
-#pragma unroll
-  for (int k = 0; k < PP_ORDER; k++) {
-    const int v = i + k - 2;
-    g[k] = v < 0 ? v + n : (v >= n ? v - n : v);
-  }
-  if (n < 4)
-#pragma unroll
-    for (int k = 0; k < PP_ORDER; k++) g[k] = pmod(i + k - 2, n);
-}
 __device__ __forceinline__ void pos_lamda(const BoxD &b, double x0, double x1, double x2, double &t0, double &t1, double &t2) {
   const double d0 = x0 - b.lo[0], d1 = x1 - b.lo[1], d2 = x2 - b.lo[2];
   const double l0 = b.hinv[0] * d0 + b.hinv[5] * d1 + b.hinv[4] * d2, l1 = b.hinv[1] * d1 + b.hinv[3] * d2, l2 = b.hinv[2] * d2;
@@ -157,8 +117,8 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread(const SimDev *sims, int sp
     const int aA = a0 + lane * rows + r, aB = aA + 1;
     const bool vA = aA < a1, vB = r + 1 < rows && aB < a1;
     if (!vA) continue;
-    double wxA[PP_ORDER], wyA[PP_ORDER], wzA[PP_ORDER], wxB[PP_ORDER] = {0, 0, 0, 0, 0}, wyB[PP_ORDER] = {0, 0, 0, 0, 0}, wzB[PP_ORDER] = {0, 0, 0, 0, 0};
-    int gxA[PP_ORDER], gyA[PP_ORDER], gzA[PP_ORDER], gxB[PP_ORDER] = {0, 0, 0, 0, 0}, gyB[PP_ORDER] = {0, 0, 0, 0, 0}, gzB[PP_ORDER] = {0, 0, 0, 0, 0};
+    double wxA[PPPM_ORDER], wyA[PPPM_ORDER], wzA[PPPM_ORDER], wxB[PPPM_ORDER] = {0, 0, 0, 0, 0}, wyB[PPPM_ORDER] = {0, 0, 0, 0, 0}, wzB[PPPM_ORDER] = {0, 0, 0, 0, 0};
+    int gxA[PPPM_ORDER], gyA[PPPM_ORDER], gzA[PPPM_ORDER], gxB[PPPM_ORDER] = {0, 0, 0, 0, 0}, gyB[PPPM_ORDER] = {0, 0, 0, 0, 0}, gzB[PPPM_ORDER] = {0, 0, 0, 0, 0};
     double l0, l1, l2;
     atom_lamda(S, b, aA, l0, l1, l2);
     const int ixA = pppm_weights(l0 * nx, wxA), iyA = pppm_weights(l1 * ny, wyA), izA = pppm_weights(l2 * nz, wzA);
@@ -174,17 +134,17 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread(const SimDev *sims, int sp
     }
     const bool merged = vB && ixA == ixB && iyA == iyB && izA == izB;
 #pragma unroll
-    for (int k = 0; k < PP_ORDER; k++) { wxA[k] *= zA; if (vB) wxB[k] *= zB; }
+    for (int k = 0; k < PPPM_ORDER; k++) { wxA[k] *= zA; if (vB) wxB[k] *= zB; }
     if (zA != 0.0 || (merged && zB != 0.0)) {
 #pragma unroll
-      for (int c = 0; c < PP_ORDER; c++) {
+      for (int c = 0; c < PPPM_ORDER; c++) {
 #pragma unroll
-        for (int bb = 0; bb < PP_ORDER; bb++) {
+        for (int bb = 0; bb < PPPM_ORDER; bb++) {
           const double zyA = wzA[c] * wyA[bb], zyB = merged ? wzB[c] * wyB[bb] : 0.0;   // (B's weights are zeros where there is no B)
           const int row = (gzA[c] * ny + gyA[bb]) * nxp;
           double *prow = s_grid + row + ixA;   // PADX
 #pragma unroll
-          for (int k = 0; k < PP_ORDER; k++) {
+          for (int k = 0; k < PPPM_ORDER; k++) {
             const double val = fma(zyB, wxB[k], zyA * wxA[k]);
             if (LDS && PADX) (void)__hip_atomic_fetch_add(prow + k, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             else if (LDS) (void)__hip_atomic_fetch_add(&s_grid[row + gxA[k]], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -195,14 +155,14 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread(const SimDev *sims, int sp
     }
     if (vB && !merged && zB != 0.0) {
 #pragma unroll
-      for (int c = 0; c < PP_ORDER; c++) {
+      for (int c = 0; c < PPPM_ORDER; c++) {
 #pragma unroll
-        for (int bb = 0; bb < PP_ORDER; bb++) {
+        for (int bb = 0; bb < PPPM_ORDER; bb++) {
           const double zyB = wzB[c] * wyB[bb];
           const int row = (gzB[c] * ny + gyB[bb]) * nxp;
           double *prow = s_grid + row + ixB;   // PADX
 #pragma unroll
-          for (int k = 0; k < PP_ORDER; k++) {
+          for (int k = 0; k < PPPM_ORDER; k++) {
             if (LDS && PADX) (void)__hip_atomic_fetch_add(prow + k, zyB * wxB[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             else if (LDS) (void)__hip_atomic_fetch_add(&s_grid[row + gxB[k]], zyB * wxB[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             else atomicAdd(&rho[row + gxB[k]].x, zyB * wxB[k]);
@@ -293,7 +253,7 @@ __global__ __launch_bounds__(PP_BIN_TPB) void k_pppm_bins(const SimDev *sims, in
       if (q[j] != 0.0) {
         double l0, l1, l2;
         pos_lamda(b, x0[j], x1[j], x2[j], l0, l1, l2);
-        const int ix = min(max(pppm_nearest(l0 * nx), 0), nx), iy = pmod(pppm_nearest(l1 * ny), ny), iz = pmod(pppm_nearest(l2 * nz), nz);
+        const int ix = min(max(pppm_nearest(l0 * nx), 0), nx), iy = pppm_mod(pppm_nearest(l1 * ny), ny), iz = pppm_mod(pppm_nearest(l2 * nz), nz);
         bin = (iz * ny + iy) * nbx + ix;
         rank = atomicAdd(&s_cnt[bin], 1);
       }
@@ -383,7 +343,7 @@ __global__ __launch_bounds__(256) void k_pppm_spread_binned(const SimDev *sims, 
       px[j] = S.x[3 * at[j]]; py[j] = S.x[3 * at[j] + 1]; pz[j] = S.x[3 * at[j] + 2];
       zq[j] = j < n ? delvolinv * S.q[at[j]] : 0.0;
     }
-    double wx[M][PP_ORDER], wy[M][PP_ORDER], wz[M][PP_ORDER];
+    double wx[M][PPPM_ORDER], wy[M][PPPM_ORDER], wz[M][PPPM_ORDER];
 #pragma unroll
     for (int j = 0; j < M; j++) {
       double l0, l1, l2;
@@ -391,35 +351,30 @@ __global__ __launch_bounds__(256) void k_pppm_spread_binned(const SimDev *sims, 
       pppm_blend(0.5 - ((double)ix - l0 * nx), wx[j]);
       pppm_weights_at(l1 * ny, ny, iy, wy[j]); pppm_weights_at(l2 * nz, nz, iz, wz[j]);
 #pragma unroll
-      for (int k = 0; k < PP_ORDER; k++) wx[j][k] *= zq[j];
+      for (int k = 0; k < PPPM_ORDER; k++) wx[j][k] *= zq[j];
     }
-    int gy[PP_ORDER], gz[PP_ORDER];
+    int gy[PPPM_ORDER], gz[PPPM_ORDER];
     pppm_wrap(iy, ny, gy); pppm_wrap(iz, nz, gz);
 #pragma unroll
-    for (int c = 0; c < PP_ORDER; c++) {
+    for (int c = 0; c < PPPM_ORDER; c++) {
 #pragma unroll
-      for (int bb = 0; bb < PP_ORDER; bb++) {
-        double acc[PP_ORDER] = {0, 0, 0, 0, 0};
+      for (int bb = 0; bb < PPPM_ORDER; bb++) {
+        double acc[PPPM_ORDER] = {0, 0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < M; j++) {
           const double zy = wz[j][c] * wy[j][bb];
 #pragma unroll
-          for (int k = 0; k < PP_ORDER; k++) acc[k] = fma(zy, wx[j][k], acc[k]);
+          for (int k = 0; k < PPPM_ORDER; k++) acc[k] = fma(zy, wx[j][k], acc[k]);
         }
         double *prow = s_grid + (gz[c] * ny + gy[bb]) * nxp + ix;
 #pragma unroll
-        for (int k = 0; k < PP_ORDER; k++) (void)__hip_atomic_fetch_add(prow + k, acc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for (int k = 0; k < PPPM_ORDER; k++) (void)__hip_atomic_fetch_add(prow + k, acc[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
   }
   pppm_grid_out<true>(S, nx, ny, nz, split);
 }
 
-__device__ __forceinline__ double sinc_pow10(double x) {
-  if (x == 0.0) return 1.0;
-  const double s = sin(x) / x, s2 = s * s, s4 = s2 * s2;
-  return s4 * s4 * s2;
-}
 // optimal influence function of the current box (ik differentiation), alias sums |m| <= 2 per dimension
 __global__ __launch_bounds__(256) void k_pppm_gf(const SimDev *sims) {
   const SimDev &S = sims[blockIdx.y];
@@ -427,37 +382,9 @@ __global__ __launch_bounds__(256) void k_pppm_gf(const SimDev *sims) {
   if (nx == 0) return;
   const int NG = nx * ny * nz, idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= NG) return;
-  const int m1 = idx % nx, m2 = (idx / nx) % ny, m3 = idx / (nx * ny);
-  const int p1 = m1 - nx * (2 * m1 / nx), p2 = m2 - ny * (2 * m2 / ny), p3 = m3 - nz * (2 * m3 / nz);
-  if (p1 == 0 && p2 == 0 && p3 == 0) { S.pgf[idx] = 0.0; return; }
   BoxD b;
   box_derive(S.sc->box, b);
-  const double twopi = 2.0 * MD_PI;
-  const double kx = twopi * (b.hinv[0] * p1), ky = twopi * (b.hinv[5] * p1 + b.hinv[1] * p2), kz = twopi * (b.hinv[4] * p1 + b.hinv[3] * p2 + b.hinv[2] * p3);
-  const double sqk = kx * kx + ky * ky + kz * kz, g2inv4 = 0.25 / (S.g_ewald * S.g_ewald);
-  double wxs[5], wys[5], wzs[5];   // squared transform of the assignment function, per lattice index
-#pragma unroll
-  for (int a = 0; a < 5; a++) {
-    wxs[a] = sinc_pow10(MD_PI * (double)(p1 + nx * (a - 2)) / nx);
-    wys[a] = sinc_pow10(MD_PI * (double)(p2 + ny * (a - 2)) / ny);
-    wzs[a] = sinc_pow10(MD_PI * (double)(p3 + nz * (a - 2)) / nz);
-  }
-  double num = 0.0, den = 0.0;
-  for (int a3 = 0; a3 < 5; a3++)
-    for (int a2 = 0; a2 < 5; a2++) {
-      const int q2 = p2 + ny * (a2 - 2), q3 = p3 + nz * (a3 - 2);
-      const double w23 = wys[a2] * wzs[a3];
-#pragma unroll
-      for (int a1 = 0; a1 < 5; a1++) {
-        const int q1 = p1 + nx * (a1 - 2);
-        const double qx = twopi * (b.hinv[0] * q1), qy = twopi * (b.hinv[5] * q1 + b.hinv[1] * q2), qz = twopi * (b.hinv[4] * q1 + b.hinv[3] * q2 + b.hinv[2] * q3);
-        const double dot2 = qx * qx + qy * qy + qz * qz;
-        const double w2 = wxs[a1] * w23;
-        den += w2;
-        num += (kx * qx + ky * qy + kz * qz) / dot2 * exp(-dot2 * g2inv4) * w2;
-      }
-    }
-  S.pgf[idx] = 4.0 * MD_PI / sqk * num / (den * den);
+  S.pgf[idx] = pppm_gf(b.hinv, S.g_ewald, nx, ny, nz, idx % nx, (idx / nx) % ny, idx / (nx * ny));
 }
 
 // one reciprocal mode: wave vector of grid index idx, and -- with the (unnormalised) transform r of the charge grid -- its share of
@@ -465,23 +392,16 @@ __global__ __launch_bounds__(256) void k_pppm_gf(const SimDev *sims) {
 __device__ __forceinline__ double2 pppm_mode(const SimDev &S, const BoxD &b, int idx, int nx, int ny, int nz, double2 r, double (&kv)[3], double (&v)[6], double &e) {
   const int NG = nx * ny * nz;
   const int m1 = idx % nx, m2 = (idx / nx) % ny, m3 = idx / (nx * ny);
-  const int p1 = m1 - nx * (2 * m1 / nx), p2 = m2 - ny * (2 * m2 / ny), p3 = m3 - nz * (2 * m3 / nz);
-  const double twopi = 2.0 * MD_PI;
-  const double kx = twopi * (b.hinv[0] * p1), ky = twopi * (b.hinv[5] * p1 + b.hinv[1] * p2), kz = twopi * (b.hinv[4] * p1 + b.hinv[3] * p2 + b.hinv[2] * p3);
+  double kx, ky, kz;
+  pppm_kvec(b.hinv, pppm_signed(m1, nx), pppm_signed(m2, ny), pppm_signed(m3, nz), kx, ky, kz);
   kv[0] = kx; kv[1] = ky; kv[2] = kz;
   const double gf = S.pgf[idx], scaleinv = 1.0 / (double)NG;
   const double ar = r.x * scaleinv, ai = r.y * scaleinv;
-  if (gf != 0.0) {
-    const double sqk = kx * kx + ky * ky + kz * kz;
-    const double eg = 0.5 * b.vol * MD_QQRD2E * gf * (ar * ar + ai * ai);
-    const double vterm = -2.0 * (1.0 / sqk + 0.25 / (S.g_ewald * S.g_ewald));
-    e += eg;
-    v[0] += eg * (1.0 + vterm * kx * kx); v[1] += eg * (1.0 + vterm * ky * ky); v[2] += eg * (1.0 + vterm * kz * kz);
-    v[3] += eg * vterm * kx * ky; v[4] += eg * vterm * kx * kz; v[5] += eg * vterm * ky * kz;
-  }
+  double pr, pi;
+  pppm_mode_term(b.vol, MD_QQRD2E, S.g_ewald, kx, ky, kz, ar, ai, gf, v, e, pr, pi);
   if (idx == 0)   // self energy and neutralising background
     e -= MD_QQRD2E * (S.g_ewald * S.qsqsum / sqrt(MD_PI) + 0.5 * MD_PI * S.qsum * S.qsum / (S.g_ewald * S.g_ewald * b.vol));
-  return make_double2(gf * ar, gf * ai);
+  return make_double2(pr, pi);
 }
 
 // energy, virial and the three field spectra; the charge grid holds rho(k) (unnormalised), the field grids receive E_x, E_y, E_z (k)
@@ -724,21 +644,21 @@ __global__ __launch_bounds__(TPB_) void k_pppm_force(const SimDev *sims, int spl
     }
     double l0, l1, l2;
     atom_lamda(S, b, a, l0, l1, l2);
-    double wx[PP_ORDER], wy[PP_ORDER], wz[PP_ORDER];
-    int gx[PP_ORDER], gy[PP_ORDER], gz[PP_ORDER];
+    double wx[PPPM_ORDER], wy[PPPM_ORDER], wz[PPPM_ORDER];
+    int gx[PPPM_ORDER], gy[PPPM_ORDER], gz[PPPM_ORDER];
     pppm_wrap(pppm_weights(l0 * nx, wx), nx, gx);
     pppm_wrap(pppm_weights(l1 * ny, wy), ny, gy);
     pppm_wrap(pppm_weights(l2 * nz, wz), nz, gz);
     double fx = 0.0, fy = 0.0, fz = 0.0;
 #pragma unroll
-    for (int c = 0; c < PP_ORDER; c++) {
+    for (int c = 0; c < PPPM_ORDER; c++) {
 #pragma unroll
-      for (int bb = 0; bb < PP_ORDER; bb++) {
+      for (int bb = 0; bb < PPPM_ORDER; bb++) {
         const double zy = wz[c] * wy[bb];
         const int row = LDS ? gz[c] * ps + gy[bb] * rs : (gz[c] * ny + gy[bb]) * nx;
         double rx = 0.0, ry = 0.0, rz = 0.0;
 #pragma unroll
-        for (int k = 0; k < PP_ORDER; k++) {
+        for (int k = 0; k < PPPM_ORDER; k++) {
           const int g = row + gx[k];
           if (LDS) { rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[FS + g], ry); rz = fma(wx[k], s_grid[2 * FS + g], rz); }
           else if (REALF) { const double *fr = (const double *)S.pfield; rx = fma(wx[k], fr[g], rx); ry = fma(wx[k], fr[gs + g], ry); rz = fma(wx[k], fr[2 * gs + g], rz); }
@@ -772,7 +692,7 @@ __global__ __launch_bounds__(256) void k_pppm_keys(const SimDev *sims) {
   box_uniform(b);
   double l0, l1, l2;
   atom_lamda(S, b, a, l0, l1, l2);
-  const int iy = pmod(pppm_nearest(l1 * ny), ny), iz = pmod(pppm_nearest(l2 * nz), nz);
+  const int iy = pppm_mod(pppm_nearest(l1 * ny), ny), iz = pppm_mod(pppm_nearest(l2 * nz), nz);
   pppm_keys_of(S)[a] = iy | (iz << 16) | (S.q[a] == 0.0 ? (int)0x80000000 : 0);
 }
 // the tile of this workgroup: origin and extent of its brick (false: the replica has fewer tiles, or no mesh)
@@ -838,8 +758,8 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread_tiled(const SimDev *sims, 
     }
     if (!found) break;
     const int aB = aA + 1;
-    double wxA[PP_ORDER], wyA[PP_ORDER], wzA[PP_ORDER], wxB[PP_ORDER] = {0, 0, 0, 0, 0}, wyB[PP_ORDER] = {0, 0, 0, 0, 0}, wzB[PP_ORDER] = {0, 0, 0, 0, 0};
-    int gxA[PP_ORDER], gyA[PP_ORDER], gzA[PP_ORDER], gxB[PP_ORDER] = {0, 0, 0, 0, 0}, gyB[PP_ORDER] = {0, 0, 0, 0, 0}, gzB[PP_ORDER] = {0, 0, 0, 0, 0};
+    double wxA[PPPM_ORDER], wyA[PPPM_ORDER], wzA[PPPM_ORDER], wxB[PPPM_ORDER] = {0, 0, 0, 0, 0}, wyB[PPPM_ORDER] = {0, 0, 0, 0, 0}, wzB[PPPM_ORDER] = {0, 0, 0, 0, 0};
+    int gxA[PPPM_ORDER], gyA[PPPM_ORDER], gzA[PPPM_ORDER], gxB[PPPM_ORDER] = {0, 0, 0, 0, 0}, gyB[PPPM_ORDER] = {0, 0, 0, 0, 0}, gzB[PPPM_ORDER] = {0, 0, 0, 0, 0};
     double l0, l1, l2;
     atom_lamda(S, b, aA, l0, l1, l2);
     const int ixA = pppm_weights(l0 * nx, wxA);
@@ -857,35 +777,35 @@ __global__ __launch_bounds__(TPB_) void k_pppm_spread_tiled(const SimDev *sims, 
     }
     const bool merged = vB && ixA == ixB && kA == kB;
 #pragma unroll
-    for (int k = 0; k < PP_ORDER; k++) { wxA[k] *= zA; wxB[k] *= zB; }
+    for (int k = 0; k < PPPM_ORDER; k++) { wxA[k] *= zA; wxB[k] *= zB; }
 #pragma unroll
-    for (int c = 0; c < PP_ORDER; c++) {
+    for (int c = 0; c < PPPM_ORDER; c++) {
       const int lz = gzA[c] - z0;
       if ((unsigned)lz >= (unsigned)bzc) continue;
 #pragma unroll
-      for (int bb = 0; bb < PP_ORDER; bb++) {
+      for (int bb = 0; bb < PPPM_ORDER; bb++) {
         const int ly = gyA[bb] - y0;
         if ((unsigned)ly >= (unsigned)byc) continue;
         const double zyA = wzA[c] * wyA[bb], zyB = merged ? wzB[c] * wyB[bb] : 0.0;
         double *prow = s_grid + (lz * byc + ly) * nx;
 #pragma unroll
-        for (int k = 0; k < PP_ORDER; k++)
+        for (int k = 0; k < PPPM_ORDER; k++)
           (void)__hip_atomic_fetch_add(prow + gxA[k], fma(zyB, wxB[k], zyA * wxA[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
     if (vB && !merged) {
 #pragma unroll
-      for (int c = 0; c < PP_ORDER; c++) {
+      for (int c = 0; c < PPPM_ORDER; c++) {
         const int lz = gzB[c] - z0;
         if ((unsigned)lz >= (unsigned)bzc) continue;
 #pragma unroll
-        for (int bb = 0; bb < PP_ORDER; bb++) {
+        for (int bb = 0; bb < PPPM_ORDER; bb++) {
           const int ly = gyB[bb] - y0;
           if ((unsigned)ly >= (unsigned)byc) continue;
           const double zyB = wzB[c] * wyB[bb];
           double *prow = s_grid + (lz * byc + ly) * nx;
 #pragma unroll
-          for (int k = 0; k < PP_ORDER; k++) (void)__hip_atomic_fetch_add(prow + gxB[k], zyB * wxB[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          for (int k = 0; k < PPPM_ORDER; k++) (void)__hip_atomic_fetch_add(prow + gxB[k], zyB * wxB[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
     }
@@ -916,7 +836,7 @@ __global__ __launch_bounds__(TPB_) void k_pppm_force_tiled(const SimDev *sims, i
   const double *fr = (const double *)S.pfield;
   for (int k = threadIdx.x; k < SN; k += T) {
     const int row = k / nx, x = k - row * nx, j = row / sy, i = row - j * sy;
-    const int g = ((hz ? pmod(z0 - 2 + j, nz) : j) * ny + (hy ? pmod(y0 - 2 + i, ny) : i)) * nx + x;
+    const int g = ((hz ? pppm_mod(z0 - 2 + j, nz) : j) * ny + (hy ? pppm_mod(y0 - 2 + i, ny) : i)) * nx + x;
     if (REALF) { s_grid[k] = fr[g]; s_grid[SN + k] = fr[gs + g]; s_grid[2 * SN + k] = fr[2 * gs + g]; }
     else { s_grid[k] = ex[g].x; s_grid[SN + k] = ey[g].x; s_grid[2 * SN + k] = ez[g].x; }
   }
@@ -942,24 +862,24 @@ __global__ __launch_bounds__(TPB_) void k_pppm_force_tiled(const SimDev *sims, i
     }
     double l0, l1, l2;
     atom_lamda(S, b, at, l0, l1, l2);
-    double wx[PP_ORDER], wy[PP_ORDER], wz[PP_ORDER];
-    int gx[PP_ORDER], jy[PP_ORDER], jz[PP_ORDER];
+    double wx[PPPM_ORDER], wy[PPPM_ORDER], wz[PPPM_ORDER];
+    int gx[PPPM_ORDER], jy[PPPM_ORDER], jz[PPPM_ORDER];
     const int iy = PP_KEY_Y(key), iz = PP_KEY_Z(key);
     pppm_wrap(pppm_weights(l0 * nx, wx), nx, gx);
     pppm_weights_at(l1 * ny, ny, iy, wy); pppm_weights_at(l2 * nz, nz, iz, wz);
     pppm_wrap(iy, ny, jy); pppm_wrap(iz, nz, jz);
 #pragma unroll
-    for (int k = 0; k < PP_ORDER; k++) { if (hy) jy[k] = iy - y0 + k; if (hz) jz[k] = iz - z0 + k; }
+    for (int k = 0; k < PPPM_ORDER; k++) { if (hy) jy[k] = iy - y0 + k; if (hz) jz[k] = iz - z0 + k; }
     double fx = 0.0, fy = 0.0, fz = 0.0;
 #pragma unroll
-    for (int c = 0; c < PP_ORDER; c++) {
+    for (int c = 0; c < PPPM_ORDER; c++) {
 #pragma unroll
-      for (int bb = 0; bb < PP_ORDER; bb++) {
+      for (int bb = 0; bb < PPPM_ORDER; bb++) {
         const double zy = wz[c] * wy[bb];
         const int row = (jz[c] * sy + jy[bb]) * nx;
         double rx = 0.0, ry = 0.0, rz = 0.0;
 #pragma unroll
-        for (int k = 0; k < PP_ORDER; k++) {
+        for (int k = 0; k < PPPM_ORDER; k++) {
           const int g = row + gx[k];
           rx = fma(wx[k], s_grid[g], rx); ry = fma(wx[k], s_grid[SN + g], ry); rz = fma(wx[k], s_grid[2 * SN + g], rz);
         }

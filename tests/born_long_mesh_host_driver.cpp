@@ -1,5 +1,6 @@
 // born_long_mesh_host_driver.cpp -- TEST HARNESS, not part of the product: a stand-alone program that runs the functions of
-// scema_amd/csrc/ionic/blm_core.h (the arithmetic the HIP kernels of md_born_long_mesh.hip execute) as plain loops on the host, with a plain
+// scema_amd/csrc/pppm/pppm_core.h and ionic/blm_core.h (the arithmetic the HIP kernels of md_born_long_mesh.hip execute, and -- the core --
+// those of md_pppm.hip) as plain loops on the host, with a plain
 // DFT in place of hipFFT and the table of the product's reader, so that tests/test_born_long_mesh_host.py can hold energies, forces and
 // virial against tests/born_long_mesh_numpy.py without a GPU.  The loop structure follows the kernels: real space as
 // born_long_host_driver.cpp; per atom 125 fixed-point adds to the charge grid (k_blm_assign), fixed point -> complex (k_blm_convert), the
@@ -117,10 +118,10 @@ int main(int argc, char **argv) {
   for (int i = n - 1; i >= 0; i--) {
     double t[3], wx[5], wy[5], wz[5];
     blm_frac(h, lo, &x[3 * i], t);
-    const int ix = blm_weights(t[0] * mesh[0], wx), iy = blm_weights(t[1] * mesh[1], wy), iz = blm_weights(t[2] * mesh[2], wz);
+    const int ix = pppm_weights(t[0] * mesh[0], wx), iy = pppm_weights(t[1] * mesh[1], wy), iz = pppm_weights(t[2] * mesh[2], wz);
     for (int p = 0; p < 125; p++) {
       const int c = p / 25, b = (p / 5) % 5, k = p % 5;
-      const int idx = (blm_wrap(iz + c - 2, mesh[2]) * mesh[1] + blm_wrap(iy + b - 2, mesh[1])) * mesh[0] + blm_wrap(ix + k - 2, mesh[0]);
+      const int idx = (pppm_wrap1(iz + c - 2, mesh[2]) * mesh[1] + pppm_wrap1(iy + b - 2, mesh[1])) * mesh[0] + pppm_wrap1(ix + k - 2, mesh[0]);
       const double w = wz[c] * wy[b] * wx[k];
       gidx[(size_t)i * 125 + p] = idx; gw[(size_t)i * 125 + p] = w;
       igrid[idx] += blm_to_fixed(q[i] * delvolinv * w, shift);
@@ -132,12 +133,14 @@ int main(int argc, char **argv) {
   dft3(rho, mesh, -1);
   // k_blm_gf, k_blm_poisson
   std::vector<cplx> field[3] = {std::vector<cplx>(ng), std::vector<cplx>(ng), std::vector<cplx>(ng)};
-  double er = 0.0;
+  double er = 0.0, hinv[6];
+  bl_hinv(h, hinv);
   for (int idx = 0; idx < ng; idx++) {
     const int m1 = idx % mesh[0], m2 = (idx / mesh[0]) % mesh[1], m3 = idx / (mesh[0] * mesh[1]);
-    const double gf = blm_gf(h, g, mesh, m1, m2, m3);
+    const double gf = pppm_gf(hinv, g, mesh[0], mesh[1], mesh[2], m1, m2, m3), scaleinv = 1.0 / (double)ng;
     double kv[3], pr, pi;
-    blm_mode(h, g, kc, mesh, m1, m2, m3, rho[idx].real(), rho[idx].imag(), gf, kv, wc, &er, &pr, &pi);
+    pppm_kvec(hinv, pppm_signed(m1, mesh[0]), pppm_signed(m2, mesh[1]), pppm_signed(m3, mesh[2]), kv[0], kv[1], kv[2]);
+    pppm_mode_term(vol, kc, g, kv[0], kv[1], kv[2], rho[idx].real() * scaleinv, rho[idx].imag() * scaleinv, gf, wc, er, pr, pi);
     for (int c = 0; c < 3; c++) field[c][idx] = cplx(kv[c] * pi, -kv[c] * pr);
   }
   e_coul += er;
