@@ -368,6 +368,12 @@ int scema_md_pppm_tiling(scema_md_engine *e, int32_t mode, int32_t lds_bytes);
  * mean charged atoms per grid point; -1 keeps.  SCEMA_MD_PPPM_BINNED=0/1 in the environment forces 0 / 1 whatever is set here.  Results do
  * not depend on it beyond the order of summation. */
 int scema_md_pppm_binning(scema_md_engine *e, int32_t mode);
+/* Stream of the bonded kernel.  mode 0: one descriptor per term; 1: the grouped stream of csrc/md_bonded_groups.h -- the dihedrals around
+ * one central bond evaluated by one thread (eight positions read once, eight forces added once), every 1-2 / 1-3 special pair inside the
+ * bond / angle term that already holds its two atoms; -1: the default (grouped).  SCEMA_MD_BONDED_GROUPED=0/1 in the environment forces
+ * 0 / 1 whatever is set here.  The parity hook (scema_md_debug_compute) always runs the per-term stream.  Forces and virials of the two
+ * agree to rounding (two formulations of one sum). */
+int scema_md_bonded_grouping(scema_md_engine *e, int32_t mode);
 /* LDS layout of the staged interpolation kernel (k_pppm_force with the three field grids of a replica in LDS).  mode 0: the dense layout,
  * plane stride nx ny; 1: the plane stride of the rule in csrc/md_pppm_fstride.h, which keeps the stencil points of neighbouring atoms off
  * each other's LDS banks (dense where the padded copy does not fit the LDS budget, would cost a resident workgroup, or the mesh has a

@@ -36,7 +36,7 @@ SYMBOLS = [
     "scema_md_comm_world", "scema_md_comm_rank", "scema_md_comm_stats", "scema_md_comm_handshakes", "scema_md_state_owner", "scema_md_last_plan",
     "scema_plan_dir_create", "scema_plan_dir_destroy", "scema_plan_update", "scema_md_kspace_setup",
     "scema_md_save_state_dump", "scema_md_replica_natoms", "scema_md_save_replica_file", "scema_md_equilibrate", "scema_md_debug_minimize", "scema_md_debug_run_nh",
-    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_binning", "scema_md_pppm_force_layout", "scema_md_pppm_force_strides", "scema_md_pppm_binned_launches", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
+    "scema_md_reax_configure", "scema_md_reax_activate", "scema_md_reax_set", "scema_md_reax_concurrency", "scema_md_batch_split", "scema_md_get_concurrency", "scema_md_pppm_plan_count", "scema_md_pppm_tiling", "scema_md_pppm_binning", "scema_md_bonded_grouping","scema_md_pppm_force_layout", "scema_md_pppm_force_strides", "scema_md_pppm_binned_launches", "scema_md_pppm_paths", "scema_md_pppm_tile_shape", "scema_md_unsettled_updates", "scema_md_reax_debug_compute", "scema_md_reax_stats", "scema_md_box_fma_tflops",
     "scema_md_sw_configure", "scema_md_sw_debug_compute", "scema_md_sw_read_params",
     "scema_md_tersoff_configure", "scema_md_tersoff_debug_compute", "scema_md_tersoff_read_params",
     "scema_md_eam_configure", "scema_md_eam_debug_compute", "scema_md_eam_read_setfl",
@@ -490,6 +490,10 @@ class Engine:
     def pppm_binning(self, mode: int = -1):
         """binned charge assignment: 0 off, 1 on for every eligible launch, 2 (default) by the launch policy; -1 keeps"""
         self._chk(lib().scema_md_pppm_binning(self.h, C.c_int32(mode)))
+
+    def bonded_grouping(self, mode: int = -1):
+        """stream of the bonded kernel: 0 one descriptor per term, 1 grouped (dihedrals per central bond, 1-2 / 1-3 pairs in their host term), -1 the default (grouped)"""
+        self._chk(lib().scema_md_bonded_grouping(self.h, C.c_int32(mode)))
 
     def pppm_force_layout(self, mode: int = -1):
         """LDS layout of the staged interpolation kernel: 0 dense, 1 the stride rule of md_pppm_fstride.h, -1 the default (the rule)"""

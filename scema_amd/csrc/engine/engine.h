@@ -161,6 +161,7 @@ struct Topo {
   int rtype_stamp = -1;
   DevBuf d_type, d_q, d_mass, d_lj, d_bt_terms, d_bt_coef, d_ex_start, d_ex_list, d_clus_at, d_clus_n, d_clus_d, d_free_at, d_bt_desc, d_bt_atoms, d_bt_rank;
   int bt_ntile = 0, bt_maxloc = 1, bt_maxchunk = 1, bt_ncoef = 0, bt_cf_off[4] = {0, 0, 0, 0};
+  int bt_ngroups = 0, bt_nattached = 0;         // dihedral groups and special pairs attached to a bond / angle in the grouped stream (md_bonded_groups.h)
   double sp_w[6] = {0, 0, 0, 0, 0, 0};   // special_bonds weights: lj 1-2, 1-3, 1-4, coul 1-2, 1-3, 1-4
   std::string matid;       // the material the replica was registered under (a row potential is attached to a material id)
   DevBuf d_eltype;         // row potentials: element per atom (index into the material's tables), valid for eltype_stamp
@@ -391,6 +392,7 @@ struct scema_md_engine {
   std::vector<std::unique_ptr<DevBuf>> bak_x, bak_v;
   int pppm_tile_mode = 1, pppm_lds_bytes = 0;   // scema_md_pppm_tiling: tiled kernels for meshes beyond the LDS; forced LDS budget (0: mdk_pppm_lds_limit())
   int pppm_paths[8] = {0, 0, 0, 0, 0, 0, 0, 1}; // scema_md_pppm_paths: what the last PPPM launch group took
+  int bonded_group_mode = -1;                   // scema_md_bonded_grouping: k_bonded on the per-term stream 0, on the grouped stream 1, -1 the default (grouped)
   int pppm_bin_mode = 2;                        // scema_md_pppm_binning: binned charge assignment 0 off, 1 wherever eligible, 2 by the launch policy (PppmBinPolicy)
   int pppm_flayout_mode = 1;                    // scema_md_pppm_force_layout: staged interpolation 0 the dense LDS layout, 1 the strides of md_pppm_fstride.h
   long long pppm_binned_launches = 0;           // scema_md_pppm_binned_launches: spreading launches that took the binned kernels

@@ -58,6 +58,7 @@ const EnvSwitch k_env[] = {
     {"SCEMA_MD_PPPM_FLAYOUT", "0 / 1: the staged interpolation kernel keeps its field grids in LDS densely / at the plane stride of md_pppm_fstride.h (default: the stride rule)"},
     {"SCEMA_MD_PPPM_FTPB", "256 / 512: threads per workgroup of the staged interpolation kernel (default: 512 with the strided layout, 256 with the dense one)"},
     {"SCEMA_MD_PPPM_BINNED", "0 / 1: the charge assignment of meshes kept whole in LDS never / wherever eligible as k_pppm_bins + k_pppm_spread_binned, atoms grouped by nearest grid point (default: by launch size and atoms per grid point)"},
+    {"SCEMA_MD_BONDED_GROUPED", "0 / 1: the bonded kernel on one descriptor per term / on the grouped stream, dihedrals per central bond and 1-2 / 1-3 special pairs inside their bond / angle term (default: grouped; results agree to rounding)"},
     {"SCEMA_MD_PPPM_FFT", "hipFFT for every PPPM grid (default: grids of up to 2 900 points are solved in LDS)"},
     {"SCEMA_MD_FUSED_TAIL", "0 / 1: force assembly + SHAKE + second kick as three kernels / as k_finish (default: by batch size)"},
     {"SCEMA_MD_BONDED_SIDE", "0: the bonded kernel of a small batch always on the main stream behind the pair kernel (default: behind the PPPM chain on the side stream on steps without a new influence function)"},

@@ -439,6 +439,12 @@ int scema_md_pppm_binning(scema_md_engine *e, int32_t mode) {
   if (mode >= 0) e->pppm_bin_mode = mode;
   return SCEMA_MD_OK;
 }
+int scema_md_bonded_grouping(scema_md_engine *e, int32_t mode) {
+  if (!e) return SCEMA_MD_ERR_ARG;
+  if (mode < -1 || mode > 1) return fail(e, SCEMA_MD_ERR_ARG, "scema_md_bonded_grouping: mode %d (0 one descriptor per term, 1 the grouped stream, -1 the default)", mode);
+  e->bonded_group_mode = mode;
+  return SCEMA_MD_OK;
+}
 int scema_md_pppm_force_layout(scema_md_engine *e, int32_t mode) {
   if (!e) return SCEMA_MD_ERR_ARG;
   if (mode < -1 || mode > 1) return fail(e, SCEMA_MD_ERR_ARG, "scema_md_pppm_force_layout: mode %d (0 the dense layout, 1 the stride rule, -1 the default)", mode);

@@ -70,6 +70,14 @@ namespace {
 
 constexpr int MAXP = 4;   // part batches at most (plan_launch)
 
+// k_bonded on the tiles' grouped stream (md_bonded_groups.h) or on one descriptor per term: the environment, else the engine's setting
+// (scema_md_bonded_grouping), else grouped at every launch size
+int bonded_grouped(const scema_md_engine *e) {
+  static const int env = scema_env("SCEMA_MD_BONDED_GROUPED") ? (atoi(scema_env("SCEMA_MD_BONDED_GROUPED")) != 0 ? 1 : 0) : -1;
+  if (env >= 0) return env;
+  return e->bonded_group_mode < 0 ? 1 : e->bonded_group_mode;
+}
+
 struct Policy {
   // by the batch size, the run and the engine's streams (plan_launch)
   int kspace_threads = 1;
@@ -639,7 +647,7 @@ int OplsRun::pppm_fork(hipStream_t st, int pos0, int na, bool new_box, bool with
   HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
   const int rc = pppm_stage(e->stream2, pos0, na, new_box, 0);
   if (rc) return rc;
-  if (with_bonded) mdk_bonded(e->stream2, D + pos0, na, L.maxbt, L.maxloc, L.maxcoef, 0);   // (needs the positions only, like the chain before it)
+  if (with_bonded) mdk_bonded(e->stream2, D + pos0, na, L.maxbt, L.maxloc, L.maxcoef, 0, bonded_grouped(e));   // (needs the positions only, like the chain before it)
   HIPCHK(hipEventRecord(e->ev_join, e->stream2));
   return SCEMA_MD_OK;
 }
@@ -653,7 +661,7 @@ hipError_t OplsRun::force_stage(hipStream_t st, const SimDev *Dh, int na, bool s
     mdk_ewald_recip(e->stream2, Dh, na, L.maxk, L.mmax, L.maxgrp);
     if ((rc = hipEventRecord(e->ev_join, e->stream2)) != hipSuccess) return rc;
   }
-  mdk_bonded(st, Dh, na, L.maxbt, L.maxloc, L.maxcoef, bparts);
+  mdk_bonded(st, Dh, na, L.maxbt, L.maxloc, L.maxcoef, bparts, bonded_grouped(e));
   if (side) {
     if ((rc = hipStreamWaitEvent(st, e->ev_join, 0)) != hipSuccess) return rc;
   } else {
@@ -738,7 +746,7 @@ int OplsRun::launch_step(const Part &pt, int na, bool timed) {
   if (pol.fused_tail) {
     // no per-atom reciprocal sum: the bonded kernel, the PPPM chain (its forces stored in f, from the side stream or here), then
     // assembly of f, fix shake and the second half-kick in one pass (k_finish)
-    if (!pol.bonded_side) mdk_bonded(st, Dh, na, L.maxbt, L.maxloc, L.maxcoef, 0);
+    if (!pol.bonded_side) mdk_bonded(st, Dh, na, L.maxbt, L.maxloc, L.maxcoef, 0, bonded_grouped(e));
     if (pol.pppm_side) HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
     else if ((rc = pppm_stage(st, pt.off, na, spec.deform, 0))) return rc;
     mdk_finish(st, Dh, na, L.maxunits, ev, L.maxgrid > 0 ? 1 : 0);

@@ -1,5 +1,6 @@
 // engine_topo.cpp -- topology preprocessing of a registered replica (immutable, shared by every quadrature point that uses it)
 #include "engine.h"
+#include "../md_bonded_groups.h"
 
 namespace scema_eng {
 
@@ -237,6 +238,26 @@ int build_topo(scema_md_engine *e, const scema_md_system *s, Topo &t) {
   for (int m = 0; m < s->ndihedrals; m++) add_term(&dih_at[4 * m], 4, BT_DIHEDRAL, m);
   for (int m = 0; m < s->nimpropers; m++) add_term(&imp_at[4 * m], 4, BT_IMPROPER, m);
   for (int m = 0; m < t.nspecial; m++) add_term(&sp_at[2 * m], 2, BT_SPECIAL, m);
+  // ---- the grouped stream (md_bonded_groups.h): dihedrals per central bond, special pairs on the bond / angle that holds their atoms ----
+  const bonded_groups::DihedralGroups dg = bonded_groups::group_dihedrals(s->ndihedrals, dih_at.data(), s->dihedral_type);
+  const bonded_groups::SpecialHosts hosts = bonded_groups::attach_specials(t.nspecial, sp_at.data(), s->nbonds, bond_at.data(), s->nangles, angle_at.data());
+  std::vector<char> dih_grouped(s->ndihedrals, 1);
+  for (int m : dg.left) dih_grouped[m] = 0;
+  struct GroupRef { int idx, count; };
+  std::vector<std::vector<GroupRef>> tile_groups(ntile);
+  {
+    std::vector<int> tiles;
+    int ga[2 + 2 * BTG_SIDE];
+    for (size_t gi = 0; gi < dg.groups.size(); gi++) {
+      const int na = bonded_groups::group_atoms(dg.groups[gi], ga);
+      bonded_groups::tiles_of(ga, na, rank.data(), BT_OWNERS, tiles);
+      const int ct = bonded_groups::group_count_tile(dg.groups[gi], rank.data(), BT_OWNERS);
+      for (int tl : tiles) tile_groups[tl].push_back({(int)gi, tl == ct ? 1 : 0});
+    }
+  }
+  t.bt_ngroups = (int)dg.groups.size();
+  t.bt_nattached = 0;
+  for (int k : hosts.pair_host_kind) t.bt_nattached += k ? 1 : 0;
   // Tile-ordered term stream: ONE 64-bit descriptor per term (BT_D_* in md_types.h: four 10-bit local atom indices, the
   // term's type, kind, special-bond level and the count flag); coefficients are looked up by type in small tables the
   // kernel stages in LDS.  Kinds follow each other, each padded to whole chunks of 64 descriptors, so a wave always
@@ -291,44 +312,87 @@ int build_topo(scema_md_engine *e, const scema_md_system *s, Topo &t) {
       for (int k = 0; k < natm[tr.kind]; k++)
         if (local_of[at[k]] < 0) { local_of[at[k]] = 0; halo.push_back(at[k]); }
     }
+    for (const GroupRef &gr : tile_groups[tl]) {
+      // (a tile that owns one end atom of a group evaluates the whole group: its other end atoms join the halo)
+      int ga[2 + 2 * BTG_SIDE];
+      const int na = bonded_groups::group_atoms(dg.groups[gr.idx], ga);
+      for (int k = 0; k < na; k++)
+        if (local_of[ga[k]] < 0) { local_of[ga[k]] = 0; halo.push_back(ga[k]); }
+    }
     std::sort(halo.begin(), halo.end(), [&](int a, int b) { return rank[a] < rank[b]; });
     for (size_t l = 0; l < halo.size(); l++) local_of[halo[l]] = (int)(members.size() + l);
     members.insert(members.end(), halo.begin(), halo.end());
     if ((int)members.size() > BT_D_LMASK + 1)
       return fail(e, SCEMA_MD_ERR_ARG, "a bonded tile touches %zu atoms (more than %d): topology too branched for the tile descriptors", members.size(), BT_D_LMASK + 1);
+    // the stream of a tile: every term on its own (grouped = false), or without the dihedrals of the groups and the attached pairs
+    auto emit_terms = [&](bool grouped) {
+      for (int kind = 0; kind < BT_NKIND; kind++) {
+        // Terms that follow each other in the input share atoms (the nine torsions around one bond): dealt to
+        // consecutive lanes they would hit the same LDS accumulators in the same instruction.  A stride
+        // permutation spreads them over the tile instead.
+        std::vector<const TermRef *> of_kind;
+        for (const TermRef &tr : tile_terms[tl])
+          if (tr.kind == kind && !(grouped && ((kind == BT_DIHEDRAL && dih_grouped[tr.idx]) || (kind == BT_SPECIAL && hosts.pair_host_kind[tr.idx])))) of_kind.push_back(&tr);
+        const int nk_ = (int)of_kind.size();
+        int stride = 1;
+        if (nk_ > 16)
+          for (stride = 13; stride < nk_; stride += 2) {   // smallest odd stride >= 13 coprime with nk_
+            int a_ = stride, b_ = nk_;
+            while (b_) { const int t_ = a_ % b_; a_ = b_; b_ = t_; }
+            if (a_ == 1) break;
+          }
+        if (stride >= nk_) stride = 1;
+        for (int q = 0; q < nk_; q++) {
+          const TermRef &tr = *of_kind[(int)(((long long)q * stride) % std::max(nk_, 1))];
+          const int m = tr.idx;
+          const int *at = term_atoms(tr);
+          unsigned long long d = BT_D_VALID | ((unsigned long long)kind << BT_D_KIND_SHIFT);
+          for (int k = 0; k < natm[kind]; k++) d |= (unsigned long long)local_of[at[k]] << (10 * k);
+          const int ty = (kind <= BT_BOND_SHAKEN) ? bond_ty[m] : (kind == BT_ANGLE) ? s->angle_type[m] : (kind == BT_DIHEDRAL) ? s->dihedral_type[m]
+                         : (kind == BT_IMPROPER) ? s->improper_type[m] : 0;
+          d |= (unsigned long long)ty << BT_D_TYPE_SHIFT;
+          if (kind == BT_SPECIAL) d |= (unsigned long long)sp_lvl[m] << BT_D_LVL_SHIFT;
+          const int attached = !grouped ? -1 : (kind <= BT_BOND_SHAKEN) ? hosts.bond_pair[m] : (kind == BT_ANGLE) ? hosts.angle_pair[m] : -1;
+          if (attached >= 0) d |= (unsigned long long)sp_lvl[attached] << BT_D_LVL_SHIFT;
+          if (!tr.count) d |= BT_D_NOCOUNT;
+          bt_terms.push_back(d);
+        }
+        while (bt_terms.size() % 64) bt_terms.push_back(0ull);   // whole chunks per kind (an invalid descriptor is all zero)
+      }
+    };
     desc[2] = (int)(bt_terms.size() / 64);   // first chunk of the tile
-    for (int kind = 0; kind < BT_NKIND; kind++) {
-      // Terms that follow each other in the input share atoms (the nine torsions around one bond): dealt to
-      // consecutive lanes they would hit the same LDS accumulators in the same instruction.  A stride
-      // permutation spreads them over the tile instead.
-      std::vector<const TermRef *> of_kind;
-      for (const TermRef &tr : tile_terms[tl])
-        if (tr.kind == kind) of_kind.push_back(&tr);
-      const int nk_ = (int)of_kind.size();
+    emit_terms(false);
+    desc[3] = (int)(bt_terms.size() / 64) - desc[2];   // chunks of the tile
+    desc[BTG_DESC_TERM0] = (int)(bt_terms.size() / 64);
+    emit_terms(true);
+    desc[BTG_DESC_NTERM] = (int)(bt_terms.size() / 64) - desc[BTG_DESC_TERM0];
+    desc[BTG_DESC_GRP0] = (int)(bt_terms.size() / 64);
+    {
+      // groups: chunks of 64, the first words of a chunk before its second words; neighbours along a chain share atoms, so the
+      // same stride permutation as for the terms
+      const std::vector<GroupRef> &tg = tile_groups[tl];
+      const int ng = (int)tg.size();
       int stride = 1;
-      if (nk_ > 16)
-        for (stride = 13; stride < nk_; stride += 2) {   // smallest odd stride >= 13 coprime with nk_
-          int a_ = stride, b_ = nk_;
+      if (ng > 16)
+        for (stride = 13; stride < ng; stride += 2) {
+          int a_ = stride, b_ = ng;
           while (b_) { const int t_ = a_ % b_; a_ = b_; b_ = t_; }
           if (a_ == 1) break;
         }
-      if (stride >= nk_) stride = 1;
-      for (int q = 0; q < nk_; q++) {
-        const TermRef &tr = *of_kind[(int)(((long long)q * stride) % std::max(nk_, 1))];
-        const int m = tr.idx;
-        const int *at = term_atoms(tr);
-        unsigned long long d = BT_D_VALID | ((unsigned long long)kind << BT_D_KIND_SHIFT);
-        for (int k = 0; k < natm[kind]; k++) d |= (unsigned long long)local_of[at[k]] << (10 * k);
-        const int ty = (kind <= BT_BOND_SHAKEN) ? bond_ty[m] : (kind == BT_ANGLE) ? s->angle_type[m] : (kind == BT_DIHEDRAL) ? s->dihedral_type[m]
-                       : (kind == BT_IMPROPER) ? s->improper_type[m] : 0;
-        d |= (unsigned long long)ty << BT_D_TYPE_SHIFT;
-        if (kind == BT_SPECIAL) d |= (unsigned long long)sp_lvl[m] << BT_D_LVL_SHIFT;
-        if (!tr.count) d |= BT_D_NOCOUNT;
-        bt_terms.push_back(d);
+      if (stride >= ng) stride = 1;
+      for (int q0 = 0; q0 < ng; q0 += 64) {
+        unsigned long long w[2][64] = {};
+        for (int q = q0; q < std::min(ng, q0 + 64); q++) {
+          const GroupRef &gr = tg[(int)(((long long)q * stride) % ng)];
+          unsigned long long ww[2];
+          bonded_groups::pack_group(dg.groups[gr.idx], [&](int atom) { return local_of[atom]; }, gr.count != 0, ww);
+          w[0][q - q0] = ww[0]; w[1][q - q0] = ww[1];
+        }
+        bt_terms.insert(bt_terms.end(), w[0], w[0] + 64);
+        bt_terms.insert(bt_terms.end(), w[1], w[1] + 64);
       }
-      while (bt_terms.size() % 64) bt_terms.push_back(0ull);   // whole chunks per kind (an invalid descriptor is all zero)
+      desc[BTG_DESC_NGRP] = (ng + 63) / 64;
     }
-    desc[3] = (int)(bt_terms.size() / 64) - desc[2];   // chunks of the tile
     desc[1] = (int)members.size();
     desc[14] = r1 - r0;   // owners
     t.bt_maxloc = std::max(t.bt_maxloc, (int)members.size());

@@ -15,7 +15,11 @@
 //     forces of all terms accumulate in LDS (ds_add_f64);
 //   * virial and energies of a term are counted by ONE tile (the owner of its lowest-ranked atom; the others see
 //     BT_NOCOUNT on the term's first index); the lumped virial of a tile is stored per tile, without atomics;
-//   * kinds are processed one after the other, so the lanes of a wave run the same formula.
+//   * kinds are processed one after the other, so the lanes of a wave run the same formula;
+//   * grouped stream (md_bonded_groups.h; the default of the production kernel): the dihedrals around one central bond are ONE work
+//     item -- a thread reads the eight positions once, keeps G and the three B_m = H_m x G, walks the k atoms and adds each of the
+//     eight forces once (24 LDS atomics where nine separate dihedrals issue 108) -- and a 1-2 / 1-3 special pair is evaluated inside
+//     the bond / angle term that already holds its two atoms, its force added to that term's own before the atomics.
 //
 // Virial of a term = sum_a (r_a - r_ref) (x) F_a with r_ref = atom 3 for torsions, the vertex for angles,
 // atom 2 for bonds / pairs (differences by minimum image, positions are unwrapped).
@@ -26,6 +30,7 @@
 
 #include "md_device.h"
 #include "md_kernels.h"
+#include "md_bonded_groups.h"
 
 #define BT_TPB 256
 
@@ -55,27 +60,36 @@ extern __shared__ double s_bt[];  // [3*maxloc] positions, [3*maxloc] forces, [m
 #ifndef BT_OCC
 #define BT_OCC 4
 #endif
+#ifndef BT_GROUP_WAVE
+#define BT_GROUP_WAVE 1   // 0 (what-if build): the term chunks of a tile with groups are dealt to all four waves (420 against 343 us per step at 576 replicas)
+#endif
 #define BT_PRE 8   // descriptors a thread requests up front (chunks of its wave): covers 32 chunks = 2 048 terms per tile
 
 // PARTS: also split virial / energy per part (parity hook); otherwise one lumped virial
 template <bool PARTS>
-__global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restrict__ sims, int maxloc, int maxcoef) {
+__global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restrict__ sims, int maxloc, int maxcoef, int grouped) {
   const SimDev &S = sims[blockIdx.y];
   if ((int)blockIdx.x >= S.bt_ntile) return;
   SimScalars &sc = *S.sc;
   __shared__ double s_red[8 * (BT_TPB / 64)];
   const int *desc = S.bt_desc + (size_t)blockIdx.x * BT_DESC;
   // (wave-uniform: said so, so that the loops over them run on the scalar unit)
-  const int nloc = __builtin_amdgcn_readfirstlane(desc[1]), nown = __builtin_amdgcn_readfirstlane(desc[14]), nchunk = __builtin_amdgcn_readfirstlane(desc[3]);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool grp = !PARTS && grouped != 0;   // (the parity hook keeps the per-term stream)
+  const int nloc = __builtin_amdgcn_readfirstlane(desc[1]), nown = __builtin_amdgcn_readfirstlane(desc[14]);
+  const int nchunk = __builtin_amdgcn_readfirstlane(grp ? desc[BTG_DESC_NTERM] : desc[3]), ngchunk = __builtin_amdgcn_readfirstlane(grp ? desc[BTG_DESC_NGRP] : 0);
+  // A chunk of groups is a long item (nine dihedrals per lane): group chunk c goes to wave c % 4, and where a tile has groups wave 0
+  // takes no term chunk -- the terms are dealt to the other three (tw waves; wave < 0: none for this one)
+  const int lane = threadIdx.x & 63, wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tw = (BT_GROUP_WAVE && ngchunk > 0) ? BT_TPB / 64 - 1 : BT_TPB / 64, wave = wave0 - (BT_TPB / 64 - tw);
   // the wave's term descriptors first: nothing below depends on them until the positions are staged, so their latency
   // runs under the staging loads
-  const unsigned long long *td = S.bt_terms + (size_t)desc[2] * 64 + lane;
+  const unsigned long long *td = S.bt_terms + (size_t)(grp ? desc[BTG_DESC_TERM0] : desc[2]) * 64 + lane;
+  const unsigned long long *gd = S.bt_terms + (size_t)desc[BTG_DESC_GRP0] * 64 + lane;
   unsigned long long dq[BT_PRE];
 #pragma unroll
   for (int k = 0; k < BT_PRE; k++) {
-    const int c = wave + (BT_TPB / 64) * k;
-    dq[k] = (c < nchunk) ? td[(size_t)c * 64] : 0ull;
+    const int c = wave + tw * k;
+    dq[k] = (wave >= 0 && c < nchunk) ? td[(size_t)c * 64] : 0ull;
   }
   const int *atoms = S.bt_atoms + desc[0];
   const int nt = S.ntypes, nt2 = nt * nt;
@@ -114,6 +128,31 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
       for (int k = 0; k < 6; k++) vsum[k] += v[k];
     }
   };
+  // weighted real-space pair term of a special pair at level lvl (k-space minus (1-f_coul) q q / r): force / r of the Lennard-Jones and
+  // the Coulomb part (and their energies for the parity hook)
+  auto special_pair = [&](int l1, int l2, int lvl, double rsq, double rinv, bool counted, double &flj, double &fc, double &en, double &en2) {
+    const double wl = S.sp_w[lvl - 1], wc = S.sp_w[2 + lvl];
+    if (rsq >= S.excl_cut2 && counted) atomicOr(&sc.overflow, 2);  // excluded pair escaped the build-time exclusion gate
+    const double r2inv = rinv * rinv;
+    flj = 0.0; fc = 0.0; en = 0.0; en2 = 0.0;
+    if (rsq < S.cut_coul2 && g > 0.0) {
+      // erf(x) - 2x/sqrt(pi) exp(-x^2) = x H(x^2): the polynomial of k_pair (md_pair.hip) instead of erf + exp
+      const double qq = MD_QQRD2E * s_q[l1] * s_q[l2];
+      const double tq = fma(rsq, g2u, -1.0);
+      double p = S.coul_poly[np - 1];
+      for (int k = np - 2; k >= 0; k--) p = fma(p, tq, S.coul_poly[k]);
+      const double grij = g * rsq * rinv;
+      const double pref = qq * rinv;
+      fc = pref * fma(-grij, p, wc) * r2inv;
+      if (PARTS) en2 = pref * (wc - erf(grij));
+    }
+    if (rsq < S.cut_lj2 && wl != 0.0) {
+      const int tt = s_t[l1] + s_t[l2] / nt;
+      const double r6inv = r2inv * r2inv * r2inv;
+      flj = wl * r6inv * (s_lj[2 * tt] * r6inv - s_lj[2 * tt + 1]) * r2inv;
+      if (PARTS) en = wl * r6inv * (s_lj[2 * nt2 + 2 * tt] * r6inv - s_lj[2 * nt2 + 2 * tt + 1]);
+    }
+  };
   auto term = [&](unsigned long long d) {
     // the kind is the same for the whole chunk (kinds are padded to whole chunks): a scalar branch
     const int kind = __builtin_amdgcn_readfirstlane((int)(d >> BT_D_KIND_SHIFT) & 7);
@@ -124,16 +163,23 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
     const int ty = (int)((d >> BT_D_TYPE_SHIFT) & BT_D_TMASK);
     if (kind == BT_BOND || kind == BT_BOND_SHAKEN) {
       // ---- bonds (the SHAKE'd ones only while fix shake is off) ----
-      if (kind == BT_BOND_SHAKEN && S.use_shake) return;
-      if (!valid) return;
-      const double K = cf_bond[2 * ty], r0 = cf_bond[2 * ty + 1];
+      // (grouped stream: the level of an attached 1-2 special pair, which a SHAKE'd bond evaluates all the same)
+      const int lvl = (int)((d >> BT_D_LVL_SHIFT) & 3);
+      const bool harmonic = !(kind == BT_BOND_SHAKEN && S.use_shake);
+      if (!valid || !(harmonic || lvl)) return;
+      const double K = harmonic ? cf_bond[2 * ty] : 0.0, r0 = cf_bond[2 * ty + 1];
       double dd[3] = {s_x[3 * l1] - s_x[3 * l2], s_x[3 * l1 + 1] - s_x[3 * l2 + 1], s_x[3 * l1 + 2] - s_x[3 * l2 + 2]};
       minimg(b, dd[0], dd[1], dd[2]);
       const double rsq = dot3(dd, dd);
       const double rinv = (rsq > 0.0) ? rsq64(rsq) : 0.0;
       const double r = rsq * rinv;
       const double dr = r - r0, rk = K * dr;
-      const double fb = -2.0 * rk * rinv;
+      double fb = -2.0 * rk * rinv;
+      if (lvl) {
+        double flj, fc, en, en2;
+        special_pair(l1, l2, lvl, rsq, rinv, counted, flj, fc, en, en2);
+        fb += flj + fc;
+      }
       const double f1[3] = {dd[0] * fb, dd[1] * fb, dd[2] * fb}, f2[3] = {-f1[0], -f1[1], -f1[2]};
       lds_add3(s_f, l1, f1);
       lds_add3(s_f, l2, f2);
@@ -157,11 +203,23 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
       const double a11 = a * c * (r1i * r1i), a12 = -a * (r1i * r2i), a22 = a * c * (r2i * r2i);
       double f1[3], f3[3], f2[3];
       for (int k = 0; k < 3; k++) { f1[k] = a11 * d1[k] + a12 * d2[k]; f3[k] = a22 * d2[k] + a12 * d1[k]; f2[k] = -(f1[k] + f3[k]); }
+      double v[6] = {0, 0, 0, 0, 0, 0};
+      vt(v, d1, f1); vt(v, d2, f3);
+      const int lvl = (int)((d >> BT_D_LVL_SHIFT) & 3);
+      if (lvl) {
+        // grouped stream: the attached 1-3 special pair (l1, l3), r13 = d1 - d2
+        const double dd[3] = {d1[0] - d2[0], d1[1] - d2[1], d1[2] - d2[2]};
+        const double rsq = dot3(dd, dd);
+        double flj, fc, en, en2;
+        special_pair(l1, l3, lvl, rsq, rsq64(rsq), counted, flj, fc, en, en2);
+        const double fp = flj + fc;
+        const double fq[3] = {dd[0] * fp, dd[1] * fp, dd[2] * fp};
+        for (int k = 0; k < 3; k++) { f1[k] += fq[k]; f3[k] -= fq[k]; }
+        vt(v, dd, fq);
+      }
       lds_add3(s_f, l1, f1);
       lds_add3(s_f, l2, f2);
       lds_add3(s_f, l3, f3);
-      double v[6] = {0, 0, 0, 0, 0, 0};
-      vt(v, d1, f1); vt(v, d2, f3);
       emit(counted, P_ANGLE, v, tk * dth);
     } else if (kind == BT_DIHEDRAL || kind == BT_IMPROPER) {
       // ---- dihedrals (opls) and impropers (harmonic): same geometry, different dE/dcos ----
@@ -225,30 +283,11 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
       // ---- special pairs: weighted real-space pair term (k-space minus (1-f_coul) q q / r) ----
       if (!valid) return;
       const int lvl = (int)((d >> BT_D_LVL_SHIFT) & 3);
-      const double wl = S.sp_w[lvl - 1], wc = S.sp_w[2 + lvl];
-      const int tt = s_t[l1] + s_t[l2] / nt;
-      const double qq = MD_QQRD2E * s_q[l1] * s_q[l2];
       double dd[3] = {s_x[3 * l1] - s_x[3 * l2], s_x[3 * l1 + 1] - s_x[3 * l2 + 1], s_x[3 * l1 + 2] - s_x[3 * l2 + 2]};
       minimg(b, dd[0], dd[1], dd[2]);
       const double rsq = dot3(dd, dd);
-      if (rsq >= S.excl_cut2 && counted) atomicOr(&sc.overflow, 2);  // excluded pair escaped the build-time exclusion gate
-      const double rinv = rsq64(rsq), r2inv = rinv * rinv;
-      double flj = 0.0, fc = 0.0, en = 0.0, en2 = 0.0;
-      if (rsq < S.cut_coul2 && g > 0.0) {
-        // erf(x) - 2x/sqrt(pi) exp(-x^2) = x H(x^2): the polynomial of k_pair (md_pair.hip) instead of erf + exp
-        const double tq = fma(rsq, g2u, -1.0);
-        double p = S.coul_poly[np - 1];
-        for (int k = np - 2; k >= 0; k--) p = fma(p, tq, S.coul_poly[k]);
-        const double grij = g * rsq * rinv;
-        const double pref = qq * rinv;
-        fc = pref * fma(-grij, p, wc) * r2inv;
-        if (PARTS) en2 = pref * (wc - erf(grij));
-      }
-      if (rsq < S.cut_lj2 && wl != 0.0) {
-        const double r6inv = r2inv * r2inv * r2inv;
-        flj = wl * r6inv * (s_lj[2 * tt] * r6inv - s_lj[2 * tt + 1]) * r2inv;
-        if (PARTS) en = wl * r6inv * (s_lj[2 * nt2 + 2 * tt] * r6inv - s_lj[2 * nt2 + 2 * tt + 1]);
-      }
+      double flj, fc, en, en2;
+      special_pair(l1, l2, lvl, rsq, rsq64(rsq), counted, flj, fc, en, en2);
       const double fp = flj + fc;
       const double f1[3] = {dd[0] * fp, dd[1] * fp, dd[2] * fp}, f2[3] = {-f1[0], -f1[1], -f1[2]};
       lds_add3(s_f, l1, f1);
@@ -265,16 +304,107 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
       }
     }
   };
+  // ---- a dihedral group: G = r2-r3, F_k = r_k-r2, H_m = r_m-r3, A_k = F_k x G, B_m = H_m x G; per listed (k, m) the cosine and dE/dc of
+  // the opls branch above, SA_k += dE/dc gA, SB_m += dE/dc gB; by linearity f(k) = -G x SA_k, f(m) = -G x SB_m,
+  // f(2) = -T + G x sum SA_k, f(3) = T + G x sum SB_m with T = sum SA_k x F_k + sum SB_m x H_m.  Registers: G, the three unit vectors
+  // B_m / |B_m| and the three SB_m, T and the sum of the SA_k stay for the whole group; A_k, SA_k, F_k only for the current k, whose force
+  // leaves at the end of its turn; H_m is read again for the closing cross products.
+  auto group = [&](unsigned long long w0, unsigned long long w1) {
+    const bool valid = (w1 & BTG_VALID) != 0ull;
+    if (!valid) return;
+    const bool counted = !(w1 & BTG_NOCOUNT);
+    const int l2 = (int)(w0 & BT_D_LMASK), l3 = (int)((w0 >> 10) & BT_D_LMASK);
+    const int nk = (int)((w0 >> 60) & 3), nm = (int)(w0 >> 62);
+    const int lm[BTG_SIDE] = {(int)((w0 >> 50) & BT_D_LMASK), (int)(w1 & BT_D_LMASK), (int)((w1 >> 10) & BT_D_LMASK)};
+    double G[3] = {s_x[3 * l2] - s_x[3 * l3], s_x[3 * l2 + 1] - s_x[3 * l3 + 1], s_x[3 * l2 + 2] - s_x[3 * l3 + 2]};
+    minimg(b, G[0], G[1], G[2]);
+    // (unit vectors a_k = A_k / |A_k|, b_m = B_m / |B_m|: c = a_k.b_m, gA = (b_m - c a_k) / |A_k|, gB = (a_k - c b_m) / |B_m|; the factor
+    // 1 / |B_m| is applied once, when H_m is read again)
+    double B[BTG_SIDE][3], SB[BTG_SIDE][3];
+#pragma unroll
+    for (int m = 0; m < BTG_SIDE; m++) {
+      double H[3] = {0.0, 0.0, 0.0};
+      if (m < nm) {
+        for (int k = 0; k < 3; k++) H[k] = s_x[3 * lm[m] + k] - s_x[3 * l3 + k];
+        minimg(b, H[0], H[1], H[2]);
+      }
+      cross3(H, G, B[m]);
+      const double ib = (m < nm) ? rsq64(dot3(B[m], B[m])) : 0.0;
+      for (int q = 0; q < 3; q++) { B[m][q] *= ib; SB[m][q] = 0.0; }
+    }
+    double T[3] = {0.0, 0.0, 0.0}, SAs[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int k = 0; k < nk; k++) {
+      const int lk = (int)((w0 >> (20 + 10 * k)) & BT_D_LMASK);
+      const unsigned tyk = (unsigned)(w1 >> (BTG_TYPE_SHIFT + BTG_TYPE_BITS * BTG_SIDE * k));
+      double F[3] = {s_x[3 * lk] - s_x[3 * l2], s_x[3 * lk + 1] - s_x[3 * l2 + 1], s_x[3 * lk + 2] - s_x[3 * l2 + 2]};
+      minimg(b, F[0], F[1], F[2]);
+      double A[3], SA[3] = {0.0, 0.0, 0.0};
+      cross3(F, G, A);
+      const double ia = rsq64(dot3(A, A));
+      for (int q = 0; q < 3; q++) A[q] *= ia;
+#pragma unroll
+      for (int m = 0; m < BTG_SIDE; m++) {
+        const int t = (int)((tyk >> (BTG_TYPE_BITS * m)) & ((1u << BTG_TYPE_BITS) - 1u));
+        if (t == 0) continue;   // no such dihedral (also every m >= nm)
+        const double *K = cf_dih + 4 * (t - 1);
+        double c = dot3(A, B[m]);
+        c = fmin(1.0, fmax(-1.0, c));
+        const double c2 = c * c;
+        const double dEdc = 0.5 * (K[0] - K[1] * 4.0 * c + K[2] * (12.0 * c2 - 3.0) - K[3] * (32.0 * c2 * c - 16.0 * c));
+        for (int q = 0; q < 3; q++) {
+          SA[q] += dEdc * (B[m][q] - c * A[q]);
+          SB[m][q] += dEdc * (A[q] - c * B[m][q]);
+        }
+      }
+      for (int q = 0; q < 3; q++) SA[q] *= ia;
+      double fk[3], u[3];
+      cross3(SA, G, fk);   // = -G x SA_k
+      lds_add3(s_f, lk, fk);
+      cross3(SA, F, u);
+      for (int q = 0; q < 3; q++) { T[q] += u[q]; SAs[q] += SA[q]; }
+      if (counted) {
+        const double FG[3] = {F[0] + G[0], F[1] + G[1], F[2] + G[2]};
+        vt(vsum, FG, fk);
+      }
+    }
+    double SBs[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int m = 0; m < BTG_SIDE; m++) {
+      if (m >= nm) continue;
+      double H[3] = {s_x[3 * lm[m]] - s_x[3 * l3], s_x[3 * lm[m] + 1] - s_x[3 * l3 + 1], s_x[3 * lm[m] + 2] - s_x[3 * l3 + 2]};
+      minimg(b, H[0], H[1], H[2]);
+      double Bm[3], fm[3], u[3];
+      cross3(H, G, Bm);
+      const double ib = rsq64(dot3(Bm, Bm));
+      for (int q = 0; q < 3; q++) SB[m][q] *= ib;
+      cross3(SB[m], G, fm);   // = -G x SB_m
+      lds_add3(s_f, lm[m], fm);
+      cross3(SB[m], H, u);
+      for (int q = 0; q < 3; q++) { T[q] += u[q]; SBs[q] += SB[m][q]; }
+      if (counted) vt(vsum, H, fm);
+    }
+    double gA[3], gB[3], f2[3], f3[3];
+    cross3(G, SAs, gA); cross3(G, SBs, gB);
+    for (int q = 0; q < 3; q++) { f2[q] = gA[q] - T[q]; f3[q] = gB[q] + T[q]; }
+    lds_add3(s_f, l2, f2);
+    lds_add3(s_f, l3, f3);
+    if (counted) vt(vsum, G, f2);
+  };
   // one copy of the term code (it is large): the descriptor of pass k is picked out of the preloaded registers
 #pragma unroll 1
   for (int k = 0; k < BT_PRE; k++) {
-    if (wave + (BT_TPB / 64) * k >= nchunk) break;
+    if (wave < 0 || wave + tw * k >= nchunk) break;
     unsigned long long d = dq[0];
 #pragma unroll
     for (int q = 1; q < BT_PRE; q++) d = (k == q) ? dq[q] : d;
     term(d);
   }
-  for (int c = wave + (BT_TPB / 64) * BT_PRE; c < nchunk; c += BT_TPB / 64) term(td[(size_t)c * 64]);   // very large tiles
+  if (wave >= 0)
+    for (int c = wave + tw * BT_PRE; c < nchunk; c += tw) term(td[(size_t)c * 64]);   // very large tiles
+  // (the groups after the terms: the preloaded descriptors are dead by now, and a wave's finish does not depend on the order)
+  if constexpr (!PARTS)
+    for (int c = wave0; c < ngchunk; c += BT_TPB / 64) group(gd[(size_t)c * 128], gd[(size_t)c * 128 + 64]);
   __syncthreads();
   // flush: the owners' forces, plain coalesced stores (consecutive ranks = consecutive local indices); halo forces
   // belong to the tiles that own those atoms, which evaluate the same terms themselves
@@ -299,7 +429,7 @@ __global__ __launch_bounds__(BT_TPB, BT_OCC) void k_bonded(const SimDev *__restr
   }
 }
 
-void mdk_bonded(hipStream_t st, const SimDev *d, int ns, int maxtiles, int maxloc, int maxcoef, int parts) {
+void mdk_bonded(hipStream_t st, const SimDev *d, int ns, int maxtiles, int maxloc, int maxcoef, int parts, int grouped) {
   const dim3 g((unsigned)maxtiles, (unsigned)ns, 1);
   const size_t lds = ((size_t)7 * maxloc + maxcoef + (parts ? 4 : 2) * MD_MAXTYPES * MD_MAXTYPES) * sizeof(double) + (size_t)maxloc * sizeof(int);
   static size_t optin_tab[16] = {0};
@@ -309,6 +439,6 @@ void mdk_bonded(hipStream_t st, const SimDev *d, int ns, int maxtiles, int maxlo
     (void)hipFuncSetAttribute((const void *)k_bonded<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     optin = lds;
   }
-  if (parts) hipLaunchKernelGGL(k_bonded<true>, g, dim3(BT_TPB), lds, st, d, maxloc, maxcoef);
-  else hipLaunchKernelGGL(k_bonded<false>, g, dim3(BT_TPB), lds, st, d, maxloc, maxcoef);
+  if (parts) hipLaunchKernelGGL(k_bonded<true>, g, dim3(BT_TPB), lds, st, d, maxloc, maxcoef, 0);
+  else hipLaunchKernelGGL(k_bonded<false>, g, dim3(BT_TPB), lds, st, d, maxloc, maxcoef, grouped);
 }

@@ -1,0 +1,335 @@
+"""The grouping behind the grouped stream of k_bonded (scema_amd/csrc/md_bonded_groups.h: dihedrals per central bond, special pairs
+attached to the bond or angle term that holds their atoms), compiled for the host as a stand-alone program
+(tests/bonded_groups_host_driver.cpp) and checked against restatements in Python.  No GPU needed.
+
+Inputs: the 360-atom polyethylene crystal, the 512- and 1000-atom networks with and without fractional 1-4 weights, each also under
+a random renumbering of its atoms -- and two hand-made molecules for the cases those fixtures cannot hold (their atoms have at most four
+bonds, their chains no ends and their rings six members): a butane with CH3 ends, a four-ring, and a centre with five substituents
+next to an ordinary bond, with one dihedral listed twice and one of a type beyond the group's type field.  Every case is asserted to be present before anything is compared.
+"""
+import collections
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import hostdrv
+from test_oracle_topologies import OWNERS, bond_levels, permuted, with_weights
+
+MAXTYPE = 15          # BTG_MAXTYPE: dihedral types a group's four-bit field holds
+SRC = ["tests/bonded_groups_host_driver.cpp"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# inputs
+# ---------------------------------------------------------------------------------------------------------------------
+def bfs_rank(n, bonds):
+    """breadth-first ranks as build_topo assigns them: roots in index order, neighbours in bond-input order"""
+    adj = [[] for _ in range(n)]
+    for i, j in bonds:
+        adj[i].append(int(j)); adj[j].append(int(i))
+    rank = -np.ones(n, np.int64)
+    nr = 0
+    for root in range(n):
+        if rank[root] >= 0:
+            continue
+        rank[root] = nr; nr += 1
+        queue = [root]
+        for h in queue:
+            for c in adj[h]:
+                if rank[c] < 0:
+                    rank[c] = nr; nr += 1
+                    queue.append(c)
+    return rank
+
+
+def special_pairs(d):
+    """pairs (i < j) within three bonds whose weights are not both 1, with their level"""
+    lvl = bond_levels(d)
+    wl, wc = np.asarray(d["special_lj"]), np.asarray(d["special_coul"])
+    keep = np.zeros_like(lvl, bool)
+    for k in range(3):
+        if not (wl[k] == 1.0 and wc[k] == 1.0):
+            keep |= lvl == k + 1
+    ij = np.argwhere(np.triu(keep))
+    return ij, lvl[ij[:, 0], ij[:, 1]]
+
+
+def topology_of(d, owners=OWNERS):
+    n = int(d["natoms"])
+    bonds = np.asarray(d["bonds"]).reshape(-1, 2)
+    pairs, levels = special_pairs(d)
+    return dict(n=n, owners=owners, rank=bfs_rank(n, bonds), bonds=bonds, angles=np.asarray(d["angles"]).reshape(-1, 3),
+                dihedrals=np.asarray(d["dihedrals"]).reshape(-1, 4), dihedral_type=np.asarray(d["dihedral_type"]).ravel(),
+                pairs=pairs, levels=levels)
+
+
+def molecule(n, bonds, special=(True, True, True), owners=4, extra_dihedrals=(), reverse_every=2):
+    """every angle and proper dihedral of a bond graph (every `reverse_every`-th dihedral listed backwards), special pairs at the levels
+    flagged; tiles of `owners` atoms, so that a molecule of a dozen atoms spans several"""
+    adj = [[] for _ in range(n)]
+    for i, j in bonds:
+        adj[i].append(j); adj[j].append(i)
+    angles = [(a, v, c) for v in range(n) for a in adj[v] for c in adj[v] if a < c]
+    dih = []
+    for j, k in bonds:
+        for i in adj[j]:
+            for l in adj[k]:
+                if i != k and l != j and i != l:
+                    dih.append((i, j, k, l) if len(dih) % reverse_every else (l, k, j, i))
+    dtype = [(i + l) % 3 for i, _, _, l in dih]
+    for row, ty in extra_dihedrals:
+        dih.append(row); dtype.append(ty)
+    d = dict(natoms=n, bonds=np.array(bonds), special_lj=np.where(special, 0.0, 1.0), special_coul=np.where(special, 0.0, 1.0))
+    pairs, levels = special_pairs(d)
+    return dict(n=n, owners=owners, rank=bfs_rank(n, bonds), bonds=np.array(bonds), angles=np.array(angles).reshape(-1, 3),
+                dihedrals=np.array(dih).reshape(-1, 4), dihedral_type=np.array(dtype), pairs=pairs, levels=levels)
+
+
+def butane():
+    """C0..C3 with hydrogens 4..13: CH3 at both ends"""
+    bonds = [(0, 1), (1, 2), (2, 3), (0, 4), (0, 5), (0, 6), (1, 7), (1, 8), (2, 9), (2, 10), (3, 11), (3, 12), (3, 13)]
+    return molecule(14, bonds)
+
+
+def four_ring():
+    """ring 0-1-2-3 with one substituent each: the 1-3 pairs (0, 2) and (1, 3) are the outer atoms of two angles"""
+    return molecule(8, [(0, 1), (1, 2), (2, 3), (3, 0), (0, 4), (1, 5), (2, 6), (3, 7)])
+
+
+def five_substituents():
+    """atom 0 with substituents 1..5 and a bond to atom 6 (substituents 7, 8); 7 carries 9.  Central bond (0, 6) has five end atoms on one
+    side.  Extra: the dihedral 8-6-7-9 of central bond (6, 7) listed a second time, and 10-11-12-13 of type 15 on a chain of its own."""
+    bonds = [(0, 1), (0, 2), (0, 3), (0, 4), (0, 5), (0, 6), (6, 7), (6, 8), (7, 9), (10, 11), (11, 12), (12, 13)]
+    t = molecule(14, bonds, extra_dihedrals=[((8, 6, 7, 9), 1)])
+    sel = [q for q, row in enumerate(t["dihedrals"]) if set(row[1:3]) == {11, 12}]
+    assert len(sel) == 1
+    t["dihedral_type"][sel[0]] = MAXTYPE
+    return t
+
+
+def fixtures(small_pe):
+    from scema_amd.systems import build_network
+    out = {"pe": topology_of(with_weights(small_pe, (0.0, 0.0, 0.5), (0.0, 0.0, 0.5))), "pe_no14": topology_of(small_pe)}
+    for size, drop, seed in ((4, 0.15, 3), (5, 0.0, 5)):
+        frac = build_network(size, drop=drop, seed=seed, special_lj=(0.0, 0.0, 0.5), special_coul=(0.0, 0.0, 0.8333))
+        out[f"net{size}"] = topology_of(frac)
+        out[f"net{size}_no14"] = topology_of(with_weights(frac, (0.0, 0.0, 1.0), (0.0, 0.0, 1.0)))
+        if size == 4:
+            perm = np.random.default_rng(17).permutation(frac["natoms"])
+            assert (perm != np.arange(len(perm))).mean() > 0.9
+            out["net4_scrambled"] = topology_of(permuted(frac, perm))
+    pe = with_weights(small_pe, (0.0, 0.0, 0.5), (0.0, 0.0, 0.5))
+    out["pe_scrambled"] = topology_of(permuted(pe, np.random.default_rng(17).permutation(pe["natoms"])))
+    out["butane"] = butane()
+    out["ring4"] = four_ring()
+    out["five"] = five_substituents()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the driver
+# ---------------------------------------------------------------------------------------------------------------------
+def write_input(t, path):
+    with open(path, "w") as f:
+        f.write(f"{t['n']} {t['owners']}\n" + " ".join(str(int(r)) for r in t["rank"]) + "\n")
+        f.write(f"{len(t['dihedrals'])}\n")
+        for row, ty in zip(t["dihedrals"], t["dihedral_type"]):
+            f.write(" ".join(str(int(v)) for v in row) + f" {int(ty)}\n")
+        for key in ("pairs", "bonds", "angles"):
+            f.write(f"{len(t[key])}\n")
+            for row in t[key]:
+                f.write(" ".join(str(int(v)) for v in row) + "\n")
+
+
+def run_driver(exe, t, tmp_path, name):
+    path = os.path.join(tmp_path, name + ".txt")
+    write_input(t, path)
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    groups, left, pair_host, bond_pair, angle_pair = [], [], {}, {}, {}
+    for line in r.stdout.splitlines():
+        w = line.split()
+        v = [int(x) for x in w[1:]]
+        if w[0] == "G":
+            groups.append(dict(c2=v[0], c3=v[1], nk=v[2], nm=v[3], k=v[4:7], m=v[7:10], type=v[10:19], count_tile=v[19], w0=v[20], w1=v[21], tiles=v[23:23 + v[22]]))
+        elif w[0] == "L":
+            left.append(v[0])
+        elif w[0] == "P":
+            pair_host[v[0]] = (v[1], v[2])
+        elif w[0] == "B":
+            bond_pair[v[0]] = v[1]
+        elif w[0] == "A":
+            angle_pair[v[0]] = v[1]
+    return dict(groups=groups, left=left, pair_host=pair_host, bond_pair=bond_pair, angle_pair=angle_pair, stdout=r.stdout)
+
+
+@pytest.fixture(scope="module")
+def inputs(small_pe):
+    return fixtures(small_pe)
+
+
+@pytest.fixture(scope="module")
+def results(inputs, tmp_path_factory):
+    exe = hostdrv.build("bonded_groups_host", SRC, shared=False)
+    tmp = str(tmp_path_factory.mktemp("bonded_groups"))
+    return {name: run_driver(exe, t, tmp, name) for name, t in inputs.items()}
+
+
+def canon(row, ty):
+    row = tuple(int(v) for v in row)
+    return (min(row, row[::-1]), int(ty))
+
+
+def sides(t):
+    """per unordered central bond: the distinct end atoms on the side of the lower and of the higher central atom, and the (k, m) list"""
+    out = collections.defaultdict(lambda: (set(), set(), []))
+    for (a, b, c, d_), ty in zip(t["dihedrals"], t["dihedral_type"]):
+        if b > c:
+            a, b, c, d_ = d_, c, b, a
+        s = out[(int(b), int(c))]
+        s[0].add(int(a)); s[1].add(int(d_)); s[2].append((int(a), int(d_), int(ty)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tests
+# ---------------------------------------------------------------------------------------------------------------------
+def test_inputs_hold_the_cases_they_are_there_for(inputs):
+    # a chain-end CH3: a central bond with three end atoms on a side, none of which has a further bond
+    t = inputs["butane"]
+    deg = np.bincount(t["bonds"].ravel(), minlength=t["n"])
+    ends = [s for s in sides(t).values() if any(len(side) == 3 and all(deg[a] == 1 for a in side) for side in s[:2])]
+    assert len(ends) == 2
+    # the crystal's chains: three end atoms on both sides of every central bond (two hydrogens and a carbon)
+    assert all(len(s[0]) == 3 and len(s[1]) == 3 for s in sides(inputs["pe"]).values())
+    # a side with more than three atoms; a dihedral listed twice; a type beyond the field
+    five = sides(inputs["five"])
+    assert len(five[(0, 6)][0]) == 5
+    assert collections.Counter((k, m) for k, m, _ in five[(6, 7)][2])[(8, 9)] == 2
+    assert [ty for _, _, ty in five[(11, 12)][2]] == [MAXTYPE]
+    # the fixtures' atoms have at most four bonds (why the molecule above is needed)
+    for name in ("pe", "net4", "net5"):
+        assert np.bincount(inputs[name]["bonds"].ravel()).max() == 4
+    # reversed dihedrals: listed with the higher-numbered central atom first
+    for name, t in inputs.items():
+        assert (t["dihedrals"][:, 1] > t["dihedrals"][:, 2]).any(), name
+    # a 1-3 pair with two candidate angles: the four-ring has two such pairs, the fixtures none
+    for name, t in inputs.items():
+        outer = collections.Counter((min(int(a), int(c)), max(int(a), int(c))) for a, _, c in t["angles"])
+        assert sum(1 for p in t["pairs"] if outer[(int(p[0]), int(p[1]))] >= 2) == (2 if name == "ring4" else 0), name
+    # special pairs without a host: the weighted 1-4 pairs
+    for name in ("pe", "net4", "net5", "butane"):
+        assert (inputs[name]["levels"] == 3).sum() > 0, name
+    assert (inputs["pe_no14"]["levels"] == 3).sum() == 0 and (inputs["net5_no14"]["levels"] == 3).sum() == 0
+    # tiles: every fixture spans several, and groups reach across them
+    for name, t in inputs.items():
+        assert t["rank"].max() // t["owners"] >= 1, name
+
+
+def test_groups_and_leftovers_expand_to_the_input(inputs, results):
+    for name, t in inputs.items():
+        r = results[name]
+        want = collections.Counter(canon(row, ty) for row, ty in zip(t["dihedrals"], t["dihedral_type"]))
+        got = collections.Counter(canon(t["dihedrals"][i], t["dihedral_type"][i]) for i in r["left"])
+        assert len(set(r["left"])) == len(r["left"])
+        for g in r["groups"]:
+            assert 1 <= g["nk"] <= 3 and 1 <= g["nm"] <= 3, name
+            ks, ms = g["k"][:g["nk"]], g["m"][:g["nm"]]
+            assert len(set(ks)) == g["nk"] and len(set(ms)) == g["nm"] and g["c2"] < g["c3"]
+            for ik in range(3):
+                for im in range(3):
+                    ty = g["type"][3 * ik + im]
+                    if ik >= g["nk"] or im >= g["nm"]:
+                        assert ty == -1
+                    elif ty >= 0:
+                        assert ty < MAXTYPE
+                        got[canon((ks[ik], g["c2"], g["c3"], ms[im]), ty)] += 1
+        assert got == want, name
+        # what stays a term is what the rule says, no more: all dihedrals of a central bond with more than three end atoms on a
+        # side, a (k, m) listed twice or a type the field does not hold
+        s = sides(t)
+        must_stay = {bond for bond, (ka, ma, km) in s.items()
+                     if len(ka) > 3 or len(ma) > 3 or len({(k, m) for k, m, _ in km}) < len(km) or any(ty >= MAXTYPE for _, _, ty in km)}
+        left_bonds = {tuple(sorted((int(t["dihedrals"][i][1]), int(t["dihedrals"][i][2])))) for i in r["left"]}
+        assert left_bonds == must_stay, name
+        assert {(g["c2"], g["c3"]) for g in r["groups"]} == set(s) - must_stay
+        assert len(r["left"]) == sum(len(s[bond][2]) for bond in must_stay)
+    assert results["five"]["left"] and not results["pe"]["left"] and not results["butane"]["left"]
+    # (the networks list most of their dihedrals from both ends: those central bonds keep their terms, the rest are groups)
+    assert len(results["net4"]["groups"]) > 50 and len(results["net4"]["left"]) > 1000 and not results["net5"]["groups"]
+    assert {(g["c2"], g["c3"]) for g in results["five"]["groups"]} == set()   # (0,6), (6,7), (11,12) all stay: nothing else has dihedrals
+    assert max(g["nk"] * g["nm"] for g in results["butane"]["groups"]) == 9
+
+
+def test_special_pairs_attach_once_and_exactly_where_a_host_exists(inputs, results):
+    for name, t in inputs.items():
+        r = results[name]
+        bond_of = {}
+        for b, (i, j) in enumerate(t["bonds"]):
+            bond_of.setdefault((min(int(i), int(j)), max(int(i), int(j))), b)
+        angle_of = {}
+        for a, (i, _, j) in enumerate(t["angles"]):
+            angle_of.setdefault((min(int(i), int(j)), max(int(i), int(j))), a)      # the lowest angle index where a ring offers two
+        hosted = collections.Counter()
+        for p, (i, j) in enumerate(t["pairs"]):
+            key = (int(i), int(j))
+            kind, host = r["pair_host"][p]
+            if key in bond_of:                                                       # bonds are tried before angles
+                assert (kind, host) == (1, bond_of[key]), (name, p)
+                assert t["levels"][p] == 1
+            elif key in angle_of:
+                assert (kind, host) == (2, angle_of[key]), (name, p)
+                assert t["levels"][p] == 2
+            else:
+                assert (kind, host) == (0, -1), (name, p)
+            if kind:
+                hosted[(kind, host)] += 1
+        assert all(c == 1 for c in hosted.values())                                  # a term hosts at most one pair
+        back = {(1, b): p for b, p in r["bond_pair"].items() if p >= 0}
+        back.update({(2, a): p for a, p in r["angle_pair"].items() if p >= 0})
+        assert back == {kh: p for p, kh in r["pair_host"].items() if kh[0]}
+        # the fixtures' bonds and angles are all in the file: every 1-2 and 1-3 pair has a host, no 1-4 pair has
+        kinds = np.array([r["pair_host"][p][0] for p in range(len(t["pairs"]))], int)
+        if len(kinds):
+            assert (kinds[t["levels"] == 3] == 0).all() and (kinds[t["levels"] < 3] > 0).all(), name
+    assert sum(1 for k, _ in results["net4"]["pair_host"].values() if k == 0) > 0
+
+
+def test_every_group_and_host_term_is_counted_by_one_tile_that_evaluates_it(inputs, results):
+    for name, t in inputs.items():
+        r = results[name]
+        tile = t["rank"] // t["owners"]
+        spanning = 0
+        for g in r["groups"]:
+            atoms = [g["c2"], g["c3"]] + g["k"][:g["nk"]] + g["m"][:g["nm"]]
+            assert sorted(set(g["tiles"])) == sorted(g["tiles"]) == sorted({int(tile[a]) for a in atoms}), name
+            assert g["count_tile"] == int(min(t["rank"][g["c2"]], t["rank"][g["c3"]])) // t["owners"]
+            assert g["tiles"].count(g["count_tile"]) == 1                            # counted once, by a tile that evaluates it
+            spanning += len(g["tiles"]) > 1
+            # the packed words (local index = atom & 1023; the driver packs for the first tile of the list)
+            w0, w1 = g["w0"], g["w1"]
+            idx = [(w0 >> (10 * q)) & 1023 for q in range(6)] + [w1 & 1023, (w1 >> 10) & 1023]
+            want = [g["c2"], g["c3"]] + [a if q < g["nk"] else 0 for q, a in enumerate(g["k"])] + [a if q < g["nm"] else 0 for q, a in enumerate(g["m"])]
+            assert idx == [a & 1023 for a in want]
+            assert ((w0 >> 60) & 3, w0 >> 62) == (g["nk"], g["nm"])
+            assert [((w1 >> (20 + 4 * q)) & 15) - 1 for q in range(9)] == g["type"]
+            assert (w1 >> 57) & 1 == 1 and (w1 >> 56) & 1 == (0 if g["tiles"][0] == g["count_tile"] else 1) and w1 >> 58 == 0
+        assert spanning > 0 or not r["groups"], name
+        # a host term is counted by the owner of its lowest-ranked atom; an attached pair goes with it, and every tile that needs the
+        # pair's force (an owner of either atom) evaluates the host, whose atoms include both
+        for (kind, host), p in [((k, h), p) for p, (k, h) in r["pair_host"].items() if k]:
+            atoms = t["bonds"][host] if kind == 1 else t["angles"][host]
+            host_tiles = {int(tile[a]) for a in atoms}
+            assert int(t["rank"][atoms].min()) // t["owners"] in host_tiles
+            assert {int(tile[a]) for a in t["pairs"][p]} <= host_tiles
+            assert set(int(a) for a in t["pairs"][p]) == ({int(atoms[0]), int(atoms[-1])})
+
+
+def test_the_driver_under_address_and_undefined_behaviour_sanitizers(inputs, results, tmp_path):
+    """the same program built with -fsanitize=address,undefined, run stand-alone on every input: the same output, no report"""
+    exe = hostdrv.build("bonded_groups_host_asan", SRC, shared=False, flags=["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    for name, t in inputs.items():
+        r = run_driver(exe, t, str(tmp_path), name)
+        assert r["stdout"] == results[name]["stdout"], name
