@@ -3,9 +3,12 @@ attached to the bond or angle term that holds their atoms), compiled for the hos
 (tests/bonded_groups_host_driver.cpp) and checked against restatements in Python.  No GPU needed.
 
 Inputs: the 360-atom polyethylene crystal, the 512- and 1000-atom networks with and without fractional 1-4 weights, each also under
-a random renumbering of its atoms -- and two hand-made molecules for the cases those fixtures cannot hold (their atoms have at most four
+a random renumbering of its atoms -- and three hand-made molecules for the cases those fixtures cannot hold (their atoms have at most four
 bonds, their chains no ends and their rings six members): a butane with CH3 ends, a four-ring, and a centre with five substituents
-next to an ordinary bond, with one dihedral listed twice and one of a type beyond the group's type field.  Every case is asserted to be present before anything is compared.
+next to an ordinary bond, with one dihedral listed twice and one of a type beyond the group's type field.  These three reach the grouping
+at four owners per tile.  At the kernel's 192 owners per tile: the zoo of small molecules and the united-atom chain of tests/bonded_zoo.py
+(which also holds the restatement of ranks, special pairs and the grouping rule that this file shares with the GPU tests), the zoo also
+renumbered.  Every case is asserted to be present before anything is compared.
 """
 import collections
 import os
@@ -15,56 +18,15 @@ import numpy as np
 import pytest
 
 import hostdrv
-from test_oracle_topologies import OWNERS, bond_levels, permuted, with_weights
+from bonded_zoo import MAXTYPE, W_B, bfs_rank, sides, special_pairs, stays_a_term, topology_of, ua_chain, zoo, zoo_cases, zoo_stats
+from test_oracle_topologies import permuted, with_weights
 
-MAXTYPE = 15          # BTG_MAXTYPE: dihedral types a group's four-bit field holds
 SRC = ["tests/bonded_groups_host_driver.cpp"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # inputs
 # ---------------------------------------------------------------------------------------------------------------------
-def bfs_rank(n, bonds):
-    """breadth-first ranks as build_topo assigns them: roots in index order, neighbours in bond-input order"""
-    adj = [[] for _ in range(n)]
-    for i, j in bonds:
-        adj[i].append(int(j)); adj[j].append(int(i))
-    rank = -np.ones(n, np.int64)
-    nr = 0
-    for root in range(n):
-        if rank[root] >= 0:
-            continue
-        rank[root] = nr; nr += 1
-        queue = [root]
-        for h in queue:
-            for c in adj[h]:
-                if rank[c] < 0:
-                    rank[c] = nr; nr += 1
-                    queue.append(c)
-    return rank
-
-
-def special_pairs(d):
-    """pairs (i < j) within three bonds whose weights are not both 1, with their level"""
-    lvl = bond_levels(d)
-    wl, wc = np.asarray(d["special_lj"]), np.asarray(d["special_coul"])
-    keep = np.zeros_like(lvl, bool)
-    for k in range(3):
-        if not (wl[k] == 1.0 and wc[k] == 1.0):
-            keep |= lvl == k + 1
-    ij = np.argwhere(np.triu(keep))
-    return ij, lvl[ij[:, 0], ij[:, 1]]
-
-
-def topology_of(d, owners=OWNERS):
-    n = int(d["natoms"])
-    bonds = np.asarray(d["bonds"]).reshape(-1, 2)
-    pairs, levels = special_pairs(d)
-    return dict(n=n, owners=owners, rank=bfs_rank(n, bonds), bonds=bonds, angles=np.asarray(d["angles"]).reshape(-1, 3),
-                dihedrals=np.asarray(d["dihedrals"]).reshape(-1, 4), dihedral_type=np.asarray(d["dihedral_type"]).ravel(),
-                pairs=pairs, levels=levels)
-
-
 def molecule(n, bonds, special=(True, True, True), owners=4, extra_dihedrals=(), reverse_every=2):
     """every angle and proper dihedral of a bond graph (every `reverse_every`-th dihedral listed backwards), special pairs at the levels
     flagged; tiles of `owners` atoms, so that a molecule of a dozen atoms spans several"""
@@ -125,6 +87,13 @@ def fixtures(small_pe):
     out["butane"] = butane()
     out["ring4"] = four_ring()
     out["five"] = five_substituents()
+    # the inputs of tests/test_gpu_bonded_zoo.py, all three levels weighted
+    z = zoo(W_B)
+    out["zoo"] = topology_of(z)
+    perm = np.random.default_rng(23).permutation(z["natoms"])
+    assert (perm != np.arange(len(perm))).mean() > 0.9
+    out["zoo_scrambled"] = topology_of(permuted(z, perm))
+    out["ua_chain"] = topology_of(ua_chain(W_B))
     return out
 
 
@@ -182,17 +151,6 @@ def canon(row, ty):
     return (min(row, row[::-1]), int(ty))
 
 
-def sides(t):
-    """per unordered central bond: the distinct end atoms on the side of the lower and of the higher central atom, and the (k, m) list"""
-    out = collections.defaultdict(lambda: (set(), set(), []))
-    for (a, b, c, d_), ty in zip(t["dihedrals"], t["dihedral_type"]):
-        if b > c:
-            a, b, c, d_ = d_, c, b, a
-        s = out[(int(b), int(c))]
-        s[0].add(int(a)); s[1].add(int(d_)); s[2].append((int(a), int(d_), int(ty)))
-    return out
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # tests
 # ---------------------------------------------------------------------------------------------------------------------
@@ -218,7 +176,7 @@ def test_inputs_hold_the_cases_they_are_there_for(inputs):
     # a 1-3 pair with two candidate angles: the four-ring has two such pairs, the fixtures none
     for name, t in inputs.items():
         outer = collections.Counter((min(int(a), int(c)), max(int(a), int(c))) for a, _, c in t["angles"])
-        assert sum(1 for p in t["pairs"] if outer[(int(p[0]), int(p[1]))] >= 2) == (2 if name == "ring4" else 0), name
+        assert sum(1 for p in t["pairs"] if outer[(int(p[0]), int(p[1]))] >= 2) == {"ring4": 2, "zoo": 8, "zoo_scrambled": 8}.get(name, 0), name
     # special pairs without a host: the weighted 1-4 pairs
     for name in ("pe", "net4", "net5", "butane"):
         assert (inputs[name]["levels"] == 3).sum() > 0, name
@@ -226,6 +184,7 @@ def test_inputs_hold_the_cases_they_are_there_for(inputs):
     # tiles: every fixture spans several, and groups reach across them
     for name, t in inputs.items():
         assert t["rank"].max() // t["owners"] >= 1, name
+    zoo_cases(zoo(W_B), ua_chain(W_B))
 
 
 def test_groups_and_leftovers_expand_to_the_input(inputs, results):
@@ -250,13 +209,19 @@ def test_groups_and_leftovers_expand_to_the_input(inputs, results):
         # what stays a term is what the rule says, no more: all dihedrals of a central bond with more than three end atoms on a
         # side, a (k, m) listed twice or a type the field does not hold
         s = sides(t)
-        must_stay = {bond for bond, (ka, ma, km) in s.items()
-                     if len(ka) > 3 or len(ma) > 3 or len({(k, m) for k, m, _ in km}) < len(km) or any(ty >= MAXTYPE for _, _, ty in km)}
+        must_stay = {bond for bond, side in s.items() if stays_a_term(side)}
         left_bonds = {tuple(sorted((int(t["dihedrals"][i][1]), int(t["dihedrals"][i][2])))) for i in r["left"]}
         assert left_bonds == must_stay, name
         assert {(g["c2"], g["c3"]) for g in r["groups"]} == set(s) - must_stay
         assert len(r["left"]) == sum(len(s[bond][2]) for bond in must_stay)
-    assert results["five"]["left"] and not results["pe"]["left"] and not results["butane"]["left"]
+    assert results["five"]["left"] and not results["pe"]["left"] and not results["butane"]["left"] and not results["ua_chain"]["left"]
+    # the zoo: what the driver groups is what zoo_stats restates
+    for name, d in (("zoo", zoo(W_B)), ("ua_chain", ua_chain(W_B))):
+        st = zoo_stats(d)
+        assert {(g["nk"], g["nm"]) for g in results[name]["groups"]} == st["shapes"], name
+        assert sorted((g["c2"], g["c3"]) for g in results[name]["groups"] if sum(ty >= 0 for ty in g["type"]) < g["nk"] * g["nm"]) == sorted(st["absent"])
+        per_tile = np.bincount([tl for g in results[name]["groups"] for tl in g["tiles"]], minlength=len(st["groups_per_tile"]))
+        assert (per_tile == st["groups_per_tile"]).all(), name
     # (the networks list most of their dihedrals from both ends: those central bonds keep their terms, the rest are groups)
     assert len(results["net4"]["groups"]) > 50 and len(results["net4"]["left"]) > 1000 and not results["net5"]["groups"]
     assert {(g["c2"], g["c3"]) for g in results["five"]["groups"]} == set()   # (0,6), (6,7), (11,12) all stay: nothing else has dihedrals

@@ -14,6 +14,7 @@ network (six tiles, no group: attached pairs and left-over terms alone).  tests/
 import numpy as np
 import pytest
 
+from bonded_zoo import masses, probe
 from test_oracle_topologies import KW, OWNERS, network_fixture, topo_stats, with_weights
 
 pytestmark = pytest.mark.gpu
@@ -59,32 +60,6 @@ def net4():
 def net5():
     from scema_amd.systems import build_network
     return build_network(5, drop=0.0, seed=5, special_lj=(0.0, 0.0, 0.5), special_coul=(0.0, 0.0, 0.8333))
-
-
-def masses(d):
-    return np.asarray(d["mass"])[np.asarray(d["type"])][:, None]
-
-
-def one_step(eng, name, d, state, use_shake):
-    """m (v1 - v0) and the sampled pressure of one step without thermostat from `state`"""
-    box, x, v = state
-    eng.set_state(3, name, 1, box, x, v)
-    p = eng.debug_run(name, 1, 1, 1.0, 300.0, qp=3, nvt=False, use_shake=use_shake, sample=True)
-    _, _, v1 = eng.get_state(3, name, 1)
-    return masses(d) * (v1 - v), np.array(p)
-
-
-def probe(eng, name, d, state, use_shake, bound_f, bound_p, what):
-    """mode 1 against mode 0 on one state; returns mode 1's (force, pressure)"""
-    eng.bonded_grouping(0)
-    f0, p0 = one_step(eng, name, d, state, use_shake)
-    eng.bonded_grouping(1)
-    f1, p1 = one_step(eng, name, d, state, use_shake)
-    df, dp = np.abs(f1 - f0).max() / np.abs(f0).max(), np.abs(p1 - p0).max() / max(1.0, np.abs(p0).max())
-    print(f"{what}: force difference {df:.3e} of the largest force, pressure difference {dp:.3e} of max(1, |p|) (largest |p| {np.abs(p0).max():.3e})")
-    assert np.abs(f0).max() > 0.0 and df <= bound_f, (what, df)
-    assert dp <= bound_p, (what, dp)
-    return f1, p1
 
 
 # Measured mode-1-minus-mode-0 differences on an MI355X, relative (force, pressure), per input: the largest over the states of the test
