@@ -755,6 +755,49 @@ int scema_md_born_long_kvectors(const char *path, int32_t energy_unit, const dou
 int scema_md_born_long_mesh(const char *path, int32_t energy_unit, const double *box, int32_t natoms, double qsqsum, double *g_ewald, int32_t *grid,
                             char *errbuf, int32_t errcap);
 
+/* ---- embedded-atom replicas with a long-range Coulomb sum (`pair_style hybrid/overlay coul/long <cut_coul> eam/alloy`, `kspace_style
+ * ewald|pppm <accuracy>`) ----
+ * The many-body form oxide models of the Cooper-Rushton-Grimes kind are written in (UO2, ThO2, CeO2 and their mixed oxides): the
+ * embedded-atom terms of scema_md_eam_configure on a setfl file plus the Coulomb sum of scema_md_born_long_configure over the replica's
+ * charges, the first stage made of two potentials.  `script_path` is any text file that holds the script lines themselves
+ * (in.strain.lammps included); blank-separated words, `#` starts a comment, every other command is ignored:
+ *   units metal|real                                          (optional; must not contradict energy_unit)
+ *   pair_style hybrid/overlay coul/long <cut_coul> eam/alloy  (the two sub-styles in either order)
+ *   pair_coeff * * coul/long
+ *   pair_coeff * * eam/alloy <file> <El> ...                  (one element per atom type)
+ *   kspace_style ewald|pppm <accuracy>
+ * <file> with a `${locs}/` prefix, or a relative name, is taken relative to the script's own folder; an absolute path as given.
+ * energy_unit 0: the setfl tables are eV and are converted with 23.060549, K = 14.399645 eV A; 1: as written, K = 332.06371.  The form:
+ *   E_eam  = sum_i F(rho_i) + 1/2 sum phi(r)                                over 0 < r^2 < (setfl cutoff)^2, as scema_md_eam_configure
+ *   E_coul = the four Coulomb terms of scema_md_born_long_configure        real space inside cut_coul, which may lie on either side of
+ *                                                                          the setfl cutoff
+ * One fused real-space kernel walks an atom's row once for both; the reciprocal part (Ewald sum or PPPM mesh per replica and run,
+ * scema_md_eam_coul_kspace), its limits and refusals, the box flips and the rules of attachment and skin are those of the Born/long
+ * stage.  Forces repeat bit for bit.  Refused with SCEMA_MD_ERR_IO and "<path> line <n>: <reason>": a pair style that is not
+ * hybrid/overlay, a third or another sub-style, either pair_coeff line missing or given twice, NULL as an element, no kspace_style line
+ * or two of them, a kspace_modify line, cut_coul <= 0, an accuracy outside (0, 1), and everything scema_md_eam_read_setfl refuses (its
+ * message is passed on).  A charged topology-free replica with nothing attached configures itself from such a `pair_style
+ * hybrid/overlay` line of <scripts_folder>/in.strain.lammps, searched after the two ionic styles; script lines the reader refuses there
+ * are SCEMA_MD_ERR_ARG, as for the two ionic styles (the request cannot run), while the setfl file's refusals stay SCEMA_MD_ERR_IO.
+ * Left on that row: eam/fs and funcfl
+ * readers, other sub-style pairs under hybrid/overlay, charge equilibration, more than four elements. */
+int scema_md_eam_coul_configure(scema_md_engine *e, const char *matid, const char *script_path, int32_t energy_unit, double skin);
+/* static evaluation: f [natoms*3], e_eam (embedding and pair energy), e_coul (real space, reciprocal space, self and background;
+ * kcal/mol), virial[6] (xx,yy,zz,xy,xz,yz), info[6]: that of scema_md_born_long_debug_compute with info[2] = ordered pairs inside the
+ * setfl cutoff (info[3]: inside cut_coul) */
+int scema_md_eam_coul_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_eam, double *e_coul,
+                                    double *virial, double *info);
+/* the three modes of scema_md_born_long_kspace for a material of this kind */
+int scema_md_eam_coul_kspace(scema_md_engine *e, const char *matid, int32_t mode);
+/* grid[3]: the mesh of the last scema_md_eam_coul_debug_compute, zeros if it ran the Ewald sum */
+int scema_md_eam_coul_last_mesh(scema_md_engine *e, int32_t *grid);
+/* The reader as a pure host function (no GPU, no engine; energy_unit may be -1: 1 iff the script says `units real`).  head[6]: cut_coul,
+ * accuracy, solver (0 ewald, 1 pppm), K (kcal A/mol), cutmax = max(setfl cutoff, cut_coul), the setfl cutoff; n_types and
+ * type_map[n_types] (room for type_cap): the element of the tables per atom type; setfl_path (room for setfl_cap bytes): the resolved
+ * file.  Any output may be null.  Refusals as for scema_md_eam_coul_configure, in errbuf. */
+int scema_md_eam_coul_read_params(const char *path, int32_t energy_unit, double *head, int32_t *n_types, int32_t *type_map, int32_t type_cap,
+                                  char *setfl_path, int32_t setfl_cap, char *errbuf, int32_t errcap);
+
 typedef struct {
   int64_t pair_launches;     /* timed pair-kernel launches */
   double pair_ms;             /* sum of their HIP-event durations */

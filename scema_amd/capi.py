@@ -49,6 +49,8 @@ SYMBOLS = [
     "scema_md_born_dsf_configure", "scema_md_born_dsf_debug_compute", "scema_md_born_dsf_read_params", "scema_md_born_dsf_eval",
     "scema_md_born_long_configure", "scema_md_born_long_debug_compute", "scema_md_born_long_read_params", "scema_md_born_long_eval",
     "scema_md_born_long_kvectors", "scema_md_born_long_kspace", "scema_md_born_long_last_mesh", "scema_md_born_long_mesh",
+    "scema_md_eam_coul_configure", "scema_md_eam_coul_debug_compute", "scema_md_eam_coul_kspace", "scema_md_eam_coul_last_mesh",
+    "scema_md_eam_coul_read_params",
 ]
 COMM_ID_BYTES = 128
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -659,6 +661,36 @@ class Engine:
         self._chk(lib().scema_md_born_long_last_mesh(self.h, _p(grid)))
         return tuple(int(v) for v in grid)
 
+    def eam_coul_configure(self, matid: str, path: str, energy_unit: int = 0, skin: float = -1.0):
+        """pair_style hybrid/overlay coul/long <cut_coul> eam/alloy for the replicas of one material id: `path` is a text file with the
+        script lines themselves (that pair_style line, pair_coeff * * coul/long, pair_coeff * * eam/alloy <file> <El> ..., kspace_style
+        ewald|pppm accuracy; optionally units real|metal); <file> is taken relative to the script's folder unless absolute; energy_unit 0:
+        the setfl tables are eV, K = 14.399645 eV A, 1: kcal/mol as written, K = 332.06371.  The charges are those of the registered
+        replica (ionic_system).  Replaces whatever potential the material held"""
+        self._chk(lib().scema_md_eam_coul_configure(self.h, matid.encode(), path.encode(), C.c_int32(energy_unit), C.c_double(skin)))
+
+    def eam_coul_compute(self, matid, replica, qp=QP_NONE):
+        """e_eam: embedding and pair energy; e_coul: real space, reciprocal space, self and background; npairs: ordered pairs inside the
+        setfl cutoff; ncoul: ordered pairs inside cut_coul; nk: k-vectors of the half space; g_ewald of the evaluation"""
+        n = self.natoms(matid, replica)
+        f = np.zeros((n, 3)); ea = C.c_double(0.0); eb = C.c_double(0.0); w = np.zeros(6); info = np.zeros(6)
+        self._chk(lib().scema_md_eam_coul_debug_compute(self.h, C.c_int32(qp), matid.encode(), C.c_int32(replica), _p(f), C.byref(ea), C.byref(eb), _p(w),
+                                                        _p(info)))
+        return {"f": f, "e_eam": ea.value, "e_coul": eb.value, "w": w, "maxrow": int(info[0]), "rowcap": int(info[1]), "npairs": int(info[2]),
+                "ncoul": int(info[3]), "nk": int(info[4]), "g_ewald": float(info[5])}
+
+    eam_coul_debug_compute = eam_coul_compute
+
+    def eam_coul_kspace(self, matid: str, mode: int = 0):
+        """the reciprocal solver of an EAM/coul material's replicas: the three modes of born_long_kspace"""
+        self._chk(lib().scema_md_eam_coul_kspace(self.h, matid.encode(), C.c_int32(mode)))
+
+    def eam_coul_last_mesh(self):
+        """the mesh (nx, ny, nz) of the last eam_coul_compute, zeros if it ran the Ewald sum"""
+        grid = np.zeros(3, np.int32)
+        self._chk(lib().scema_md_eam_coul_last_mesh(self.h, _p(grid)))
+        return tuple(int(v) for v in grid)
+
     def adp_configure(self, matid: str, path: str, elements=("Cu",), energy_unit: int = 0, skin: float = -1.0):
         """pair_style adp + pair_coeff * * <path> <elements> for the replicas of one material id (an extended setfl file); energy_unit 0: F
         and r phi are eV, u and w the square root of eV per A and per A^2; 1: kcal/mol as written.  Replaces whatever potential the material held"""
@@ -845,6 +877,22 @@ def born_long_mesh(path: str, box, natoms: int, qsqsum: float, energy_unit: int 
     if rc != 0:
         raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
     return dict(g_ewald=g.value, grid=tuple(int(v) for v in grid))
+
+
+def eam_coul_read_params(path: str, energy_unit: int = 0):
+    """dict of the hybrid/overlay coul/long eam/alloy lines of a text file and the setfl file it names (scema_md_eam_coul_read_params, a
+    pure host function, no GPU): cut_coul, accuracy, solver ("ewald" or "pppm"), K (kcal A/mol), cutmax, cutoff (of the setfl file),
+    type_map (element of the tables per atom type) and setfl (the resolved path); raises IOError with the reader's message"""
+    read = lib().scema_md_eam_coul_read_params
+    read.restype = C.c_int
+    head, nt, tmap = np.zeros(6), C.c_int32(0), np.zeros(64, np.int32)
+    setfl, err = C.create_string_buffer(4096), C.create_string_buffer(512)
+    rc = read(path.encode(), C.c_int32(energy_unit), _p(head), C.byref(nt), _p(tmap), C.c_int32(len(tmap)), setfl, C.c_int32(len(setfl)), err,
+              C.c_int32(len(err)))
+    if rc != 0:
+        raise IOError(f"rc={rc}: {err.value.decode(errors='replace')}")
+    return dict(cut_coul=head[0], accuracy=head[1], solver="pppm" if head[2] else "ewald", K=head[3], cutmax=head[4], cutoff=head[5],
+                type_map=[int(v) for v in tmap[:min(nt.value, len(tmap))]], setfl=setfl.value.decode())
 
 
 SW_FIELDS = ["epsilon", "sigma", "a", "lambda", "gamma", "costheta0", "A", "B", "p", "q", "tol"]

@@ -48,6 +48,7 @@
 #include "host/meam_spline_params.h"
 #include "host/born_dsf_params.h"
 #include "host/born_long_params.h"
+#include "host/eam_coul_params.h"
 #include <hipfft/hipfft.h>
 
 #include "md_kernels.h"
@@ -66,6 +67,7 @@
 #include "md_born_dsf.h"
 #include "md_born_long.h"
 #include "md_born_long_mesh.h"
+#include "md_eam_coul.h"
 #include "md_rowcells.h"
 #include "md_types.h"
 
@@ -206,7 +208,7 @@ struct RowSlot {
   DevBuf cstart, ccur, clist, cellof;
 };
 
-enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline, BornDsf, BornLong };
+enum class RowKind { Opls, Reax, Sw, Tersoff, Eam, TersoffMod, TersoffZbl, Vashishta, Adp, Edip, MeamSpline, BornDsf, BornLong, EamCoul };
 
 // a row potential attached to a material id (scema_md_sw_configure, scema_md_tersoff_configure, scema_md_eam_configure, ...: row_pots).  A material
 // holds one: configuring replaces whatever it held, and rows and element arrays never pass from one attachment to the next (stamp)
@@ -216,9 +218,9 @@ struct RowMaterial {
   double cutmax = 0.0;         // largest cutoff of the tables
   double skin = 1.0;           // `neighbor 1.0 nsq` (lammps_scripts_sisw/in.set.lammps)
   long long stamp = 0;         // unique per configure call: rows and element arrays built under another stamp are rebuilt
-  double kspace_cut = 0.0, kspace_acc = 0.0;   // Born/long: cut_coul and the accuracy of the kspace_style line (the k-space set-up of a run: ewald_setup)
+  double kspace_cut = 0.0, kspace_acc = 0.0;   // Born/long, EAM/coul: cut_coul and the accuracy of the kspace_style line (the k-space set-up of a run: ewald_setup)
   int kspace_pppm = 0, kspace_mode = 0;        // Born/long: 1: the script said `kspace_style pppm`; scema_md_born_long_kspace (0 by the script and the Ewald limits, 1 the mesh, 2 the Ewald sum)
-  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable / BlTable on the device
+  DevBuf d_tab;                // the SwTable / TsTable / EAM block (eam/eam_core.h) / TsModTable / TsZblTable / VsTable / ADP block (eam/adp_core.h) / EdipTable / MsTable / BdTable / BlTable / EAM/coul block (eam/ec_core.h) on the device
 };
 
 // what the neighbour rows of a slot were built for: a run that follows on the same slot keeps them if all of it still holds.  Every stage
@@ -589,7 +591,7 @@ struct RowRun {
 };
 int run_rows(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, RowStage &stage);
 // The potentials on full neighbour rows (engine_rowpot.cpp), one entry each in the order Stillinger-Weber, Tersoff, EAM, Tersoff/mod,
-// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline, Born/DSF, Born/long: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
+// Tersoff/ZBL, Vashishta, ADP, EDIP, MEAM/spline, Born/DSF, Born/long, EAM/coul: the order in which a run or an update that mixes kinds names the kind it refuses, and in which a bare replica's scripts
 // folder is searched
 struct RowPot {
   RowKind kind;
@@ -599,7 +601,7 @@ struct RowPot {
   int (*configure)(scema_md_engine *e, const char *matid, const char *path, const char *const *elements, int32_t n_elements, int32_t energy_unit, double skin);
   RowStage *(*stage)(scema_md_engine *e, int ns, const RowPot &pot);   // a new force stage for a run of ns simulations
 };
-constexpr int ROW_NPOT = 11;
+constexpr int ROW_NPOT = 12;
 extern const RowPot row_pots[ROW_NPOT];
 // the entry of the potential attached to a material id, or null
 const RowPot *row_pot_of(scema_md_engine *e, const char *matid);
@@ -616,6 +618,8 @@ bool ionic_replica(const Topo &t);
 int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 // the same for a `pair_style born/coul/long` or `buck/coul/long` line (host/born_long_params.h), called after the DSF one
 int born_long_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
+// the same for a `pair_style hybrid/overlay` line (coul/long with eam/alloy: host/eam_coul_params.h), called after the two ionic styles
+int eam_coul_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder);
 // engine_state.cpp
 State *find_state(scema_md_engine *e, int qp, const char *matid, int replica);
 Topo *find_topo(scema_md_engine *e, const char *matid, int replica);

@@ -262,6 +262,7 @@ int scema_md_strain_batch(scema_md_engine *e, scema_mdsim *sims, int32_t n_sims,
       } else if (t && ionic_replica(*t)) {   // (the one row kind that reads charges: `pair_style born/coul/dsf` in in.strain.lammps)
         rc_cfg = born_dsf_from_scripts(e, sims[i].matid, folder);
         if (!rc_cfg && !row_pot_of(e, sims[i].matid)) rc_cfg = born_long_from_scripts(e, sims[i].matid, folder);   // (`born/coul/long`, `buck/coul/long`)
+        if (!rc_cfg && !row_pot_of(e, sims[i].matid)) rc_cfg = eam_coul_from_scripts(e, sims[i].matid, folder);    // (`hybrid/overlay coul/long eam/alloy`)
       }
       if (rc_cfg && !collective_call) return rc_cfg;
       if (rc_cfg && !pre_status) pre_status = rc_cfg;   // (a file one rank cannot read: the others must hear of it)

@@ -1,5 +1,5 @@
 // engine_rowpot.cpp -- host side of the potentials on full neighbour rows (`pair_style sw`: the reference's examples/streched_polyhedron;
-// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`; `pair_style born/coul/dsf`; `pair_style born/coul/long`, `buck/coul/long`): the stage they
+// `pair_style tersoff`; `pair_style eam/alloy`; `pair_style tersoff/mod`, `tersoff/mod/c`; `pair_style tersoff/zbl`; `pair_style vashishta`; `pair_style adp`; `pair_style edip`, `edip/multi`; `pair_style meam/spline`; `pair_style born/coul/dsf`; `pair_style born/coul/long`, `buck/coul/long`; `pair_style hybrid/overlay coul/long eam/alloy`): the stage they
 // share, the table that tells them apart (row_pots), their stages and their entry points of the C ABI.  A further potential is one entry of the table, a reader for its configure entry point and a kernel.
 #include "engine.h"
 #include "../md_env.h"
@@ -230,7 +230,7 @@ int RowPotStage::crowded(int fault) {
 }
 
 // ---- the stages: each launches its kernels (mdk_row_forces for the list kernels of md_sw.h, md_tersoff.h, md_vashishta.h, md_edip.h;
-// mdk_row_stage for the stages with launches of their own: md_eam.h, md_adp.h, md_meam_spline.h, md_born_dsf.h, md_born_long.h) ----
+// mdk_row_stage for the stages with launches of their own: md_eam.h, md_adp.h, md_meam_spline.h, md_born_dsf.h, md_born_long.h, md_eam_coul.h) ----
 
 namespace {
 
@@ -474,7 +474,9 @@ struct BlStage : RowPotStage {
     const FftCall &c = *(const FftCall *)ctx;
     return c.stage->transform(c.st, c.pos0, c.n, backward != 0);
   }
-  void launch(hipStream_t st, int pos0, int n) override {
+  void launch(hipStream_t st, int pos0, int n) override { launch_real(st, pos0, n, nullptr); }
+  // real: what a stage with a real-space part of its own enqueues in place of k_bl_force (md_born_long.h)
+  void launch_real(hipStream_t st, int pos0, int n, const std::function<void(dim3)> *real) {
     if (fft_rc) return;
     int maxnk = 0, maxgrid = 0;
     bool ewald = false;
@@ -485,14 +487,14 @@ struct BlStage : RowPotStage {
       ewald = ewald || !e->h_blviews[k].mesh;
     }
     if (maxgrid == 0) {
-      mdk_bl_forces(st, run->D + pos0, VV + pos0, BB + pos0, n, run->maxatoms, maxnk);
+      mdk_bl_forces(st, run->D + pos0, VV + pos0, BB + pos0, n, run->maxatoms, maxnk, true, nullptr, real);
       return;
     }
     // the influence function follows the box: every step of a run whose box moves (fix deform, the barostat), else the run's first call
     const RunSpec &sp = run->spec;
     const bool new_box = cur_step == 0 || sp.deform || (sp.nh && sp.npt);
     FftCall call{this, st, pos0, n};
-    fft_rc = mdk_bl_mesh_forces(st, run->D + pos0, VV + pos0, BB + pos0, MM + pos0, n, run->maxatoms, maxnk, ewald, maxgrid, new_box, transform_entry, &call);
+    fft_rc = mdk_bl_mesh_forces(st, run->D + pos0, VV + pos0, BB + pos0, MM + pos0, n, run->maxatoms, maxnk, ewald, maxgrid, new_box, transform_entry, &call, real);
     if (fft_rc) fft_msg = e->err;
   }
   // (the mesh lives in the fractional coordinates of the step's box, and the box of the step after a flip is the flipped one)
@@ -508,6 +510,30 @@ struct BlStage : RowPotStage {
 
 int born_long_configure_entry(scema_md_engine *e, const char *matid, const char *path, const char *const *, int32_t, int32_t energy_unit, double skin) {
   return scema_md_born_long_configure(e, matid, path, energy_unit, skin);
+}
+
+// EAM + long-range Coulomb (`pair_style hybrid/overlay coul/long <cut_coul> eam/alloy`): the first stage made of two potentials.  The
+// Born/long stage as it is -- the k-space set-up per run, the Ewald-or-mesh decision per replica, the transforms, the flips, the
+// refusals beyond the limits -- with the side array of the embedded-atom stage (F' per atom) and the fused real-space kernels of
+// md_eam_coul.h in the place of k_bl_force.  The element of an atom is that of the setfl tables (RowMaterial::type_map).
+struct EcStage : BlStage {
+  EamView *AA = nullptr;   // on the device (upload)
+  EcStage(scema_md_engine *e_, int ns, const RowPot &pot) : BlStage(e_, ns, pot) { e->h_eamviews.assign(ns, EamView()); }
+  int bind(int pos, const ActiveSim &A, Slot &sl, const SimDev &S, const RowNeed &need) override {
+    if (const int rc = BlStage::bind(pos, A, sl, S, need)) return rc;
+    HIPCHK(sl.row->fp.ensure((size_t)S.npad * sizeof(double)));
+    e->h_eamviews[pos].fp = (decltype(EamView::fp))sl.row->fp.as<double>();
+    return SCEMA_MD_OK;
+  }
+  int upload() override { const int rc = BlStage::upload(); return rc ? rc : upload_views(e, e->d_eamviews, e->h_eamviews, AA); }
+  void launch(hipStream_t st, int pos0, int n) override {
+    const std::function<void(dim3)> real = [&](dim3 gt) { mdk_ec_real(st, gt, run->D + pos0, VV + pos0, AA + pos0, BB + pos0); };
+    launch_real(st, pos0, n, &real);
+  }
+};
+
+int eam_coul_configure_entry(scema_md_engine *e, const char *matid, const char *path, const char *const *, int32_t, int32_t energy_unit, double skin) {
+  return scema_md_eam_coul_configure(e, matid, path, energy_unit, skin);
 }
 
 template <class Stage>
@@ -530,6 +556,7 @@ const RowPot row_pots[ROW_NPOT] = {
     {RowKind::MeamSpline, "MEAM/spline", "scema_md_meam_spline_configure", {".meam.spline", nullptr}, scema_md_meam_spline_configure, make_stage<MsStage>},
     {RowKind::BornDsf, "Born/DSF", "scema_md_born_dsf_configure", {nullptr, nullptr}, born_dsf_configure_entry, make_stage<BdStage>},
     {RowKind::BornLong, "Born/long", "scema_md_born_long_configure", {nullptr, nullptr}, born_long_configure_entry, make_stage<BlStage>},
+    {RowKind::EamCoul, "EAM/coul", "scema_md_eam_coul_configure", {nullptr, nullptr}, eam_coul_configure_entry, make_stage<EcStage>},
 };
 
 int run_phase_rowpot(scema_md_engine *e, std::vector<ActiveSim> &sims, const RunSpec &spec, const RowPot &pot) {
@@ -610,6 +637,19 @@ int born_dsf_from_scripts(scema_md_engine *e, const char *matid, const std::stri
 
 int born_long_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
   return ionic_from_scripts<BlTable>(e, matid, folder, scema::read_born_long_params, scema_md_born_long_configure);
+}
+
+// the same for `pair_style hybrid/overlay coul/long <cut_coul> eam/alloy`: the script names its own setfl file and elements
+int eam_coul_from_scripts(scema_md_engine *e, const char *matid, const std::string &folder) {
+  const std::string script = folder + "/in.strain.lammps";
+  if (!std::ifstream(script).good()) return SCEMA_MD_OK;
+  scema::EamCoulParams P;
+  std::string err;
+  bool has_style = false;
+  const bool ok = scema::read_eam_coul_script(script, -1, P, err, &has_style);
+  if (!has_style) return SCEMA_MD_OK;   // (another style's script, or none: nothing changes for the replica)
+  if (!ok) return fail(e, SCEMA_MD_ERR_ARG, "%s", err.c_str());
+  return scema_md_eam_coul_configure(e, matid, script.c_str(), P.unit, -1.0);
 }
 
 // ---- what the entry points of the C ABI share.  row_configure: `read` fills type_map from the file and says where its host table
@@ -887,15 +927,66 @@ int scema_md_born_long_configure(scema_md_engine *e, const char *matid, const ch
   return SCEMA_MD_OK;
 }
 
-int scema_md_born_long_kspace(scema_md_engine *e, const char *matid, int32_t mode) {
+// the reciprocal solver mode of a material of that kind (scema_md_born_long_kspace, scema_md_eam_coul_kspace)
+static int row_kspace_mode(scema_md_engine *e, RowKind kind, const char *matid, int32_t mode) {
   if (!e) return SCEMA_MD_ERR_ARG;
   if (!matid) return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
   auto it = e->row_mats.find(matid);
-  if (it == e->row_mats.end() || it->second->kind != RowKind::BornLong)
-    return fail(e, SCEMA_MD_ERR_ARG, "no Born/long potential attached to material %s (scema_md_born_long_configure)", matid);
+  if (it == e->row_mats.end() || it->second->kind != kind) {
+    for (const RowPot &P : row_pots)
+      if (P.kind == kind) return fail(e, SCEMA_MD_ERR_ARG, "no %s potential attached to material %s (%s)", P.name, matid, P.configure_name);
+    return fail(e, SCEMA_MD_ERR_ARG, "bad arguments");
+  }
   if (mode < 0 || mode > 2) return fail(e, SCEMA_MD_ERR_ARG, "reciprocal solver mode %d (0: by the script and the Ewald limits, 1: the mesh, 2: the Ewald sum)", mode);
   it->second->kspace_mode = mode;
   return SCEMA_MD_OK;
+}
+
+// the static evaluation of a stage with a reciprocal part: info[6], and the mesh it ran on for *_last_mesh
+static int row_kspace_debug_compute(scema_md_engine *e, RowKind kind, int32_t qp_id, const char *matid, int32_t replica, double *f, double *ea, double *eb,
+                                    double *virial, double *info) {
+  double info4[4] = {0.0, 0.0, 0.0, 0.0};
+  if (e) e->blm_last_mesh[0] = e->blm_last_mesh[1] = e->blm_last_mesh[2] = 0;
+  const int rc = row_debug_compute(e, kind, qp_id, matid, replica, f, ea, eb, virial, info4);
+  if (rc) return rc;
+  if (!e->h_blmviews.empty())
+    for (int d = 0; d < 3; d++) e->blm_last_mesh[d] = e->h_blmviews[0].n[d];
+  if (info) {
+    for (int k = 0; k < 4; k++) info[k] = info4[k];
+    info[4] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].nk;
+    info[5] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].g;
+  }
+  return SCEMA_MD_OK;
+}
+
+int scema_md_born_long_kspace(scema_md_engine *e, const char *matid, int32_t mode) { return row_kspace_mode(e, RowKind::BornLong, matid, mode); }
+
+int scema_md_eam_coul_configure(scema_md_engine *e, const char *matid, const char *path, int32_t energy_unit, double skin) {
+  if (e && energy_unit != 0 && energy_unit != 1) return fail(e, SCEMA_MD_ERR_ARG, "energy unit %d (0: the setfl tables in eV, 1: in kcal/mol)", energy_unit);
+  std::vector<double> block;
+  scema::EamCoulParams P;
+  auto read = [&](const std::vector<std::string> &, std::vector<int> &type_map, RowTableBlock &blk, std::string &err) {
+    if (!scema::build_eam_coul_block(path, energy_unit, block, type_map, P, err)) return false;
+    blk = RowTableBlock{block.data(), block.size() * sizeof(double), scema::eam_coul_table(block).bd.cutmax};
+    return true;
+  };
+  static const char *const no_elements[1] = {"*"};   // (the script's eam/alloy line names the elements)
+  const int rc = row_configure(e, RowKind::EamCoul, matid, path, no_elements, 1, skin, read);
+  if (rc) return rc;
+  RowMaterial &M = *e->row_mats[matid];
+  M.kspace_cut = P.cut_coul;
+  M.kspace_acc = P.accuracy;
+  M.kspace_pppm = P.pppm;
+  return SCEMA_MD_OK;
+}
+
+int scema_md_eam_coul_kspace(scema_md_engine *e, const char *matid, int32_t mode) { return row_kspace_mode(e, RowKind::EamCoul, matid, mode); }
+
+int scema_md_eam_coul_last_mesh(scema_md_engine *e, int32_t *grid) { return scema_md_born_long_last_mesh(e, grid); }
+
+int scema_md_eam_coul_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_eam, double *e_coul,
+                                    double *virial, double *info) {
+  return row_kspace_debug_compute(e, RowKind::EamCoul, qp_id, matid, replica, f, e_eam, e_coul, virial, info);
 }
 
 int scema_md_born_long_last_mesh(scema_md_engine *e, int32_t *grid) {
@@ -906,18 +997,7 @@ int scema_md_born_long_last_mesh(scema_md_engine *e, int32_t *grid) {
 
 int scema_md_born_long_debug_compute(scema_md_engine *e, int32_t qp_id, const char *matid, int32_t replica, double *f, double *e_born, double *e_coul,
                                      double *virial, double *info) {
-  double info4[4] = {0.0, 0.0, 0.0, 0.0};
-  if (e) e->blm_last_mesh[0] = e->blm_last_mesh[1] = e->blm_last_mesh[2] = 0;
-  const int rc = row_debug_compute(e, RowKind::BornLong, qp_id, matid, replica, f, e_born, e_coul, virial, info4);
-  if (rc) return rc;
-  if (!e->h_blmviews.empty())
-    for (int d = 0; d < 3; d++) e->blm_last_mesh[d] = e->h_blmviews[0].n[d];
-  if (info) {
-    for (int k = 0; k < 4; k++) info[k] = info4[k];
-    info[4] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].nk;
-    info[5] = e->h_blviews.empty() ? 0.0 : e->h_blviews[0].g;
-  }
-  return SCEMA_MD_OK;
+  return row_kspace_debug_compute(e, RowKind::BornLong, qp_id, matid, replica, f, e_born, e_coul, virial, info);
 }
 
 // what the two pure host entries below open with: the message buffer emptied, the common argument rules beside the entry's own

@@ -27,20 +27,24 @@ typedef struct {
   int pppm, buck;          // 1: the script said `kspace_style pppm` (honoured as the Ewald sum at that accuracy); 1: buck/coul/long
 } BlTable;
 
-// A pair of atoms with charges qi, qj at squared distance r2 > 0: the whole energies of the pair and the force factors fb, fc with
-// (force on i) = -(fb + fc) d, d = x_j - x_i, as bd_pair.  Beyond a term's cutoff its two outputs are exactly 0.
-BD_HD void bl_pair(const BlTable &T, const BdPairP &P, double g, double qi, double qj, double r2, double *e_born, double *e_coul, double *fb, double *fc) {
-  double unused_e, unused_f;
-  bd_pair(T.bd, P, 0.0, 0.0, r2, e_born, &unused_e, fb, &unused_f);   // (charges 0: the Born term alone)
+// The real-space Coulomb term of a pair at distance r > 0 (kc: K of the table): energy and force factor, exactly 0 at and beyond cut_coul
+BD_HD void bl_coul(double kc, double cut_coul, double g, double qi, double qj, double r, double *e_coul, double *fc) {
   *e_coul = *fc = 0.0;
-  const double r = sqrt(r2);
-  const double qq = T.bd.k * qi * qj;
-  if (r < T.bd.cut_coul && qq != 0.0) {
+  const double qq = kc * qi * qj;
+  if (r < cut_coul && qq != 0.0) {
     const double ir = 1.0 / r, gr = g * r;
     const double erfcc = erfc(gr), erfcd = exp(-gr * gr);
     *e_coul = qq * erfcc * ir;
     *fc = qq * (erfcc * ir + BD_TWO_OVER_SQRTPI * g * erfcd) * ir * ir;
   }
+}
+
+// A pair of atoms with charges qi, qj at squared distance r2 > 0: the whole energies of the pair and the force factors fb, fc with
+// (force on i) = -(fb + fc) d, d = x_j - x_i, as bd_pair.  Beyond a term's cutoff its two outputs are exactly 0.
+BD_HD void bl_pair(const BlTable &T, const BdPairP &P, double g, double qi, double qj, double r2, double *e_born, double *e_coul, double *fb, double *fc) {
+  double unused_e, unused_f;
+  bd_pair(T.bd, P, 0.0, 0.0, r2, e_born, &unused_e, fb, &unused_f);   // (charges 0: the Born term alone)
+  bl_coul(T.bd.k, T.bd.cut_coul, g, qi, qj, sqrt(r2), e_coul, fc);
 }
 
 // the self energy of a replica: the point term and the neutralising background (its only strain-dependent part, returned apart)

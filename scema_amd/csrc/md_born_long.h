@@ -28,7 +28,9 @@ typedef struct {
 // force), k_row_finish.  maxnk: the largest BlView::nk of the ns replicas.  Virial parts: P_LJ for the Born term, P_COUL for everything
 // Coulomb.  ewald false: no replica of the group runs the Ewald sum and the pair of reciprocal kernels is not launched; mesh: what the
 // mesh solver enqueues for its replicas between the Ewald pair and k_row_finish (md_born_long_mesh.h), given the grid of k_bl_force.
+// real: what a stage with a real-space part of its own enqueues in place of k_bl_force, given that grid (md_eam_coul.h: the density pass,
+// then the fused force pass); it stores SimDev::f and adds the real-space Coulomb energy to eacc[1].  Absent: k_bl_force.
 void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk, bool ewald = true,
-                   const std::function<void(dim3)> *mesh = nullptr);
+                   const std::function<void(dim3)> *mesh = nullptr, const std::function<void(dim3)> *real = nullptr);
 // a box flip of one replica by fxy, fxz lattice steps, after mdk_flip on the same stream: the triples keep their Cartesian vectors
 void mdk_bl_flip(hipStream_t st, const BlView *b, int fxy, int fxz);

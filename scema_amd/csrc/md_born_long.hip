@@ -192,10 +192,11 @@ __global__ void k_bl_flip(const BlView *b, int fxy, int fxz) {
 }
 
 void mdk_bl_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, int ns, int maxatoms, int maxnk, bool ewald,
-                   const std::function<void(dim3)> *mesh) {
+                   const std::function<void(dim3)> *mesh, const std::function<void(dim3)> *real) {
   mdk_row_stage(st, d, v, ns, maxatoms, [&](dim3 gt) {
     const dim3 gk((unsigned)std::max(1, (maxnk + BL_SF_TPB - 1) / BL_SF_TPB), (unsigned)ns, 1);
-    hipLaunchKernelGGL(k_bl_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
+    if (real) (*real)(gt);
+    else hipLaunchKernelGGL(k_bl_force, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);
     if (ewald) {
       hipLaunchKernelGGL(k_bl_sfac, gk, dim3(BL_SF_TPB), 0, st, d, v, b);
       hipLaunchKernelGGL(k_bl_recip, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, b);

@@ -29,6 +29,6 @@ typedef int (*BlmTransform)(void *ctx, int backward);
 // The force stage of one step for the first ns replicas, Ewald and mesh replicas alike: the row part, k_bl_force, the Ewald pair where
 // `ewald` (a replica of the group runs the Ewald sum), then for the mesh replicas (maxgrid: their largest mesh, 0 for none) k_blm_assign,
 // k_blm_convert, the forward transform, k_blm_gf where new_box, k_blm_poisson, the backward transforms, k_blm_interp; k_row_finish.
-// Returns what a transform returned (0: all enqueued).
+// Returns what a transform returned (0: all enqueued).  real: as for mdk_bl_forces, what takes the place of k_bl_force.
 int mdk_bl_mesh_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, const BlmView *m, int ns, int maxatoms, int maxnk, bool ewald,
-                       int maxgrid, bool new_box, BlmTransform transform, void *ctx);
+                       int maxgrid, bool new_box, BlmTransform transform, void *ctx, const std::function<void(dim3)> *real = nullptr);

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_blm_interp(const SimDev *sims
 }
 
 int mdk_bl_mesh_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView *b, const BlmView *m, int ns, int maxatoms, int maxnk, bool ewald,
-                       int maxgrid, bool new_box, BlmTransform transform, void *ctx) {
+                       int maxgrid, bool new_box, BlmTransform transform, void *ctx, const std::function<void(dim3)> *real) {
   int rc = 0;
   const std::function<void(dim3)> chain = [&](dim3 gt) {
     if (maxgrid <= 0) return;
@@ -211,6 +211,6 @@ int mdk_bl_mesh_forces(hipStream_t st, const SimDev *d, RowView *v, const BlView
     if ((rc = transform(ctx, 1))) return;
     hipLaunchKernelGGL(k_blm_interp, gt, dim3(ROW_FORCE_TPB), 0, st, d, v, m);
   };
-  mdk_bl_forces(st, d, v, b, ns, maxatoms, maxnk, ewald, &chain);
+  mdk_bl_forces(st, d, v, b, ns, maxatoms, maxnk, ewald, &chain, real);
   return rc;
 }

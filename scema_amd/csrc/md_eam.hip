@@ -11,56 +11,18 @@
 #include <hip/hip_runtime.h>
 
 #include "md_eam.h"
-#include "md_kernels.h"
-#include "md_rowforce.h"
+#include "md_eam_body.h"
 
-typedef const double ROW_G *EamTab;
-
-// Densities.  A workgroup owns ROW_TILE consecutive central atoms of one replica, a group of 16 lanes one of them at a time; the group's
-// first lane evaluates F and F'.  Value records only (eam_core.h).
+// Densities: the body both embedded-atom stages share (eam_density_body, md_eam_body.h): the embedding energy to eacc[1], the atoms above
+// rhomax to eacc[3].
 __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_density(const SimDev *sims, const RowView *views, const EamView *aux) {
   const RowView V = views[blockIdx.y];
-  const int n = V.n;
-  if ((int)(blockIdx.x * ROW_TILE) >= n) return;   // (the whole workgroup)
-  const EamTab blk = (EamTab)V.tab;
-  double ROW_G *fp = aux[blockIdx.y].fp;
-  __shared__ double s_sh[3 * ROW_NSHIFT];
-  __shared__ EamHead s_hd;
-  __shared__ double s_red[8 * (ROW_FORCE_TPB / 64)];
-  rowf_shifts(V, s_sh);
-  rowf_to_lds<int>(&s_hd, blk);   // (offsets are read per lane, by the partner's element)
-  __syncthreads();
-  const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
-  const int nr = s_hd.nr;
-  const double rdr = s_hd.rdr, cut2 = s_hd.cut2;
-  double esum[4] = {0.0, 0.0, 0.0, 0.0};   // pair energy (the force pass), embedding energy, ordered pairs, atoms above rhomax
-  for (int it = 0; it < ROW_TILE / ROW_NGRP; it++) {   // (uniform over the workgroup)
-    const int i = blockIdx.x * ROW_TILE + it * ROW_NGRP + grp;
-    const int ti = V.stype[min(i, n - 1)];
-    double rho = 0.0;
-    rowf_walk(V, s_sh, i, l16, [&](int j, double, double, double, double r2) __attribute__((always_inline)) {
-      if (!(r2 < cut2 && r2 > 0.0)) return;
-      int k;
-      double p;
-      eam_locate(sqrt(r2), rdr, nr, &k, &p);
-      rho += eam_value(blk + s_hd.off_rho[ti * EAM_MAXEL + V.stype[j]], k, p);
-      esum[2] += 1.0;
-    });
-    rho = row_sum(rho);
-    if (i < n && l16 == 0) {
-      const EamTab fv = blk + s_hd.off_f[ti];
-      double e, d;
-      eam_embed(fv, fv + 4 * (size_t)s_hd.nrho, s_hd.nrho, s_hd.rdrho, s_hd.rhomax, rho, &e, &d);
-      fp[i] = d;
-      esum[1] += e;
-      if (rho > s_hd.rhomax) esum[3] += 1.0;
-    }
-  }
-  block_atomic_add_n<4, ROW_FORCE_TPB / 64>(esum, (double *)V.eacc, s_red);
+  if ((int)(blockIdx.x * ROW_TILE) >= V.n) return;   // (the whole workgroup)
+  eam_density_body<1, true>(V, (EamTab)V.tab, aux[blockIdx.y].fp);
 }
 
 // Forces: the same walk; a lane's entry takes the derivative records of the two densities and both records of r phi, and F' of both
-// ends.  The group's sum is the atom's force, stored once.  Half of a pair's phi and half of its virial go to each end.
+// ends (eam_entry, md_eam_body.h).  The group's sum is the atom's force, stored once.  Half of a pair's phi and half of its virial go to each end.
 __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims, const RowView *views, const EamView *aux) {
   const RowView V = views[blockIdx.y];
   const int n = V.n;
@@ -76,7 +38,6 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
   __syncthreads();
   const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
   const int nr = s_hd.nr;
-  const size_t der = 4 * (size_t)nr;   // from a function's value records to its derivative records
   const double rdr = s_hd.rdr, cut2 = s_hd.cut2;
   double esum[4] = {0.0, 0.0, 0.0, 0.0};
   double wa[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, wb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -88,17 +49,8 @@ __global__ __launch_bounds__(ROW_FORCE_TPB) void k_eam_force(const SimDev *sims,
     double fi0 = 0.0, fi1 = 0.0, fi2 = 0.0;
     rowf_walk(V, s_sh, i, l16, [&](int j, double d0, double d1, double d2, double r2) __attribute__((always_inline)) {
       if (!(r2 < cut2 && r2 > 0.0)) return;
-      const int tj = V.stype[j];
-      const double r = sqrt(r2);
-      int k;
-      double p;
-      eam_locate(r, rdr, nr, &k, &p);
-      const EamTab zt = blk + s_hd.off_z[ti * EAM_MAXEL + tj];
-      const double z = eam_value(zt, k, p), dz = eam_deriv(zt + der, k, p);
-      const double drho_j = eam_deriv(blk + s_hd.off_rho[ti * EAM_MAXEL + tj] + der, k, p);   // what j adds to the density at i
-      const double drho_i = eam_deriv(blk + s_hd.off_rho[tj * EAM_MAXEL + ti] + der, k, p);   // what i adds at j
       double phi, fa, fb;
-      eam_pair(r, z, dz, fpi, drho_j, fp[j], drho_i, &phi, &fa, &fb);
+      eam_entry(blk, s_hd, nr, rdr, ti, V.stype[j], sqrt(r2), fpi, fp[j], &phi, &fa, &fb);
       const double fpair = fa + fb;
       fi0 -= d0 * fpair; fi1 -= d1 * fpair; fi2 -= d2 * fpair;   // (x_i - x_j = -d)
       esum[0] += 0.5 * phi;

@@ -16,17 +16,27 @@ per evaluation at 1 fs.  The replica per potential:
              tests/golden/NaCl.born_dsf: pair_style born/coul/dsf 0.25 10.0, about 190 neighbours per ion)
   born_long  the born_dsf replica under tests/golden/NaCl.born_long: pair_style born/coul/long 10.0 with kspace_style ewald 1.0e-5, the
              same neighbours beside 709 k-vectors per replica; --kspace mesh puts the reciprocal part on the PPPM mesh (24^3) instead
+  eam_coul   324 ions of fluorite UO2 (3 x 3 x 3 cells of 5.47 A, O -1.1104 and U +2.2208, masses 15.9994 and 238.02891, thermal velocities
+             at 300 K) under tests/golden/UO2.eam_coul: pair_style hybrid/overlay coul/long 9.0 eam/alloy on the synthetic UO2.eam.alloy with
+             kspace_style ewald 1.0e-5 (709 k-vectors); --kspace as for born_long.  Its two parents on the SAME replica, for the sum the
+             fused stage is measured against: eam_coul_eam (the ions without their charges under pair_style eam/alloy on UO2.eam.alloy) and
+             eam_coul_coul (pair_style born/coul/long 9.0 with every Born constant zero and the same kspace_style line, written to a
+             temporary file; --kspace applies).  Point charges without a short-range term fall into each other under dynamics, so the
+             Coulomb parent leaves the lattice and rebuilds its rows on most steps; --heavy multiplies the masses of these three legs
+             by 1e8 (the thermal velocities shrink with them), so the ions of all three stay on their sites over the run, every leg
+             walks the same rows and builds its lists equally often (neigh_builds of the JSON line), and the times compare kernels
 One warm-up update, then the timed ones, each continuing from the states of the one before; a host clock around strain_batch, which ends
 in a device synchronise.  Prints one JSON line.  For the per-kernel table run it under `rocprofv3 --kernel-trace --stats -- python
 tools/rowpot_bench.py --potential sw --updates 2` (a run of its own: tracing slows the host).
 
-  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf|born_long [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--kspace ewald|mesh] [--dump stress.npy]
+  python tools/rowpot_bench.py --potential sw|edip|tersoff|tersoff_mod|tersoff_zbl|eam|adp|meam_spline|vashishta|born_dsf|born_long|eam_coul|eam_coul_eam|eam_coul_coul [--sims 576] [--updates 5] [--nss 100] [--split 1] [--cells K] [--kspace ewald|mesh] [--heavy] [--dump stress.npy]
 """
 import argparse
 import itertools
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -123,12 +133,40 @@ def make_born_long(e, cells=None):
     e.born_long_configure("nacl", os.path.join(GOLD, "NaCl.born_long"))
 
 
+FLUORITE = FCC + [[i, j, k] for i in (1, 3) for j in (1, 3) for k in (1, 3)]   # (U on the fcc sites, O on the eight tetrahedral sites)
+UO2 = dict(a=5.47, mass=(15.9994, 238.02891), basis_types=[1] * 4 + [0] * 8, type_charges=(-1.1104, 2.2208))
+HEAVY = 1.0     # --heavy: 1e8
+
+
+def uo2_mass():
+    return tuple(m * HEAVY for m in UO2["mass"])
+
+
+def make_eam_coul(e, cells=None):
+    register_lattice(e, "uo2", FLUORITE, cells or (3, 3, 3), UO2["a"], uo2_mass(), basis_types=UO2["basis_types"], type_charges=UO2["type_charges"])
+    e.eam_coul_configure("uo2", os.path.join(GOLD, "UO2.eam_coul"))
+
+
+def make_eam_coul_eam(e, cells=None):
+    register_lattice(e, "uo2", FLUORITE, cells or (3, 3, 3), UO2["a"], uo2_mass(), basis_types=UO2["basis_types"])
+    e.eam_configure("uo2", os.path.join(GOLD, "UO2.eam.alloy"), ("O", "U"))
+
+
+def make_eam_coul_coul(e, cells=None):
+    register_lattice(e, "uo2", FLUORITE, cells or (3, 3, 3), UO2["a"], uo2_mass(), basis_types=UO2["basis_types"], type_charges=UO2["type_charges"])
+    with tempfile.NamedTemporaryFile("w", suffix=".born_long") as f:
+        f.write("units metal\npair_style born/coul/long 9.0\nkspace_style ewald 1.0e-5\npair_coeff * * 0.0 1.0 0.0 0.0 0.0\n")
+        f.flush()
+        e.born_long_configure("uo2", f.name)
+
+
 # potential -> (workload of the JSON line, material id, what registers the one replica and attaches the potential)
 POTENTIALS = {"sw": ("sw_si_192", "sic", make_sw), "tersoff": ("tersoff_si_192", "si", make_tersoff), "eam": ("eam_cu_256", "cu", make_eam),
               "tersoff_mod": ("tersoff_mod_si_192", "si", make_tersoff_mod), "tersoff_zbl": ("tersoff_zbl_si_192", "si", make_tersoff_zbl),
               "vashishta": ("vashishta_sic_512", "sic", make_vashishta), "adp": ("adp_cu_256", "cu", make_adp), "edip": ("edip_si_192", "sic", make_edip),
               "meam_spline": ("meam_spline_ti_256", "ti", make_meam_spline), "born_dsf": ("born_dsf_nacl_512", "nacl", make_born_dsf),
-              "born_long": ("born_long_nacl_512", "nacl", make_born_long)}
+              "born_long": ("born_long_nacl_512", "nacl", make_born_long), "eam_coul": ("eam_coul_uo2_324", "uo2", make_eam_coul),
+              "eam_coul_eam": ("eam_uo2_324", "uo2", make_eam_coul_eam), "eam_coul_coul": ("coul_long_uo2_324", "uo2", make_eam_coul_coul)}
 
 
 def main():
@@ -140,17 +178,24 @@ def main():
     ap.add_argument("--split", type=int, default=-1, help="scema_md_batch_split: 0 whole, 1 part batches, -1 the default")
     ap.add_argument("--cells", type=int, default=None, metavar="K", help="K x K x K lattice cells per replica instead of the potential's shape above (sw: diamond silicon of 5.431 A "
                     "instead of the example's file); the JSON line then names the atoms and the list builds through cells (SCEMA_MD_ROW_CELLS, DESIGN.md 7m)")
-    ap.add_argument("--kspace", default=None, choices=("ewald", "mesh"), help="born_long only: the reciprocal solver of every replica, the Ewald sum (born_long_kspace "
+    ap.add_argument("--kspace", default=None, choices=("ewald", "mesh"), help="born_long, eam_coul and eam_coul_coul: the reciprocal solver of every replica, the Ewald sum (born_long_kspace "
                     "mode 2) or the PPPM mesh (mode 1); default: by the script and the Ewald limits (mode 0)")
+    ap.add_argument("--heavy", action="store_true", help="eam_coul, eam_coul_eam and eam_coul_coul: masses times 1e8, so the ions stay on their sites and the "
+                    "three legs build their rows equally often")
     ap.add_argument("--dump", default=None, metavar="FILE", help="write the stresses of the last update as FILE (.npy, float64, one row of six per quadrature point)")
     a = ap.parse_args()
     workload, mat, make = POTENTIALS[a.potential]
+    if a.heavy:
+        if not a.potential.startswith("eam_coul"):
+            ap.error("--heavy needs --potential eam_coul, eam_coul_eam or eam_coul_coul")
+        global HEAVY
+        HEAVY = 1.0e8
     e = capi.Engine(capi.default_params())
     make(e, None if a.cells is None else (a.cells,) * 3)
     if a.kspace is not None:
-        if a.potential != "born_long":
-            ap.error("--kspace needs --potential born_long")
-        e.born_long_kspace(mat, {"ewald": 2, "mesh": 1}[a.kspace])
+        if a.potential not in ("born_long", "eam_coul", "eam_coul_coul"):
+            ap.error("--kspace needs --potential born_long, eam_coul or eam_coul_coul")
+        (e.eam_coul_kspace if a.potential == "eam_coul" else e.born_long_kspace)(mat, {"ewald": 2, "mesh": 1}[a.kspace])
     e.batch_split(a.split)
     box, _, _ = e.get_state(capi.QP_NONE, mat, 1)
     L = box[3:6] - box[:3]
@@ -180,6 +225,8 @@ def main():
     extra = {}
     if a.kspace is not None:
         extra["kspace"] = a.kspace
+    if a.heavy:
+        extra["heavy"] = True
     if a.cells is not None:
         natoms = e.natoms(mat, 1)
         workload = "%s_%d" % (workload.rsplit("_", 1)[0], natoms)
